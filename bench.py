@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — mel-frames/sec of the FCL-taco2-S synthesis hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -11,9 +11,15 @@ durations clip(Poisson(10),1,50), ~25.6 k mel frames), inputs already resident i
 before the clock starts), prenet dropout on in its production (on-device RNG) mode, fp32 arithmetic.
 Utterances are independent, so N ranks run N independent batches (different seeds; weak scaling, no
 data-path collective); the clock is barrier + synchronize on both sides, MAX over ranks; `value` is the
-whole-job frames / that time.  Rank 0 additionally reports (N=1 only) the live roofline figures of the
-dominant kernel (HIP events on the launching stream, via fcl_prof_*) and a bounded CPU baseline (the
-oracle = this build's CPU restatement of the reference, "port").  Prints ONE JSON line.
+whole-job frames / that time.  Exactly K steps are timed (one region; --regions R repeats it, median).
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs)
+and prints ONE JSON line.  --full adds what takes runs of its own: on rank 0 (N=1 only) the other feeds and
+duration forms of the same workload (replay only, predicted durations, calibrated capacities, the decode
+driver), the live roofline figures of the dominant kernel (HIP events on the launching stream, via
+fcl_prof_*), a bounded CPU baseline (the oracle = this build's CPU restatement of the reference, "port"),
+and two child runs (the KD step, the headline in exact fp32); the training and vocoder workloads likewise
+keep their profiled update, one-rank RCCL leg and CPU baseline behind --full.
 """
 import argparse
 import json
@@ -81,6 +87,38 @@ def emit(obj):
         os.write(1, line)
     else:
         os.write(_REAL_STDOUT, line)
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` (name -> array-like) as DIR/<name>.npy, float64 where the values are float64 or integers (exact), float32 otherwise.
+    At most DUMP_LIMIT_BYTES in all: an array beyond what is left keeps a fixed seeded sample of its rows (sorted), whose indices go to
+    DIR/<name>_rows.npy.  Returns {name: shape written}."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64 if (a.dtype == np.float64 or a.dtype.kind in "iub") else np.float32)
+    left, written = DUMP_LIMIT_BYTES - 2 * 4096 * len(conv), {}  # (room for the .npy headers)
+    for name in sorted(conv, key=lambda k: conv[k].nbytes):  # the small arrays first: only the largest one can need a sample
+        a = conv[name]
+        if a.nbytes > left and a.ndim >= 1 and a.shape[0] > 1:
+            row_bytes = a.nbytes // a.shape[0]
+            k = max(1, min(a.shape[0], (left - 8 * a.shape[0]) // (row_bytes + 8)))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], size=k, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.nbytes
+            a = a[rows]
+        if a.nbytes > left:
+            raise SystemExit("bench.py: --dump-outputs: %s does not fit in %d bytes" % (name, DUMP_LIMIT_BYTES))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def timed_regions(one_region, barrier, regions):
@@ -325,7 +363,9 @@ def e2e_workload(args, rank, world, dev, dist):
                                "device noise" % (B, frames, audio_s, "" if e2e else " OUTSIDE the timed region"),
                    "parallelism": "%d independent replicas (utterance-sharded, no collective)" % world},
     }
-    if rank == 0 and world == 1:
+    if args.dump_outputs and rank == 0:  # the waveforms of the last timed step, utterances back to back (lengths: frames x hop)
+        out["dumped"] = dump_outputs(args.dump_outputs, {"wav": torch.cat([w.reshape(-1) for w in wavs]).cpu().numpy(), "utt_frames": np.asarray(lens)})
+    if args.full and rank == 0 and world == 1:
         # ---- live roofline of the dominant kernel (the fused residual block): HBM bytes it must move per launch / its HIP-event duration
         torch.cuda.synchronize()
         _lib.prof_enable(True)
@@ -405,6 +445,8 @@ def forward_tf_workload(args, rank, world, dev, dist, batch, frames, S, T):
         barrier()
         dt = time.perf_counter() - t0
     dt, frames_all = sharding.aggregate_throughput(dt, frames, dist, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": [float(loss)]})
     return {
         "metric": "mel-frames/sec (FCL-taco2-S teacher-forced forward(), eval + no_grad, batch=%d, 80-mel)" % args.batch,
         "value": frames_all * args.steps / dt, "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -474,6 +516,14 @@ def train_workload(args, rank, world, dev, dist):
 
     agg = [sharding.aggregate_throughput(t, frames, dist, dev) for t in timed_regions(region, barrier, max(1, args.regions))]
     rep = last[0]
+    if args.dump_outputs and rank == 0:  # what the update hands its caller: the named losses and the gradient norm of the last timed step
+        sc = {}
+        for k, v in rep.items():
+            v = v() if callable(v) else v
+            v = v.item() if torch.is_tensor(v) and v.numel() == 1 else v
+            if isinstance(v, (int, float)) and not isinstance(v, bool):
+                sc[k] = [float(v)]
+        dump_outputs(args.dump_outputs, sc)
     dts = [a[0] for a in agg]
     dt, frames_all = median(dts), agg[0][1]
     ms = 1e3 * dt / steps
@@ -484,7 +534,7 @@ def train_workload(args, rank, world, dev, dist):
     # ---- dominant kernel of the step: HIP events around every launch of ONE more update (single stream order per stream; the events serialise nothing
     # but add host time, so this update is not part of the timed regions), grouped per kernel family as in the synthesis leg
     dom_roof, launches_per_step, host_ms = None, None, None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from fcl_taco2_amd import _lib
 
         torch.cuda.synchronize()
@@ -527,7 +577,7 @@ def train_workload(args, rank, world, dev, dist):
     # ---- the same update on the schedule a rank of an N-GPU job runs (VERDICT r3 #5c): a ONE-rank RCCL group, every bucket's
     # all_reduce(AVG, async_op=True) issued from the weight-gradient stream while backward continues, waited for in optimizer_step()
     dp_sched = None
-    if rank == 0 and world == 1 and not args.no_dp_schedule:
+    if args.full and rank == 0 and world == 1 and not args.no_dp_schedule:
         try:
             import socket
 
@@ -554,7 +604,7 @@ def train_workload(args, rank, world, dev, dist):
             dp_sched = {"error": repr(e)}
     name = "KD step" if kd else "teacher training step"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # ---- CPU baseline ("port"): the same update through the oracle's differentiable restatement + torch autograd + torch.optim.Adam on a bounded
         # sample (the first 2 utterances of the batch; the reference's own 32-utterance CPU step took ~38 s in the survey container)
         from oracle import fcl_oracle as O
@@ -659,10 +709,14 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="kd_step: run teacher forward and student update back to back on one stream")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the bounded baseline sample")
-    ap.add_argument("--regions", type=int, default=11, help="repetitions of the timed region (each EXACTLY --steps steps between barrier + synchronize); "
-                    "value / ms_per_step are the MEDIAN region")
-    ap.add_argument("--no-extras", action="store_true", help="synthesis, 1 GPU: skip the two child runs whose numbers ride on the default line "
+    ap.add_argument("--regions", type=int, default=1, help="repetitions of the timed region (each EXACTLY --steps steps between barrier + synchronize); "
+                    "value / ms_per_step are the MEDIAN region (default 1: the timed steps are exactly --steps)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: other feeds and duration forms, the decode driver, "
+                    "roofline and per-kernel figures, CPU baselines, the one-rank RCCL leg, and (synthesis, 1 GPU) the two child runs "
                     "(kd_step_ms + its CPU baseline; value_fp32_exact under FCL_PRECISION=0)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, synthesis, 1 GPU: skip the two child runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all); the inputs are seeded, so runs with the same arguments see the same inputs")
     ap.add_argument("--dry-run-launch", action="store_true", help="exercise the N-rank launch path on CPU (gloo), no GPU work")
     args = ap.parse_args()
 
@@ -682,11 +736,12 @@ def main():
         import __graft_entry__ as ge0
 
         ge0.build()
-    # ---- numbers that ride on the default line, measured in CHILD processes started before this one touches the GPU: the second north-star number
-    # (student-KD step time, with its own CPU baseline) and the headline metric in exact-fp32 arithmetic (FCL_PRECISION is read once per process)
+    # ---- --full: numbers that ride on the line, measured in CHILD processes started before this one touches the GPU: the second north-star number
+    # (student-KD step time, with its own CPU baseline) and the headline metric in exact-fp32 arithmetic (FCL_PRECISION is read once per process).
+    # The children run --full themselves and keep the median of 11 timed regions these two figures have always been quoted as.
     extras = {}
-    if args.workload == "synthesis" and world == 1 and not args.no_extras:
-        common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--no-extras"]
+    if args.full and args.workload == "synthesis" and world == 1 and not args.no_extras:
+        common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--regions", "11", "--full", "--no-extras"]
         kd = run_child(["--workload", "kd_step", "--cpu-threads", str(args.cpu_threads)] + common + (["--no-cpu-baseline"] if args.no_cpu_baseline else []),
                        {}, 900)
         extras["kd_step"] = ({k: kd.get(k) for k in ("metric", "value", "unit", "ms_per_step", "steps", "frames_per_s", "dtype", "roofline", "cpu_baseline",
@@ -769,12 +824,13 @@ def main():
     # `value_calibrated_caps` / `value_decode_driver`.
     caps = engine.Caps.for_batches(host_maps, slack_steps=args.cap_slack)
     fresh = args.feed == "fresh" and not args.eager
+    eager_out = [None]  # --eager: (mel, per-utterance frames) of the last pass
     if args.eager:
         streams = engine.shared_streams(dev, args.streams) if args.streams > 1 else [torch.cuda.current_stream()]
 
         def one_pass(i, seed):
             with torch.cuda.stream(streams[i % len(streams)]):
-                engine.run(plan, prep, ops.DROP_RNG, seed=seed)
+                eager_out[0] = engine.run(plan, prep, ops.DROP_RNG, seed=seed)
             return frames
     elif fresh:
         pass_streams = engine.shared_streams(dev, args.streams)  # one pool per process: every later runner set and the decode driver reuse these queues
@@ -848,7 +904,24 @@ def main():
                                       "hipGraph replay of one prepared batch (host-built maps outside the clock)")},
     }
 
-    if rank == 0 and world == 1:
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its LAST step (pass number counter[0]): the packed mel rows of that batch, utterances back
+        # to back, and their frame counts
+        last = counter[0]
+        if args.eager:
+            mel, utt = eager_out[0][0], eager_out[0][1]
+            utt = utt.resolve() if isinstance(utt, engine.DeviceFrames) else utt
+        elif fresh:
+            r = runners[last % len(runners)]
+            mel, utt = r.mel, r.frames()
+        else:
+            r = runners[last % len(runners)]
+            mel, utt = r.mel, r.utt_frames
+        torch.cuda.synchronize()
+        utt = np.asarray([int(n) for n in utt], dtype=np.int64)
+        out["dumped"] = dump_outputs(args.dump_outputs, {"mel": mel[: int(utt.sum())].float().cpu().numpy(), "utt_frames": utt})
+
+    if args.full and rank == 0 and world == 1:
         # ---- the same workload the way rounds 1-2 timed it (one prepared batch replayed, host maps outside the clock), and with PREDICTED durations
         # (synthetic duration head, SYN.positive_duration_head: the closed-form head predicts ~0 frames) through the same kind of capacity graph
         if fresh:
@@ -1012,7 +1085,8 @@ def main():
             if v.get("fill_bytes"):
                 e["mfma_frac"] = e["tflops"] / peak
                 b_ = binding_record(k, v["ms"], v["fill_bytes"], pmc_wl)
-                e["binding"] = {kk: b_[kk] for kk in ("achieved_B_per_clk_per_cu", "frac", "lds_idx_active_over_sq_busy")}
+                if b_:
+                    e["binding"] = {kk: b_[kk] for kk in ("achieved_B_per_clk_per_cu", "frac", "lds_idx_active_over_sq_busy")}
             out["kernels"][k] = e
 
         # ---- CPU baseline: the oracle ("port" of the reference's per-utterance inference) on the host cores

@@ -92,8 +92,12 @@ def test_unsupported_configurations_fail_loudly():
         m.train().forward(torch.zeros(1, 3, dtype=torch.long), [3], torch.zeros(1, 3, 80), [3])
     m.eval()
     from fcl_taco2_amd import _lib
-    with pytest.raises(_lib.FclError):  # no GPU here: inference must not fall back to torch CPU ops
-        m.inference(torch.tensor([1, 2, 3]), None, dur=torch.tensor([1, 1, 1]))
+    if not torch.cuda.is_available():
+        with pytest.raises(_lib.FclError):  # no GPU here: inference must not fall back to torch CPU ops
+            m.inference(torch.tensor([1, 2, 3]), None, dur=torch.tensor([1, 1, 1]))
+    else:  # a GPU here: the model held on the CPU synthesises on cuda:0 through the HIP path, never with torch CPU ops
+        mel = m.inference(torch.tensor([1, 2, 3]), None, dur=torch.tensor([1, 1, 1]))
+        assert mel.is_cuda and tuple(mel.shape) == (3, 80)
 
 
 def test_loss_configuration_is_gated_loudly():

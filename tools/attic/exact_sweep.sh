@@ -1,7 +1,7 @@
 # developer aid: exact-fp32 mode (FCL_PRECISION=0) tile choices of the LDS-DMA kernels: the eager kernel table and the 4-stream bench value
 cd $GRAFT_REPO_ROOT
 run() {
-  env FCL_PRECISION=0 "$@" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+  env FCL_PRECISION=0 "$@" python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 p=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$*  value %.2f M  replay %.2f M' % (p['value']/1e6, p.get('value_replay_only',0)/1e6))

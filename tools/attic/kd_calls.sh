@@ -2,7 +2,7 @@
 OUT=gpurun_out/kdprof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d $OUT -o kd --output-format csv -- python3 bench.py --workload ${1:-kd_step} --amp ${2:-none} --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $OUT -o kd --output-format csv -- python3 bench.py --full --workload ${1:-kd_step} --amp ${2:-none} --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench.json 2>/dev/null
 python3 - <<PY
 import csv, glob
 f = glob.glob("$OUT/*kernel_stats.csv")[0]

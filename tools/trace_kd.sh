@@ -3,7 +3,7 @@ W=${1:-kd_step}
 OUT=gpurun_out/kdtrace
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace -d $OUT/raw -o t --output-format csv -- python3 bench.py --workload $W --steps 6 --warmup 3 --regions 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --kernel-trace -d $OUT/raw -o t --output-format csv -- python3 bench.py --full --workload $W --steps 6 --warmup 3 --regions 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/err.log
 f=$(find $OUT/raw -name "*kernel_trace.csv" | head -1)
 python3 - "$f" $OUT/${W}_trace.csv <<'PY'
 import csv, sys

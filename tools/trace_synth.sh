@@ -2,7 +2,7 @@
 OUT=gpurun_out/kdtrace
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace -d $OUT/raws -o t --output-format csv -- python3 bench.py --no-cpu-baseline --no-extras --steps 24 --warmup 8 --regions 1 $* > $OUT/bench_synth.json 2> $OUT/err_synth.log
+rocprofv3 --kernel-trace -d $OUT/raws -o t --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 24 --warmup 8 --regions 1 $* > $OUT/bench_synth.json 2> $OUT/err_synth.log
 f=$(find $OUT/raws -name "*kernel_trace.csv" | head -1)
 python3 - "$f" $OUT/synth_trace.csv <<'PY'
 import csv, sys
