@@ -160,6 +160,10 @@ class _Decoder(torch.nn.Module):
                 torch.nn.init.xavier_uniform_(m.weight, torch.nn.init.calculate_gain("tanh"))
 
 
+_REPORT_ORDER = ["l1_loss", "mse_loss", "dur_loss", "pitch_loss", "energy_loss", "output_l1_loss", "output_mse_loss", "encoder_loss", "decoder_loss",
+                 "prosody_loss", "loss"]
+
+
 class _HipLoss(torch.autograd.Function):
     """loss value computed by the HIP engine; backward returns the engine's gradients (scaled by the incoming grad)."""
 
@@ -320,38 +324,21 @@ class Tacotron2Base(TTSInterface, torch.nn.Module):
                      ds_nonzeros=ds_nonzeros, f0=f0, energy=energy, spembs=spembs)
         if self.training:
             return self._forward_train(batch, teacher_knowledge, kwargs.get("masks"))
-        order = ["l1_loss", "mse_loss", "dur_loss", "pitch_loss", "energy_loss", "output_l1_loss", "output_mse_loss", "encoder_loss",
-                 "decoder_loss", "prosody_loss", "loss"]
-        if self.hp.reduction_factor != 1:
-            # round 5: the no-gradient forward of teacher_forced.py covers reduction_factor 1; with r > 1 (teacher class only: the reference's KD
-            # classes fail on it) the evaluator's forward runs the training engine's eval form -- running-stat BatchNorm, expectation zoneout, the
-            # prenet's dropout on as in the reference (decoder_sa.py:156-158) -- and leaves the engine's gradient buffers as it found them
-            eng = self.train_engine()
-            eng.invalidate_planes()
-            kept = eng.gflat.clone()
-            try:
-                with torch.no_grad():
-                    rep = eng.forward_backward(batch, None, mode="eval", masks=kwargs.get("masks"), reduce=False)
-            finally:
-                eng.gflat.copy_(kept)
-            self.reporter.report([{k: float(rep[k])} for k in order if k in rep])
-            return torch.tensor(float(rep["loss"]), dtype=torch.float32, device=eng.dev)
-        from .. import teacher_forced as TF
-
-        plan = self.plan(xs.device if xs.is_cuda else None)
-        kw = dict(seed=int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
-        kw.update({k: kwargs[k] for k in ("dropout_mode", "prenet_keep", "seed") if k in kwargs})
+        # eval: the engine's eval form (running-stat BatchNorm, nn.Dropout off, expectation zoneout, the prenet's dropout on as in the reference,
+        # decoder_sa.py:156-158), losses only; the engine's training state is left as it was (TrainEngine.evaluate)
+        eng = self.train_engine()
+        eng.invalidate_planes()  # (the caller's optimizer may have moved the weights since the last forward)
+        masks = kwargs.get("masks")
+        if "prenet_keep" in kwargs:
+            masks = {"prenet": kwargs["prenet_keep"]}  # [lmax, prenet_layers, N, prenet_units], the converter's row order
+        if kwargs.get("dropout_mode") == ops.DROP_NONE:
+            masks = {"prenet": None}
         with torch.no_grad():
             if self.role == "kd_teacher":
-                return TF.knowledge_tuple(TF.forward_pass(plan, batch, **kw))
-            if self.role == "student":
-                rep, _ = TF.student_forward(plan, batch, teacher_knowledge, self.share_proj,
-                                            (self.distill_output_knowledge, self.distill_encoder_knowledge,
-                                             self.distill_decoder_knowledge, self.distill_prosody_knowledge), **kw)
-            else:
-                rep, _ = TF.teacher_forward(plan, batch, **kw)
-        self.reporter.report([{k: float(rep[k])} for k in order if k in rep])
-        return torch.tensor(float(rep["loss"]), dtype=torch.float32, device=plan.device)
+                return eng.knowledge(batch, mode="eval", masks=masks, seed=kwargs.get("seed"))
+            rep = eng.evaluate(batch, teacher_knowledge, masks=masks, seed=kwargs.get("seed"))
+        self.reporter.report([{k: float(rep[k])} for k in _REPORT_ORDER if k in rep])
+        return torch.tensor(float(rep["loss"]), dtype=torch.float32, device=eng.dev)
 
     def train_engine(self, **kw):
         """The fused forward/backward engine bound to this module's parameters (created on first use; parameters are re-pointed into its
@@ -381,9 +368,7 @@ class Tacotron2Base(TTSInterface, torch.nn.Module):
             rep = eng.forward_backward(batch, teacher_knowledge, mode="train", masks=masks, reduce=False)
         finally:
             eng.accum_grad = accum
-        order = ["l1_loss", "mse_loss", "dur_loss", "pitch_loss", "energy_loss", "output_l1_loss", "output_mse_loss", "encoder_loss",
-                 "decoder_loss", "prosody_loss", "loss"]
-        self.reporter.report([{k: float(rep[k])} for k in order if k in rep])
+        self.reporter.report([{k: float(rep[k])} for k in _REPORT_ORDER if k in rep])
         names = [k for k, p in self.named_parameters() if p.requires_grad]
         params = [p for _, p in self.named_parameters() if p.requires_grad]
         value = torch.tensor(float(rep["loss"]), dtype=torch.float32, device=eng.dev)

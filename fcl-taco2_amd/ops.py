@@ -393,7 +393,7 @@ def row_maps_request(n, b, lmax_cap, frames_cap, dur_i64=None, dur_i32=None, row
 
 
 def decoder_loop(dw, att_c, dur_i32, live_rows, frame_off_i32, n_frames, teacher_ys=None, dropout_mode=DROP_NONE,
-                 prenet_keep=None, seed=0, want_taps=False, seed_dev=None, zero_init=False, att_c_p=None, want_before_p=False, live_rows_dev=None,
+                 prenet_keep=None, seed=0, want_taps=False, seed_dev=None, att_c_p=None, want_before_p=False, live_rows_dev=None,
                  status=None, tail_from=0):
     """dw: plan.DecoderPack (holds the ctypes DecoderWeights + the tensors it points to).
     live_rows: host numpy int32 [Lmax].  Returns before [F, odim] (+ taps).  att_c_p: P32 planes of att_c (att_c may then be None);
@@ -408,16 +408,15 @@ def decoder_loop(dw, att_c, dur_i32, live_rows, frame_off_i32, n_frames, teacher
     lmax = int(live_rows.shape[0])
     nbytes = lib.fcl_decoder_loop_workspace_bytes(C.byref(dw.struct), n)
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    alloc = torch.zeros if zero_init else torch.empty  # zero_init: frames no (row, t) maps to stay 0 (padded [B, Lmax] layout)
-    before = alloc(n_frames, dw.struct.odim, device=dev, dtype=torch.float32)
+    before = torch.empty(n_frames, dw.struct.odim, device=dev, dtype=torch.float32)
     before_p = planes_empty(n_frames, dw.struct.odim, dev) if want_before_p else None
     if live_rows_dev is not None and status is None:
         status = status_word(dev)
     taps = None
     if want_taps:
-        taps = (alloc(n_frames, dw.struct.p, device=dev, dtype=torch.float32),
-                alloc(n_frames, dw.struct.u, device=dev, dtype=torch.float32),
-                alloc(n_frames, dw.struct.u, device=dev, dtype=torch.float32))
+        taps = (torch.empty(n_frames, dw.struct.p, device=dev, dtype=torch.float32),
+                torch.empty(n_frames, dw.struct.u, device=dev, dtype=torch.float32),
+                torch.empty(n_frames, dw.struct.u, device=dev, dtype=torch.float32))
     io = _lib.DecoderIO(
         n=n, lmax=lmax, att_c=_p(att_c), dur=_p(dur_i32, torch.int32), live_rows_host=live_rows.ctypes.data,
         frame_off=_p(frame_off_i32, torch.int32), teacher_ys=_p(teacher_ys), dropout_mode=dropout_mode,

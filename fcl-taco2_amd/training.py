@@ -51,6 +51,11 @@ def _u8(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
 
 
+def _eval_seed(seed):
+    """Mask seed of an eval-form pass: `seed`, or one drawn from torch's default generator."""
+    return int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed)
+
+
 def group_of(name):
     for g, prefixes in enumerate(_GROUPS):
         if any(name.startswith(p) for p in prefixes):
@@ -930,6 +935,10 @@ class TrainEngine(object):
         return dict(self._offsets)
 
     # ------------------------------------------------------------------------------------------------ randomness
+    def _draw_seed(self, draw):
+        """Base seed of the masks of the forward with ordinal `draw` (a site adds its tag)."""
+        return self.seed * 7919 + draw * 104729
+
     def _keep(self, c, name, shape, p_one):
         """uint8 mask [shape] with P(1) = p_one: injected (c.masks) or drawn on the device."""
         if c.masks is not None:
@@ -938,14 +947,14 @@ class TrainEngine(object):
                 m = m[part]
             return _u8(m, self.dev).reshape(shape)
         tag = zlib.crc32(repr(name).encode()) & 0x7FFFFFFF
-        return ops.bernoulli_u8(shape, p_one, self.seed * 7919 + c.draw * 104729 + tag, self.dev)
+        return ops.bernoulli_u8(shape, p_one, c.mask_seed + tag, self.dev)
 
     def _keeps(self, c, sites):
         """[(name, shape, p_one)] -> masks: what _keep would return for each site (same seeds, same bytes), drawn in ONE launch per group of sites
         (ops.bernoulli_batch) instead of one each: a train-mode forward has ~22 sites."""
         if c.masks is not None:
             return [self._keep(c, name, shape, p) for name, shape, p in sites]
-        seeds = [self.seed * 7919 + c.draw * 104729 + (zlib.crc32(repr(name).encode()) & 0x7FFFFFFF) for name, _, _ in sites]
+        seeds = [c.mask_seed + (zlib.crc32(repr(name).encode()) & 0x7FFFFFFF) for name, _, _ in sites]
         return ops.bernoulli_batch([(shape, p, sd) for (_, shape, p), sd in zip(sites, seeds)], self.dev)
 
     def device_masks(self, batch, draw=None):
@@ -954,7 +963,7 @@ class TrainEngine(object):
         tag), so what the native / per-launch step used can be replayed into an independent implementation (tests: the native step vs the oracle)."""
         hp, dev = self.hp, self.dev
         c = _Ctx()
-        c.masks, c.draw = None, self.forward_count if draw is None else int(draw)
+        c.masks, c.mask_seed = None, self._draw_seed(self.forward_count if draw is None else int(draw))
         self._maps(c, batch)
         B, T, L, N, F, lmax = c.B, c.T, c.L, c.N, c.F, c.lmax
         C = hp.adim
@@ -1446,7 +1455,8 @@ class TrainEngine(object):
         PL, DL = hp.prenet_layers, hp.dlayers  # (2, 2) in every shipped recipe; other counts: decoder_sa.py:119-158, 357-369 (G18 / G19)
         c.pre_keep = [None] * PL
         c.pks = 1.0
-        if hp.dropout_rate > 0:  # the prenet's dropout is on in BOTH modes (decoder_sa.py:156-158)
+        # the prenet's dropout is on in BOTH modes (decoder_sa.py:156-158); injected masks with "prenet": None turn it off (evaluate())
+        if hp.dropout_rate > 0 and not (c.masks is not None and "prenet" in c.masks and c.masks["prenet"] is None):
             c.pks = 1.0 / (1.0 - hp.dropout_rate)
             if c.masks is not None:
                 pk = np.asarray(c.masks["prenet"])
@@ -1572,7 +1582,8 @@ class TrainEngine(object):
 
     # ------------------------------------------------------------------------------------------------ losses and their gradients
     def _losses(self, c, teacher_knowledge):
-        """Named losses into one device buffer + the gradient every loss term injects at its tap (c.inj[name])."""
+        """Named losses into one device buffer + the gradient every loss term injects at its tap (c.inj[name]).  A pass without a backward
+        (not c.save: evaluate()) computes the sums only -- no gradient, no weight-gradient GEMM."""
         dev, P, G, hp = self.dev, self.P, self.G, self.hp
         nf, ne = c.n_frames * hp.odim, c.n_enc
         sums = self._z((48, 3), torch.float64)
@@ -1581,6 +1592,8 @@ class TrainEngine(object):
         def term(name, a, b, valid, count, w_l1, w_mse, b_log=None, da=None, want_planes=False):
             a2, b2 = (a.reshape(-1, 1), b.reshape(-1, 1)) if a.dim() == 1 else (a, b)
             names.append(name)
+            if not c.save:
+                return ops.masked_l1_mse(a2, b2, valid, sums[len(names) - 1], b_log)
             return ops.l1_mse_loss_grad(a2, b2, valid, count * self.accum_grad, w_l1, w_mse, sums[len(names) - 1], da=da,
                                         b_log_offset=b_log, want_planes=want_planes)  # loss sums + d(loss / accum_grad) in one pass
 
@@ -1606,18 +1619,20 @@ class TrainEngine(object):
                 lp, pp = ["dec.lstm0_proj", "dec.lstm1_proj"], ["dec.post%d_proj" % i for i in range(4)]
 
             def kd(name, s_in, proj, t, valid, nvalid):
-                """MSE(s_in . W^T, t) over valid rows: accumulates dW, returns the gradient w.r.t. s_in."""
+                """MSE(s_in . W^T, t) over valid rows: accumulates dW, returns the gradient w.r.t. s_in (loss only: the sums alone)."""
                 w = P[proj + ".weight"]
                 n, k = w.shape
-                if ops.planes_enabled() and n % 32 == 0 and k % 32 == 0 and s_in.shape[0] >= 4096:
-                    # the projections over every frame (7 taps x ~25 k rows x up to [1024, 256]) on pre-split operands: the tap is packed once, the
-                    # loss kernel hands its gradient over as planes too (r3 trace: 1.4 ms of the update's critical path on the fp32-operand kernel)
-                    s = ops.linear_planes(ops.pack_planes(s_in), self._wplanes(proj + ".weight", w), n, k)[0]
+                # the projections over every frame (7 taps x ~25 k rows x up to [1024, 256]) on pre-split operands: the tap is packed once, the
+                # loss kernel hands its gradient over as planes too (r3 trace: 1.4 ms of the update's critical path on the fp32-operand kernel)
+                pl = ops.planes_enabled() and n % 32 == 0 and k % 32 == 0 and s_in.shape[0] >= 4096
+                s = ops.linear_planes(ops.pack_planes(s_in), self._wplanes(proj + ".weight", w), n, k)[0] if pl else ops.linear(s_in, w)
+                if not c.save:
+                    return term(name, s, t, valid, nvalid * n, 0.0, 1.0)
+                if pl:
                     ds_, ds_p = term(name, s, t, valid, nvalid * n, 0.0, 1.0, want_planes=True)
                     self._dw(lambda: self._dw_gemm(ds_, [(s_in, G[proj + ".weight"])]))
                     return ops.linear_planes(ds_p, self._wplanes(proj + ".weight.t", self._wt(w)), k, n)[0]
-                s = ops.linear(s_in, w)
-                ds_ = term(name, s, t, valid, nvalid * s.shape[1], 0.0, 1.0)
+                ds_ = term(name, s, t, valid, nvalid * n, 0.0, 1.0)
                 self._dw(lambda: ops.gemm_tn(ds_, s_in, G[proj + ".weight"]))
                 return ops.linear(ds_, self._wt(w))
 
@@ -1793,7 +1808,9 @@ class TrainEngine(object):
     def zero_grad(self):
         self.gflat.zero_()
 
-    def _ctx(self, batch, mode, masks, save=True, reduce=True):
+    def _ctx(self, batch, mode, masks, save=True, reduce=True, seed=None):
+        """seed None: the masks come from the engine's own stream (engine seed, forward ordinal) and the ordinal advances; a seed: a one-off draw
+        that leaves the ordinal, hence every later train-form mask, as it was (the eval form of evaluate() / knowledge())."""
         if mode not in ("eval", "train"):
             raise ValueError("mode must be 'eval' or 'train'")
         c = _Ctx()
@@ -1805,21 +1822,41 @@ class TrainEngine(object):
             self._dw_keep.clear()
             self._pred_ev = self._late_ev = None
         self.arena.begin()
-        self.forward_count += 1
-        c.draw = self.forward_count
+        if seed is None:
+            self.forward_count += 1
+            c.mask_seed = self._draw_seed(self.forward_count)
+        else:
+            c.mask_seed = int(seed)
         self._maps(c, batch)
         return c
 
-    def knowledge(self, batch, mode="train", masks=None, native=False):
+    def knowledge(self, batch, mode="train", masks=None, native=False, seed=None):
         """Forward only: the frozen KD teacher's 5-tuple (tts_distill.py:159; the reference leaves the teacher in train mode).
         native=True (KDPipeline, when both engines have the native step): a NativeKnowledge -- pointers into the native engine's arena, decoder
-        taps cell-major -- instead of the reference-shaped tuple of tensors."""
+        taps cell-major -- instead of the reference-shaped tuple of tensors.
+        mode="eval": the forward_count and seed rules of evaluate()."""
         if native and mode == "train" and masks is None and self.native is not None:
             return self.native.knowledge(batch)
         with torch.cuda.device(self.dev), ops.gemm_mode(self.amp):
-            c = self._ctx(batch, mode, masks, save=False)
+            c = self._ctx(batch, mode, masks, save=False, seed=None if mode == "train" else _eval_seed(seed))
             self._forward(c, batch)
             return self._knowledge(c)
+
+    def evaluate(self, batch, teacher_knowledge=None, masks=None, seed=None):
+        """The evaluator's loss (model.eval(); model(**batch) under no_grad, tts.py:76-108): the eval form's forward and named losses, no backward.
+        The training state stays as it was: gradients, Adam moments, BatchNorm buffers, the update counter and forward_count (so the train-form masks
+        of later steps do not move).  The prenet's dropout, on in eval mode (decoder_sa.py:156-158), draws from `seed`, by default one taken from
+        torch's default generator (torch.manual_seed makes an evaluation repeatable); masks={"prenet": keep} injects it, {"prenet": None} turns it
+        off.  fp32-equivalent GEMMs whatever `amp` is."""
+        if self.role == "kd_teacher":
+            raise ValueError("the KD teacher computes no loss: knowledge(batch, mode='eval')")
+        if self.role == "student" and (teacher_knowledge is None or isinstance(teacher_knowledge, NativeKnowledge)):
+            raise ValueError("the student's evaluation needs teacher_knowledge as the reference's tuple (tts_distill.py:159-161)")
+        with torch.cuda.device(self.dev), ops.gemm_mode(None):
+            c = self._ctx(batch, "eval", masks, save=False, seed=_eval_seed(seed))
+            self._forward(c, batch)
+            self._losses(c, teacher_knowledge)
+            return self._report(c)
 
     def forward_backward(self, batch, teacher_knowledge=None, mode="eval", masks=None, reduce=True):
         """One micro-batch: named losses (floats) and d(loss / accum_grad) accumulated into the flat gradient buffer.

@@ -193,7 +193,7 @@ def test_bilstm_both_algorithms(ops, hp):
         assert max_abs(out.cpu().reshape(B, T, 2 * H), ref) < 2e-5, algo
 
 
-def _decoder_case(ops, hp, n_rows, seed, teacher_forced, masked):
+def _decoder_case(ops, hp, n_rows, seed, forced, masked):
     from fcl_taco2_amd.plan import SynthesisPlan
 
     rng = np.random.RandomState(seed)
@@ -205,7 +205,7 @@ def _decoder_case(ops, hp, n_rows, seed, teacher_forced, masked):
     foff = np.concatenate([[0], np.cumsum(dur)[:-1]]).astype(np.int32)
     F_ = int(dur.sum())
     live = np.ascontiguousarray((dur[None, :] > np.arange(lmax)[:, None]).sum(1).astype(np.int32))
-    ys = rnd(rng, n_rows, lmax, hp.odim) if teacher_forced else None
+    ys = rnd(rng, n_rows, lmax, hp.odim) if forced else None
     keep = SYN.closed_form_keep_mask((lmax, 2, n_rows, hp.prenet_units), seed) if masked else None
     before, taps = ops.decoder_loop(plan.decoder, dev(att), dev(dur), live, dev(foff), F_,
                                     teacher_ys=dev(ys) if ys is not None else None,
@@ -222,10 +222,10 @@ def _decoder_case(ops, hp, n_rows, seed, teacher_forced, masked):
 
 @pytest.mark.parametrize("hp,n_rows", [(TINY_S, 37), (TINY_T, 5), (HP.student_hparams(dropout_rate=0.0), 300),
                                        (HP.student_hparams(), 97), (HP.teacher_hparams(), 70)], ids=["tinyS", "tinyT", "S_nodrop", "S_mask", "T_mask"])
-@pytest.mark.parametrize("teacher_forced", [False, True])
-def test_decoder_loop_vs_oracle(ops, hp, n_rows, teacher_forced):
+@pytest.mark.parametrize("forced", [False, True])
+def test_decoder_loop_vs_oracle(ops, hp, n_rows, forced):
     masked = hp.dropout_rate > 0
-    (before, taps), (ref_before, ref_taps) = _decoder_case(ops, hp, n_rows, 5, teacher_forced, masked)
+    (before, taps), (ref_before, ref_taps) = _decoder_case(ops, hp, n_rows, 5, forced, masked)
     assert max_abs(before, ref_before) < 1e-4  # frame-major scatter (H10) + H6-H8 maths
     for a, b in zip(taps, ref_taps):
         assert max_abs(a, b) < 1e-4
@@ -290,10 +290,10 @@ def test_prenet_rng_dropout_is_fair_and_independent(ops):
 
 
 # ------------------------------------------------------------------------------------------ end to end
-def _plan(hp, thp=None, share=True):
+def _plan(hp, thp=None):
     from fcl_taco2_amd.plan import SynthesisPlan
 
-    return SynthesisPlan(np_state_dict(hp, thp, share), hp, DEV)
+    return SynthesisPlan(np_state_dict(hp, thp), hp, DEV)
 
 
 @pytest.mark.parametrize("tag,hp,thp", [("student_share", TINY_S, TINY_T), ("teacher", TINY_T, None)])
@@ -523,18 +523,18 @@ def test_masked_l1_mse_kernel(ops):
     assert np.allclose(out.cpu().numpy(), ref, rtol=1e-5)
 
 
-def test_forward_eval_losses_vs_reference(ops, golden):
-    """H9/H12/H14: eval-mode forward() of teacher, KD teacher and student (share_proj on/off) on the HIP path vs the
+def test_eval_form_losses_vs_reference(ops, golden):
+    """H9/H12/H14: the eval form (TrainEngine.evaluate / knowledge(mode="eval")) of teacher, KD teacher and student (share_proj on/off) vs the
     REAL reference's numbers (G1 forward: losses, and the KD teacher's 5-tuple)."""
-    from fcl_taco2_amd import teacher_forced as TF
+    from fcl_taco2_amd.training import TrainEngine
 
     g = golden("g1_forward")
     b = _conv_batch(golden)
-    plan_t = _plan(TINY_T)
-    rep, r = TF.teacher_forward(plan_t, b, dropout_mode=ops.DROP_NONE)
+    off = {"prenet": None}  # (dropout_mode=DROP_NONE of the plug-in's forward)
+    rep = TrainEngine(SYN.build_model("teacher", TINY_T, None, DEV)).evaluate(b, masks=off)
     for k in ("loss", "l1_loss", "mse_loss", "dur_loss", "pitch_loss", "energy_loss"):
         assert abs(rep[k] - float(g["teacher_" + k])) < tol(1e-4, 5e-4) * max(1.0, abs(float(g["teacher_" + k]))), k
-    know = TF.knowledge_tuple(r)
+    know = TrainEngine(SYN.build_model("kd_teacher", TINY_T, None, DEV)).knowledge(b, mode="eval", masks=off)
     assert max_abs(know[0].cpu(), g["t_after"]) < tol(1e-4, 3e-4) and max_abs(know[1].cpu(), g["t_before"]) < tol(1e-4, 3e-4)
     for grp, items in (("t_enc", know[2]), ("t_dec", know[3]), ("t_pro", know[4])):
         for i, it in enumerate(items):
@@ -543,8 +543,7 @@ def test_forward_eval_losses_vs_reference(ops, golden):
                 [torch.from_numpy(g["t_dec%d" % i]) for i in range(8)], [torch.from_numpy(g["t_pro%d" % i]) for i in range(5)])
     for share in (True, False):
         tag = "student_%s_" % ("share" if share else "noshare")
-        plan_s = _plan(TINY_S, TINY_T, share)
-        rep, _ = TF.student_forward(plan_s, b, ref_know, share, dropout_mode=ops.DROP_NONE)
+        rep = TrainEngine(SYN.build_model("student", TINY_S, TINY_T, DEV, share_proj=share)).evaluate(b, ref_know, masks=off)
         for k in ("loss", "l1_loss", "mse_loss", "dur_loss", "pitch_loss", "energy_loss", "output_l1_loss", "output_mse_loss",
                   "encoder_loss", "decoder_loss", "prosody_loss"):
             assert abs(rep[k] - float(g[tag + k])) < tol(1e-4, 5e-4) * max(1.0, abs(float(g[tag + k]))), (share, k, rep[k], float(g[tag + k]))

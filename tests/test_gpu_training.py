@@ -240,6 +240,19 @@ def test_kd_update_train_mode_vs_reference_g9():
     _check_vs_oracle(eng, sd, tol=1e-3)
 
 
+def _training_state(eng):
+    """What the evaluator's forward() leaves as it found it: gradients, Adam moments, the update counter, BatchNorm buffers (num_batches_tracked
+    included) and the forward ordinal the train-form masks are drawn from."""
+    return [t.clone() for t in (eng.gflat, eng.mflat, eng.vflat, eng.step_dev, *eng.B.values())], eng.forward_count
+
+
+def _assert_training_state(eng, kept):
+    now = _training_state(eng)
+    assert now[1] == kept[1], ("forward_count", now[1], kept[1])
+    for i, (a, b) in enumerate(zip(now[0], kept[0])):
+        assert torch.equal(a, b), i
+
+
 def test_unmasked_loss_variant_vs_reference_g10():
     """G10: `--use-masking False` on the HIP path -- the teacher step and the student KD step against the real reference's losses and gradients
     (mel / prosody / output-KD means over the padded tensors), and every other gradient against the oracle's autograd."""
@@ -256,10 +269,12 @@ def test_unmasked_loss_variant_vs_reference_g10():
     sd = _grad_sd(TINY_TU)
     O.model_forward(sd, TINY_TU, _cpu(batch), "teacher")["loss"].backward()
     _check_vs_oracle(eng, sd)
+    kept = _training_state(eng)
     m.eval()
     with torch.no_grad():
-        loss = m(**{k: v for k, v in batch.items() if not k.startswith("_")})  # the evaluator's forward() (teacher_forced.py)
+        loss = m(**{k: v for k, v in batch.items() if not k.startswith("_")})  # the evaluator's forward() (TrainEngine.evaluate)
     assert abs(float(loss) - float(g["loss"])) < 5e-4 * abs(float(g["loss"]))
+    _assert_training_state(eng, kept)
     g = _golden("g10_student_kd_unmasked")
     eng = TrainEngine(_model("student", TINY_SU, TINY_TU))
     rep = eng.forward_backward(batch, teacher_knowledge=_g1_knowledge())
@@ -603,11 +618,12 @@ def test_reduction_factor_2_vs_reference_g21():
     assert abs(float(loss_e) - float(g["loss"])) < 5e-4 * max(1.0, abs(float(g["loss"]))), (float(loss_e), float(g["loss"]))
     model.train()
     loss_t = model(**batch)  # (train form: BatchNorm's running statistics move, so the order matters above)
-    g_before = model.train_engine().gflat.clone()
+    kept = _training_state(model.train_engine())
     model.eval()
     with torch.no_grad():
         model(**batch)
-    assert torch.equal(model.train_engine().gflat, g_before) and loss_t.requires_grad
+    _assert_training_state(model.train_engine(), kept)
+    assert loss_t.requires_grad
 
 
 def test_kd_refuses_other_cell_counts_and_the_native_step_declines_the_options():
@@ -1050,29 +1066,31 @@ def test_one_rank_nccl_group_runs_the_data_parallel_branch_on_one_gpu():
     assert wmax <= 2 * 1e-3 * 3 and wmean < 3e-5, (wmax, wmean)
 
 
-def test_full_size_kd_step_properties():
+def test_full_size_kd_step_properties_vs_oracle():
     """BASELINE-size dims (FCL-taco2-S student, FCL-taco2-T teacher, 8 utterances of 60-100 phonemes) through size-independent properties:
-    (1) the training engine's eval-form forward and the synthesis-path teacher-forced forward() are two independent implementations of the same
-    losses; (2) the analytic gradient predicts the loss change along itself (central finite difference on three parameter tensors);
-    (3) the first Adam step moves every parameter by at most lr (|m/sqrt(v)| <= 1).  (A loss decrease after that step is NOT a property of these
+    (1) the evaluator's forward() (the plug-in class in eval mode) gives the fp64 oracle's losses; (2) the analytic gradient predicts the loss
+    change along itself (central finite difference on three parameter tensors); (3) the first Adam step moves every parameter by at most lr (|m/sqrt(v)| <= 1).  (A loss decrease after that step is NOT a property of these
     closed-form weights: a sign step of 1e-5 on all 6.5 M coordinates raises the loss 17.8 -> 23 here as it does in torch; descent is checked along
     the gradient in (2).)"""
-    from fcl_taco2_amd import hparams as HP, synthetic as SYN, teacher_forced as TF
+    from fcl_taco2_amd import hparams as HP, synthetic as SYN
     from fcl_taco2_amd.converter import CustomConverter
-    from fcl_taco2_amd.training import TrainEngine
 
     S, T = HP.student_hparams(dropout_rate=0.0), HP.teacher_hparams(dropout_rate=0.0)
     xs, ys, ds, f0, en = SYN.training_batch(80, S.idim, batch=8, t_lo=60, t_hi=100, seed=77, zero_frac=0.03, lam=10.0, hi=50)
     batch = CustomConverter(1, True, True)([(xs, ys, None, ds, f0, en)])
     teacher = SYN.build_model("kd_teacher", T, None, DEV).eval()
     student = SYN.build_model("student", S, T, DEV).eval()
+    f64 = lambda t: t.detach().cpu().double() if t.dtype.is_floating_point else t.detach().cpu()
     with torch.no_grad():
         know = teacher(**{k: v for k, v in batch.items()})
-    eng = TrainEngine(student)
-    rep = eng.forward_backward(batch, teacher_knowledge=know)
-    ref, _ = TF.student_forward(student.plan(), batch, know, True, dropout_mode=0)
+        student(teacher_knowledge=know, **batch)
+        ref = O.model_forward({k: f64(v) for k, v in student.state_dict().items()}, S, {k: (f64(v) if torch.is_tensor(v) else v) for k, v in batch.items()},
+                              "student", T, True, (f64(know[0]), f64(know[1])) + tuple([f64(t) for t in grp] for grp in know[2:]), bn_train=False)
     for k in KD_KEYS:
-        assert abs(rep[k] - ref[k]) < 2e-4 * max(1.0, abs(ref[k])), (k, rep[k], ref[k])
+        got = student.reporter.last[k]
+        assert abs(got - float(ref[k])) < 2e-4 * max(1.0, abs(float(ref[k]))), (k, got, float(ref[k]))
+    eng = student.train_engine()
+    rep = eng.forward_backward(batch, teacher_knowledge=know)
     g_all = eng.gflat.clone()
     assert bool(torch.isfinite(g_all).all()) and float(g_all.abs().max()) > 0
     # relative part of the bound per tensor: the linear maps behind no ReLU agree to 1e-4 (measured 7e-5 / 5e-5); along the encoder convolution's gradient

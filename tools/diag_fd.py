@@ -1,5 +1,5 @@
 """Central finite difference of the KD loss along the gradient at several step sizes, repeated (developer aid for the bound in
-tests/test_gpu_training.py::test_full_size_kd_step_properties: the loss carries ~2e-5 of summation-order noise)."""
+tests/test_gpu_training.py::test_full_size_kd_step_properties_vs_oracle: the loss carries ~2e-5 of summation-order noise)."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
