@@ -205,6 +205,94 @@ __global__ void variance_embed_add_kernel(const float* __restrict__ hs, const fl
     }
 }
 
+// ---- prosody control: the two launches above with per-row controls folded in -------------------------------------------------------
+// Controls of padded row i: ctl[(i / row_div) * ld + {0: duration scale, 1: pitch scale, 2: pitch shift, 3: energy scale, 4: energy shift}].
+// Identity values leave the prediction untouched bit for bit (the affine is skipped, not evaluated as fmaf(v, 1, 0)).
+__device__ __forceinline__ const float* ctl_row(const float* ctl, int ld, int row_div, int i) {
+    return ctl + (size_t)(i / row_div) * ld;
+}
+
+__device__ __forceinline__ float ctl_affine(float v, float s, float b) { return (s != 1.f || b != 0.f) ? fmaf(v, s, b) : v; }
+
+__global__ void duration_round_ctl_kernel(const float* __restrict__ x, int64_t* __restrict__ out, int n, int linear_domain, float offset,
+                                          const uint8_t* __restrict__ pad_mask, const float* __restrict__ ctl, int ctl_ld, int ctl_row_div) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v = x[i];
+    if (!linear_domain) v = expf(v) - offset;
+    v = rintf(v);  // round-half-to-even == torch.round
+    v = fmaxf(v, 0.f);
+    if (ctl && v >= 1.f) {  // a predicted 0 stays 0 (and raises downstream); a scaled duration never becomes 0
+        const float a = ctl_row(ctl, ctl_ld, ctl_row_div, i)[0];
+        if (a != 1.f) {
+            const float prod = v * a;  // the fp32 product of LengthRegulator(alpha): round(ds.float() * alpha)
+            v = fmaxf(rintf(prod), 1.f);
+        }
+    }
+    int64_t d = (int64_t)v;
+    if (pad_mask && pad_mask[i]) d = 0;
+    out[i] = d;
+}
+
+// The embed stencil of variance_embed_add_kernel on controlled inputs: every tap applies the control of the row it reads, with the same
+// arithmetic that produces p_out / e_out, so the convolution sees exactly the values written there.
+__global__ void variance_embed_add_ctl_kernel(const float* __restrict__ hs, const float* __restrict__ p, const float* __restrict__ e,
+                                              const float* __restrict__ wp, const float* __restrict__ bp, const float* __restrict__ we,
+                                              const float* __restrict__ be, const int* __restrict__ seg_lo, const int* __restrict__ seg_hi,
+                                              const float* __restrict__ ctl, int ctl_ld, int ctl_row_div, float* __restrict__ out,
+                                              float* __restrict__ p_emb, float* __restrict__ e_emb, float* __restrict__ p_out,
+                                              float* __restrict__ e_out, int m, int c, int k) {
+    const int row = blockIdx.x;
+    if (row >= m) return;
+    const int lo = seg_lo[row], hi = seg_hi[row], pad = (k - 1) / 2;
+    if (threadIdx.x == 0 && (p_out || e_out)) {
+        float pv = p[row], ev = e[row];
+        if (ctl) {
+            const float* cr = ctl_row(ctl, ctl_ld, ctl_row_div, row);
+            pv = ctl_affine(pv, cr[1], cr[2]);
+            ev = ctl_affine(ev, cr[3], cr[4]);
+        }
+        if (p_out) p_out[row] = pv;
+        if (e_out) e_out[row] = ev;
+    }
+    if (!out && !p_emb && !e_emb) return;
+    for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
+        float ap = bp[ch], ae = be[ch];
+        for (int j = 0; j < k; ++j) {
+            const int r = row + j - pad;
+            if (r >= lo && r < hi) {
+                float pv = p[r], ev = e[r];
+                if (ctl) {
+                    const float* cr = ctl_row(ctl, ctl_ld, ctl_row_div, r);
+                    pv = ctl_affine(pv, cr[1], cr[2]);
+                    ev = ctl_affine(ev, cr[3], cr[4]);
+                }
+                ap = fmaf(wp[ch * k + j], pv, ap);
+                ae = fmaf(we[ch * k + j], ev, ae);
+            }
+        }
+        const size_t o = (size_t)row * c + ch;
+        if (p_emb) p_emb[o] = ap;
+        if (e_emb) e_emb[o] = ae;
+        if (out) out[o] = (hs[o] + ap) + ae;  // reference order: (h + p_embs) + e_embs
+    }
+}
+
+// "Predictions only" (no embedding output): the controlled scalars alone, one thread per row.
+__global__ void variance_ctl_rows_kernel(const float* __restrict__ p, const float* __restrict__ e, const float* __restrict__ ctl, int ctl_ld,
+                                         int ctl_row_div, float* __restrict__ p_out, float* __restrict__ e_out, int m) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= m) return;
+    float pv = p[row], ev = e[row];
+    if (ctl) {
+        const float* cr = ctl_row(ctl, ctl_ld, ctl_row_div, row);
+        pv = ctl_affine(pv, cr[1], cr[2]);
+        ev = ctl_affine(ev, cr[3], cr[4]);
+    }
+    if (p_out) p_out[row] = pv;
+    if (e_out) e_out[row] = ev;
+}
+
 // ---- speaker embedding: hs <- cat[hs, F.normalize(spemb)] (..._sa.py:555-557, 636-638) -------------------------------------------------
 // out[row, 0:C] = hs[row, 0:C]; out[row, C:C+S] = spk[b] / max(||spk[b]||_2, 1e-12) with b = row / T (the padded [B, T] row layout).  One wave per
 // row: the norm of its utterance's vector by a wave reduction (S <= a few hundred floats, L2-resident), then C + S contiguous outputs; outp
@@ -560,6 +648,39 @@ int fcl_variance_embed_add_fwd(const float* hs, const float* p, const float* e, 
     hipLaunchKernelGGL(variance_embed_add_kernel, dim3(m), dim3(c >= 256 ? 256 : 64), 0, (hipStream_t)stream, hs, p, e, wp, bp, we, be,
                        seg_lo, seg_hi, out, p_emb, e_emb, m, c, k);
     return check_hip(hipGetLastError(), "variance_embed_add_fwd");
+}
+
+int fcl_duration_round_ctl_fwd(const float* x, int64_t* out, int n, int linear_domain, float offset, const uint8_t* pad_mask, const float* ctl,
+                               int ctl_ld, int ctl_row_div, fcl_stream_t stream) {
+    FCL_REQUIRE(x && out && n >= 0, FCL_ERR_INVALID, "duration_round_ctl_fwd: bad arguments (null pointer or n < 0)");
+    FCL_REQUIRE(!ctl || (ctl_ld >= 5 && ctl_row_div >= 1), FCL_ERR_INVALID, "duration_round_ctl_fwd: ctl_ld < 5 or ctl_row_div < 1");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(duration_round_ctl_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, out, n, linear_domain, offset, pad_mask,
+                       ctl, ctl_ld, ctl_row_div);
+    return check_hip(hipGetLastError(), "duration_round_ctl_fwd");
+}
+
+int fcl_variance_embed_add_ctl_fwd(const float* hs, const float* p, const float* e, const float* wp, const float* bp, const float* we, const float* be,
+                                   const int32_t* seg_lo, const int32_t* seg_hi, const float* ctl, int ctl_ld, int ctl_row_div, float* out, float* p_emb,
+                                   float* e_emb, float* p_out, float* e_out, int m, int c, int k, fcl_stream_t stream) {
+    FCL_REQUIRE(p && e && m >= 0, FCL_ERR_INVALID, "variance_embed_add_ctl_fwd: bad arguments (null p / e or m < 0)");
+    FCL_REQUIRE(!ctl || (ctl_ld >= 5 && ctl_row_div >= 1), FCL_ERR_INVALID, "variance_embed_add_ctl_fwd: ctl_ld < 5 or ctl_row_div < 1");
+    FCL_REQUIRE(out || p_emb || e_emb || p_out || e_out, FCL_ERR_INVALID, "variance_embed_add_ctl_fwd: no output");
+    FCL_REQUIRE((!p_out || p_out != p) && (!e_out || e_out != e), FCL_ERR_INVALID, "variance_embed_add_ctl_fwd: p_out / e_out alias p / e");
+    const bool emb = out || p_emb || e_emb;
+    if (emb) {
+        FCL_REQUIRE(wp && bp && we && be && seg_lo && seg_hi && c > 0 && k > 0 && (k & 1), FCL_ERR_INVALID,
+                    "variance_embed_add_ctl_fwd: bad arguments (null weights / segments, c <= 0 or even k)");
+        FCL_REQUIRE(!out || hs, FCL_ERR_INVALID, "variance_embed_add_ctl_fwd: out needs hs");
+    }
+    if (m == 0) return 0;
+    if (emb)
+        hipLaunchKernelGGL(variance_embed_add_ctl_kernel, dim3(m), dim3(c >= 256 ? 256 : 64), 0, (hipStream_t)stream, hs, p, e, wp, bp, we, be, seg_lo,
+                           seg_hi, ctl, ctl_ld, ctl_row_div, out, p_emb, e_emb, p_out, e_out, m, c, k);
+    else
+        hipLaunchKernelGGL(variance_ctl_rows_kernel, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, e, ctl, ctl_ld, ctl_row_div, p_out,
+                           e_out, m);
+    return check_hip(hipGetLastError(), "variance_embed_add_ctl_fwd");
 }
 
 int fcl_masked_l1_mse_fwd(const float* a, int lda, const float* b, int ldb, const uint8_t* row_valid, int m, int c, int b_log,

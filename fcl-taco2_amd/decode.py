@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from .kaldi_io import ArkScpWriter
+from .prosody import FIELDS as PROSODY_FIELDS, ProsodyControl
 from .sharding import shard_utterances
 
 MODULE_MAP = {
@@ -112,8 +113,9 @@ class _Pool(object):
     """The capacity graphs of one phoneme-length bucket: BatchRunners (predicted durations, created on first use) sharing the bucket's
     capacities; kept on the plan, so later decode() calls on the same model replay the graphs captured by earlier ones."""
 
-    def __init__(self, plan, batch, t_cap, caps, streams, seed):
+    def __init__(self, plan, batch, t_cap, caps, streams, seed, controls=False):
         self.plan, self.batch, self.caps, self.t_cap, self.streams, self.seed = plan, batch, caps, t_cap, streams, seed
+        self.controls = controls  # the runners take prosody controls (BatchRunner(controls=True))
         self.runners, self.slots, self.next, self.grow = [None] * len(streams), [None] * len(streams), 0, None
         self._slab = None
 
@@ -124,7 +126,7 @@ class _Pool(object):
             pools_ = self.plan.__dict__.setdefault("_decode_cache", {}).setdefault("graph_mempools", {})
             mp = pools_.setdefault(self.streams[j].cuda_stream, torch.cuda.graph_pool_handle()) if SHARE_GRAPH_POOLS else None  # one per pass stream (stream-ordered graphs)
             r = self.runners[j] = engine.BatchRunner(self.plan, self.batch, self.t_cap, self.caps, forced=False, stream=self.streams[j], seed=self.seed + 7919 * j,
-                                                     pack_outputs=True, mempool=mp)
+                                                     pack_outputs=True, mempool=mp, controls=self.controls)
             odim = int(r.mel.shape[1])
             w = _Slot.words(self.caps.frames, odim, self.batch)
             if self._slab is None:  # the landing areas of every runner of the bucket: one pinned allocation
@@ -169,7 +171,7 @@ def release_graphs(model_or_plan):
 
 
 @torch.no_grad()
-def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None, keep_graphs=True, max_buckets=None):
+def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None, keep_graphs=True, max_buckets=None, prosody=None):
     """utts: [(utt_id, ids)] or, for a model with spk_embed_dim, [(utt_id, ids, spemb)].  Writes PREFIX.ark/.scp (out_prefix None: nothing is written); returns (frames, seconds).
     Every batch runs as ONE captured graph with predicted durations (engine.BatchRunner): the host packs the phoneme ids, enqueues one
     graph launch (its first node pulls the packed block into HBM) and one D2H copy of the mel buffer + the per-utterance frame starts, and only synchronises on a batch when it
@@ -183,7 +185,10 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
     landing buffers per graph); keep_graphs=False releases all of them when the call returns (release_graphs() does it later).
     An error inside the loop (a zero-duration phoneme raising like the reference, a failing writer) still drains the device, stops the writer
     thread and closes the ark before it propagates.
-    stats (dict, optional): receives `device_seconds` — first submit -> last batch complete on the GPU, excluding the ark writing."""
+    stats (dict, optional): receives `device_seconds` — first submit -> last batch complete on the GPU, excluding the ark writing.
+    prosody: None, one prosody.ProsodyControl for every utterance, or a dict {utt_id: ProsodyControl or {field: value}} (utterances not named:
+    identity).  Controlled runs keep their graphs (BatchRunner(controls=True)) and calibration under keys of their own; the eager
+    calibration batch of a bucket runs with its controls, so the capacities follow the duration scale."""
     from . import engine, ops
 
     torch.manual_seed(seed)
@@ -194,13 +199,23 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
     if has_spk and any(len(u) < 3 for u in utts):
         raise ValueError("fcl-taco2_amd: the model has spk_embed_dim=%d: every utterance needs a speaker embedding" % plan.hp.spk_embed_dim)
     spk_of = (lambda chunk: [u[2] for u in chunk]) if has_spk else (lambda chunk: None)
+    controlled = prosody is not None
+    if isinstance(prosody, dict):  # {utt_id: control}
+        per_utt = {k: ProsodyControl.coerce(v) for k, v in prosody.items()}
+        ctl_of = lambda chunk: [per_utt.get(u[0]) for u in chunk]
+    elif controlled:
+        one = ProsodyControl.coerce(prosody)
+        ctl_of = lambda chunk: [one] * len(chunk)
+    else:
+        ctl_of = lambda chunk: None
+    ckey = ("ctl",) if controlled else ()  # controlled graphs and calibrations never replace the uncontrolled ones
     frames = 0
     depth = max(1, int(depth))
     cache = plan.__dict__.setdefault("_decode_cache", {})
     streams = engine.shared_streams(dev, depth)  # the process's pass streams (one pool per device: see engine.shared_streams)
     import collections
 
-    pools = cache.setdefault(("pools", batch_size, depth), collections.OrderedDict())
+    pools = cache.setdefault(("pools", batch_size, depth) + ckey, collections.OrderedDict())
     max_buckets = max(1, int(MAX_BUCKETS if max_buckets is None else max_buckets))
     pending = []
     n_eager = n_graph = n_redo = n_evict = n_est = 0
@@ -228,7 +243,7 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
 
     def eager(chunk):
         """Host-round-trip pass (calibration / fallback): exact maps of THIS batch."""
-        prep = engine.prepare(plan, [u[1] for u in chunk], spembs=spk_of(chunk))
+        prep = engine.prepare(plan, [u[1] for u in chunk], spembs=spk_of(chunk), prosody=ctl_of(chunk))
         mel, utt_frames, inter = engine.run(plan, prep, ops.DROP_RNG, seed=int(torch.randint(0, 2 ** 31 - 1, (1,)).item()), return_intermediates=True)
         arr = mel.cpu().numpy()
         wq.put((chunk, arr, list(utt_frames), None))
@@ -286,12 +301,12 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
                     g = _grown_caps(engine, pool.grow, batch_size * t_cap, scale=1.6)
                     lmax = max(g.lmax, pool.caps.lmax)
                     caps = engine.Caps(lmax, max(g.frames, pool.caps.frames), np.full(lmax, batch_size * t_cap, np.int32), tail_from=g.tail_from)
-                    pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, caps, streams, seed + 31 * bi)
-                cal = cache.get(("calibration", batch_size))  # (exact maps, phoneme count) of the first eagerly calibrated batch of this model
+                    pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, caps, streams, seed + 31 * bi, controlled)
+                cal = cache.get(("calibration", batch_size) + ckey)  # (exact maps, phoneme count) of the first eagerly calibrated batch of this model
                 if pool is None and cal is not None and ESTIMATE_CAPS:
                     # a later bucket: capacities ESTIMATED from the phoneme count (no eager batch, no host round trip); the batch itself goes through the graph below
                     est = _ScaledMaps(cal[0], cal[1], sum(len(u[1]) for u in chunk))
-                    pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, _grown_caps(engine, est, batch_size * t_cap), streams, seed + 31 * bi)
+                    pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, _grown_caps(engine, est, batch_size * t_cap), streams, seed + 31 * bi, controlled)
                     n_est += 1
                     while len(pools) > max_buckets:
                         old_cap, old_pool = next(iter(pools.items()))
@@ -306,8 +321,8 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
                     got, maps = eager(chunk)
                     frames += got
                     n_eager += 1
-                    cache.setdefault(("calibration", batch_size), (maps, sum(len(u[1]) for u in chunk)))
-                    pools[t_cap] = _Pool(plan, batch_size, t_cap, _grown_caps(engine, maps, batch_size * t_cap), streams, seed + 31 * bi)
+                    cache.setdefault(("calibration", batch_size) + ckey, (maps, sum(len(u[1]) for u in chunk)))
+                    pools[t_cap] = _Pool(plan, batch_size, t_cap, _grown_caps(engine, maps, batch_size * t_cap), streams, seed + 31 * bi, controlled)
                     while len(pools) > max_buckets:  # least recently used bucket out: its batches in flight are harvested first
                         old_cap, old_pool = next(iter(pools.items()))
                         for it in [p_ for p_ in pending if p_[0] is old_pool]:
@@ -328,7 +343,7 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
                 slot.free.wait()  # the writer thread is done with what this landing buffer held
                 slot.free.clear()
                 try:
-                    r.load([u[1] for u in chunk], spembs=spk_of(chunk))
+                    r.load([u[1] for u in chunk], spembs=spk_of(chunk), prosody=ctl_of(chunk))
                 except Exception:
                     slot.free.set()
                     raise
@@ -371,6 +386,51 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
     return frames, secs
 
 
+def add_prosody_arguments(ap):
+    g = ap.add_argument_group("prosody control (edits the predicted durations / pitch / energy; INTEGRATION.md)")
+    g.add_argument("--duration-scale", type=float, default=None, help="speaking-rate factor on the predicted durations, in (0, 8] (2: twice as long)")
+    g.add_argument("--pitch-scale", type=float, default=None, help="scale of the normalised pitch")
+    g.add_argument("--pitch-shift", type=float, default=None, help="shift of the normalised pitch")
+    g.add_argument("--energy-scale", type=float, default=None, help="scale of the normalised energy")
+    g.add_argument("--energy-shift", type=float, default=None, help="shift of the normalised energy")
+    g.add_argument("--semitones", type=float, default=None, help="pitch shift in semitones (needs --f0-en-stats)")
+    g.add_argument("--pitch-range", type=float, default=None, help="pitch-range factor (same as --pitch-scale)")
+    g.add_argument("--energy-gain", type=float, default=None, help="energy gain on the linear energy (needs --f0-en-stats)")
+    g.add_argument("--f0-en-stats", default=None, help="f0_en_stats.npy of preprocessing: [f0_mean, f0_std, en_mean, en_std]")
+    g.add_argument("--prosody-json", default=None, help="per-utterance controls {utt_id: {field: value}} on top of the global ones")
+
+
+def prosody_from_args(args, utt_ids=None):
+    """The decode flags -> None (no control), one ProsodyControl, or {utt_id: ProsodyControl}.  Raises ValueError on inconsistent flags."""
+    raw = {f: getattr(args, f) for f in PROSODY_FIELDS if getattr(args, f) is not None}
+    units = {k: getattr(args, k) for k in ("semitones", "pitch_range", "energy_gain") if getattr(args, k) is not None}
+    if ("semitones" in units or "pitch_range" in units) and ("pitch_scale" in raw or "pitch_shift" in raw):
+        raise ValueError("--semitones / --pitch-range and --pitch-scale / --pitch-shift both set the pitch control: give one of them")
+    if "energy_gain" in units and ("energy_scale" in raw or "energy_shift" in raw):
+        raise ValueError("--energy-gain and --energy-scale / --energy-shift both set the energy control: give one of them")
+    if ("semitones" in units or "energy_gain" in units) and args.f0_en_stats is None:
+        raise ValueError("--semitones / --energy-gain need --f0-en-stats (the pitch / energy statistics of preprocessing)")
+    base = dict(raw)
+    if units:
+        u = ProsodyControl.from_units(stats=args.f0_en_stats, semitones=units.get("semitones", 0.0), pitch_range=units.get("pitch_range", 1.0),
+                                      energy_gain=units.get("energy_gain", 1.0))
+        if "semitones" in units or "pitch_range" in units:
+            base.update(pitch_scale=u.pitch_scale, pitch_shift=u.pitch_shift)
+        if "energy_gain" in units:
+            base.update(energy_scale=u.energy_scale, energy_shift=u.energy_shift)
+    glob = ProsodyControl(**base)  # validates
+    if args.prosody_json is None:
+        return glob if base else None
+    with open(args.prosody_json) as f:
+        per = json.load(f)
+    if not isinstance(per, dict) or not all(isinstance(v, dict) for v in per.values()):
+        raise ValueError("--prosody-json: expected {utt_id: {field: value}}")
+    out = {k: ProsodyControl.coerce(dict(base, **v)) for k, v in per.items()}
+    for k in (utt_ids or ()):
+        out.setdefault(k, glob)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="FCL-taco2 mel synthesis on MI355X (reference-compatible decode driver)")
     ap.add_argument("--model", required=True)
@@ -383,7 +443,12 @@ def main(argv=None):
     ap.add_argument("--job", type=int, default=0, help="this process's shard (0-based)")
     ap.add_argument("--seed", type=int, default=137)
     ap.add_argument("--verbose", type=int, default=1)
+    add_prosody_arguments(ap)
     args = ap.parse_args(argv)
+    try:
+        prosody_from_args(args)  # flag errors before anything is loaded
+    except ValueError as e:
+        ap.error(str(e))
     torch.set_num_threads(4)  # kernels are launched from this thread; a one-thread-per-core intra-op pool spinning beside it slows them
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
     dev = "cuda:%d" % (args.job % max(torch.cuda.device_count(), 1))
@@ -391,7 +456,8 @@ def main(argv=None):
     utts = read_manifest(args.json)
     mine = shard_utterances([len(u[1]) for u in utts], args.nj)[args.job]
     out = args.out if args.nj == 1 else "%s.%d" % (args.out, args.job + 1)
-    frames, secs = decode(model, [utts[i] for i in mine], out, args.batch_size, args.seed)
+    prosody = prosody_from_args(args, [utts[i][0] for i in mine])
+    frames, secs = decode(model, [utts[i] for i in mine], out, args.batch_size, args.seed, prosody=prosody)
     logging.info("average inference speed = %.1f frames / sec. (%d utterances, %d frames)", frames / max(secs, 1e-9), len(mine), frames)
     return frames, secs
 

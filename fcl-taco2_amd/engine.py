@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import prosody as _prosody
 from .hparams import output_act_code
 from .plan import LN_EPS
 
@@ -129,7 +130,7 @@ class PreparedBatch(object):
     """Everything `run` needs, resident in HBM: padded ids, segment bounds, and (forced durations) row maps -- built on the host (`maps`), or
     left to the device (`dur_pad`: the forced durations in the padded [B, T] layout; run() then needs `caps`)."""
     __slots__ = ("B", "T", "lens", "ids", "seg_lo", "seg_hi", "pad", "lens_dev", "f0e", "maps", "src_rows", "dur", "frame_off",
-                 "frame_lo", "frame_hi", "dur_pad", "spk")
+                 "frame_lo", "frame_hi", "dur_pad", "spk", "ctl")
 
 
 class Caps(object):
@@ -224,17 +225,21 @@ def _upload_maps(holder, maps, dev):
         setattr(holder, k, up[o : o + n])
 
 
-def prepare(plan, xs, durs=None, f0=None, energy=None, device_maps=False, spembs=None):
+def prepare(plan, xs, durs=None, f0=None, energy=None, device_maps=False, spembs=None, prosody=None):
     """Input hand-over: pad + upload phoneme ids, build the integer segment bounds, and — when durations are
     forced — the row maps.  This is the host batch layout step (the reference's loader/converter side).  Every integer array of the batch
     travels in ONE packed int32 block (plus the ids and the pad mask) through fixed pinned staging buffers, non-blocking: three copies per
     batch instead of ten pageable ones.  device_maps: forced durations are only uploaded (padded [B, T] int32); the maps are built by
-    ops.row_maps_build inside run(), which then needs `caps`."""
+    ops.row_maps_build inside run(), which then needs `caps`.
+    prosody (prosody.ProsodyControl, a dict, or a list with one per utterance): the [B * T, 5] control block travels with the batch and run()
+    applies it with the ctl kernels; None: no control, the uncontrolled kernels."""
     dev = plan.device
     p = PreparedBatch()
     p.B = len(xs)
     p.lens = [int(len(x)) for x in xs]
     p.T = T = max(p.lens)
+    controls = _prosody.per_utterance(prosody, p.B)
+    _prosody.check_overrides(controls, forced_dur=durs is not None, forced_f0e=f0 is not None)
     ids = np.zeros((p.B, T), dtype=np.int64)
     for b, x in enumerate(xs):
         ids[b, : p.lens[b]] = x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
@@ -268,6 +273,8 @@ def prepare(plan, xs, durs=None, f0=None, energy=None, device_maps=False, spembs
             pe[0, b, : p.lens[b]] = np.asarray(f0[b]).reshape(-1)
             pe[1, b, : p.lens[b]] = np.asarray(energy[b]).reshape(-1)
         items["f0e"] = torch.from_numpy(pe.reshape(2, -1))
+    if controls is not None:
+        items["ctl"] = torch.from_numpy(_prosody.pack(controls, p.lens, T))
     if plan.hp.spk_embed_dim is not None:  # one speaker-embedding vector per utterance (tts.py:285-287, ..._sa.py:636-638)
         if spembs is None:
             raise ValueError("fcl-taco2_amd: the model was built with spk_embed_dim=%d: every utterance needs its speaker embedding" % plan.hp.spk_embed_dim)
@@ -278,7 +285,7 @@ def prepare(plan, xs, durs=None, f0=None, energy=None, device_maps=False, spembs
         raise ValueError("fcl-taco2_amd: speaker embeddings given to a model without spk_embed_dim")
     with torch.cuda.device(dev):
         up = _ring().upload(items, dev)
-    p.ids, p.pad, p.f0e, p.spk = up["ids"], up["pad"], up.get("f0e"), up.get("spk")
+    p.ids, p.pad, p.f0e, p.spk, p.ctl = up["ids"], up["pad"], up.get("f0e"), up.get("spk"), up.get("ctl")
     for k, (o, n) in layout.items():
         setattr(p, k, up["i32"][o : o + n])
     return p
@@ -343,6 +350,7 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
             hs, hs_p = ops.concat_spk(hs, prep.spk, prep.T, want_f32=True, want_planes=planes)
         rm = prep  # holder of the row maps
         frames_info = None
+        ctl = getattr(prep, "ctl", None)  # prosody controls [B * T, 5] (None: the uncontrolled kernels, exactly)
         # the predictors share one geometry in the shipped recipes: one launch per layer for all of them (plan.PredictorGroup) instead of one each
         grouped = planes and prep.f0e is None and _GROUP_PREDICTORS
         m_rows = prep.B * prep.T
@@ -354,7 +362,10 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
                     d_log, p, e = _predictors_grouped(plan.group_dpe, hs_p, prep.seg_lo, prep.seg_hi, prep.pad, m_rows, [True, True, True])
                 else:
                     d_log = predictor(plan.duration, None)
-                d_int = ops.duration_round(d_log, False, 1.0, prep.pad)
+                if ctl is not None:
+                    d_int = ops.duration_round_ctl(d_log, ctl, 1, False, 1.0, prep.pad)
+                else:
+                    d_int = ops.duration_round(d_log, False, 1.0, prep.pad)
                 if inter is not None:
                     inter["d_log"], inter["d_int"] = d_log, d_int
             if caps is not None:  # device-built maps over the padded [B, T] row universe: no host round trip
@@ -377,8 +388,12 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
         elif p is None:
             p = predictor(plan.pitch, prep.pad)
             e = predictor(plan.energy, prep.pad)
-        att, p_emb, e_emb = ops.variance_embed_add(hs, p, e, plan.pitch_embed_w, plan.pitch_embed_b, plan.energy_embed_w,
-                                                   plan.energy_embed_b, prep.seg_lo, prep.seg_hi, want_embs=return_intermediates)
+        if ctl is not None:  # the same launch with the pitch / energy controls folded in; p, e become the controlled values
+            att, p_emb, e_emb, p, e = ops.variance_embed_add_ctl(hs, p, e, plan.pitch_embed_w, plan.pitch_embed_b, plan.energy_embed_w,
+                                                                 plan.energy_embed_b, prep.seg_lo, prep.seg_hi, ctl, 1, want_embs=return_intermediates)
+        else:
+            att, p_emb, e_emb = ops.variance_embed_add(hs, p, e, plan.pitch_embed_w, plan.pitch_embed_b, plan.energy_embed_w,
+                                                       plan.energy_embed_b, prep.seg_lo, prep.seg_hi, want_embs=return_intermediates)
         maps = rm.maps
         att_c, att_c_p = (ops.gather_rows(att, rm.src_rows, want_f32=False, want_planes=True) if planes else (ops.gather_rows(att, rm.src_rows), None))
         keep_dev = None
@@ -417,13 +432,14 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
 
 
 def synthesize(plan, xs, durs=None, f0=None, energy=None, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0,
-               bilstm_algo=0, return_intermediates=False, caps=None, spembs=None):
+               bilstm_algo=0, return_intermediates=False, caps=None, spembs=None, prosody=None):
     """xs: list of 1-D int64 id arrays/tensors; durs: optional list of forced durations (else predicted).
     spembs: list of speaker-embedding vectors [spk_embed_dim], one per utterance (models built with spk_embed_dim).
     f0/energy: optional lists of [T] arrays replacing the predictors (inference(f0=..., energy=...)).
     prenet_keep: optional uint8 [Lmax, 2, N, P] in (utterance, phoneme) row order (FCL_DROP_MASK).
+    prosody: prosody controls (prepare()); they edit the predictions, not forced values.
     Returns a list of mel tensors [L_b, odim] (views into one packed device buffer)."""
-    prep = prepare(plan, xs, durs, f0, energy, device_maps=caps is not None, spembs=spembs)
+    prep = prepare(plan, xs, durs, f0, energy, device_maps=caps is not None, spembs=spembs, prosody=prosody)
     out = run(plan, prep, dropout_mode, prenet_keep, seed, bilstm_algo, return_intermediates, caps=caps)
     import os
 
@@ -437,6 +453,41 @@ def synthesize(plan, xs, durs=None, f0=None, energy=None, dropout_mode=ops.DROP_
         mels.append(after[s : s + n])
         s += n
     return (mels, out[2]) if return_intermediates else mels
+
+
+def predict(plan, xs, prosody=None, spembs=None, bilstm_algo=0):
+    """The model's (controlled) prosody predictions without the decoder: encoder, the three predictors and the two ctl kernels (the embed one
+    in its scalars-only form).  Returns {"duration": [int64 [L_b]], "pitch": [float32 [L_b]], "energy": [float32 [L_b]]} -- the values a
+    synthesize(prosody=...) pass decodes; edit them and feed them back as durs / f0 / energy."""
+    prep = prepare(plan, xs, spembs=spembs, prosody=prosody)
+    with torch.cuda.device(plan.device):
+        planes = use_planes(plan)
+        if planes:
+            hs, hs_p = encode(plan, prep, bilstm_algo, planes=True)
+            predictor = lambda pp, pad: _predictor_scalar_planes(pp, hs_p, prep.seg_lo, prep.seg_hi, pad)
+        else:
+            hs = encode(plan, prep, bilstm_algo)
+            predictor = lambda pp, pad: _predictor_scalar(pp, hs, prep.seg_lo, prep.seg_hi, pad)
+        if plan.hp.spk_embed_dim is not None:
+            hs, hs_p = ops.concat_spk(hs, prep.spk, prep.T, want_f32=True, want_planes=planes)
+        grouped = planes and _GROUP_PREDICTORS  # the predictor forms run() selects for a pass without forced values
+        m_rows = prep.B * prep.T
+        p = e = None
+        if grouped and plan.group_dpe is not None:
+            d_log, p, e = _predictors_grouped(plan.group_dpe, hs_p, prep.seg_lo, prep.seg_hi, prep.pad, m_rows, [True, True, True])
+        else:
+            d_log = predictor(plan.duration, None)
+        if p is None and grouped and plan.group_pe is not None:
+            p, e = _predictors_grouped(plan.group_pe, hs_p, prep.seg_lo, prep.seg_hi, prep.pad, m_rows, [True, True])
+        elif p is None:
+            p = predictor(plan.pitch, prep.pad)
+            e = predictor(plan.energy, prep.pad)
+        d_int = ops.duration_round_ctl(d_log, prep.ctl, 1, False, 1.0, prep.pad)
+        _, _, _, p, e = ops.variance_embed_add_ctl(None, p, e, None, None, None, None, None, None, prep.ctl, 1, want_out=False)
+        d_h = d_int.view(prep.B, prep.T).cpu().numpy()
+        p_h, e_h = p.view(prep.B, prep.T).cpu().numpy(), e.view(prep.B, prep.T).cpu().numpy()
+    return {"duration": [d_h[b, :L].copy() for b, L in enumerate(prep.lens)], "pitch": [p_h[b, :L].copy() for b, L in enumerate(prep.lens)],
+            "energy": [e_h[b, :L].copy() for b, L in enumerate(prep.lens)]}
 
 
 _SHARED_STREAMS = {}
@@ -544,13 +595,17 @@ class BatchRunner(object):
     back (`frames()`): capacities are verified on the device (FCL_STATUS_*), a batch that does not fit is reported, never silently truncated.
     forced=True: the graph takes uploaded durations (load(xs, durs)); forced=False: it contains the duration predictor + rounding."""
 
-    def __init__(self, plan, batch, t_cap, caps, forced=True, stream=None, dropout_mode=ops.DROP_RNG, seed=0, depth=3, pack_outputs=False, mempool=None):
+    def __init__(self, plan, batch, t_cap, caps, forced=True, stream=None, dropout_mode=ops.DROP_RNG, seed=0, depth=3, pack_outputs=False, mempool=None,
+                 controls=False):
         """pack_outputs (round 6, the decode driver): the graph also gathers its three results -- mel [frames cap, odim], frame starts [B + 1], status word --
         into ONE float32 buffer `self.out` (two tiny copies and a ~5 us device copy inside the graph), so that a batch costs the host one device-to-host copy call
         instead of three (the driver's loop is bound by its enqueue time: 3 x ~70 us of copy calls out of ~470 us per batch).
         mempool: a torch graph-pool handle shared by the graphs that replay on THIS stream only (stream order keeps two of them from running at once): later
-        captures reuse the intermediates' memory of earlier ones instead of allocating theirs (a first decode() call: ~500 allocations -> ~150)."""
+        captures reuse the intermediates' memory of earlier ones instead of allocating theirs (a first decode() call: ~500 allocations -> ~150).
+        controls: the block also carries a [batch * t_cap, 5] prosody-control segment (load(prosody=...), identity by default) that the graph's ctl
+        kernels read, so one capture serves any control values; False: the block and the graph are those of an uncontrolled pass."""
         dev = plan.device
+        self.controls = bool(controls)
         self.plan, self.B, self.T, self.caps, self.forced = plan, int(batch), int(t_cap), caps, bool(forced)
         self.S = int(plan.hp.spk_embed_dim or 0)  # speaker-embedding width: one vector per utterance rides in the same block
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
@@ -559,7 +614,7 @@ class BatchRunner(object):
         self._off = {}
         off = 0
         for name, nbytes in (("ids", 8 * n), ("seg_lo", 4 * n), ("seg_hi", 4 * n), ("dur", 4 * n), ("lens", 4 * ((self.B + 3) // 4 * 4)), ("pad", n),
-                             ("spk", 4 * self.B * self.S)):
+                             ("spk", 4 * self.B * self.S), ("ctl", 4 * n * _prosody.NCTL if self.controls else 0)):
             self._off[name] = (off, nbytes)
             off += (nbytes + 15) // 16 * 16
         self._nbytes = off
@@ -585,6 +640,7 @@ class BatchRunner(object):
             p.dur_pad = view("dur", torch.int32) if self.forced else None
             p.f0e, p.maps = None, None
             p.spk = view("spk", torch.float32).view(self.B, self.S) if self.S else None
+            p.ctl = view("ctl", torch.float32).view(n, _prosody.NCTL) if self.controls else None
             self.prep = p
             self.seed_word = torch.zeros(1, dtype=torch.int32, device=dev)
             self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # this runner's own status word (violations are attributed to ITS batches)
@@ -598,7 +654,8 @@ class BatchRunner(object):
             # the eager warm-up pass does the library's lazy one-time setup (per-kernel dynamic-LDS opt-ins, which a capture must not contain) for
             # the kernel forms THIS geometry selects: once per (plan, geometry) -- the other runners of a bucket (the decode driver keeps one per
             # stream) capture straight away (round 5: 16 warm-ups of a first decode() call -> 4)
-            warm_key = (self.B, self.T, caps.lmax, caps.frames, caps.bounds.tobytes(), caps.tail_from, self.forced, int(dropout_mode), self.S)
+            warm_key = (self.B, self.T, caps.lmax, caps.frames, caps.bounds.tobytes(), caps.tail_from, self.forced, int(dropout_mode), self.S,
+                        self.controls)
             warmed = plan.__dict__.setdefault("_runner_warm", set())
             if warm_key not in warmed:
                 with torch.cuda.stream(self.stream):
@@ -644,11 +701,16 @@ class BatchRunner(object):
                 raise ops._lib.FclError("fcl-taco2_amd: BatchRunner: the feed node of launch %d never ran (sequence word %d; device hung?)"
                                         % (self._launched, int(self._seq_np[0])))
 
-    def load(self, xs, durs=None, spembs=None):
+    def load(self, xs, durs=None, spembs=None, prosody=None):
         """Hand one batch to the graph's input block: host packing into the pinned block the graph's first node reads (FCL_FEED_INGRAPH=0: + ONE
         non-blocking copy on this runner's stream, ordered before the next replay).
-        spembs: one speaker-embedding vector per utterance (models built with spk_embed_dim)."""
+        spembs: one speaker-embedding vector per utterance (models built with spk_embed_dim).
+        prosody (runners built with controls=True): one control for the batch or one per utterance (prosody.per_utterance); None: identity."""
         nb = len(xs)
+        if prosody is not None and not self.controls:
+            raise ValueError("BatchRunner: prosody controls need a runner built with controls=True")
+        controls = _prosody.per_utterance(prosody, nb)
+        _prosody.check_overrides(controls, forced_dur=self.forced)
         if (spembs is not None) != bool(self.S):
             raise ValueError("BatchRunner: speaker embeddings %s" % ("missing (the model has spk_embed_dim=%d)" % self.S if self.S else "given to a model without spk_embed_dim"))
         if nb > self.B or nb == 0:
@@ -673,6 +735,7 @@ class BatchRunner(object):
             spk_rows = [as_np(v).reshape(-1) for v in spembs]
             if len(spk_rows) != nb or any(v.shape[0] != self.S for v in spk_rows):
                 raise ValueError("BatchRunner: speaker embeddings must be %d vectors of %d values" % (nb, self.S))
+        ctl_rows = _prosody.pack(controls, ln, T) if controls is not None else None  # [nb * T, 5]
         j = self._slot % len(self._host)
         self._slot += 1
         if self._ingraph:
@@ -697,6 +760,11 @@ class BatchRunner(object):
             sp[nb:] = 0.0
             for i_, v in enumerate(spk_rows):
                 sp[i_] = v
+        if self.controls:
+            ctl = seg("ctl", np.float32).reshape(n, _prosody.NCTL)
+            ctl[:] = _prosody.IDENTITY
+            if ctl_rows is not None:
+                ctl[: nb * T] = ctl_rows
         seg("seg_lo", np.int32)[:] = base
         np.add(base, lfull, out=seg("seg_hi", np.int32))
         np.logical_not(valid, out=seg("pad", np.uint8).view(np.bool_))

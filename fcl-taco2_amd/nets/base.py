@@ -11,9 +11,22 @@ import argparse
 import torch
 
 from .. import engine, ops
+from .. import prosody as _prosody
 from ..hparams import HParams, param_spec
 from ..plan import SynthesisPlan
 from ..tts_interface import TTSInterface
+
+
+def prosody_from_args(args):
+    """The prosody control named by `duration_scale` / `pitch_scale` / `pitch_shift` / `energy_scale` / `energy_shift` attributes of an inference
+    args namespace (absent ones: identity); None when there are none or they are all the identity."""
+    if args is None:
+        return None
+    vals = {f: getattr(args, f) for f in _prosody.FIELDS if getattr(args, f, None) is not None}
+    if not vals:
+        return None
+    c = _prosody.ProsodyControl(**vals)
+    return None if c.is_identity else c
 
 
 def strtobool(x):
@@ -286,24 +299,37 @@ class Tacotron2Base(TTSInterface, torch.nn.Module):
 
     # ---- the reference's inference(): one utterance -----------------------------------------------
     @torch.no_grad()
-    def inference(self, x, inference_args=None, spemb=None, dur=None, f0=None, energy=None, utt_id=None, y=None, *args, **kwargs):
+    def inference(self, x, inference_args=None, spemb=None, dur=None, f0=None, energy=None, utt_id=None, y=None, *args, prosody=None, **kwargs):
         """x: LongTensor (T,) -> Tensor (L, odim), as ..._kd_student.py:804-863 / ..._sa.py:624-683.
         Prenet dropout stays ON (decoder_sa.py:156-158); masks come from the on-device generator, seeded from
-        torch's default generator so `torch.manual_seed` makes a run repeatable."""
+        torch's default generator so `torch.manual_seed` makes a run repeatable.
+        prosody (prosody.ProsodyControl or a dict): edits the predicted durations / pitch / energy; without it, `duration_scale`, `pitch_scale`,
+        `pitch_shift`, `energy_scale` / `energy_shift` attributes of inference_args do (the reference's tts_decode passes its args namespace)."""
+        if prosody is None:
+            prosody = prosody_from_args(inference_args)
         mels = self.inference_batch([x], None if dur is None else [dur], None if f0 is None else [f0],
-                                    None if energy is None else [energy], spembs=None if spemb is None else [spemb])
+                                    None if energy is None else [energy], spembs=None if spemb is None else [spemb], prosody=prosody)
         return mels[0]
 
     @torch.no_grad()
-    def inference_batch(self, xs, durs=None, f0s=None, energies=None, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=None, spembs=None):
-        """Build extension: equals len(xs) independent inference() calls, in one pass."""
+    def inference_batch(self, xs, durs=None, f0s=None, energies=None, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=None, spembs=None, prosody=None):
+        """Build extension: equals len(xs) independent inference() calls, in one pass.
+        prosody: one control for every utterance or one per utterance (prosody.per_utterance)."""
         plan = self.plan(xs[0].device if torch.is_tensor(xs[0]) and xs[0].is_cuda else None)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         cpu = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else a
         return engine.synthesize(plan, [cpu(x) for x in xs], None if durs is None else [cpu(d).reshape(-1) for d in durs],
                                  None if f0s is None else [cpu(f) for f in f0s], None if energies is None else [cpu(e) for e in energies],
-                                 dropout_mode=dropout_mode, prenet_keep=prenet_keep, seed=seed, spembs=spembs)
+                                 dropout_mode=dropout_mode, prenet_keep=prenet_keep, seed=seed, spembs=spembs, prosody=prosody)
+
+    @torch.no_grad()
+    def predict_prosody(self, xs, prosody=None, spembs=None):
+        """The (controlled) predictions a synthesis pass would decode, without the decoder: {"duration", "pitch", "energy"}, one array per
+        utterance.  Edit them and pass them back: inference(x, dur=..., f0=..., energy=...)."""
+        plan = self.plan(xs[0].device if torch.is_tensor(xs[0]) and xs[0].is_cuda else None)
+        cpu = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        return engine.predict(plan, [cpu(x) for x in xs], prosody=prosody, spembs=spembs)
 
     def forward(self, xs, ilens, ys, olens, spembs=None, extras=None, new_ys=None, non_zero_lens_mask=None, ds_nonzeros=None,
                 output_masks=None, position=None, f0=None, energy=None, teacher_knowledge=None, *args, **kwargs):

@@ -239,6 +239,41 @@ def variance_embed_add(hs, p, e, wp, bp, we, be, seg_lo, seg_hi, want_embs=False
     return out, pe, ee
 
 
+def _ctl_args(ctl, row_div):
+    """ctl: float32 [rows, ld >= 5] device tensor of prosody controls (prosody.pack), or None."""
+    if ctl is None:
+        return None, 0, 1
+    return _p(ctl), int(ctl.shape[-1]), int(row_div)
+
+
+def duration_round_ctl(x, ctl=None, ctl_row_div=1, linear_domain=False, offset=1.0, pad_mask=None):
+    """fcl_duration_round_ctl_fwd: duration_round with the duration scale of `ctl` applied (prosody.duration_rule)."""
+    out = torch.empty(x.numel(), device=x.device, dtype=torch.int64)
+    cp, ld, div = _ctl_args(ctl, ctl_row_div)
+    check(_lib.load().fcl_duration_round_ctl_fwd(_p(x), _p(out, torch.int64), x.numel(), int(linear_domain), offset, _p(pad_mask, torch.uint8),
+                                                 cp, ld, div, _stream()))
+    return out
+
+
+def variance_embed_add_ctl(hs, p, e, wp, bp, we, be, seg_lo, seg_hi, ctl=None, ctl_row_div=1, want_out=True, want_embs=False):
+    """fcl_variance_embed_add_ctl_fwd: variance_embed_add on the controlled pitch / energy.  Returns (out or None, p_emb or None, e_emb or None,
+    p_out, e_out); want_out=False and want_embs=False: only the controlled scalars (no weights read; hs, wp ... may be None)."""
+    m = p.numel()
+    emb = want_out or want_embs
+    c = hs.shape[1] if emb else 0
+    k = wp.shape[-1] if emb else 1
+    out = torch.empty_like(hs) if want_out else None
+    pe = torch.empty_like(hs) if want_embs else None
+    ee = torch.empty_like(hs) if want_embs else None
+    p_out, e_out = torch.empty_like(p), torch.empty_like(e)
+    cp, ld, div = _ctl_args(ctl, ctl_row_div)
+    check(_lib.load().fcl_variance_embed_add_ctl_fwd(_p(hs) if want_out else None, _p(p), _p(e), _p(wp) if emb else None, _p(bp) if emb else None,
+                                                     _p(we) if emb else None, _p(be) if emb else None, _p(seg_lo, torch.int32) if emb else None,
+                                                     _p(seg_hi, torch.int32) if emb else None, cp, ld, div, _p(out), _p(pe), _p(ee), _p(p_out),
+                                                     _p(e_out), m, c, k, _stream()))
+    return out, pe, ee, p_out, e_out
+
+
 def position_table(dur_i32, lmax):
     n = dur_i32.numel()
     pos = torch.empty(n, lmax, device=dur_i32.device, dtype=torch.float32)

@@ -55,7 +55,7 @@ enum { FCL_GEMM_F32 = 0, FCL_GEMM_BF16 = 1 };
 const char* fcl_last_error(void);
 /* ABI revision of this header: bumped whenever a struct layout or a signature changes (100 = round 1; 200 = round 2: fcl_gemm_term_t.a_chunk_stride,
  * fcl_pwg_layer_t, the round-2 entry points).  A binding compares it with fcl_version() of the library it loaded before passing any struct. */
-#define FCL_ABI_VERSION 422
+#define FCL_ABI_VERSION 423
 int fcl_version(void);
 void* fcl_debug_ptr(void); /* developer aid: device buffer of the last instrumented launch (FCL_PWG_TS), NULL otherwise */
 int fcl_set_gemm_mode(int mode);
@@ -184,6 +184,21 @@ int fcl_duration_round_fwd(const float* x, int64_t* out, int n, int linear_domai
 int fcl_variance_embed_add_fwd(const float* hs, const float* p, const float* e, const float* wp, const float* bp,
                                const float* we, const float* be, const int32_t* seg_lo, const int32_t* seg_hi,
                                float* out, float* p_emb, float* e_emb, int m, int c, int k, fcl_stream_t stream);
+
+/* ---- prosody control: the two entries above with per-row controls (speaking rate, pitch, energy) applied to the predictions ------------
+ * The controls of padded row i are the five floats at ctl + (i / ctl_row_div) * ctl_ld:
+ *   [0] duration scale a, [1] pitch scale, [2] pitch shift, [3] energy scale, [4] energy shift;  identity (1, 1, 0, 1, 0).
+ * ctl_row_div = t_max: one control per utterance of the padded [B, t_max] layout; 1: one per row.  ctl == NULL: exactly the entries above.
+ * Duration: d = max(rint(linear_domain ? x : exp(x) - offset), 0); if a != 1 and d >= 1: d = max(rint((float)d * a), 1) (a scaled duration is
+ * never 0; a predicted 0 stays 0); then the pad mask.  ctl_ld >= 5 and ctl_row_div >= 1 when ctl != NULL. */
+int fcl_duration_round_ctl_fwd(const float* x, int64_t* out, int n, int linear_domain, float offset, const uint8_t* pad_mask, const float* ctl,
+                               int ctl_ld, int ctl_row_div, fcl_stream_t stream);
+/* Pitch / energy: p' = fmaf(p, pitch scale, pitch shift) where (scale, shift) != (1, 0), else p unchanged (e likewise).  p_out / e_out
+ * (optional, must not alias p / e) receive p' / e'; the embed stencil reads the same p' / e'.  out, p_emb, e_emb may all be NULL (no weights or
+ * segments are read then): a launch that only writes the controlled scalars. */
+int fcl_variance_embed_add_ctl_fwd(const float* hs, const float* p, const float* e, const float* wp, const float* bp, const float* we,
+                                   const float* be, const int32_t* seg_lo, const int32_t* seg_hi, const float* ctl, int ctl_ld, int ctl_row_div,
+                                   float* out, float* p_emb, float* e_emb, float* p_out, float* e_out, int m, int c, int k, fcl_stream_t stream);
 
 /* ---- speaker embedding (..._sa.py:555-557 forward, :636-638 inference; `--spk-embed-dim`): out [M, C + S] = cat[hs, F.normalize(spemb)] over the
  *      padded [B, T] row layout (row m belongs to utterance m / t; spk [B, S]; F.normalize: x / max(||x||_2, 1e-12)).  out_p (optional, (C + S) % 32
