@@ -775,10 +775,6 @@ namespace fcl {
 
 // both directions of the training forward / reverse pass in one launch each; false = H unsupported (the caller falls back to per-step launches)
 // H = 256: groups of 4 workgroups.  ws: [2B] flags + 1 error word (zeroed here) followed by the exchange buffer.
-static bool bilstm_ksplit_enabled() {
-    static const int on = tunable("BILSTM_KSPLIT", 1);
-    return on != 0;
-}
 
 // Builds WITH packed-FP32 instructions (-DFCL_KS_EXCLUSIVE, `make NOPK=`) keep the round-5 guard, and verify it: before the first launch of a
 // lane-split kernel the runtime is asked what the loaded code object really requests (hipFuncGetAttributes: numRegs, in the hardware's 8-register granules 249 .. 256 all
@@ -832,8 +828,7 @@ bool launch_bilstm_group(const float* gx_f, const float* gx_r, const float* whh_
                          const BilstmSave* sv, void* ws, size_t ws_bytes, unsigned int* status, hipStream_t s) {
     if (!group_ok(B, H, ws, ws_bytes, status)) return false;
     unsigned int* flags = (unsigned int*)ws;
-    static const int ll_on = tunable("BILSTM_GROUP_LL", 1);
-    const bool ll = ll_on && T < 65535 &&  // 16-bit step tags
+    const bool ll = T < 65535 &&  // 16-bit step tags
                     (sv ? ks_claims_simd(bilstm_group_ks_kernel<true>, "bilstm_group_ks_kernel<true>") : ks_claims_simd(bilstm_group_ks_kernel<false>, "bilstm_group_ks_kernel<false>"));
     char* xb = group_exchange_base(ws, B);
     if (hipMemsetAsync(flags, 0, (size_t)(xb - (char*)ws) + (ll ? sizeof(unsigned long long) * 2 * (size_t)B * 2 * H : 0), s) != hipSuccess) return false;
@@ -855,8 +850,7 @@ bool launch_bilstm_group(const float* gx_f, const float* gx_r, const float* whh_
 bool launch_bilstm_bptt_group(const BilstmBwd& a, const int* lens, int B, int T, int H, void* ws, size_t ws_bytes, unsigned int* status, hipStream_t s) {
     if (!group_ok(B, H, ws, ws_bytes, status)) return false;
     unsigned int* flags = (unsigned int*)ws;
-    static const int ll_on = tunable("BILSTM_GROUP_LL", 1);
-    const bool ll = ll_on && T < 65535 && ks_claims_simd(bilstm_bptt_group_ks_kernel, "bilstm_bptt_group_ks_kernel");  // 16-bit step tags
+    const bool ll = T < 65535 && ks_claims_simd(bilstm_bptt_group_ks_kernel, "bilstm_bptt_group_ks_kernel");  // 16-bit step tags
     char* xb = group_exchange_base(ws, B);
     if (hipMemsetAsync(flags, 0, (size_t)(xb - (char*)ws) + (ll ? sizeof(unsigned long long) * 2 * (size_t)B * 2 * 4 * H : 0), s) != hipSuccess) return false;
     GroupSync gs{flags + 256, status};
@@ -875,7 +869,7 @@ bool launch_bilstm_train_persistent(const float* gx_f, const float* gx_r, const 
                                     int H, const BilstmSave& sv, hipStream_t s) {
     dim3 grid(B, 2);
     if (H != 8 && H != 16 && H != 32 && H != 64 && H != 128) return false;
-    if (H == 128 && bilstm_ksplit_enabled() && ks_claims_simd(bilstm_ksplit_kernel<true, false>, "bilstm_ksplit_kernel<true, false>")) {
+    if (H == 128 && ks_claims_simd(bilstm_ksplit_kernel<true, false>, "bilstm_ksplit_kernel<true, false>")) {
         ProfScope ps("bilstm_ksplit_kernel/train", 2.0 * 2 * B * (double)T * 4 * H * H, (double)B * T, s);
         hipLaunchKernelGGL((bilstm_ksplit_kernel<true, false>), grid, dim3(512), 0, s, gx_f, gx_r, whh_f, whh_r, lens, out, T, sv, (unsigned short*)nullptr,
                            fcl_row_maps_t());
@@ -898,7 +892,7 @@ bool launch_bilstm_train_persistent(const float* gx_f, const float* gx_r, const 
 bool launch_bilstm_bptt_persistent(const BilstmBwd& a, const int* lens, int B, int T, int H, hipStream_t s) {
     dim3 grid(B, 2);
     if (H != 8 && H != 16 && H != 32 && H != 64 && H != 128) return false;
-    if (H == 128 && bilstm_ksplit_enabled() && ks_claims_simd(bilstm_bptt_ksplit_kernel<0>, "bilstm_bptt_ksplit_kernel<0>")) {
+    if (H == 128 && ks_claims_simd(bilstm_bptt_ksplit_kernel<0>, "bilstm_bptt_ksplit_kernel<0>")) {
         ProfScope ps("bilstm_bptt_ksplit_kernel", 2.0 * 2 * B * (double)T * 4 * H * H, (double)B * T, s);
         hipLaunchKernelGGL((bilstm_bptt_ksplit_kernel<0>), grid, dim3(512), 0, s, a, lens, T);
         return true;
@@ -974,7 +968,6 @@ int fcl_bilstm_fwd(const float* x, const int32_t* lens, const float* w_ih_f, con
     // several synthesis passes are in flight on other streams (3.52 vs 3.85 M frames/s) — so algo 0 keeps the per-step launches there.
     static const int group_infer = tunable("BILSTM_GROUP_INFER", 0);
     FCL_REQUIRE(algo != 3 || status, FCL_ERR_INVALID, "bilstm_fwd: algo 3 (cooperating workgroups) needs a device status word");
-    static const int fuse_on = tunable("ROWMAPS_FUSE", 1);
     struct MapsAfter {  // the non-fused paths below return from several places
         const fcl_row_maps_t* m;
         fcl_stream_t st;
@@ -990,8 +983,8 @@ int fcl_bilstm_fwd(const float* x, const int32_t* lens, const float* w_ih_f, con
     }
     if (algo == 0 || algo == 3) algo = can_persist ? 2 : 1;
     FCL_REQUIRE(algo == 1 || (algo == 2 && can_persist), FCL_ERR_INVALID, "bilstm_fwd: algo %d unavailable for H=%d", algo, h);
-    const bool fuse_wanted = row_maps && maps_fusable && fuse_on;
-    if (algo == 2 && h == 128 && bilstm_ksplit_enabled() &&
+    const bool fuse_wanted = row_maps && maps_fusable;
+    if (algo == 2 && h == 128 &&
         (fuse_wanted ? ks_claims_simd(bilstm_ksplit_kernel<false, true>, "bilstm_ksplit_kernel<false, true>")
                      : ks_claims_simd(bilstm_ksplit_kernel<false, false>, "bilstm_ksplit_kernel<false, false>"))) {
         const bool fuse = fuse_wanted;
@@ -1005,7 +998,7 @@ int fcl_bilstm_fwd(const float* x, const int32_t* lens, const float* w_ih_f, con
         const int rc = check_hip(hipGetLastError(), "bilstm k-split launch");
         return fuse ? rc : after.finish(rc);
     }
-    if (algo == 2 && h == 128 && row_maps && maps_fusable && fuse_on) {
+    if (algo == 2 && h == 128 && fuse_wanted) {
         ProfScope ps("bilstm_persistent_kernel+maps", 2.0 * 2 * b * (double)t * 4 * h * h, (double)b * t, s);
         hipLaunchKernelGGL((bilstm_persistent_kernel<128, false, true>), dim3(b + 1, 2), dim3(512), 0, s, gx_f, gx_r, w_hh_f, w_hh_r, lens, out, t, BilstmSave(),
                            out_p, *row_maps);
@@ -1054,8 +1047,7 @@ int fcl_bilstm_fwd(const float* x, const int32_t* lens, const float* w_ih_f, con
     };
     // the two directions are independent recurrences: while a step is small enough for the wave-per-gate kernel both go out in ONE launch per time
     // step (T dependent launches instead of 2T)
-    static const int pair = tunable("BILSTM_PAIR", 1);
-    if (pair && lstm_step_is_small(b, h)) {
+    if (lstm_step_is_small(b, h)) {
         int cur = 0;
         for (int st = 0; st < t; ++st) {
             int rc = launch_lstm_small_pair(step_args(0, st, cur), step_args(1, st, cur), s);

@@ -323,8 +323,8 @@ int fcl_conv1d_planes_group_fwd(const uint16_t* xp, int ldxp, int64_t x_group_st
     FCL_REQUIRE(k >= 3 && (k & 1) && k <= FCL_MAX_TERMS, FCL_ERR_SHAPE, "conv1d_planes_group_fwd: kernel size %d must be odd, 3 .. %d", k, FCL_MAX_TERMS);
     FCL_REQUIRE(act >= FCL_ACT_NONE && act <= FCL_ACT_TANH, FCL_ERR_INVALID, "conv1d_planes_group_fwd: bad act %d", act);
     FCL_REQUIRE(ldxp * 32 >= cin && cin <= 384 && !(cout & 31), FCL_ERR_SHAPE, "conv1d_planes_group_fwd: needs Cin <= 384 (the stencil kernel) and Cout %% 32 == 0");
-    FCL_REQUIRE(tunable("PRECISION", 1) != 0 && tunable("PLANES", 1) != 0 && tunable("PCONV", 1) != 0, FCL_ERR_INVALID,
-                "conv1d_planes_group_fwd: the pre-split stencil path is off (FCL_PRECISION / FCL_PLANES / FCL_PCONV)");
+    FCL_REQUIRE(tunable("PRECISION", 1) != 0 && tunable("PLANES", 1) != 0, FCL_ERR_INVALID,
+                "conv1d_planes_group_fwd: the pre-split stencil path is off (FCL_PRECISION / FCL_PLANES)");
     const int ldw = (cin + 31) / 32;
     GemmArgs g = {};
     for (int j = 0; j < k; ++j) {
@@ -582,9 +582,6 @@ int fcl_decoder_loop_fwd(const fcl_decoder_weights_t* w, const fcl_decoder_io_t*
     const bool tile_ok = planes && w->stream && decoder_tile_shape_ok(w) && io->lmax <= 64 && !io->teacher_ys && !io->tap_prenet && !io->tap_lstm0 && !io->tap_lstm1 &&
                          drop_mode != FCL_DROP_MASK && gemm_mode() != FCL_GEMM_BF16;
     const int tail_from = (tile_ok && io->tail_from > 0 && io->tail_from < io->lmax) ? io->tail_from : 0;
-    static const int fused = tunable("FUSED_PRENET", 1);
-    FCL_REQUIRE(fused || !io->live_rows, FCL_ERR_INVALID, "decoder_loop_fwd: device live_rows need the fused feat/prenet kernel (FCL_FUSED_PRENET=1)");
-    FCL_REQUIRE(fused || !tail_from, FCL_ERR_INVALID, "decoder_loop_fwd: tail_from needs the fused feat/prenet kernel (FCL_FUSED_PRENET=1)");
     int cur = 0;
     for (int t = 0; t <= io->lmax; ++t) {
         const bool hand_over = tail_from > 0 && t == tail_from;      // this step and all later ones: the tile kernel (after feat_out(t - 1) of every row live at t - 1)
@@ -594,53 +591,25 @@ int fcl_decoder_loop_fwd(const fcl_decoder_weights_t* w, const fcl_decoder_io_t*
         const uint8_t* keep1 = drop_mode == FCL_DROP_MASK && t < io->lmax ? io->prenet_keep + ((size_t)(t * 2 + 1) * N) * P : nullptr;
         const unsigned seed0 = io->seed * 2654435761u + (unsigned)(t * 2 + 0), seed1 = seed0 + 1;
         const float* teacher_in = (io->teacher_ys && t > 0) ? io->teacher_ys + (size_t)(t - 1) * O : nullptr;
-        int rc;
-        if (fused) {
-            // H8 feat_out(t-1) [+ H10 scatter] -> H6 prenet(t), one launch
-            FeatPrenetArgs fp = {};
-            fp.M_feat = n_prev; fp.M_pre = n; fp.U = U; fp.O = O; fp.P = P;
-            fp.h1 = t > 0 ? ws.h1[cur] : nullptr; fp.wf_h = w->wf_h; fp.F0 = ws.F0;
-            fp.before = io->before; fp.frame_off = io->frame_off; fp.t_prev = t - 1; fp.t_cur = t;
-            fp.teacher_in = teacher_in; fp.teacher_ld = io->lmax * O;
-            if (t < io->lmax && !hand_over) { fp.w0 = w->prenet_w0; fp.b0 = w->prenet_b0; fp.w1 = w->prenet_w1; fp.b1 = w->prenet_b1; }
-            fp.wf_hi = w->wf_h_hi; fp.wf_lo = w->wf_h_lo; fp.w0_hi = w->prenet_w0_hi; fp.w0_lo = w->prenet_w0_lo;
-            fp.w1_hi = w->prenet_w1_hi; fp.w1_lo = w->prenet_w1_lo;
-            fp.wf_ff = w->wf_h_ff; fp.w0_ff = w->prenet_w0_ff; fp.w1_ff = w->prenet_w1_ff;
-            fp.drop_mode = drop_mode; fp.keep0 = keep0; fp.keep1 = keep1; fp.keep_scale = keep_scale; fp.drop_p = w->prenet_dropout;
-            fp.seed0 = seed0; fp.seed1 = seed1; fp.seed_dev = io->seed_dev; fp.pre_out = ws.pre_b; fp.tap_prenet = io->tap_prenet;
-            fp.live = io->live_rows; fp.status = io->status; fp.out_act = w->out_act;
-            if (planes) {
-                fp.before_p = io->before_p;
-                if (!small_step(n)) { fp.pre_out_p = ws.pre_p; fp.pre_out = nullptr; }  // the big-tile LSTM step reads planes only
-            }
-            rc = launch_feat_prenet(fp, s);
-            if (rc) return rc;
-        } else {
-            if (t > 0) {  // H8 feat_out(t-1) (+ H10 scatter): out = h1 . Wf_h^T + F0
-                GemmArgs f = {};
-                f.term[0] = GemmTerm{ws.h1[cur], w->wf_h, U, U, U, 0};
-                f.nterms = 1; f.M = n_prev; f.N = O; f.C0 = ws.F0; f.ldc0 = O; f.Y = ws.prev; f.ldy = O;
-                f.Y2 = io->before; f.ldy2 = O; f.y2_row_base = io->frame_off; f.y2_row_add = t - 1;
-                rc = launch_gemm(f, s);
-                if (rc) return rc;
-            }
-            if (t < io->lmax) {  // H6 prenet: 2 x {Linear -> ReLU -> dropout (always on)}
-                GemmArgs p0 = {};
-                if (teacher_in) p0.term[0] = GemmTerm{teacher_in, w->prenet_w0, io->lmax * O, O, O, 0};
-                else p0.term[0] = GemmTerm{ws.prev, w->prenet_w0, O, O, O, 0};
-                p0.nterms = 1; p0.M = n; p0.N = P; p0.bias = w->prenet_b0; p0.act = FCL_ACT_RELU; p0.Y = ws.pre_a; p0.ldy = P;
-                p0.drop_mode = drop_mode; p0.keep_scale = keep_scale; p0.drop_p = w->prenet_dropout;
-                p0.keep = keep0; p0.ldkeep = P; p0.rng_seed = seed0; p0.seed_dev = io->seed_dev;
-                rc = launch_gemm(p0, s);
-                if (rc) return rc;
-                GemmArgs p1 = p0;
-                p1.term[0] = GemmTerm{ws.pre_a, w->prenet_w1, P, P, P, 0};
-                p1.bias = w->prenet_b1; p1.Y = ws.pre_b; p1.keep = keep1; p1.rng_seed = seed1;
-                if (io->tap_prenet) { p1.Y2 = io->tap_prenet; p1.ldy2 = P; p1.y2_row_base = io->frame_off; p1.y2_row_add = t; }
-                rc = launch_gemm(p1, s);
-                if (rc) return rc;
-            }
+        // H8 feat_out(t-1) [+ H10 scatter] -> H6 prenet(t), one launch
+        FeatPrenetArgs fp = {};
+        fp.M_feat = n_prev; fp.M_pre = n; fp.U = U; fp.O = O; fp.P = P;
+        fp.h1 = t > 0 ? ws.h1[cur] : nullptr; fp.wf_h = w->wf_h; fp.F0 = ws.F0;
+        fp.before = io->before; fp.frame_off = io->frame_off; fp.t_prev = t - 1; fp.t_cur = t;
+        fp.teacher_in = teacher_in; fp.teacher_ld = io->lmax * O;
+        if (t < io->lmax && !hand_over) { fp.w0 = w->prenet_w0; fp.b0 = w->prenet_b0; fp.w1 = w->prenet_w1; fp.b1 = w->prenet_b1; }
+        fp.wf_hi = w->wf_h_hi; fp.wf_lo = w->wf_h_lo; fp.w0_hi = w->prenet_w0_hi; fp.w0_lo = w->prenet_w0_lo;
+        fp.w1_hi = w->prenet_w1_hi; fp.w1_lo = w->prenet_w1_lo;
+        fp.wf_ff = w->wf_h_ff; fp.w0_ff = w->prenet_w0_ff; fp.w1_ff = w->prenet_w1_ff;
+        fp.drop_mode = drop_mode; fp.keep0 = keep0; fp.keep1 = keep1; fp.keep_scale = keep_scale; fp.drop_p = w->prenet_dropout;
+        fp.seed0 = seed0; fp.seed1 = seed1; fp.seed_dev = io->seed_dev; fp.pre_out = ws.pre_b; fp.tap_prenet = io->tap_prenet;
+        fp.live = io->live_rows; fp.status = io->status; fp.out_act = w->out_act;
+        if (planes) {
+            fp.before_p = io->before_p;
+            if (!small_step(n)) { fp.pre_out_p = ws.pre_p; fp.pre_out = nullptr; }  // the big-tile LSTM step reads planes only
         }
+        int rc = launch_feat_prenet(fp, s);
+        if (rc) return rc;
         if (hand_over) return launch_decoder_tile(w, io, ws.G0, ws.F0, ws.c0, ws.c1, drop_mode, t, ws.h0[cur], ws.h1[cur], s);
         if (t == io->lmax) break;
         // H7 layer 0: gates = G0 + prenet . W_pre^T + pos * w_pos + h0 . W_hh^T ; cell ; zoneout

@@ -1122,11 +1122,6 @@ __global__ __launch_bounds__(256) void lstm_small_pair_kernel(const LstmStepArgs
     else lstm_small_body(a1);
 }
 
-static bool fp_exact_split() {
-    static const int v = tunable("FP_EXACT_SPLIT", 1);  // 0: the exact-fp32 mode keeps its fp32-operand feat/prenet and small-step kernels
-    return v != 0;
-}
-
 int launch_lstm_small(const LstmStepArgs& a, hipStream_t s) {
     double ksum = 0;
     for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
@@ -1138,7 +1133,7 @@ int launch_lstm_small(const LstmStepArgs& a, hipStream_t s) {
         ProfScope ps("lstm_small_kernel/bf16x3", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
         if (a.nterms == 2 && a.term[0].K == 256 && a.term[1].K == 256) hipLaunchKernelGGL(lstm_small_x3_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(lstm_small_x3_kernel<false>, grid, dim3(256), 0, s, a);
-    } else if (a.nterms == 2 && a.term[0].Wff && a.term[1].Wff && a.term[0].K == 256 && a.term[1].K == 256 && (a.U & 15) == 0 && fp_exact_split()) {
+    } else if (a.nterms == 2 && a.term[0].Wff && a.term[1].Wff && a.term[0].K == 256 && a.term[1].K == 256 && (a.U & 15) == 0) {
         ProfScope ps("lstm_small_ff_kernel/f32", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
         hipLaunchKernelGGL(lstm_small_ff_kernel, grid, dim3(256), 0, s, a);
     } else {
@@ -1166,13 +1161,33 @@ int launch_lstm_small_pair(const LstmStepArgs& a0, const LstmStepArgs& a1, hipSt
 // *handled = false when either step has another form (the caller launches them one after the other)
 int launch_lstm_small_pair_any(const LstmStepArgs& a0, const LstmStepArgs& a1, hipStream_t s, bool* handled) {
     *handled = false;
-    static const int on = tunable("LSTM_SMALL_PAIR", 1);
-    if (!on || a0.U != a1.U || a0.m_dev || a1.m_dev) return 0;
+    if (a0.U != a1.U || a0.m_dev || a1.m_dev) return 0;
     for (const LstmStepArgs* a : {&a0, &a1})
         for (int i = 0; i < a->nterms; ++i)
             if (!a->term[i].A || !a->term[i].W || a->term[i].Whi || a->term[i].Wff) return 0;
     *handled = true;
     return launch_lstm_small_pair(a0, a1, s);
+}
+
+// round 4: feat_prenet_split_kernel (transposed accumulators: vectorised epilogues; optional column split of layer 1).  Measured on one box, 2 400 live
+// rows, rocprofv3 durations: the round-3 kernel (RT = 2) 14.1 us; this one at (NS, RT) = (1, 1) 9.5, (1, 2) 11.9, (2, 2) 10.2, (2, 1) 9.6, (4, 1) 17
+// (600 workgroups x 245 KB: the L2 -> CU traffic of a launch, not the per-workgroup stream, is what a split costs).  The 4-stream bench line does not move
+// with any of them (44.5 - 45.7 M frames/s for all, same box): with four passes in flight the pass is bound by the sum of workgroup-time, which RT = 1
+// doubles while it halves the latency.  Launched with no split (NS = 1) and one row tile per workgroup (lowest single-pass latency: 339 -> 269 us of a
+// 1.38 ms eager pass) below 4 096 rows, two above.
+template <int RT>
+static int launch_feat_prenet_split(const FeatPrenetArgs& a, int rows, hipStream_t s) {
+    constexpr size_t lds_s = 2 * sizeof(unsigned short) * 16 * RT * ((256 + 16) + (96 + 16));
+    const dim3 g((rows + 16 * RT - 1) / (16 * RT), 1), b(512);
+    const void* fn = a.drop_mode == 1   ? reinterpret_cast<const void*>(feat_prenet_split_kernel<1, RT, 1>)
+                     : a.drop_mode == 2 ? reinterpret_cast<const void*>(feat_prenet_split_kernel<2, RT, 1>)
+                                        : reinterpret_cast<const void*>(feat_prenet_split_kernel<0, RT, 1>);
+    const int rc = ensure_dyn_lds(fn, (int)lds_s);
+    if (rc) return rc;
+    if (a.drop_mode == 1) hipLaunchKernelGGL((feat_prenet_split_kernel<1, RT, 1>), g, b, lds_s, s, a);
+    else if (a.drop_mode == 2) hipLaunchKernelGGL((feat_prenet_split_kernel<2, RT, 1>), g, b, lds_s, s, a);
+    else hipLaunchKernelGGL((feat_prenet_split_kernel<0, RT, 1>), g, b, lds_s, s, a);
+    return 0;
 }
 
 int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
@@ -1201,52 +1216,14 @@ int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
             if (rc) return rc;
         }
         ProfScope ps("feat_prenet_kernel/bf16x3", fl, rows, s);
-        static const int fast = tunable("FEAT_PRENET_FAST", 1);
-        if (fast && a.U == 256 && a.O > 64 && a.O <= 96 && a.P == 256) {
-            const dim3 b(512);
-            // round 4: feat_prenet_split_kernel (transposed accumulators: vectorised epilogues; optional column split of layer 1).  Measured on one box,
-            // 2 400 live rows, rocprofv3 durations: the round-3 kernel (RT = 2) 14.1 us; this one at (NS, RT) = (1, 1) 9.5, (1, 2) 11.9, (2, 2) 10.2,
-            // (2, 1) 9.6, (4, 1) 17 (600 workgroups x 245 KB: the L2 -> CU traffic of a launch, not the per-workgroup stream, is what a split costs).
-            // The 4-stream bench line does not move with any of them (44.5 - 45.7 M frames/s for all, same box): with four passes in flight the
-            // pass is bound by the sum of workgroup-time, which RT = 1 doubles while it halves the latency.  Default: no split, one row tile per
-            // workgroup (lowest single-pass latency: 339 -> 269 us of a 1.38 ms eager pass) below 4 096 rows, two above.
-            // FCL_FP_SPLIT = 1 / 2 / 4 / 8; FCL_FP_SPLIT_RT = row tiles per workgroup (0: by row count)
-            static const int ns_t = tunable("FP_SPLIT", 1), rt_t = tunable("FP_SPLIT_RT", 0);
-            {
-                const int rt_s = rt_t > 0 ? rt_t : (rows >= 4096 ? 2 : 1);
-#define FCL_FPS_CASE(RT_, NS_)                                                                                                           \
-    do {                                                                                                                                 \
-        constexpr size_t lds_s = 2 * sizeof(unsigned short) * 16 * RT_ * ((256 + 16) + (96 + 16));                                        \
-        const dim3 g((rows + 16 * RT_ - 1) / (16 * RT_), NS_);                                                                           \
-        const void* fn = a.drop_mode == 1   ? reinterpret_cast<const void*>(feat_prenet_split_kernel<1, RT_, NS_>)                        \
-                         : a.drop_mode == 2 ? reinterpret_cast<const void*>(feat_prenet_split_kernel<2, RT_, NS_>)                        \
-                                            : reinterpret_cast<const void*>(feat_prenet_split_kernel<0, RT_, NS_>);                       \
-        const int rc = ensure_dyn_lds(fn, (int)lds_s);                                                                                   \
-        if (rc) return rc;                                                                                                               \
-        if (a.drop_mode == 1) hipLaunchKernelGGL((feat_prenet_split_kernel<1, RT_, NS_>), g, b, lds_s, s, a);                            \
-        else if (a.drop_mode == 2) hipLaunchKernelGGL((feat_prenet_split_kernel<2, RT_, NS_>), g, b, lds_s, s, a);                       \
-        else hipLaunchKernelGGL((feat_prenet_split_kernel<0, RT_, NS_>), g, b, lds_s, s, a);                                             \
-    } while (0)
-#define FCL_FPS_RT(NS_)                                                                                                                  \
-    do {                                                                                                                                 \
-        if (rt_s >= 4) FCL_FPS_CASE(4, NS_);                                                                                             \
-        else if (rt_s >= 2) FCL_FPS_CASE(2, NS_);                                                                                        \
-        else FCL_FPS_CASE(1, NS_);                                                                                                       \
-    } while (0)
-                if (ns_t >= 8) FCL_FPS_RT(8);
-                else if (ns_t >= 4) FCL_FPS_RT(4);
-                else if (ns_t >= 2) FCL_FPS_RT(2);
-                else FCL_FPS_RT(1);
-#undef FCL_FPS_RT
-#undef FCL_FPS_CASE
-            }
-        } else if (a.U == 256 && a.O == 80 && a.P == 256) {
-            hipLaunchKernelGGL((feat_prenet_x3_kernel<8, 3, 8>), dim3((rows + 15) / 16), dim3(512), lds3, s, a);
+        if (a.U == 256 && a.O > 64 && a.O <= 96 && a.P == 256) {
+            const int rc = rows >= 4096 ? launch_feat_prenet_split<2>(a, rows, s) : launch_feat_prenet_split<1>(a, rows, s);
+            if (rc) return rc;
         } else {
             hipLaunchKernelGGL((feat_prenet_x3_kernel<0, 0, 0>), dim3((rows + 15) / 16), dim3(512), lds3, s, a);
         }
     } else if (a.wf_ff && a.w0_ff && a.w1_ff && a.U == 256 && a.P == 256 && a.O > 64 && a.O <= 96 && !a.teacher_in && !a.pre_out_p && !a.before_p &&
-               (!a.w0 || a.pre_out) && fp_exact_split()) {
+               (!a.w0 || a.pre_out)) {
         // exact-fp32 mode with fragment-major fp32 weights: the register-resident form (19.2 -> ~9 us per launch at 2 400 rows)
         ProfScope ps("feat_prenet_split_kernel/f32", fl, rows, s);
         constexpr size_t lds_f = sizeof(float) * 16 * ((256 + 8) + (96 + 8));

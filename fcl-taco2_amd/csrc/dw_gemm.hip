@@ -218,9 +218,8 @@ static void dw_launch(const DwArgs& g, dim3 grid, bool seg, bool hi_only, hipStr
 // the launcher behind fcl_gemm_tn_taps_fwd (backward.hip) for the bf16x3 / bf16 modes; returns false when the shape stays on the old kernel
 bool launch_dw_mfma(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k, int shift0, int ntaps, size_t c_tap_stride,
                     const int32_t* seg_lo, const int32_t* seg_hi, int hi_only, hipStream_t stream) {
-    static const int on = tunable("DW_MFMA", 1);
     static const int min_rows = tunable("DW_MFMA_MIN_ROWS", 256);
-    if (!on || m < min_rows || n < 32 || k < 32) return false;  // (k = 4: the position column's gradient)
+    if (m < min_rows || n < 32 || k < 32) return false;  // (k = 4: the position column's gradient)
     // every slice ends in tile-bytes of atomics, so (output bytes x slices) is what a small output pays: few 128 x 128 tiles -> 64 x 64 tiles,
     // which reach the same number of workgroups with a quarter of the slices
     static const int big_min = tunable("DW_BIG_TILES_MIN", 16), wgs_big = tunable("DW_WORKGROUPS", 512), wgs_small = tunable("DW_WORKGROUPS_SMALL", 768);

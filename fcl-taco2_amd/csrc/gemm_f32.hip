@@ -375,11 +375,6 @@ static int tm2_min_wg() {
     return v;
 }
 
-static int half_tile_wg() {
-    static const int v = tunable("GEMM_HALF_TILE_WG", 0);  // measured: 32 x 64 tiles lose (39 vs 47 TFLOP/s) even when 64 x 64 leaves CUs idle; off
-    return v;
-}
-
 static int precision() {
     static const int p = tunable("PRECISION", 1);
     return p;
@@ -506,12 +501,8 @@ static void launch_lstm_cfg(const LstmStepArgs& a, hipStream_t s, const char* na
 // bases IS a set of 128-byte lines in the geometry the pre-split kernels stream (a P32 line holds 32 hi | 32 lo bf16 halves of 32 columns, an fp32
 // line the 32 columns themselves): the same loaders, ring, swizzle and epilogues run it with v_mfma_f32_16x16x4_f32 (pchunk_mma, HI = 2).
 extern thread_local bool t_exact_lines;  // gemm_planes.hip
-static bool exact_lines_on() {
-    static const int v = tunable("EXACT_LINES", 1);
-    return v != 0;
-}
 static bool exact_lines_ok(const GemmTerm* t, int n) {
-    if (precision() || !exact_lines_on()) return false;
+    if (precision()) return false;
     for (int i = 0; i < n; ++i) {
         if (!t[i].A || !t[i].W || (t[i].K & 31) || (t[i].lda & 31) || (t[i].ldw & 31) || t[i].lda < t[i].K || t[i].ldw < t[i].K || t[i].a_chunk_stride) return false;
         if ((reinterpret_cast<uintptr_t>(t[i].A) | reinterpret_cast<uintptr_t>(t[i].W)) & 127u) return false;
@@ -593,16 +584,13 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
                                a.ldr, a.Y, a.ldy, a.M, a.N);
         return check_hip(hipGetLastError(), "gemm_smallm launch");
     }
-    // 64x64 tiles measured best for every GEMM of the path (the 32x128 / 16x256 variants only win for a single 16/32-row tile)
-    static const int force = tunable("GEMM_CFG", 0);  // experiments only: 1 -> <4,1>, 2 -> <2,2>, 3 -> <1,4>
-    static const int tm2 = tunable("GEMM_TM2", 1);    // 64 x 128 workgroup tiles with 32 x 64 per wave where the grid still fills the chip
-    if (force == 0 && tm2 && a.N >= 128 && (long long)((a.M + 63) / 64) * ((a.N + 127) / 128) >= tm2_min_wg()) {
+    // 64x64 tiles measured best for every GEMM of the path (the 32x128 / 16x256 variants only win for a single 16/32-row tile); 64 x 128 workgroup
+    // tiles with 32 x 64 per wave where the grid still fills the chip
+    if (a.N >= 128 && (long long)((a.M + 63) / 64) * ((a.N + 127) / 128) >= tm2_min_wg()) {
         launch_gemm_cfg<2, 2, 2>(a, s, "gemm_kernel<2,2,tm2>", flops);
-    } else if (force == 0 && a.M > 32 && (long long)((a.M + 63) / 64) * ((a.N + 63) / 64) < half_tile_wg()) {
-        launch_gemm_cfg<2, 1>(a, s, "gemm_kernel<2,1>", flops);  // too few 64 x 64 tiles to fill 256 CUs: 32 x 64 tiles, twice the workgroups
-    } else if (force == 1 || (force == 0 && a.M > 32)) {
+    } else if (a.M > 32) {
         launch_gemm_cfg<4, 1>(a, s, "gemm_kernel<4,1>", flops);
-    } else if (force == 2 || (force == 0 && a.M > 16)) {
+    } else if (a.M > 16) {
         launch_gemm_cfg<2, 2>(a, s, "gemm_kernel<2,2>", flops);
     } else {
         launch_gemm_cfg<1, 4>(a, s, "gemm_kernel<1,4>", flops);
@@ -613,7 +601,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
 bool lstm_step_is_small(int M, int U) {
     static const int small_m = tunable("LSTM_SMALL_M", 0);  // 0 = by width: the wave-per-gate small-tile kernel re-streams W per 16-row tile,
     // which stops paying earlier at U = 1024 (FCL-taco2-T); with the pre-split operand kernels available (32-row tiles) at ~500 rows for U = 256
-    static const bool planes_on = (tunable("PRECISION", 1) != 0 && tunable("PLANES", 1) != 0) || (tunable("PRECISION", 1) == 0 && tunable("EXACT_LINES", 1) != 0);
+    static const bool planes_on = tunable("PRECISION", 1) == 0 || tunable("PLANES", 1) != 0;
     // (U >= 512: 256 -> 64 rows in round 3 -- FCL-taco2-T synthesis 6.88 -> 7.18 M frames/s, teacher update 12.93 -> 12.78 ms: at 4 096 gate columns the
     // 32-row pre-split tiles beat the wave-per-gate kernel's W re-streaming from 65 rows on)
     return M <= (small_m ? small_m : (U >= 512 ? (planes_on ? 64 : 256) : (planes_on ? 512 : 1024)));
@@ -654,8 +642,7 @@ int launch_lstm_step(const LstmStepArgs& a, hipStream_t s) {
     for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
     const double flops = 2.0 * a.M * 4.0 * a.U * ksum;
     const long long wg64 = (long long)((a.M + 63) / 64) * ((a.U + 15) / 16);
-    static const int tm2 = tunable("GEMM_TM2", 1);
-    if (tm2 && a.U >= 32 && (long long)((a.M + 63) / 64) * ((a.U + 31) / 32) >= tm2_min_wg()) {
+    if (a.U >= 32 && (long long)((a.M + 63) / 64) * ((a.U + 31) / 32) >= tm2_min_wg()) {
         launch_lstm_cfg<2, 2, 2>(a, s, "lstm_step_kernel<2,2,tm2>", flops);
     } else if (wg64 >= 256 || a.U <= 16) {
         launch_lstm_cfg<4, 1>(a, s, "lstm_step_kernel<4,1>", flops);

@@ -719,15 +719,6 @@ bool planes_ok(const GemmTerm* t, int n) {
     return true;
 }
 
-static int loader_waves() {
-    // dedicated LDS-DMA waves per workgroup (0: every wave loads and computes).  Measured: 2 loaders -9 % per isolated launch over 0; 4 loaders another
-    // +1.5 % (S, batch 32: 41.8 -> 42.4 M frames/s over 3 runs each) to +3.6 % (batch 64) on the whole pass -- the issue rate of global_load_lds per
-    // wave is part of the per-chunk time
-    static const int t = tunable("PLANES_LOADERS", 4);
-    static const int v = t >= 4 ? 4 : (t ? 2 : 0);
-    return v;
-}
-
 template <int WM, int WN, int TM, int TN, int NST, int LW, int HI>
 static int launch_pgemm_lw(const GemmArgs& a, hipStream_t s, double flops) {
     using G = PGeo<WM, WN, TM, TN, NST, LW>;
@@ -776,13 +767,14 @@ static int launch_pgemm_lw(const GemmArgs& a, hipStream_t s, double flops) {
 // set by launch_gemm / launch_lstm_step (gemm_f32.hip) around a dispatch whose "planes" are plain fp32 rows: the exact-fp32 instantiations
 thread_local bool t_exact_lines = false;
 
+// dedicated LDS-DMA waves per workgroup (LW).  Measured: 2 loaders -9 % per isolated launch over none; 4 loaders another +1.5 % (S, batch 32: 41.8 ->
+// 42.4 M frames/s over 3 runs each) to +3.6 % (batch 64) on the whole pass -- the issue rate of global_load_lds per wave is part of the per-chunk time
 template <int WM, int WN, int TM, int TN, int NST>
 static int launch_pgemm_cfg(const GemmArgs& a, hipStream_t s, double flops) {
     if (t_exact_lines) return launch_pgemm_lw<WM, WN, TM, TN, NST, 4, 2>(a, s, flops);
     if (gemm_mode() == FCL_GEMM_BF16)  // autocast: bf16-rounded operands (the hi planes alone), one MFMA per product
-        return loader_waves() ? launch_pgemm_lw<WM, WN, TM, TN, NST, 2, true>(a, s, flops) : launch_pgemm_lw<WM, WN, TM, TN, NST, 0, true>(a, s, flops);
-    if (loader_waves() == 4) return launch_pgemm_lw<WM, WN, TM, TN, NST, 4, false>(a, s, flops);
-    return loader_waves() ? launch_pgemm_lw<WM, WN, TM, TN, NST, 2, false>(a, s, flops) : launch_pgemm_lw<WM, WN, TM, TN, NST, 0, false>(a, s, flops);
+        return launch_pgemm_lw<WM, WN, TM, TN, NST, 2, true>(a, s, flops);
+    return launch_pgemm_lw<WM, WN, TM, TN, NST, 4, false>(a, s, flops);
 }
 
 // --------------------------------------------------------------------------------------------------------------------------------------
@@ -980,89 +972,65 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void pconv_kernel(const GemmAr
     pgemm_epilogue<WN, TM, TN, G::BM, G::BN, G::CTHREADS, G::LDS_BYTES, true>(a, acc, smem, m0, n0, gz * a.g_bias, gz * a.g_y, gz * a.g_yp);
 }
 
-template <int WM, int WN, int TM, int TN, int NL, int NSTW = 3>
-static int launch_pconv_nl(const GemmArgs& a, hipStream_t s, double flops) {
-    using G = CGeo<WM, WN, TM, TN, NL, NSTW>;
-    const bool hi = gemm_mode() == FCL_GEMM_BF16 && !t_exact_lines;
-    const void* fn = t_exact_lines ? reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 2, NL, NSTW>)
-                     : hi          ? reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 1, NL, NSTW>)
-                                   : reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 0, NL, NSTW>);
+// two loader waves, three W ring stages (measured r3: two W stages for the 128 x 128 tile -- 68 KB, two workgroups per CU -- LOSE 1 % on the fresh
+// feed, 39.2 vs 39.6 M frames/s over three runs each: one bundle ahead exposes the W latency of a 5-tap step)
+template <int WM, int WN, int TM, int TN>
+static int launch_pconv_cfg(const GemmArgs& a, hipStream_t s, double flops) {
+    constexpr int NL = 2;
+    using G = CGeo<WM, WN, TM, TN, NL>;
+    const bool hi = gemm_mode() == FCL_GEMM_BF16;
+    const void* fn = hi ? reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 1, NL>) : reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 0, NL>);
     const int rc = ensure_dyn_lds(fn, G::LDS_BYTES);
     if (rc) return rc;
     const int ncols = a.Yp ? max(a.N, a.ldyp * 32) : a.N;
     const int groups = (a.g_a || a.g_w || a.g_y || a.g_yp) ? max(1, a.nblk) : 1;  // (nblk carries the group count of a grouped Conv1d)
     dim3 grid((ncols + G::BN - 1) / G::BN, (a.M + G::BM - 1) / G::BM, groups);
     char full[48];
-    snprintf(full, sizeof(full), "pconv_kernel<%d,%d,%d,%d,%d>%s%s", WM, WN, TM, TN, NL, NSTW == 2 ? "/2st" : "", t_exact_lines ? "/f32" : hi ? "/bf16" : "");
+    snprintf(full, sizeof(full), "pconv_kernel<%d,%d,%d,%d,%d>%s", WM, WN, TM, TN, NL, hi ? "/bf16" : "");
     // LDS-DMA bytes: per 32-channel chunk of the input a tile streams its row window once (BM + halo rows) and one BN-row weight slab per tap
     const double fill = (double)grid.x * grid.y * grid.z * (double)((a.term[0].K + 31) >> 5) * ((double)G::AROWS + (double)a.conv_k * G::BN) * 128.0;
     ProfScope ps(full, flops, a.M, s, fill);
     static const int dbg = tunable("PGEMM_DBG", 0);
     GemmArgs b = a;
     b.dbg_phase = dbg;
-    if (t_exact_lines) hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 2, NL, NSTW>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
-    else if (hi) hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 1, NL, NSTW>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
-    else hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 0, NL, NSTW>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
+    if (hi) hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 1, NL>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
+    else hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 0, NL>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
     return check_hip(hipGetLastError(), "pconv launch");
-}
-
-template <int WM, int WN, int TM, int TN>
-static int launch_pconv_cfg(const GemmArgs& a, hipStream_t s, double flops) {
-    static const int nl = tunable("PCONV_LOADERS", 2);
-    // 128 x 128 tiles (the postnet): two W stages = 68 KB, 10 waves, 96 VGPRs -> two workgroups per CU.  Measured r3: the fresh feed LOSES 1 %
-    // with it (39.2 vs 39.6 M frames/s over three runs each: one bundle ahead exposes the W latency of a 5-tap step) -> off
-    static const int two = tunable("PCONV_2STAGE", 0);
-    if (two && WM * TM == 8 && WN * TN == 8 && nl < 4) return launch_pconv_nl<WM, WN, TM, TN, 2, 2>(a, s, flops);
-    return nl >= 4 ? launch_pconv_nl<WM, WN, TM, TN, 4>(a, s, flops) : launch_pconv_nl<WM, WN, TM, TN, 2>(a, s, flops);
 }
 
 int launch_gemm_planes(const GemmArgs& a, hipStream_t s) {
     double ksum = 0;
     for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
     const double flops = 2.0 * a.M * (double)a.N * ksum;
-    static const int force = tunable("PGEMM_CFG", 0);
     const long long t64x128 = (long long)((a.M + 63) / 64) * ((a.N + 127) / 128);
     const long long t128x128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
     // measured on MI355X (tools/probe/planes_gemm_probe): 8-wave 128 x 128 tiles where they still give >= ~150 workgroups, 64 x 128 with three
     // stages (two workgroups per CU) down to ~250, 64 x 64 below that (the encoder-side GEMMs: M = 3 200, N = 256-384)
-    static const int pconv = tunable("PCONV", 1);
     // Conv1d: the stencil kernel (shared A halo tile).  In isolation it is within +-10 % of the K-term form (3 200 x 256 x 5 x 256: 20.7 vs 18.8 us;
     // 25 026 x 128 x 5 x 128: 24.7 vs 25.6); its smaller LDS footprint (44 vs 64 KB, 86 vs 96 KB) and 10 instead of 12 waves are what raise the
     // pass rate with several passes in flight (+1.7 ... +4 %, batch 64 +3.6 %).  At Cin >= 512 (FCL-taco2-T: 33.8 vs 28.0, 124 vs 115 us) the
-    // single-stream training step loses 2 % with it, so those keep the K-term form (PCONV=2 forces the stencil everywhere).
-    // exact-fp32 lines (round 5, pconv_kernel<HI = 2>): built, parity-green under FCL_PRECISION=0 and SLOWER -- 22.6 vs 23.2 M frames/s on the
-    // four-stream line: that mode's loops are bound by their 32-cycle fp32 MFMAs, not by the input-tile re-fetch the stencil saves -> opt-in
-    static const int pconv_exact = tunable("PCONV_EXACT", 0);
-    if (pconv && (!t_exact_lines || pconv_exact) && a.conv_k >= 3 && a.conv_k <= 17 && !a.accumulate && (a.term[0].K <= 384 || pconv >= 2)) {
+    // single-stream training step loses 2 % with it, so those keep the K-term form.
+    // exact-fp32 lines keep the K-term form too (round 5: the stencil there measured 22.6 vs 23.2 M frames/s on the four-stream line -- that mode's
+    // loops are bound by their 32-cycle fp32 MFMAs, not by the input-tile re-fetch the stencil saves)
+    if (!t_exact_lines && a.conv_k >= 3 && a.conv_k <= 17 && !a.accumulate && a.term[0].K <= 384) {
         // (round 6: 150 -> 60 -- the 128-row stencil wherever it has 60 tiles: +0.4 ... +1.0 % on the four-pass line in three same-box scans, everything else flat:
         // profiles/r6_tile_sweep.log, r6_tunable_scan_synth_pconv.log)
         static const int cbig_min = tunable("PCONV_BIG_MIN", 60);
-        if (force == 1 || (force == 0 && t128x128 >= cbig_min && a.N >= 128)) return launch_pconv_cfg<4, 2, 2, 4>(a, s, flops);
-        if (force == 2 || (force == 0 && t64x128 >= 250 && a.N >= 96)) return launch_pconv_cfg<2, 2, 2, 4>(a, s, flops);
+        if (t128x128 >= cbig_min && a.N >= 128) return launch_pconv_cfg<4, 2, 2, 4>(a, s, flops);
+        if (t64x128 >= 250 && a.N >= 96) return launch_pconv_cfg<2, 2, 2, 4>(a, s, flops);
         return launch_pconv_cfg<2, 2, 2, 2>(a, s, flops);
     }
-    if (a.accumulate && force == 0)  // split contraction fills the device whatever the tile count: the largest tiles that fit the output
+    if (a.accumulate)  // split contraction fills the device whatever the tile count: the largest tiles that fit the output
         return (a.M >= 128 && a.N >= 128) ? launch_pgemm_cfg<4, 2, 2, 4, 3>(a, s, flops) : launch_pgemm_cfg<2, 2, 2, 2, 4>(a, s, flops);
-    // 256 x 128 tiles (64 x 64 per wave): 48 KB instead of 64 KB of LDS-DMA per 256 x 128 x 32 MACs -- the main loop is bound by the global -> LDS
-    // fill rate, so -25 % bytes per FLOP.  Measured r3 (tools/time_pgemm.py): +6 ... +12 % on frame-sized GEMMs with K >= 512 (12 400 x 4 096 x 512:
-    // 203 -> 226 TFLOP/s fp32-equivalent), -10 ... -50 % at K <= 256 (the epilogue of a 256-row tile is not overlapped by anything at one workgroup
-    // per CU), and no change of the KD / teacher update (12.58 / 12.93 vs 12.60 / 12.95 ms: few of their GEMMs qualify) -> off unless asked for
-    // After the epilogue pass (plain element loop) the 256-row tile no longer pays for its epilogue: 24 300 x 1 024 x 256 64 -> 58 us,
-    // 12 400 x 4 096 x 512 222 -> 188, 31 000 x 512 x 512 65 -> 54.5; still slower at N = 128 and below two rounds of workgroups -> ON for N >= 256,
-    // K >= 256, >= 512 tiles (KD / teacher update: 11.84 / 12.42 vs 11.88 / 12.40 ms)
-    static const int big_min = tunable("PGEMM_BIG_MIN_WG", 1 << 30);  // (off again: the two-stage 128 x 128 configuration below beats it on every shape)
-    const long long t256x128 = (long long)((a.M + 255) / 256) * ((a.N + 127) / 128);
-    if (force == 3 || (force == 0 && t256x128 >= big_min && a.N >= 256 && ksum >= 256)) return launch_pgemm_cfg<4, 2, 4, 4, 3>(a, s, flops);
-    if (force == 6) return launch_pgemm_cfg<4, 2, 2, 4, 4>(a, s, flops);  // 128 x 128 tiles, FOUR ring stages (three chunks = 96 KB in flight per CU)
     // 128 x 128 tiles with TWO ring stages: 64 KB of LDS and 80 VGPRs = two workgroups per CU, so one's epilogue (staging + stores, 2 - 3 us that
     // nothing overlapped at one workgroup per CU) runs beside the other's main loop.  Only where the launch has more than one round of workgroups
     // (a single round runs one per CU whatever it could share): 24 300 x 1 024 x 256 63 -> 52 us, 12 400 x 4 096 x 512 199 -> 152 (343 TFLOP/s
     // fp32-equivalent), 31 000 x 512 x 512 64 -> 49, 2 480 x 4 096 x 1 024 72 -> 66; N = 128 is 13 % slower with it (tools/time_pgemm.py)
     static const int two_stage_min = tunable("PGEMM_2STAGE_MIN_WG", 300);
-    if (force == 7 || (force == 0 && t128x128 >= two_stage_min && a.N >= 256)) return launch_pgemm_cfg<4, 2, 2, 4, 2>(a, s, flops);
+    if (t128x128 >= two_stage_min && a.N >= 256) return launch_pgemm_cfg<4, 2, 2, 4, 2>(a, s, flops);
     static const int gbig_min = tunable("PGEMM_BIG_MIN", 150);
-    if (force == 1 || (force == 0 && t128x128 >= gbig_min && a.N >= 128)) return launch_pgemm_cfg<4, 2, 2, 4, 3>(a, s, flops);
-    if (force == 2 || (force == 0 && t64x128 >= 250 && a.N >= 96)) return launch_pgemm_cfg<2, 2, 2, 4, 3>(a, s, flops);
+    if (t128x128 >= gbig_min && a.N >= 128) return launch_pgemm_cfg<4, 2, 2, 4, 3>(a, s, flops);
+    if (t64x128 >= 250 && a.N >= 96) return launch_pgemm_cfg<2, 2, 2, 4, 3>(a, s, flops);
     return launch_pgemm_cfg<2, 2, 2, 2, 4>(a, s, flops);
 }
 
@@ -1095,10 +1063,8 @@ static int launch_plstm_lw(const LstmStepArgs& a, hipStream_t s, double flops) {
 template <int WM, int WN, int TM, int NST>
 static int launch_plstm_cfg(const LstmStepArgs& a, hipStream_t s, double flops) {
     if (t_exact_lines) return launch_plstm_lw<WM, WN, TM, NST, 4, 2>(a, s, flops);
-    if (gemm_mode() == FCL_GEMM_BF16)
-        return loader_waves() ? launch_plstm_lw<WM, WN, TM, NST, 2, true>(a, s, flops) : launch_plstm_lw<WM, WN, TM, NST, 0, true>(a, s, flops);
-    if (loader_waves() == 4) return launch_plstm_lw<WM, WN, TM, NST, 4, false>(a, s, flops);
-    return loader_waves() ? launch_plstm_lw<WM, WN, TM, NST, 2, false>(a, s, flops) : launch_plstm_lw<WM, WN, TM, NST, 0, false>(a, s, flops);
+    if (gemm_mode() == FCL_GEMM_BF16) return launch_plstm_lw<WM, WN, TM, NST, 2, true>(a, s, flops);
+    return launch_plstm_lw<WM, WN, TM, NST, 4, false>(a, s, flops);
 }
 
 int launch_lstm_planes(const LstmStepArgs& a, hipStream_t s) {
@@ -1107,19 +1073,11 @@ int launch_lstm_planes(const LstmStepArgs& a, hipStream_t s) {
     double ksum = 0;
     for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
     const double flops = 2.0 * a.M * 4.0 * a.U * ksum;
-    static const int force = tunable("PLSTM_CFG", 0);
     const long long t128 = (long long)((a.M + 127) / 128) * ((a.U + 31) / 32);
     const long long t64 = (long long)((a.M + 63) / 64) * ((a.U + 31) / 32);
-    const long long t96 = (long long)((a.M + 95) / 96) * ((a.U + 31) / 32);
-    static const int use96 = tunable("PLSTM_TILE96", 0);
-    // 96-row tiles where they still fit one wave of workgroups and 128-row tiles would leave CUs idle: a workgroup's main loop takes
-    // (BM + BN) * K * 4 bytes / ~47 GB/s, so 96 + 128 instead of 128 + 128 rows is -12.5 % per workgroup
-    if ((force == 5 || (force == 0 && use96 && t128 >= 150 && t128 < 230 && t96 <= 256)) && loader_waves() > 0 && gemm_mode() != FCL_GEMM_BF16)
-        return loader_waves() == 4 ? launch_plstm_lw<3, 2, 2, 3, 4, false>(a, s, flops) : launch_plstm_lw<3, 2, 2, 3, 2, false>(a, s, flops);  // (6 compute waves: loader-specialised only)
     // thresholds as tunables (r3, 4 passes in flight, B = 32: 64-row tiles everywhere -- two workgroups per CU, also from different streams -- are +1.5 ...
     // +4.5 % on the replayed pass and within noise on the fresh feed, but -22 % on FCL-taco2-T synthesis and +6 % on the KD update: the 128-row tiles
     // stay where they are; PLSTM_BIG_MIN=300 PLSTM_MID_MIN=80 is the S-only variant)
-    if (force == 6) return launch_plstm_cfg<4, 2, 2, 4>(a, s, flops);  // 128-row tiles, four ring stages
     // 128-row tiles, TWO ring stages = two workgroups per CU (see pgemm): where the launch has more than one round of workgroups (FCL-taco2-T,
     // batch >= 64 at FCL-taco2-S): the step kernel itself +10 % (FCL-taco2-T: frac 0.33 -> 0.36), batch 64 +2.7 %, T synthesis +1 %.  Synthesis
     // steps only: in the KD update the frozen teacher's forward runs BESIDE the student's critical path, and a teacher step that holds two
@@ -1130,7 +1088,7 @@ int launch_lstm_planes(const LstmStepArgs& a, hipStream_t s) {
     // passes, -2.7 % alone.
     static const int two_stage_min = tunable("PLSTM_2STAGE_MIN_WG", 125);
     static const int two_stage_min_exact = tunable("PLSTM_2STAGE_MIN_WG_EXACT", 300);  // (exact-fp32 lines are MFMA-bound: 125 costs that mode 5 %, 23.2 -> 22.0 M frames/s)
-    if (force == 7 || (force == 0 && t128 >= (t_exact_lines ? two_stage_min_exact : two_stage_min) && !a.zone_keep_h && !a.save_gates)) return launch_plstm_cfg<4, 2, 2, 2>(a, s, flops);
+    if (t128 >= (t_exact_lines ? two_stage_min_exact : two_stage_min) && !a.zone_keep_h && !a.save_gates) return launch_plstm_cfg<4, 2, 2, 2>(a, s, flops);
     // narrow synthesis steps (U <= 256, no training-side outputs: FCL-taco2-S inference) have their own pair of thresholds: 64-row tiles (two
     // workgroups per CU, also of different passes) up to 300 128-row tiles -- same-box A/B, three rounds, (150, 200) vs (300, 80): replayed pass
     // 47.5 -> 48.6 M frames/s, fresh feed 39.4 -> 39.8 M; the wide / training steps keep the 128-row tiles (-22 % on FCL-taco2-T synthesis otherwise)
@@ -1138,10 +1096,10 @@ int launch_lstm_planes(const LstmStepArgs& a, hipStream_t s) {
     static const int mid_min_t = tunable("PLSTM_MID_MIN", 200), mid_min_s = tunable("PLSTM_MID_MIN_S", 80);
     const bool narrow = a.U <= 256 && !a.zone_keep_h && !a.save_gates;
     const int big_min = narrow ? big_min_s : big_min_t, mid_min = narrow ? mid_min_s : mid_min_t;
-    if (force == 1 || (force == 0 && t128 >= big_min)) return launch_plstm_cfg<4, 2, 2, 3>(a, s, flops);
-    if (force == 2 || (force == 0 && t64 >= mid_min)) return launch_plstm_cfg<2, 2, 2, 3>(a, s, flops);
+    if (t128 >= big_min) return launch_plstm_cfg<4, 2, 2, 3>(a, s, flops);
+    if (t64 >= mid_min) return launch_plstm_cfg<2, 2, 2, 3>(a, s, flops);
     static const int row32_m = tunable("PLSTM_ROW32_M", 1100);
-    if (force == 4 || (force == 0 && a.M <= row32_m)) return launch_plstm_cfg<2, 2, 1, 4>(a, s, flops);  // 32 x 128 tiles: M = 500 .. 1100 (measured)
+    if (a.M <= row32_m) return launch_plstm_cfg<2, 2, 1, 4>(a, s, flops);  // 32 x 128 tiles: M = 500 .. 1100 (measured)
     return launch_plstm_cfg<2, 1, 2, 4>(a, s, flops);  // 64 x 64 gate-column tiles (16 units): M <~ 1600 at U = 256
 }
 
@@ -1171,8 +1129,7 @@ static int launch_plstm_pair_cfg(const LstmStepArgs& a0, const LstmStepArgs& a1,
 // (the caller then launches the two steps one after the other)
 int launch_lstm_planes_pair(const LstmStepArgs& a0, const LstmStepArgs& a1, hipStream_t s, bool* handled) {
     *handled = false;
-    static const int on = tunable("PLSTM_PAIR", 1);
-    if (!on || a0.U != a1.U || t_exact_lines || loader_waves() != 4 || a0.m_dev || a1.m_dev) return 0;
+    if (a0.U != a1.U || t_exact_lines || a0.m_dev || a1.m_dev) return 0;
     for (const LstmStepArgs* a : {&a0, &a1})
         if (a->h_out_p && !((a->U & 31) == 0 && a->ld_hp * 32 >= a->U && (reinterpret_cast<uintptr_t>(a->h_out_p) & 127u) == 0)) return 0;
     *handled = true;
@@ -1191,13 +1148,11 @@ int launch_lstm_planes_pair(const LstmStepArgs& a0, const LstmStepArgs& a1, hipS
 #define FCL_PAIR(WM_, WN_, TM_, NST_) (hi ? launch_plstm_pair_cfg<WM_, WN_, TM_, NST_, 1>(a0, a1, s, flops) : launch_plstm_pair_cfg<WM_, WN_, TM_, NST_, 0>(a0, a1, s, flops))
     // two ring stages = 64 KB of LDS = TWO workgroups per CU for the pair's 128-row tiles, from ..MIN_WG to below ..MAX_WG tiles per problem.  Round 6 (tools/tunable_scan.sh,
     // profiles/r6_tunable_scan.log): on for 256 <= tiles < 512 -- the teacher's own update (16 utterances: 10 x 32 tiles per problem, 640 per pair on 256 CUs = 2.5 rounds
-    // of one-per-CU workgroups): 9.42 -> 9.36 ms; everywhere (FCL_PLSTM_PAIR_NST2=1) the KD update, whose pairs have 160 and 640 tiles, loses 1 %
+    // of one-per-CU workgroups): 9.42 -> 9.36 ms; everywhere (two stages for every pair, r5 A/B) the KD update, whose pairs have 160 and 640 tiles, loses 1 %
     static const int two_stage = tunable("PLSTM_PAIR_2STAGE_MIN_WG", 256), two_stage_max = tunable("PLSTM_PAIR_2STAGE_MAX_WG", 512);
-    static const int all2 = tunable("PLSTM_PAIR_NST2", 0);  // (r5 A/B: two ring stages everywhere = <= 64 KB of LDS and <= 80 VGPRs per workgroup, so that
-                                                           // the frozen teacher's steps and the student's can share a CU in the KD update)
     if (t128 >= two_stage && t128 < two_stage_max) return FCL_PAIR(4, 2, 2, 2);
-    if (t128 >= big_min) return all2 ? FCL_PAIR(4, 2, 2, 2) : FCL_PAIR(4, 2, 2, 3);
-    if (t64 >= mid_min) return all2 ? FCL_PAIR(2, 2, 2, 2) : FCL_PAIR(2, 2, 2, 3);
+    if (t128 >= big_min) return FCL_PAIR(4, 2, 2, 3);
+    if (t64 >= mid_min) return FCL_PAIR(2, 2, 2, 3);
     if (M <= row32_m) return FCL_PAIR(2, 2, 1, 4);
     return FCL_PAIR(2, 1, 2, 4);
 #undef FCL_PAIR
@@ -1745,7 +1700,6 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
     if (exp_terms > 0) a.nterms = exp_terms;  // developer timing aid: fewer K-terms (results are then garbage)
     const bool hi = gemm_mode() == FCL_GEMM_BF16;
     const double flops = 2.0 * (double)L.m * 2.0 * R * ((double)L.ksize * R + L.aux + R);
-    static const int persist = tunable("PWG_PERSIST", 1);
     const bool auxf = L.kp != nullptr;
     if (auxf) {  // one chunk: coefficient lines (one line per sample) x the tile's frame window
         GemmTerm& T = a.term[L.ksize];
@@ -1753,18 +1707,15 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
         T.Ap = L.kp; T.lda_p = 1; T.a_chunk_stride = 0;
         T.Wp = L.pt_a; T.ldw_p = L.ld_pt;
         a.pt_a = L.pt_a; a.pt_b = L.pt_b; a.hop = L.hop;
-        FCL_REQUIRE(persist && !dbg && exp_terms <= 0, FCL_ERR_INVALID, "pwg_layer_fwd: the frame-rate auxiliary term runs on the persistent kernel only");
+        FCL_REQUIRE(!dbg && exp_terms <= 0, FCL_ERR_INVALID, "pwg_layer_fwd: the frame-rate auxiliary term runs on the persistent kernel only");
     }
-    if (persist && !dbg && exp_terms <= 0 && (auxf || L.aux > 64)) {  // (the persistent kernel is written for 3 x 2 + 3 chunks: r = 64, ksize = 3, 64 < aux <= 96)
+    if (!dbg && exp_terms <= 0 && (auxf || L.aux > 64)) {  // (the persistent kernel is written for 3 x 2 + 3 chunks: r = 64, ksize = 3, 64 < aux <= 96)
         constexpr int LDS = PGeo<4, 2, 2, 4, 3, 2>::LDS_BYTES + 2 * 32768;
-        static const int plw = tunable("PWG_LOADERS", 4);  // 4 loader waves: 151.9 -> 145.1 ms per 30 blocks
-        const int lwv = plw >= 4 ? 4 : 2;
+        constexpr int lwv = 4;  // 4 loader waves over 2: 151.9 -> 145.1 ms per 30 blocks
         typedef void (*kern_t)(const PwgFusedArgs, const int);
-        static const kern_t table[2][2][2] = {{{pwg_layer_pkernel<false, 2, false>, pwg_layer_pkernel<false, 2, true>},
-                                               {pwg_layer_pkernel<false, 4, false>, pwg_layer_pkernel<false, 4, true>}},
-                                              {{pwg_layer_pkernel<true, 2, false>, pwg_layer_pkernel<true, 2, true>},
-                                               {pwg_layer_pkernel<true, 4, false>, pwg_layer_pkernel<true, 4, true>}}};
-        const kern_t fn = table[hi ? 1 : 0][lwv == 4 ? 1 : 0][auxf ? 1 : 0];
+        static const kern_t table[2][2] = {{pwg_layer_pkernel<false, lwv, false>, pwg_layer_pkernel<false, lwv, true>},
+                                           {pwg_layer_pkernel<true, lwv, false>, pwg_layer_pkernel<true, lwv, true>}};
+        const kern_t fn = table[hi ? 1 : 0][auxf ? 1 : 0];
         const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(fn), LDS);
         if (rc) return rc;
         int dev = 0, cus = 256;
@@ -1776,12 +1727,8 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
         hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(64 * (8 + lwv)), LDS, s, a, ntiles);
         return check_hip(hipGetLastError(), "pwg_layer persistent launch");
     }
-    // measured on MI355X, 64 x 800 frames, ms per layer: 128-row tiles + 3-deep ring + W_os in LDS 7.07 (default); the same with a 4-deep ring and
-    // W_os fragments from L2 8.4 (the main loop alone is 4.05 either way: not bound by bytes in flight); 64-row tiles, two workgroups per CU 7.5
-    static const int cfg = tunable("PWG_CFG", 0);  // 1: 128 rows, 4-deep ring; 3: 64-row tiles, 3-deep; 4: 64-row tiles, 4-deep
-    if (cfg == 1) return hi ? launch_pwg_cfg<4, 4, true>(a, L.m, flops, s) : launch_pwg_cfg<4, 4, false>(a, L.m, flops, s);
-    if (cfg == 3) return hi ? launch_pwg_cfg<2, 3, true>(a, L.m, flops, s) : launch_pwg_cfg<2, 3, false>(a, L.m, flops, s);
-    if (cfg == 4) return hi ? launch_pwg_cfg<2, 4, true>(a, L.m, flops, s) : launch_pwg_cfg<2, 4, false>(a, L.m, flops, s);
+    // measured on MI355X, 64 x 800 frames, ms per layer: 128-row tiles + 3-deep ring + W_os in LDS 7.07; the same with a 4-deep ring and W_os
+    // fragments from L2 8.4 (the main loop alone is 4.05 either way: not bound by bytes in flight); 64-row tiles, two workgroups per CU 7.5
     return hi ? launch_pwg_cfg<4, 3, true>(a, L.m, flops, s) : launch_pwg_cfg<4, 3, false>(a, L.m, flops, s);
 }
 

@@ -736,8 +736,7 @@ int row_maps_check(const fcl_row_maps_t* a, bool* fusable) {
     FCL_REQUIRE(a->src_rows && a->dur_sorted && a->frame_off && a->live_rows && a->utt_frame0 && a->frame_lo && a->frame_hi &&
                     a->totals && a->status,
                 FCL_ERR_INVALID, "row_maps_build: null pointer");
-    static const int fast_on = tunable("ROWMAPS_FAST", 1);
-    if (fusable) *fusable = fast_on && a->scratch && a->lmax_cap < RMF_V - 1;
+    if (fusable) *fusable = a->scratch && a->lmax_cap < RMF_V - 1;
     return 0;
 }
 }  // namespace fcl

@@ -433,16 +433,10 @@ int conv_bn_fwd(E_t& E, const float* x, const uint16_t* xp, int m, const std::st
     TE_TRY(conv_cp(E, wn, cout, cin, k, false, true, nullptr, &wpp));
     float* z = f32(E, m, cout);
     float *mean = f32(E, cout), *invstd = f32(E, cout);
-    // FCL_TE_BN_FUSED=1 (round 6, VERDICT r5 #1b): the batch statistics come out of the convolution's epilogue (fcl_conv1d_planes_bn_fwd: same fp64 sums, same ticketed
-    // finalize) -- one launch and one pass over z [m, cout] less per block
-    static const int bn_fused = tunable("TE_BN_FUSED", 1);
-    if (bn_fused && tunable("PRECISION", 1) != 0 && tunable("PLANES", 1) != 0) {
-        TE_L(fcl_conv1d_planes_bn_fwd(xp, (cin + 31) / 32, wpp, lo, hi, z, m, cin, cout, k, BN_EPS, BN_MOMENTUM, mean, invstd, E.B.at(prefix + ".1.running_mean"),
-                                      E.B.at(prefix + ".1.running_var"), bnws(E), E.cur));
-    } else {
-        TE_L(fcl_conv1d_planes_fwd(xp, (cin + 31) / 32, wpp, nullptr, lo, hi, nullptr, z, nullptr, m, cin, cout, k, FCL_ACT_NONE, E.cur));
-        TE_L(fcl_bn_stats_ws_fwd(z, m, cout, BN_EPS, BN_MOMENTUM, mean, invstd, E.B.at(prefix + ".1.running_mean"), E.B.at(prefix + ".1.running_var"), bnws(E), E.cur));
-    }
+    // (round 6, VERDICT r5 #1b) the batch statistics come out of the convolution's epilogue (fcl_conv1d_planes_bn_fwd: same fp64 sums, same ticketed finalize as
+    // fcl_bn_stats_ws_fwd) -- one launch and one pass over z [m, cout] less per block
+    TE_L(fcl_conv1d_planes_bn_fwd(xp, (cin + 31) / 32, wpp, lo, hi, z, m, cin, cout, k, BN_EPS, BN_MOMENTUM, mean, invstd, E.B.at(prefix + ".1.running_mean"),
+                                  E.B.at(prefix + ".1.running_var"), bnws(E), E.cur));
     const float ks = keep ? 1.0f / (1.0f - p_drop) : 1.0f;
     // (round 6) a forward that saves nothing for a backward (the frozen KD teacher) and drops: the pre-dropout activation has no reader -- one [m, cout] write less per block
     float* y_act = (E.c.save || !keep) ? f32(E, m, cout) : nullptr;
@@ -945,10 +939,9 @@ static int te_kd_fwd(fcl_te& E, LossBatchBuilder& lb, std::vector<KdTerm>& pend,
     q.lname = lname; q.proj = proj; q.key = key; q.s_in = s_in; q.rows = rows; q.n = n; q.k = k; q.t = t; q.valid = valid; q.nvalid = nvalid;
     q.planes = n % 32 == 0 && k % 32 == 0 && rows >= 4096;
     Param& W = E.Pm(proj + ".weight");
-    // FCL_TE_KD_FUSED=1 (round 6): a term on the planes kernels is ONE launch -- projection, masked MSE and gradient in the GEMM's epilogue
-    // (fcl_linear_planes_mse_fwd); the projected tensor [rows, n] is never written or read back (8 of the 20 bytes per element the term moved)
-    static const int fused = tunable("TE_KD_FUSED", 1);
-    const bool fuse = fused && q.planes && (reinterpret_cast<uintptr_t>(t) & 15u) == 0 && (n & 3) == 0;
+    // (round 6) a term on the planes kernels is ONE launch -- projection, masked MSE and gradient in the GEMM's epilogue (fcl_linear_planes_mse_fwd); the
+    // projected tensor [rows, n] is never written or read back (8 of the 20 bytes per element the term moved)
+    const bool fuse = q.planes && (reinterpret_cast<uintptr_t>(t) & 15u) == 0 && (n & 3) == 0;
     float* s = fuse ? nullptr : f32(E, rows, n);
     if (q.planes) {
         const uint16_t* sp;
@@ -1021,11 +1014,10 @@ static int te_losses(fcl_te& E, const fcl_te_knowledge_t* know) {
                                cf.share_proj ? "enc.convs_proj.0" : "enc.convs_proj.2"};
     const std::string lp[2] = {cf.share_proj ? "dec.lstm_proj" : "dec.lstm0_proj", cf.share_proj ? "dec.lstm_proj" : "dec.lstm1_proj"};
     auto pp = [&](int i) { return cf.share_proj ? std::string("dec.post_proj") : ("dec.post" + std::to_string(i) + "_proj"); };
-    // FCL_TE_R6: bit 0 = the late group is enqueued BEFORE the student's stream's own terms, so that it runs beside them (-0.15 ms per KD update, same-box A/B); bit 1 =
-    // the prosody embedding terms join the late group (their gradients are wanted at backward stage 2).  (Bit 0 was off for most of round 6: beside the late group's
+    // (round 6) the late group is enqueued BEFORE the student's stream's own terms, so that it runs beside them (-0.15 ms per KD update, same-box A/B), and the
+    // prosody embedding terms join it (their gradients are wanted at backward stage 2).  (The early enqueue was off for most of round 6: beside the late group's
     // GEMMs the loss kernel's packed-FP32 arithmetic came out stale in lanes 48 - 63 in ~10 % of fresh engines' first updates -- DESIGN 4c; the library is built
     // without packed-FP32 instructions since.)
-    static const int r6 = tunable("TE_R6", 3);
     auto late_group = [&]() -> int {  // the KD terms whose gradients the backward needs LATE run on the weight-gradient stream beside the frame-level terms and the postnet's backward
         const bool fork = cf.pred_stream && c.save && cf.late_losses;
         hipStream_t saved = E.cur;
@@ -1059,7 +1051,7 @@ static int te_losses(fcl_te& E, const fcl_te_knowledge_t* know) {
             }
             TE_TRY(te_kd_fwd(E, lb, pend, "enc4", "hs", c.hs, BT, "enc.blstm_proj", cf.t_eunits, C, know->enc[4], b.enc_valid, ne));
         }
-        if (cf.distill_prosody && (r6 & 2)) {  // the embedding taps' gradients are wanted at backward stage 2: late as well
+        if (cf.distill_prosody) {  // the embedding taps' gradients are wanted at backward stage 2: late as well
             TE_TRY(te_kd_fwd(E, lb, pend, "pro3", "p_embs", c.p_embs, BT, "pemb_proj", cf.t_eunits, C, know->pro[3], b.enc_valid, ne));
             TE_TRY(te_kd_fwd(E, lb, pend, "pro4", "e_embs", c.e_embs, BT, "eemb_proj", cf.t_eunits, C, know->pro[4], b.enc_valid, ne));
         }
@@ -1072,14 +1064,10 @@ static int te_losses(fcl_te& E, const fcl_te_knowledge_t* know) {
         }
         return 0;
     };
-    if (student && (r6 & 1)) TE_TRY(late_group());
+    if (student) TE_TRY(late_group());
     // the student's stream: the postnet taps' projections, ONE loss launch (their terms + every element-wise term), their backward halves
     LossBatchBuilder lb(E);
     std::vector<KdTerm> pend;
-    if (student && cf.distill_prosody && !(r6 & 2)) {
-        TE_TRY(te_kd_fwd(E, lb, pend, "pro3", "p_embs", c.p_embs, BT, "pemb_proj", cf.t_eunits, C, know->pro[3], b.enc_valid, ne));
-        TE_TRY(te_kd_fwd(E, lb, pend, "pro4", "e_embs", c.e_embs, BT, "eemb_proj", cf.t_eunits, C, know->pro[4], b.enc_valid, ne));
-    }
     if (student && cf.distill_decoder)
         for (int i = 0; i < 4; ++i) {
             char nm[8];
@@ -1109,7 +1097,6 @@ static int te_losses(fcl_te& E, const fcl_te_knowledge_t* know) {
     }
     TE_TRY(lb.flush());
     for (int i = (int)pend.size() - 1; i >= 0; --i) TE_TRY(te_kd_bwd(E, pend[i]));  // the postnet's backward consumes post3 first
-    if (student && !(r6 & 1)) TE_TRY(late_group());
     return 0;
 }
 
@@ -1152,41 +1139,13 @@ static int te_backward_stage0(fcl_te& E) {  // predictors' backward forked; post
     return 0;
 }
 
-// round 5, measured and NOT adopted (FCL_TE_DX_PLANES=1 turns it on): four input-gradient GEMMs whose A operand is a gradient tensor nobody has planes of (K = odim
-// = 80 or K = 4 U / 4 H contractions) run on the fp32-operand kernel (`gemm_kernel<...>/bf16x3`, 25 - 60 TFLOP/s: 0.5 ms of kernel time per teacher update).  With
-// planes from the producer (the gathers write them) or one packing pass and the LDS-DMA kernels instead: teacher update 9.82 vs 9.77 ms, KD 9.03 vs 9.09 ms on one
-// box (`gpurun_out/r6i`) -- they are off the critical path and the packing passes cost what the faster GEMMs save.
-static bool dx_planes() {
-    static const int on = tunable("TE_DX_PLANES", 0);
-    return on != 0 && tunable("PRECISION", 1) != 0 && tunable("PLANES", 1) != 0;
-}
-// Y[m, n] = A[m, k] . Wt^T for a weight kept as the transposed form `key` ([n, k] rows): planes when ap / a packing pass can provide them
-static int dx_linear(fcl_te& E, const float* a, const uint16_t* ap, int m, int k, const std::string& key, const float* wsrc, int rows, int cols, int ld, float* y, int n) {
-    if (dx_planes() && n % 4 == 0) {
-        if (!ap) {
-            uint16_t* t = pl16(E, m, k);
-            TE_L(fcl_pack_planes(a, k, m, k, t, E.cur));
-            ap = t;
-        }
-        const uint16_t* wtp;
-        TE_TRY(w_t(E, key, wsrc, rows, cols, ld, false, true, nullptr, &wtp));
-        TE_L(fcl_linear_planes_fwd(ap, (k + 31) / 32, wtp, nullptr, y, n, nullptr, m, n, k, FCL_ACT_NONE, E.cur));
-        return 0;
-    }
-    const float* wt;
-    TE_TRY(w_t(E, key, wsrc, rows, cols, ld, true, false, &wt, nullptr));
-    TE_L(fcl_linear_fwd(a, k, wt, k, nullptr, y, n, m, n, k, FCL_ACT_NONE, E.cur));
-    return 0;
-}
-
 static int te_backward_stage1(fcl_te& E) {  // decoder BPTT + prenet
     const fcl_te_config_t& cf = E.cfg;
     Ctx& c = E.c;
     const fcl_te_batch_t& b = c.b;
     const int N = b.N, F = b.F, O = cf.odim, U = cf.dunits, Pn = cf.prenet_units, C = cf.eunits;
     float* d_out_cells = f32(E, F, O);
-    uint16_t* d_out_cells_p = dx_planes() ? pl16(E, F, O) : nullptr;
-    TE_L(fcl_gather_rows_sum_fwd(c.inj["before"], c.inj["after"], c.d_post_in, b.cell_frame, d_out_cells, d_out_cells_p, F, O, E.cur));
+    TE_L(fcl_gather_rows_sum_fwd(c.inj["before"], c.inj["after"], c.d_post_in, b.cell_frame, d_out_cells, nullptr, F, O, E.cur));
     Param& WF = E.Pm("dec.feat_out.weight");
     {
         SideScope sc(E);
@@ -1198,13 +1157,10 @@ static int te_backward_stage1(fcl_te& E) {  // decoder BPTT + prenet
     TE_TRY(w_cols(E, "dec.feat_out.weight", O, U + C, 0, U, true, &wf_h, nullptr));
     TE_TRY(w_cols(E, "dec.feat_out.weight", O, U + C, U, C, true, &wf_att, nullptr));
     float* dh1_all = f32(E, F, U);
-    if (!dx_planes()) {  // round 6: the KD gradient at the h1 tap joins as the GEMM's residual
+    {  // round 6: the KD gradient at the h1 tap joins as the GEMM's residual
         const float* wt;
         TE_TRY(w_t(E, "dec.feat_out.weight/h", WF.p, O, U, U + C, true, false, &wt, nullptr));
         TE_L(fcl_linear2_fwd(d_out_cells, O, wt, O, O, nullptr, 0, nullptr, 0, 0, nullptr, c.inj.count("h1") ? c.inj["h1"] : nullptr, U, dh1_all, U, F, U, FCL_ACT_NONE, E.cur));
-    } else {
-        TE_TRY(dx_linear(E, d_out_cells, d_out_cells_p, F, O, "dec.feat_out.weight/h", WF.p, O, U, U + C, dh1_all, U));
-        if (c.inj.count("h1")) TE_L(fcl_add2d(dh1_all, U, c.inj["h1"], U, F, U, 1.0f, nullptr, E.cur));
     }
     float* dF0 = zf32(E, (long long)N * O);
     TE_L(fcl_scatter_add_rows(d_out_cells, b.cell_row_i64, dF0, F, O, -1, E.cur));
@@ -1215,7 +1171,6 @@ static int te_backward_stage1(fcl_te& E) {  // decoder BPTT + prenet
         E.dw_pending = true;
     }
     c.d_att_c = f32(E, N, C);
-    if (dx_planes()) TE_TRY(dx_linear(E, dF0, nullptr, N, O, "dec.feat_out.weight/att", WF.p + U, O, C, U + C, c.d_att_c, C));
     float *dg0_all = f32(E, F, 4 * U), *dg1_all = f32(E, F, 4 * U);
     const std::string w1ih = "dec.lstm.1.cell.weight_ih", w1hh = "dec.lstm.1.cell.weight_hh", w0hh = "dec.lstm.0.cell.weight_hh", wih0 = "dec.lstm.0.cell.weight_ih";
     const int ld0 = C + Pn + 1;
@@ -1286,15 +1241,11 @@ static int te_backward_stage1(fcl_te& E) {  // decoder BPTT + prenet
         TE_L(fcl_gemm_tn_fwd(dG0, 4 * U, c.att_c, C, g_ih0, ld0, N, 4 * U, C, 0, nullptr, nullptr, E.cur));
         E.dw_pending = true;
     }
-    if (!dx_planes()) {  // round 6: the two input gradients that reach att_c (through feat_out and through LSTM 0's input block) in ONE two-term GEMM
+    {  // round 6: the two input gradients that reach att_c (through feat_out and through LSTM 0's input block) in ONE two-term GEMM
         const float *wt_f, *wt_g;
         TE_TRY(w_t(E, "dec.feat_out.weight/att", WF.p + U, O, C, U + C, true, false, &wt_f, nullptr));
         TE_TRY(w_t(E, wih0 + "/att", E.Pm(wih0).p, 4 * U, C, ld0, true, false, &wt_g, nullptr));
         TE_L(fcl_linear2_fwd(dF0, O, wt_f, O, O, dG0, 4 * U, wt_g, 4 * U, 4 * U, nullptr, nullptr, 0, c.d_att_c, C, N, C, FCL_ACT_NONE, E.cur));
-    } else {
-        float* t = f32(E, N, C);
-        TE_TRY(dx_linear(E, dG0, nullptr, N, 4 * U, wih0 + "/att", E.Pm(wih0).p, 4 * U, C, ld0, t, C));
-        TE_L(fcl_add2d(c.d_att_c, C, t, C, N, C, 1.0f, nullptr, E.cur));
     }
     // prenet (batched over all cells)
     const std::string w0n = "dec.prenet.prenet.0.0.weight", b0n = "dec.prenet.prenet.0.0.bias", w1n = "dec.prenet.prenet.1.0.weight", b1n = "dec.prenet.prenet.1.0.bias";
@@ -1375,7 +1326,7 @@ static int te_backward_stage3(fcl_te& E) {  // encoder
         TE_L(fcl_sum_rows(srcs, ns, b.enc_valid, d_hs_live, nullptr, BT, C, E.cur));
     }
     // BiLSTM backward
-    float* dx = dx_planes() ? zf32(E, (long long)BT * Cc) : f32(E, BT, Cc);
+    float* dx = f32(E, BT, Cc);
     float* dgx2[2] = {nullptr, nullptr};
     {
         fcl_bilstm_bptt_t a{};
@@ -1394,8 +1345,7 @@ static int te_backward_stage3(fcl_te& E) {  // encoder
         TE_L(fcl_bilstm_bptt(&a, E.cur));
         for (int d = 0; d < 2; ++d) {
             float* dgx = f32(E, BT, 4 * H);
-            uint16_t* dgx_p = dx_planes() ? pl16(E, BT, 4 * H) : nullptr;
-            TE_L(fcl_gather_rows_fwd(dgs[d], b.perm_tb, dgx, dgx_p, BT, 4 * H, E.cur));  // back to (b, t) rows like x
+            TE_L(fcl_gather_rows_fwd(dgs[d], b.perm_tb, dgx, nullptr, BT, 4 * H, E.cur));  // back to (b, t) rows like x
             const std::string s_ = sfx[d];
             {
                 SideScope sc(E);
@@ -1406,14 +1356,8 @@ static int te_backward_stage3(fcl_te& E) {  // encoder
                 E.dw_pending = true;
             }
             dgx2[d] = dgx;
-            if (dx_planes()) {
-                const std::string wn = "enc.blstm.weight_ih_l0" + s_;
-                float* t = f32(E, BT, Cc);
-                TE_TRY(dx_linear(E, dgx, dgx_p, BT, 4 * H, wn, E.Pm(wn).p, 4 * H, Cc, Cc, t, Cc));
-                TE_L(fcl_add2d(dx, Cc, t, Cc, BT, Cc, 1.0f, nullptr, E.cur));
-            }
         }
-        if (!dx_planes()) {  // round 6: both directions' input gradients in ONE two-term GEMM
+        {  // round 6: both directions' input gradients in ONE two-term GEMM
             const std::string wf = "enc.blstm.weight_ih_l0", wr = "enc.blstm.weight_ih_l0_reverse";
             const float *wt_f, *wt_r;
             TE_TRY(w_t(E, wf, E.Pm(wf).p, 4 * H, Cc, Cc, true, false, &wt_f, nullptr));

@@ -142,17 +142,7 @@ int fcl_decoder_train_fwd(const fcl_decoder_train_t* a, fcl_stream_t stream) {
     // recurrences run as a WAVEFRONT: [L0(0)] -> [L0(1) | L1(0)] -> [L0(2) | L1(1)] -> ... -> [L1(lmax - 1)].  L0(t + 1) reads h0(t) from
     // h0[(t + 1) & 1] and writes h0[t & 1], whose last readers -- L0(t), L1(t - 1) -- ran in earlier launches; L1(t) reads h0(t) beside it.
     // One launch per pair where both steps run the same kernel family (round 5): lmax + 1 dependent launches instead of 2 lmax, and twice the
-    // workgroups per launch (fewer part-filled rounds of 128-row tiles at FCL-taco2-T width).  FCL_TRAIN_WAVEFRONT=0: the step-by-step order.
-    static const int wavefront = tunable("TRAIN_WAVEFRONT", 1);
-    if (!wavefront) {
-        for (int t = 0; t < a->lmax; ++t) {
-            int rc = launch_lstm_step(layer0(t), s);
-            if (rc) return rc;
-            rc = launch_lstm_step(layer1(t), s);
-            if (rc) return rc;
-        }
-        return 0;
-    }
+    // workgroups per launch (fewer part-filled rounds of 128-row tiles at FCL-taco2-T width).
     int rc = launch_lstm_step(layer0(0), s);
     if (rc) return rc;
     for (int t = 0; t < a->lmax; ++t) {
@@ -210,7 +200,7 @@ int fcl_decoder_bptt(const fcl_decoder_bptt_t* a, fcl_stream_t stream) {
         return g;
     };
     size_t off = total;
-    if (a->w1_cat_t && (!planes || a->w1_cat_t_p) && tunable("BPTT_FUSE", 1)) {
+    if (a->w1_cat_t && (!planes || a->w1_cat_t_p)) {
         // Four launches per step instead of five: the two GEMMs that leave layer 1's gate gradients (dg1 . W1_hh -> layer 1's carry, dg1 . W1_ih ->
         // layer 0's carry) are ONE GEMM against [W1_hh^T ; W1_ih^T] into X [N, 2U] = [carry of layer 1 | carry of layer 0], which both cell
         // kernels read and write in place (their "keep" path is the GEMMs' residual): 38 fewer dependent launches on a KD update's critical path
@@ -298,7 +288,7 @@ int fcl_bilstm_train_fwd(const fcl_bilstm_train_t* a, fcl_stream_t stream) {
     FCL_REQUIRE(a->b > 0 && a->t > 0 && a->h > 0 && (a->h & 3) == 0, FCL_ERR_SHAPE, "bilstm_train_fwd: bad sizes");
     hipStream_t s = (hipStream_t)stream;
     const int B = a->b, T = a->t, H = a->h;
-    if (!tunable("BILSTM_TRAIN_STEPS", 0)) {  // one persistent launch for both directions (H in {8,16,32,64,128})
+    {  // one persistent launch for both directions (H in {8,16,32,64,128}), the cooperating workgroups (H = 256), else the per-step launches below
         BilstmSave sv;
         for (int d = 0; d < 2; ++d) { sv.gates[d] = a->s[d][0]; sv.c_new[d] = a->s[d][1]; sv.c_old[d] = a->s[d][2]; sv.h_old[d] = a->s[d][3]; }
         sv.B = B;
@@ -353,7 +343,7 @@ int fcl_bilstm_bptt(const fcl_bilstm_bptt_t* a, fcl_stream_t stream) {
     FCL_REQUIRE(a->b > 0 && a->t > 0 && a->h > 0 && (a->h & 3) == 0 && a->ld_dout >= 2 * a->h, FCL_ERR_SHAPE, "bilstm_bptt: bad sizes");
     hipStream_t s = (hipStream_t)stream;
     const int B = a->b, T = a->t, H = a->h, G4 = 4 * a->h;
-    if (!tunable("BILSTM_TRAIN_STEPS", 0)) {
+    {  // the persistent / cooperating-workgroup kernels where they take H, else the per-step launches below
         BilstmBwd bw;
         for (int d = 0; d < 2; ++d) { bw.gates[d] = a->s[d][0]; bw.c_new[d] = a->s[d][1]; bw.c_old[d] = a->s[d][2]; bw.whh_t[d] = a->w_hh_t[d]; bw.dg[d] = a->dg[d]; }
         bw.d_out = a->d_out;

@@ -1,4 +1,4 @@
-"""Isolated Conv1d-on-planes timings (developer tool): FCL_PCONV=0/1 python tools/bench_conv.py"""
+"""Isolated Conv1d-on-planes timings (developer tool): python tools/bench_conv.py"""
 import sys, time
 sys.path.insert(0, ".")
 import numpy as np, torch

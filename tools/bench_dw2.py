@@ -27,7 +27,7 @@ SHAPES = [  # (m, n, k, taps, what)
     (13800, 512, 512, 5, "T: postnet conv"),
     (1400, 512, 512, 5, "T: encoder conv"),
 ]
-CONFIGS = [("old gemm_tn_kernel", {"FCL_DW_MFMA": "0"}), ("dw_mfma default", {}), ("dw_mfma all 128x128", {"FCL_DW_BIG_TILES_MIN": "1"}),
+CONFIGS = [("dw_mfma default", {}), ("dw_mfma all 128x128", {"FCL_DW_BIG_TILES_MIN": "1"}),
            ("dw_mfma all 64x64", {"FCL_DW_BIG_TILES_MIN": "100000"})]
 
 

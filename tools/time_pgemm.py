@@ -1,4 +1,4 @@
-"""Isolated timings of the pre-split GEMM (ops.linear_planes) at the training step's frame-sized shapes; FCL_PGEMM_CFG picks the tile configuration."""
+"""Isolated timings of the pre-split GEMM (ops.linear_planes) at the training step's frame-sized shapes."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,4 +22,4 @@ for m, n, k in ((24300, 1024, 256), (24300, 256, 1024), (24300, 512, 128), (2430
     e.record()
     torch.cuda.synchronize()
     us = s.elapsed_time(e) / 20 * 1e3
-    print("cfg %s  M %6d N %5d K %5d: %7.1f us  %6.1f TFLOP/s fp32-eq  (max err %.1e)" % (os.environ.get("FCL_PGEMM_CFG", "auto"), m, n, k, us, 2.0 * m * n * k / us / 1e6, err))
+    print("M %6d N %5d K %5d: %7.1f us  %6.1f TFLOP/s fp32-eq  (max err %.1e)" % (m, n, k, us, 2.0 * m * n * k / us / 1e6, err))

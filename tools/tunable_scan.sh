@@ -21,7 +21,5 @@ run TN_WORKGROUPS 512
 run TN_WORKGROUPS 2048
 run GEMM_SMALLM 128
 run GEMM_SMALLM 512
-run PLSTM_PAIR_NST2 1
-run TE_DX_PLANES 1
 run NOTHING 1
 cat $OUT/scan.log
