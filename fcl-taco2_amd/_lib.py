@@ -234,6 +234,13 @@ SIGNATURES = {
     "fcl_pwg_first_conv": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _P]),
     "fcl_pwg_layer_fwd": (_I, [_P, _P]),
     "fcl_pwg_last_fwd": (_I, [_P, _F, _P, _P, _P, _F, _P, _P, _P, C.c_int64, _I, _P]),
+    "fcl_pwg_maps_build": (_I, [_P, _P, _I, C.c_int64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fcl_pwg_gather_pad": (_I, [_P, C.c_int64, _P, _P, C.c_int64, _I, _P, _P]),
+    "fcl_pwg_noise_cap": (_I, [_P, C.c_int64, C.c_uint32, _P, _P, _P]),
+    "fcl_pwg_first_conv_cap": (_I, [_P, _P, _P, _P, C.c_int64, _I, _P, _P]),
+    "fcl_pwg_layer_cap_fwd": (_I, [_P, _P, _P]),
+    "fcl_pwg_last_cap_fwd": (_I, [_P, _F, _P, _P, _P, _F, _P, C.c_int64, _I, _P, _P]),
+    "fcl_pcm16_fwd": (_I, [_P, _P, C.c_int64, _P, _P, _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),
@@ -263,6 +270,7 @@ SIGNATURES = {
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 DROP_NONE, DROP_MASK, DROP_RNG = 0, 1, 2
 STATUS_GROUP_TIMEOUT, STATUS_ZERO_DURATION, STATUS_LMAX_CAP, STATUS_FRAMES_CAP, STATUS_ROWS_CAP = 1, 2, 4, 8, 16  # FCL_STATUS_* bits of a device status word
+STATUS_VOCODER_CAP, STATUS_PCM_NONFINITE = 32, 64  # the vocoder stage of a text -> waveform pass
 
 _lib = None
 

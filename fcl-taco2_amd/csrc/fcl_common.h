@@ -229,9 +229,9 @@ bool planes_ok(const GemmTerm* t, int n);                  // every term carries
 int launch_gemm_planes(const GemmArgs& a, hipStream_t s);  // gemm_planes.hip
 int launch_lstm_planes(const LstmStepArgs& a, hipStream_t s);
 int launch_lstm_planes_pair(const LstmStepArgs& a0, const LstmStepArgs& a1, hipStream_t s, bool* handled);  // two independent steps, one launch
-int launch_pwg_layer_fused(const fcl_pwg_layer_t& a, hipStream_t s);  // one Parallel WaveGAN residual block in one launch (r = 64, ksize = 3, aux <= 96)
+int launch_pwg_layer_fused(const fcl_pwg_layer_t& a, hipStream_t s, const int* live = nullptr);  // one Parallel WaveGAN residual block in one launch (r = 64, ksize = 3, aux <= 96)
 int launch_pwg_last_fused(const float* skips, float scale, const unsigned short* w1p, const float* b1, const float* w2, float b2, float* wav, long long m,
-                          hipStream_t s);  // last_conv_layers in one launch (64 skip channels)
+                          hipStream_t s, const int* live = nullptr);  // last_conv_layers in one launch (64 skip channels)
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 // dw_gemm.hip: dW[n, k] += sum_m a[m, n] * b[m + shift, k] on bf16x3 MFMAs with transposing LDS reads; false = shape left to gemm_tn_kernel
 bool launch_dw_mfma(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k, int shift0, int ntaps, size_t c_tap_stride,
@@ -250,6 +250,13 @@ int tunable(const char* name, int dflt);  // FCL_<NAME> environment override, re
 // `func` is launched on it (thread-safe; every later call is a map lookup).  Returns 0 or FCL_ERR_HIP.
 int ensure_dyn_lds(const void* func, int bytes);
 
+
+// wave-uniform read of word k of a small device record (e.g. the capacity vocoder's live record, fcl_pwg_maps_build): a uniform address in the
+// constant address space becomes ONE scalar load per wave, and the value lives in an SGPR (no vector register, no per-lane load)
+__device__ __forceinline__ int uniform_word(const int* rec, int k) {
+    typedef const int __attribute__((address_space(4))) cint_k;
+    return __builtin_amdgcn_readfirstlane(*reinterpret_cast<cint_k*>(reinterpret_cast<uintptr_t>(rec + k)));
+}
 
 // counter hash shared by the rng-dropout epilogue (and mirrored nowhere on the host: rng mode is the
 // production mode and is not bit-reproducible against the reference's torch RNG stream by design).

@@ -1396,7 +1396,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
 // AUXF: the auxiliary term at frame rate -- 3 x 2 + 1 chunks per tile instead of 3 x 2 + 3, the last one (coefficient lines x a 32-frame window of
 // the projected features) with a W tile that depends on the tile's frame.
 template <bool HI, int LW, bool AUXF>
-__global__ __launch_bounds__(64 * (8 + LW)) void pwg_layer_pkernel(const PwgFusedArgs a, const int ntiles) {
+__device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int ntiles) {
     using G = PGeo<4, 2, 2, 4, 3, LW>;
     constexpr int TM = 2, TN = 4, WN = 2, BM = 128, NST = 3, NCH = AUXF ? 7 : 9;
     constexpr int WOS = G::LDS_BYTES, GA = WOS + 32768;
@@ -1656,6 +1656,19 @@ __global__ __launch_bounds__(64 * (8 + LW)) void pwg_layer_pkernel(const PwgFuse
     }
 }
 
+template <bool HI, int LW, bool AUXF>
+__global__ __launch_bounds__(64 * (8 + LW)) void pwg_layer_pkernel(const PwgFusedArgs a, const int ntiles) {
+    pwg_layer_pbody<HI, LW, AUXF>(a, ntiles);
+}
+
+// capacity form (fcl_pwg_layer_cap_fwd; live = {frames, samples, ...} of fcl_pwg_maps_build, one scalar load per wave): a.M, the chunk strides and the grid are those of the CAPACITY; the tiles that are walked are those of the
+// live samples, read from the device.  live is a multiple of hop, hence of 128: every live tile is a full tile, as in an exact-size call.
+template <bool HI, int LW, bool AUXF>
+__global__ __launch_bounds__(64 * (8 + LW)) void pwg_layer_cap_pkernel(const PwgFusedArgs a, const int* __restrict__ live) {
+    const int ntiles = (min(uniform_word(live, 1), a.M) + 127) >> 7;
+    pwg_layer_pbody<HI, LW, AUXF>(a, ntiles);
+}
+
 template <int WM, int NST, bool HI>
 static int launch_pwg_cfg(const PwgFusedArgs& a, long long m, double flops, hipStream_t s) {
     using G = PGeo<WM, 2, 2, 4, NST, 2>;
@@ -1671,7 +1684,7 @@ static int launch_pwg_cfg(const PwgFusedArgs& a, long long m, double flops, hipS
     return check_hip(hipGetLastError(), "pwg_layer launch");
 }
 
-int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
+int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s, const int* live) {
     PwgFusedArgs a = {};
     const int R = L.r, ldx = R / 32, ldc = (L.aux + 31) / 32;
     for (int j = 0; j < L.ksize; ++j) {
@@ -1709,6 +1722,8 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
         a.pt_a = L.pt_a; a.pt_b = L.pt_b; a.hop = L.hop;
         FCL_REQUIRE(!dbg && exp_terms <= 0, FCL_ERR_INVALID, "pwg_layer_fwd: the frame-rate auxiliary term runs on the persistent kernel only");
     }
+    FCL_REQUIRE(!live || (!dbg && exp_terms <= 0 && !want_ts && (auxf || L.aux > 64)), FCL_ERR_SHAPE,
+                "pwg_layer_cap_fwd: the capacity form runs on the persistent kernel only (frame-rate auxiliary term, or 64 < aux <= 96; no developer switches)");
     if (!dbg && exp_terms <= 0 && (auxf || L.aux > 64)) {  // (the persistent kernel is written for 3 x 2 + 3 chunks: r = 64, ksize = 3, 64 < aux <= 96)
         constexpr int LDS = PGeo<4, 2, 2, 4, 3, 2>::LDS_BYTES + 2 * 32768;
         constexpr int lwv = 4;  // 4 loader waves over 2: 151.9 -> 145.1 ms per 30 blocks
@@ -1723,6 +1738,17 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
         const int ntiles = (int)((L.m + 127) / 128);
         static const int wg_per_cu = tunable("PWG_PERSIST_WGS", 0);  // 0: one workgroup per CU (160 KB of LDS each)
         int nwg = std::min(ntiles, wg_per_cu > 0 ? wg_per_cu : cus);
+        if (live) {  // the grid is the capacity's; workgroups without a live tile exit at once
+            typedef void (*ckern_t)(const PwgFusedArgs, const int*);
+            static const ckern_t ctable[2][2] = {{pwg_layer_cap_pkernel<false, lwv, false>, pwg_layer_cap_pkernel<false, lwv, true>},
+                                                 {pwg_layer_cap_pkernel<true, lwv, false>, pwg_layer_cap_pkernel<true, lwv, true>}};
+            const ckern_t cfn = ctable[hi ? 1 : 0][auxf ? 1 : 0];
+            const int rcc = ensure_dyn_lds(reinterpret_cast<const void*>(cfn), LDS);
+            if (rcc) return rcc;
+            ProfScope ps(hi ? "pwg_layer_cap_pkernel/bf16" : "pwg_layer_cap_pkernel", flops, (int)L.m, s);
+            hipLaunchKernelGGL(cfn, dim3((unsigned)nwg), dim3(64 * (8 + lwv)), LDS, s, a, live);
+            return check_hip(hipGetLastError(), "pwg_layer capacity launch");
+        }
         ProfScope ps(hi ? "pwg_layer_pkernel/bf16" : "pwg_layer_pkernel", flops, (int)L.m, s);
         hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(64 * (8 + lwv)), LDS, s, a, ntiles);
         return check_hip(hipGetLastError(), "pwg_layer persistent launch");
@@ -1737,10 +1763,9 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s) {
 // bf16x3 split go straight into LDS in the fragment layout (swizzled 128-byte lines, one 32-column chunk after the other), W1's planes are
 // staged once per workgroup, the 64 x 64 GEMM runs on the MFMA pipe, and the 64 -> 1 projection is an in-register dot + a 16-lane reduction.
 template <bool HI>
-__global__ __launch_bounds__(256) void pwg_last_kernel(const float* __restrict__ skips, float scale, const u16* __restrict__ w1p, const float* __restrict__ b1,
-                                                       const float* __restrict__ w2, float b2, float* __restrict__ wav, int M, int ntiles) {
+__device__ __forceinline__ void pwg_last_body(u8* smem, const float* __restrict__ skips, float scale, const u16* __restrict__ w1p, const float* __restrict__ b1,
+                                              const float* __restrict__ w2, float b2, float* __restrict__ wav, int M, int ntiles) {
     constexpr int TM = 2, TN = 4, AB = 0, WB = 32768;
-    __shared__ __attribute__((aligned(1024))) u8 smem[32768 + 16384];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < 1024; i += 256) {  // W1 [64, 64] planes -> LDS, chunk-major
         const int n = i >> 4, c = (i >> 3) & 1, p = i & 7;
@@ -1803,12 +1828,36 @@ __global__ __launch_bounds__(256) void pwg_last_kernel(const float* __restrict__
     }
 }
 
-int launch_pwg_last_fused(const float* skips, float scale, const u16* w1p, const float* b1, const float* w2, float b2, float* wav, long long m, hipStream_t s) {
+template <bool HI>
+__global__ __launch_bounds__(256) void pwg_last_kernel(const float* __restrict__ skips, float scale, const u16* __restrict__ w1p, const float* __restrict__ b1,
+                                                       const float* __restrict__ w2, float b2, float* __restrict__ wav, int M, int ntiles) {
+    __shared__ __attribute__((aligned(1024))) u8 smem[32768 + 16384];
+    pwg_last_body<HI>(smem, skips, scale, w1p, b1, w2, b2, wav, M, ntiles);
+}
+
+// capacity form: the samples and the tile count come from the device's live record; the grid is the capacity's
+template <bool HI>
+__global__ __launch_bounds__(256) void pwg_last_cap_kernel(const float* __restrict__ skips, float scale, const u16* __restrict__ w1p, const float* __restrict__ b1,
+                                                           const float* __restrict__ w2, float b2, float* __restrict__ wav, int m_cap, const int* __restrict__ live) {
+    __shared__ __attribute__((aligned(1024))) u8 smem[32768 + 16384];
+    const int M = min(uniform_word(live, 1), m_cap);
+    if ((int)blockIdx.x * 128 >= M) return;
+    pwg_last_body<HI>(smem, skips, scale, w1p, b1, w2, b2, wav, M, (M + 127) >> 7);
+}
+
+int launch_pwg_last_fused(const float* skips, float scale, const u16* w1p, const float* b1, const float* w2, float b2, float* wav, long long m, hipStream_t s,
+                          const int* live) {
     const bool hi = gemm_mode() == FCL_GEMM_BF16;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const int ntiles = (int)((m + 127) / 128);
     const unsigned grid = (unsigned)std::min(ntiles, cus * 3);  // 48 KB of LDS: three workgroups per CU
+    if (live) {
+        ProfScope ps(hi ? "pwg_last_cap_kernel/bf16" : "pwg_last_cap_kernel", 2.0 * (double)m * 64 * 65, (int)m, s);
+        if (hi) hipLaunchKernelGGL(pwg_last_cap_kernel<true>, dim3(grid), dim3(256), 0, s, skips, scale, w1p, b1, w2, b2, wav, (int)m, live);
+        else hipLaunchKernelGGL(pwg_last_cap_kernel<false>, dim3(grid), dim3(256), 0, s, skips, scale, w1p, b1, w2, b2, wav, (int)m, live);
+        return check_hip(hipGetLastError(), "pwg_last capacity launch");
+    }
     ProfScope ps(hi ? "pwg_last_kernel/bf16" : "pwg_last_kernel", 2.0 * (double)m * 64 * 65, (int)m, s);
     if (hi) hipLaunchKernelGGL(pwg_last_kernel<true>, dim3(grid), dim3(256), 0, s, skips, scale, w1p, b1, w2, b2, wav, (int)m, ntiles);
     else hipLaunchKernelGGL(pwg_last_kernel<false>, dim3(grid), dim3(256), 0, s, skips, scale, w1p, b1, w2, b2, wav, (int)m, ntiles);

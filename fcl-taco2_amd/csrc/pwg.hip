@@ -176,13 +176,192 @@ __global__ __launch_bounds__(256) void pwg_aux_coeff_kernel(const float* __restr
 }
 
 // z ~ N(0, 1): Box-Muller on two hashed 24-bit uniforms per element (counter-based: element i of a given seed is reproducible on any grid)
+__device__ __forceinline__ float pwg_noise_at(long long i, unsigned int seed) {
+    const unsigned int lo = (unsigned int)i, hi = (unsigned int)(i >> 32);
+    const unsigned int h1 = hash_u32(lo ^ hash_u32(seed ^ (hi * 0x9E3779B9u))), h2 = hash_u32(h1 ^ 0x85EBCA6Bu ^ lo);
+    const float u1 = ((h1 >> 8) + 1) * (1.0f / 16777216.0f), u2 = (h2 >> 8) * (1.0f / 16777216.0f);  // u1 in (0, 1]
+    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530717958647692f * u2);
+}
+
 __global__ __launch_bounds__(256) void pwg_noise_kernel(float* __restrict__ z, long long n, unsigned int seed) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned int lo = (unsigned int)i, hi = (unsigned int)(i >> 32);
-        const unsigned int h1 = hash_u32(lo ^ hash_u32(seed ^ (hi * 0x9E3779B9u))), h2 = hash_u32(h1 ^ 0x85EBCA6Bu ^ lo);
-        const float u1 = ((h1 >> 8) + 1) * (1.0f / 16777216.0f), u2 = (h2 >> 8) * (1.0f / 16777216.0f);  // u1 in (0, 1]
-        z[i] = sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530717958647692f * u2);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) z[i] = pwg_noise_at(i, seed);
+}
+
+// ---- capacity forms (fcl_hip.h "capacity form of the vocoder"): every buffer and grid is sized by a CAPACITY; what is live comes from the device.
+// live record int32 [4] = {frames, samples, padded frame rows, utterances with frames}, written by pwg_maps_kernel.
+constexpr int PWG_MAPS_MAX_UTT = 1024;
+
+// largest u in [0, n) with a[u] <= v (a non-decreasing, a[0] <= v): with equal neighbours (utterances without frames) the LAST one, i.e. the
+// utterance that owns v
+__device__ __forceinline__ int pwg_owner(const int* a, int n, int v) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] <= v) lo = mid;
+        else hi = mid;
     }
+    return lo;
+}
+
+// The vocoder's index maps from the synthesis pass's frame starts, to capacity, in one launch.  Every workgroup rebuilds the two small prefix tables
+// (frame starts, padded-row starts: B + 1 words each) in LDS and then fills its share of the maps.  Frames [live, frames_cap) form one pseudo-utterance
+// (index B) whose padded rows are [live_pad, pad_cap) and whose samples are [live * hop, frames_cap * hop): dead rows only ever see dead rows.
+__global__ __launch_bounds__(256) void pwg_maps_kernel(const int* __restrict__ utt_frame0, unsigned int* status, int B, int frames_cap, int ctx, int hop,
+                                                       int* __restrict__ pad_idx, int* __restrict__ lo, int* __restrict__ hi, int* __restrict__ keep,
+                                                       int* __restrict__ frame_utt, int* __restrict__ utt_off, int* __restrict__ seg_lo,
+                                                       int* __restrict__ seg_hi, int* __restrict__ live) {
+    __shared__ int off[PWG_MAPS_MAX_UTT + 1], pb[PWG_MAPS_MAX_UTT + 1];
+    __shared__ int s_ok;
+    const int tid = threadIdx.x;
+    for (int i = tid; i <= B; i += blockDim.x) off[i] = utt_frame0[i];
+    __syncthreads();
+    if (tid == 0) {
+        // *status is read here by every workgroup while workgroup 0 may OR FCL_STATUS_VOCODER_CAP into it at the end of the kernel; nothing orders
+        // the two, and nothing has to.  Workgroup 0 writes only when ITS `ok` is false, and `ok` is a function of the word as it was at launch and of
+        // utt_frame0 (read-only here): a reader that sees the old word evaluates exactly what workgroup 0 evaluated -> false; a reader that sees the
+        // new word sees a non-zero word -> false as well.  When `ok` is true nobody writes.  So all workgroups agree on `ok`, whatever they observe.
+        bool ok = *status == 0u && off[0] == 0 && off[B] <= frames_cap;
+        for (int u = 0; u < B; ++u) ok = ok && off[u + 1] >= off[u];
+        s_ok = ok ? 1 : 0;
+    }
+    __syncthreads();
+    const bool ok = s_ok != 0;
+    if (!ok)
+        for (int i = tid; i <= B; i += blockDim.x) off[i] = 0;  // nothing is live: the whole capacity is the dead pseudo-utterance
+    __syncthreads();
+    if (tid == 0) {
+        int p = 0;
+        for (int u = 0; u < B; ++u) {
+            pb[u] = p;
+            if (off[u + 1] > off[u]) p += off[u + 1] - off[u] + 2 * ctx;
+        }
+        pb[B] = p;
+    }
+    __syncthreads();
+    const int nlive = off[B], live_pad = pb[B];
+    const int pad_cap = frames_cap + 2 * ctx * (B + 1);
+    const long long m_live = (long long)nlive * hop, m_cap = (long long)frames_cap * hop;
+    const long long g0 = blockIdx.x * (long long)blockDim.x + tid, gs = (long long)gridDim.x * blockDim.x;
+    for (long long f = g0; f < frames_cap; f += gs) {
+        int u = B, k = live_pad + ctx + ((int)f - nlive);
+        if (f < nlive) {
+            u = pwg_owner(off, B, (int)f);
+            k = pb[u] + ctx + ((int)f - off[u]);
+        }
+        frame_utt[f] = u;
+        keep[f] = k;
+    }
+    for (long long j = g0; j < pad_cap; j += gs) {
+        int src = 0, l = live_pad, h = pad_cap;
+        if (j < live_pad) {
+            const int u = pwg_owner(pb, B, (int)j), n = off[u + 1] - off[u];
+            src = off[u] + min(max((int)j - pb[u] - ctx, 0), n - 1);
+            l = pb[u];
+            h = pb[u] + n + 2 * ctx;
+        }
+        pad_idx[j] = src;
+        lo[j] = l;
+        hi[j] = h;
+    }
+    for (long long q = g0; q * 4 < m_cap; q += gs) {  // four samples of one frame (hop % 4 == 0) per item
+        const long long m = q * 4;
+        int l = (int)m_live, h = (int)m_cap;
+        if (m < m_live) {
+            const int u = pwg_owner(off, B, (int)(m / hop));
+            l = off[u] * hop;
+            h = off[u + 1] * hop;
+        }
+        *reinterpret_cast<int4*>(seg_lo + m) = make_int4(l, l, l, l);
+        *reinterpret_cast<int4*>(seg_hi + m) = make_int4(h, h, h, h);
+    }
+    if (blockIdx.x == 0) {
+        for (int i = tid; i <= B; i += blockDim.x) utt_off[i] = off[i];
+        if (tid == 0) {
+            utt_off[B + 1] = frames_cap;
+            int nz = 0;
+            for (int u = 0; u < B; ++u) nz += off[u + 1] > off[u];
+            live[0] = nlive;
+            live[1] = (int)m_live;
+            live[2] = live_pad;
+            live[3] = nz;
+            if (!ok) atomicOr(status, (unsigned int)FCL_STATUS_VOCODER_CAP);
+        }
+    }
+}
+
+// replicate-padded feature rows of the live utterances; zeros for the dead rows (whatever the synthesis buffer holds past its total never enters)
+__global__ __launch_bounds__(256) void pwg_gather_pad_kernel(const float* __restrict__ mel, int mel_rows, const int* __restrict__ pad_idx,
+                                                             const int* __restrict__ live, int pad_cap, int C, float* __restrict__ out) {
+    const int cq = C >> 2, live_pad = uniform_word(live, 2);
+    const long long total = (long long)pad_cap * cq;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(i / cq), c = (int)(i - (long long)j * cq) * 4;
+        f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+        if (j < live_pad) {
+            const int src = pad_idx[j];
+            if ((unsigned)src < (unsigned)mel_rows) v = *reinterpret_cast<const f32x4_t*>(mel + (size_t)src * C + c);
+        }
+        *reinterpret_cast<f32x4_t*>(out + (size_t)j * C + c) = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void pwg_noise_cap_kernel(float* __restrict__ z, long long n_cap, unsigned int seed, const unsigned int* __restrict__ seed_dev,
+                                                            const int* __restrict__ live) {
+    const long long n = min((long long)uniform_word(live, 1), n_cap);
+    if (seed_dev) seed += *seed_dev;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) z[i] = pwg_noise_at(i, seed);
+}
+
+// first_conv into chunk-major planes whose chunk stride is the capacity's
+__global__ __launch_bounds__(256) void pwg_first_conv_cap_kernel(const float* __restrict__ z, const float* __restrict__ w, const float* __restrict__ b,
+                                                                 u16* __restrict__ xp, long long m_cap, int R, const int* __restrict__ live) {
+    const int rq = R >> 2;
+    const long long total = min((long long)uniform_word(live, 1), m_cap) * rq;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long m = i / rq;
+        const int ch = (int)(i - m * rq) * 4;
+        const float zm = z[m];
+        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(w + ch) * zm + *reinterpret_cast<const f32x4_t*>(b + ch);
+        uint2 h, l;
+        split4(v, h, l);
+        u16* line = xp + ((size_t)(ch >> 5) * m_cap + m) * 64 + (ch & 31);
+        *reinterpret_cast<uint2*>(line) = h;
+        *reinterpret_cast<uint2*>(line + 32) = l;
+    }
+}
+
+// float waveform -> int16: clip(rint(double(x) * 32767), -32768, 32767), ties to even (a float times 32767 is exact in double, so this is the numpy
+// rule of vocoder_decode.write_wav bit for bit); a non-finite sample becomes 0 and raises FCL_STATUS_PCM_NONFINITE.  Four samples per item.
+__global__ __launch_bounds__(256) void pwg_pcm16_kernel(const float* __restrict__ wav, short* __restrict__ pcm, long long n_cap, const int* __restrict__ live,
+                                                        unsigned int* status) {
+    const long long n = live ? min((long long)uniform_word(live, 1), n_cap) : n_cap;
+    bool bad = false;
+    for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q * 4 < n; q += (long long)gridDim.x * blockDim.x) {
+        const long long i = q * 4;
+        short o[4] = {0, 0, 0, 0};
+        if (i + 4 <= n) {
+            const f32x4_t v = *reinterpret_cast<const f32x4_t*>(wav + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float x = v[e];
+                if (!(fabsf(x) <= 3.4028234663852886e38f)) { bad = true; continue; }
+                o[e] = (short)fmin(fmax(rint((double)x * 32767.0), -32768.0), 32767.0);
+            }
+            uint2 w;
+            w.x = (unsigned)(unsigned short)o[0] | ((unsigned)(unsigned short)o[1] << 16);
+            w.y = (unsigned)(unsigned short)o[2] | ((unsigned)(unsigned short)o[3] << 16);
+            *reinterpret_cast<uint2*>(pcm + i) = w;
+        } else {
+            for (long long k = i; k < n; ++k) {
+                const float x = wav[k];
+                short r = 0;
+                if (!(fabsf(x) <= 3.4028234663852886e38f)) bad = true;
+                else r = (short)fmin(fmax(rint((double)x * 32767.0), -32768.0), 32767.0);
+                pcm[k] = r;
+            }
+        }
+    }
+    if (bad) atomicOr(status, (unsigned int)FCL_STATUS_PCM_NONFINITE);
 }
 
 static unsigned grid_1d(long long n, int per_block) {
@@ -228,6 +407,84 @@ int fcl_pwg_first_conv(const float* z, const float* w, const float* b, float* x,
                 "pwg_first_conv: w / b / x must be 16-byte aligned, the planes 128-byte aligned");
     hipLaunchKernelGGL(pwg_first_conv_kernel, dim3(grid_1d(m * (r / 4), 256)), dim3(256), 0, (hipStream_t)stream, z, w, b, x, xp, (long long)m, r, chunk_major);
     return check_hip(hipGetLastError(), "pwg_first_conv");
+}
+
+int fcl_pwg_maps_build(const int32_t* utt_frame0, uint32_t* status, int batch, int64_t frames_cap, int ctx, int hop, int32_t* pad_idx, int32_t* lo, int32_t* hi,
+                       int32_t* keep, int32_t* frame_utt, int32_t* utt_off, int32_t* seg_lo, int32_t* seg_hi, int32_t* live, fcl_stream_t stream) {
+    FCL_REQUIRE(utt_frame0 && status && pad_idx && lo && hi && keep && frame_utt && utt_off && seg_lo && seg_hi && live, FCL_ERR_INVALID,
+                "pwg_maps_build: null argument");
+    FCL_REQUIRE(batch >= 1 && batch <= PWG_MAPS_MAX_UTT && frames_cap >= 1 && ctx >= 0 && ctx <= 64, FCL_ERR_INVALID,
+                "pwg_maps_build: 1 <= batch <= %d, frames_cap >= 1 and 0 <= aux_context_window <= 64 expected", PWG_MAPS_MAX_UTT);
+    FCL_REQUIRE(hop >= 128 && hop % 128 == 0, FCL_ERR_SHAPE, "pwg_maps_build: the capacity form needs a hop that is a multiple of 128 (got %d)", hop);
+    FCL_REQUIRE(frames_cap * (int64_t)hop < 0x7fffffffLL && frames_cap + 2LL * ctx * (batch + 1) < 0x7fffffffLL, FCL_ERR_SHAPE,
+                "pwg_maps_build: frames_cap * hop must stay below 2^31 samples");
+    FCL_REQUIRE(aligned16(seg_lo) && aligned16(seg_hi), FCL_ERR_ALIGN, "pwg_maps_build: seg_lo / seg_hi must be 16-byte aligned");
+    ProfScope ps("pwg_maps_kernel", 0.0, (double)frames_cap, (hipStream_t)stream);
+    const unsigned grid = std::min(grid_1d(frames_cap * (int64_t)hop / 4, 1024), 2048u);
+    hipLaunchKernelGGL(pwg_maps_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, utt_frame0, status, batch, (int)frames_cap, ctx, hop, pad_idx, lo, hi, keep,
+                       frame_utt, utt_off, seg_lo, seg_hi, live);
+    return check_hip(hipGetLastError(), "pwg_maps_build");
+}
+
+int fcl_pwg_gather_pad(const float* mel, int64_t mel_rows, const int32_t* pad_idx, const int32_t* live, int64_t pad_cap, int c, float* out, fcl_stream_t stream) {
+    FCL_REQUIRE(mel && pad_idx && live && out && mel_rows >= 1 && mel_rows <= 0x7fffffffLL && pad_cap >= 1 && pad_cap <= 0x7fffffffLL && c > 0 && (c & 3) == 0,
+                FCL_ERR_INVALID, "pwg_gather_pad: bad arguments (channels must be a multiple of 4)");
+    FCL_REQUIRE(aligned16(mel) && aligned16(out), FCL_ERR_ALIGN, "pwg_gather_pad: mel / out must be 16-byte aligned");
+    ProfScope ps("pwg_gather_pad_kernel", 0.0, (double)pad_cap, (hipStream_t)stream);
+    hipLaunchKernelGGL(pwg_gather_pad_kernel, dim3(grid_1d(pad_cap * (c / 4), 256)), dim3(256), 0, (hipStream_t)stream, mel, (int)mel_rows, pad_idx, live,
+                       (int)pad_cap, c, out);
+    return check_hip(hipGetLastError(), "pwg_gather_pad");
+}
+
+int fcl_pwg_noise_cap(float* z, int64_t n_cap, uint32_t seed, const uint32_t* seed_dev, const int32_t* live, fcl_stream_t stream) {
+    FCL_REQUIRE(z && live && n_cap > 0, FCL_ERR_INVALID, "pwg_noise_cap: bad arguments");
+    ProfScope ps("pwg_noise_cap_kernel", 0.0, (double)n_cap, (hipStream_t)stream);
+    hipLaunchKernelGGL(pwg_noise_cap_kernel, dim3(grid_1d(n_cap, 1024)), dim3(256), 0, (hipStream_t)stream, z, (long long)n_cap, seed, seed_dev, live);
+    return check_hip(hipGetLastError(), "pwg_noise_cap");
+}
+
+int fcl_pwg_first_conv_cap(const float* z, const float* w, const float* b, uint16_t* xp, int64_t m_cap, int r, const int32_t* live, fcl_stream_t stream) {
+    FCL_REQUIRE(z && w && b && xp && live && m_cap > 0 && r > 0 && (r & 31) == 0, FCL_ERR_INVALID, "pwg_first_conv_cap: bad arguments (R must be a multiple of 32)");
+    FCL_REQUIRE(aligned16(w) && aligned16(b) && (reinterpret_cast<uintptr_t>(xp) & 127u) == 0, FCL_ERR_ALIGN,
+                "pwg_first_conv_cap: w / b must be 16-byte aligned, the planes 128-byte aligned");
+    ProfScope ps("pwg_first_conv_cap_kernel", 0.0, (double)m_cap, (hipStream_t)stream);
+    hipLaunchKernelGGL(pwg_first_conv_cap_kernel, dim3(grid_1d(m_cap * (r / 4), 256)), dim3(256), 0, (hipStream_t)stream, z, w, b, xp, (long long)m_cap, r, live);
+    return check_hip(hipGetLastError(), "pwg_first_conv_cap");
+}
+
+int fcl_pwg_layer_cap_fwd(const fcl_pwg_layer_t* a, const int32_t* live, fcl_stream_t stream) {
+    FCL_REQUIRE(a && live && a->m > 0 && a->xp_out && a->xp && (a->kp || (a->cp && a->w_aux_p)) && a->w_conv_p && a->b_conv && a->w_os_p && a->b_os && a->skips &&
+                    a->seg_lo && a->seg_hi,
+                FCL_ERR_INVALID, "pwg_layer_cap_fwd: null argument (the capacity form is the one-launch block: xp_out is required)");
+    FCL_REQUIRE(a->r == 64 && a->ksize == 3 && a->aux > 0 && a->aux <= 96 && a->dilation >= 1 && a->xp_out != a->xp, FCL_ERR_SHAPE,
+                "pwg_layer_cap_fwd: the capacity form is built for r = 64, ksize = 3, aux <= 96 and needs xp_out != xp");
+    FCL_REQUIRE(a->m <= 0x7fffffffLL && a->m % 128 == 0, FCL_ERR_SHAPE, "pwg_layer_cap_fwd: the capacity must be a multiple of 128 samples below 2^31");
+    FCL_REQUIRE(((reinterpret_cast<uintptr_t>(a->xp) | reinterpret_cast<uintptr_t>(a->xp_out) | reinterpret_cast<uintptr_t>(a->cp)) & 127u) == 0, FCL_ERR_ALIGN,
+                "pwg_layer_cap_fwd: xp / xp_out / cp must be 128-byte aligned");
+    if (a->kp) {
+        FCL_REQUIRE(a->pt_a && a->pt_b && a->ld_pt > 0, FCL_ERR_INVALID, "pwg_layer_cap_fwd: the frame-rate auxiliary term needs pt_a / pt_b / ld_pt");
+        FCL_REQUIRE(a->hop > 0 && a->hop % 128 == 0, FCL_ERR_SHAPE, "pwg_layer_cap_fwd: hop must be a multiple of 128");
+        FCL_REQUIRE(((reinterpret_cast<uintptr_t>(a->kp) | reinterpret_cast<uintptr_t>(a->pt_a) | reinterpret_cast<uintptr_t>(a->pt_b)) & 127u) == 0, FCL_ERR_ALIGN,
+                    "pwg_layer_cap_fwd: kp / pt_a / pt_b must be 128-byte aligned");
+        FCL_REQUIRE((a->m + a->hop - 1) / a->hop + 16 <= (int64_t)a->ld_pt * 32, FCL_ERR_SHAPE, "pwg_layer_cap_fwd: ld_pt does not cover the capacity's frames");
+    }
+    return launch_pwg_layer_fused(*a, (hipStream_t)stream, live);
+}
+
+int fcl_pwg_last_cap_fwd(const float* skips, float scale, const uint16_t* w1p, const float* b1, const float* w2, float b2, float* wav, int64_t m_cap, int s_ch,
+                         const int32_t* live, fcl_stream_t stream) {
+    FCL_REQUIRE(skips && w1p && b1 && w2 && wav && live && m_cap > 0 && m_cap <= 0x7fffffffLL, FCL_ERR_INVALID, "pwg_last_cap_fwd: bad arguments");
+    FCL_REQUIRE(s_ch == 64, FCL_ERR_SHAPE, "pwg_last_cap_fwd: the capacity form is built for 64 skip channels (got %d)", s_ch);
+    FCL_REQUIRE(aligned16(skips) && (reinterpret_cast<uintptr_t>(w1p) & 15u) == 0, FCL_ERR_ALIGN, "pwg_last_cap_fwd: skips / w1p must be 16-byte aligned");
+    return launch_pwg_last_fused(skips, scale, w1p, b1, w2, b2, wav, m_cap, (hipStream_t)stream, live);
+}
+
+int fcl_pcm16_fwd(const float* wav, int16_t* pcm, int64_t n_cap, const int32_t* live, uint32_t* status, fcl_stream_t stream) {
+    FCL_REQUIRE(wav && pcm && status && n_cap > 0, FCL_ERR_INVALID, "pcm16_fwd: bad arguments");
+    FCL_REQUIRE(aligned16(wav) && (reinterpret_cast<uintptr_t>(pcm) & 7u) == 0, FCL_ERR_ALIGN, "pcm16_fwd: wav must be 16-byte, pcm 8-byte aligned");
+    ProfScope ps("pwg_pcm16_kernel", 0.0, (double)n_cap, (hipStream_t)stream);
+    hipLaunchKernelGGL(pwg_pcm16_kernel, dim3(grid_1d((n_cap + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, wav, pcm, (long long)n_cap, live, status);
+    return check_hip(hipGetLastError(), "pcm16_fwd");
 }
 
 int fcl_pwg_layer_fwd(const fcl_pwg_layer_t* a, fcl_stream_t stream) {

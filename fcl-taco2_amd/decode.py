@@ -159,6 +159,17 @@ class _ScaledMaps(object):
         self.n_frames = int(np.ceil(maps.n_frames * ratio))
 
 
+def widened_caps(engine, maps, old, n_rows):
+    """Capacities of a bucket after one of its batches (exact maps `maps`, from its eager redo) overflowed `old`: more slack on every count, never
+    less than before, and every step may keep every row."""
+    g = _grown_caps(engine, maps, n_rows, scale=1.6)
+    lmax = max(g.lmax, old.lmax)
+    return engine.Caps(lmax, max(g.frames, old.frames), np.full(lmax, n_rows, np.int32), tail_from=g.tail_from)
+
+
+grown_caps, ScaledMaps = _grown_caps, _ScaledMaps  # the capacity sizing shared with the text -> waveform driver (tts.py)
+
+
 SHARE_GRAPH_POOLS = os.environ.get("FCL_DECODE_SHARE_POOLS", "1") not in ("", "0")  # the graphs of one pass stream share a memory pool (first call: fewer allocations)
 ESTIMATE_CAPS = os.environ.get("FCL_DECODE_ESTIMATE_CAPS", "1") not in ("", "0")  # capacities of later buckets from phoneme counts (0: one eager batch per bucket)
 MAX_BUCKETS = 8  # captured-graph pools kept per (batch size, depth): least recently used buckets are released beyond this
@@ -298,9 +309,7 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
                     for it in [p_ for p_ in pending if p_[0] is pool]:
                         pending.remove(it)
                         frames += harvest(it)
-                    g = _grown_caps(engine, pool.grow, batch_size * t_cap, scale=1.6)
-                    lmax = max(g.lmax, pool.caps.lmax)
-                    caps = engine.Caps(lmax, max(g.frames, pool.caps.frames), np.full(lmax, batch_size * t_cap, np.int32), tail_from=g.tail_from)
+                    caps = widened_caps(engine, pool.grow, pool.caps, batch_size * t_cap)
                     pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, caps, streams, seed + 31 * bi, controlled)
                 cal = cache.get(("calibration", batch_size) + ckey)  # (exact maps, phoneme count) of the first eagerly calibrated batch of this model
                 if pool is None and cal is not None and ESTIMATE_CAPS:

@@ -596,14 +596,17 @@ class BatchRunner(object):
     forced=True: the graph takes uploaded durations (load(xs, durs)); forced=False: it contains the duration predictor + rounding."""
 
     def __init__(self, plan, batch, t_cap, caps, forced=True, stream=None, dropout_mode=ops.DROP_RNG, seed=0, depth=3, pack_outputs=False, mempool=None,
-                 controls=False):
+                 controls=False, tail=None):
         """pack_outputs (round 6, the decode driver): the graph also gathers its three results -- mel [frames cap, odim], frame starts [B + 1], status word --
         into ONE float32 buffer `self.out` (two tiny copies and a ~5 us device copy inside the graph), so that a batch costs the host one device-to-host copy call
         instead of three (the driver's loop is bound by its enqueue time: 3 x ~70 us of copy calls out of ~470 us per batch).
         mempool: a torch graph-pool handle shared by the graphs that replay on THIS stream only (stream order keeps two of them from running at once): later
         captures reuse the intermediates' memory of earlier ones instead of allocating theirs (a first decode() call: ~500 allocations -> ~150).
         controls: the block also carries a [batch * t_cap, 5] prosody-control segment (load(prosody=...), identity by default) that the graph's ctl
-        kernels read, so one capture serves any control values; False: the block and the graph are those of an uncontrolled pass."""
+        kernels read, so one capture serves any control values; False: the block and the graph are those of an uncontrolled pass.
+        tail: optional callable(runner), invoked INSIDE the capture right after the synthesis pass, on the runner's stream (self.mel, self._frames,
+        self.status and self.seed_word are set): what it enqueues becomes part of the same graph, behind the pass (SpeechRunner: the capacity
+        vocoder).  It must be capturable and already warmed up.  None: the capture is the synthesis pass alone."""
         dev = plan.device
         self.controls = bool(controls)
         self.plan, self.B, self.T, self.caps, self.forced = plan, int(batch), int(t_cap), caps, bool(forced)
@@ -676,6 +679,8 @@ class BatchRunner(object):
                 else:
                     ops.u32_add(self.seed_word, 1)
                 self.mel, self._frames = run(plan, p, dropout_mode, seed=seed, seed_dev=self.seed_word, caps=caps, status=self.status)
+                if tail is not None:
+                    tail(self)
                 self.out = None
                 if pack_outputs:
                     n, b1 = self.mel.numel(), self.B + 1
@@ -788,3 +793,53 @@ class BatchRunner(object):
         self.stream.synchronize()
         self._frames._host = None
         return self._frames.resolve()[: self.n_loaded]
+
+
+class SpeechRunner(BatchRunner):
+    """Text -> waveform in ONE captured graph per batch: a BatchRunner whose graph continues, on the same stream (a chain, no parallel branches),
+    into the capacity form of the vocoder (vocoder.CapacitySynth: device-built index maps, live-extent launches) and the PCM conversion.  The
+    durations -- predicted (forced=False, the default here), forced, or prosody-controlled -- never reach the host: the vocoder takes the pass's
+    device frame starts, and both stages report into the runner's one status word.
+
+        r = SpeechRunner(plan, gen, batch=64, t_cap=100, caps=caps)        # voc_frames_cap defaults to caps.frames
+        r.load(xs); r.replay(); pcm = r.waveforms()                        # list of int16 arrays, hop x frames samples each
+
+    The vocoder's noise seed is `seed` + the runner's device seed word, which the graph advances once per replay: replays of one batch differ,
+    and replay k of a runner built with a given seed is reproducible (`noise_seed()` tells the seed of the last replay).
+    Memory: vocoder.CapacitySynth holds 1082 bytes per capacity sample (`self.synth.nbytes`): 10.4 GB at the measured BASELINE configs[4] capacity
+    (64 utterances of 60 - 100 phonemes, 37 632 frames)."""
+
+    def __init__(self, plan, gen, batch, t_cap, caps, voc_frames_cap=None, forced=False, stream=None, dropout_mode=ops.DROP_RNG, seed=0, depth=3,
+                 pack_outputs=False, mempool=None, controls=False):
+        from .vocoder import CapacitySynth  # (vocoder.py imports nothing from here)
+
+        if int(plan.hp.odim) != int(gen.plan.A):
+            raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: the model writes %d mel channels, the vocoder takes %d" % (plan.hp.odim, gen.plan.A))
+        if torch.device(gen.plan.device) != torch.device(plan.device):
+            raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: model and vocoder must live on one device")
+        self.gen, self.hop, self.seed = gen, int(gen.plan.hop), int(seed)
+        with torch.cuda.device(plan.device):
+            self.synth = CapacitySynth(gen, batch, int(voc_frames_cap) if voc_frames_cap else caps.frames, seed=seed)
+        BatchRunner.__init__(self, plan, batch, t_cap, caps, forced=forced, stream=stream, dropout_mode=dropout_mode, seed=seed, depth=depth,
+                             pack_outputs=pack_outputs, mempool=mempool, controls=controls, tail=SpeechRunner._vocoder_tail)
+        self.pcm, self.live = self.synth.pcm, self.synth.live
+
+    def _vocoder_tail(self):
+        self.synth.run(self.mel, self._frames.utt_frame0, self.status, seed_dev=self.seed_word)
+
+    def noise_seed(self):
+        """Synchronising: the vocoder noise seed of the last replay (what `synthesize_packed(..., seed=)` needs to draw the same noise)."""
+        self.stream.synchronize()
+        return (self.seed + int(self.seed_word.item())) & 0xFFFFFFFF
+
+    def waveforms(self):
+        """Synchronising (once): the last replay's 16-bit PCM, one int16 array of hop x frames samples per loaded utterance.  Raises FclError when
+        either stage reported into the status word: a synthesis or vocoder capacity, a zero duration, a non-finite sample."""
+        self.stream.synchronize()
+        bits = int(self.status.item()) & 0xFFFFFFFF
+        if bits:
+            self.status.zero_()
+            raise ops._lib.FclError("fcl-taco2_amd: device status 0x%x: %s" % (bits, ops.status_message(bits)))
+        f0 = self._frames.utt_frame0.cpu().numpy().astype(np.int64) * self.hop
+        pcm = self.pcm[: int(f0[self.B])].cpu().numpy()
+        return [pcm[int(f0[i]) : int(f0[i + 1])] for i in range(self.n_loaded)]

@@ -8,6 +8,7 @@ are parameter CONTAINERS (names, shapes, reference initialisation); they are nev
 """
 import argparse
 
+import numpy as np
 import torch
 
 from .. import engine, ops
@@ -322,6 +323,27 @@ class Tacotron2Base(TTSInterface, torch.nn.Module):
         return engine.synthesize(plan, [cpu(x) for x in xs], None if durs is None else [cpu(d).reshape(-1) for d in durs],
                                  None if f0s is None else [cpu(f) for f in f0s], None if energies is None else [cpu(e) for e in energies],
                                  dropout_mode=dropout_mode, prenet_keep=prenet_keep, seed=seed, spembs=spembs, prosody=prosody)
+
+    @torch.no_grad()
+    def synthesize_speech(self, xs, vocoder, prosody=None, spembs=None, seed=None):
+        """Text -> audio for callers that hold a model object: xs = phoneme-id sequences, vocoder = a vocoder.ParallelWaveGANGenerator on the
+        model's device.  Returns one int16 array of hop x frames samples per utterance (the 16-bit PCM `vocoder_decode.write_wav` would write:
+        fcl_pcm16_fwd on the device).  Eager: synthesis with predicted durations, the frame counts on the host, the exact-size vocoder; a loop over
+        many batches belongs in engine.SpeechRunner (one captured graph per batch; `python -m fcl_taco2_amd.tts`).  seed: noise / dropout seed
+        (default: drawn from torch's generator, so torch.manual_seed makes a run repeatable)."""
+        from .. import _lib, vocoder as _vocoder
+
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        mels = self.inference_batch(xs, spembs=spembs, prosody=prosody, seed=seed)
+        if torch.device(vocoder.plan.device) != mels[0].device:
+            raise _lib.FclError("fcl-taco2_amd: synthesize_speech: model and vocoder must live on one device")
+        lens = [int(m.shape[0]) for m in mels]
+        with torch.cuda.device(mels[0].device):
+            _, flat = vocoder.synthesize_packed(torch.cat(mels).contiguous(), lens, seed=seed, return_flat=True)
+        host = _vocoder.pcm16(flat)
+        offs = np.concatenate([[0], np.cumsum(lens)]) * vocoder.plan.hop
+        return [host[offs[i] : offs[i + 1]] for i in range(len(lens))]
 
     @torch.no_grad()
     def predict_prosody(self, xs, prosody=None, spembs=None):

@@ -317,7 +317,13 @@ def status_message(bits):
         msgs.append("the batch has more frames than the frame buffers hold (frames_cap); nothing was decoded -- rerun with a larger cap")
     if bits & _lib.STATUS_ROWS_CAP:
         msgs.append("a decoder step had more live rows than the host's bound for it (rows beyond the bound were not computed)")
-    known = (_lib.STATUS_GROUP_TIMEOUT | _lib.STATUS_ZERO_DURATION | _lib.STATUS_LMAX_CAP | _lib.STATUS_FRAMES_CAP | _lib.STATUS_ROWS_CAP)
+    if bits & _lib.STATUS_VOCODER_CAP:
+        msgs.append("vocoder capacity: the batch has more frames than the capacity vocoder holds (its frames_cap), or the synthesis pass in front of it "
+                    "failed; no waveform was generated -- rerun with a larger vocoder frames_cap")
+    if bits & _lib.STATUS_PCM_NONFINITE:
+        msgs.append("the waveform holds a non-finite sample (written as 0 in the 16-bit PCM)")
+    known = (_lib.STATUS_GROUP_TIMEOUT | _lib.STATUS_ZERO_DURATION | _lib.STATUS_LMAX_CAP | _lib.STATUS_FRAMES_CAP | _lib.STATUS_ROWS_CAP
+             | _lib.STATUS_VOCODER_CAP | _lib.STATUS_PCM_NONFINITE)
     if bits & ~known:
         msgs.append("unknown status bits 0x%x" % (bits & ~known))
     return "; ".join(msgs)

@@ -117,6 +117,213 @@ def aux_frame_rate(plan):
     return fused_block(plan) and plan.hop % 128 == 0 and os.environ.get("FCL_PWG_AUX_FRAME_RATE", "1") != "0"
 
 
+def pcm16_rule(x):
+    """float waveform -> little-endian int16, the rule of vocoder_decode.write_wav and of fcl_pcm16_fwd: clip(rint(double(x) * 32767), -32768, 32767),
+    ties to even; a non-finite sample becomes 0 (the device kernel also raises FCL_STATUS_PCM_NONFINITE for it)."""
+    x = np.asarray(x, dtype=np.float64)
+    fin = np.isfinite(x)
+    return np.where(fin, np.clip(np.rint(np.where(fin, x, 0.0) * 32767.0), -32768, 32767), 0.0).astype("<i2")
+
+
+def pcm16(wav):
+    """float32 device waveform (any shape, contiguous) -> int16 host array by fcl_pcm16_fwd (the rule of pcm16_rule, on the device: half the
+    device-to-host bytes).  Synchronising; raises FclError when the waveform holds a non-finite sample."""
+    wav = wav.reshape(-1)
+    n = wav.numel()
+    with torch.cuda.device(wav.device):
+        pcm = torch.empty(n, dtype=torch.int16, device=wav.device)
+        st = torch.zeros(1, dtype=torch.int32, device=wav.device)
+        _lib.check(_lib.load().fcl_pcm16_fwd(wav.data_ptr(), pcm.data_ptr(), n, None, st.data_ptr(), ops._stream()))
+        host = pcm.cpu().numpy()
+        bits = int(st.item()) & 0xFFFFFFFF
+    if bits:
+        raise _lib.FclError("fcl-taco2_amd: device status 0x%x: %s" % (bits, ops.status_message(bits)))
+    return host
+
+
+def capacity_sizes(batch, frames_cap, ctx, hop):
+    """Element counts of the capacity maps (fcl_pwg_maps_build): padded frame rows, samples."""
+    return int(frames_cap) + 2 * int(ctx) * (int(batch) + 1), int(frames_cap) * int(hop)
+
+
+def capacity_maps_rule(utt_frame0, frames_cap, ctx, hop, status=0):
+    """numpy statement of fcl_pwg_maps_build: the vocoder's index maps of a batch, to capacity.  utt_frame0 [B + 1]: frame starts of the B utterance
+    slots ([B] = total); an utterance without frames contributes nothing.  On the live extent the maps are those of `_maps([frames of the
+    utterances that have frames])`, with frame_utt / utt_off numbered by SLOT; frames [live, frames_cap) are one pseudo-utterance (index B) that owns
+    the rest of every buffer.  Returns a dict of int32 arrays + live = [frames, samples, padded rows, utterances with frames] + ok (False: incoming
+    status, frame starts that do not ascend from 0, or more frames than frames_cap -> nothing is live)."""
+    off = np.asarray(utt_frame0, dtype=np.int64).reshape(-1)
+    B = off.shape[0] - 1
+    ok = int(status) == 0 and off[0] == 0 and bool(np.all(np.diff(off) >= 0)) and off[B] <= frames_cap
+    if not ok:
+        off = np.zeros(B + 1, dtype=np.int64)
+    n = np.diff(off)
+    has = n > 0
+    pb = np.concatenate([[0], np.cumsum(np.where(has, n + 2 * ctx, 0))])  # first padded row of each slot; [B] = live padded rows
+    live, live_pad = int(off[B]), int(pb[B])
+    pad_cap, m_cap = capacity_sizes(B, frames_cap, ctx, hop)
+    f = np.arange(frames_cap, dtype=np.int64)
+    fu = np.full(frames_cap, B, dtype=np.int64)
+    fu[:live] = np.searchsorted(off, f[:live], side="right") - 1  # (equal starts: the last one, i.e. the slot that has frames)
+    keep = live_pad + ctx + (f - live)
+    keep[:live] = pb[fu[:live]] + ctx + (f[:live] - off[fu[:live]])
+    j = np.arange(pad_cap, dtype=np.int64)
+    pad_idx, lo, hi = np.zeros(pad_cap, dtype=np.int64), np.full(pad_cap, live_pad, dtype=np.int64), np.full(pad_cap, pad_cap, dtype=np.int64)
+    pu = np.minimum(np.searchsorted(pb, j[:live_pad], side="right") - 1, max(B - 1, 0))
+    pad_idx[:live_pad] = off[pu] + np.clip(j[:live_pad] - pb[pu] - ctx, 0, n[pu] - 1)
+    lo[:live_pad] = pb[pu]
+    hi[:live_pad] = pb[pu] + n[pu] + 2 * ctx
+    su = np.repeat(fu, hop)
+    offx = np.concatenate([off, [frames_cap]])
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return dict(pad_idx=i32(pad_idx), lo=i32(lo), hi=i32(hi), keep=i32(keep), frame_utt=i32(fu), utt_off=i32(offx), seg_lo=i32(offx[su] * hop),
+                seg_hi=i32(offx[su + 1] * hop), live=i32([live, live * hop, live_pad, int(has.sum())]), ok=ok)
+
+
+class CapacitySynth(object):
+    """The generator in CAPACITY form: every buffer, index map and grid is sized once for `batch` utterance slots and `frames_cap` mel frames; what is
+    live comes from the device (the synthesis pass's frame starts), so `run` derives no host value from the data, allocates nothing and is
+    capturable in a hipGraph behind the synthesis pass (engine.SpeechRunner).  The sample-rate launches (noise, first_conv, the 30 blocks, the
+    last stage, the PCM conversion) do no work past the live samples; the frame-rate launches and the 8-column coefficient cascade run over the
+    capacity (1/256 of the rows, resp. 32 of ~1000 bytes per sample).  A live sample is computed exactly as `synthesize_packed` computes it on
+    the same packed rows: same tiles, same frame windows, same absolute rows, same noise counter.
+
+    Memory: 1082 bytes per capacity sample measured on the default path (two x plane buffers 2 x 256 B, the fp32 skip accumulator 256 B, coefficient
+    lines 128 B, projected features 2 x 60 B, cascade ~43 B, bounds 8 B, z / wav / pcm 10 B), i.e. ~275 KB per capacity frame at hop 256 -- `nbytes`
+    is the exact figure of an instance; FCL_PWG_AUX_FRAME_RATE=0 holds planes of the upsampled features instead (~1.35 KB per sample).
+    Only the one-launch block geometry (fused_block(plan), 64 skip channels, hop a multiple of 128) has a capacity form: anything else raises FclError
+    and callers keep the two-step route (synthesis, frames() on the host, synthesize_packed)."""
+
+    def __init__(self, gen, batch, frames_cap, seed=0):
+        pl = self.plan = gen.plan
+        self.gen, self.B, self.frames_cap, self.seed = gen, int(batch), int(frames_cap), int(seed) & 0xFFFFFFFF
+        dev = pl.device
+        if not fused_block(pl) or pl.S != 64 or pl.hop % 128:
+            raise _lib.FclError("fcl-taco2_amd: the capacity vocoder is built for the one-launch block (64 residual / skip channels, kernel 3, <= 96 auxiliary "
+                                "channels, FCL_PWG_FUSED not 0) and a hop that is a multiple of 128; use synthesize_packed for this generator")
+        if not aux_frame_rate(pl) and pl.A <= 64:
+            raise _lib.FclError("fcl-taco2_amd: the capacity vocoder from upsampled planes (FCL_PWG_AUX_FRAME_RATE=0) needs more than 64 auxiliary channels")
+        if self.B < 1 or self.B > 1024 or self.frames_cap < 1 or self.frames_cap * pl.hop >= 2 ** 31 - 1:
+            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: 1..1024 utterances and fewer than 2^31 / hop frames expected (got %d, %d)"
+                                % (self.B, self.frames_cap))
+        self.ctx = ctx = int(pl.cfg["aux_context_window"])
+        self.aux_fr = aux_frame_rate(pl)
+        F, R, A, hop = self.frames_cap, pl.R, pl.A, pl.hop
+        self.pad_cap, self.M = capacity_sizes(self.B, F, ctx, hop)
+        M = self.M
+        with torch.cuda.device(dev):
+            before = torch.cuda.memory_allocated(dev)
+            i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+            f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+            self.maps = dict(pad_idx=i32(self.pad_cap), lo=i32(self.pad_cap), hi=i32(self.pad_cap), keep=i32(F), frame_utt=i32(F), utt_off=i32(self.B + 2),
+                             seg_lo=i32(M), seg_hi=i32(M))
+            self.live = i32(4)
+            self.z, self.wav, self.skips = f32(M), f32(M), f32(M, R)
+            self.pcm = torch.empty(M, dtype=torch.int16, device=dev)
+            self.xp = torch.empty(R // 32, M, 64, dtype=torch.int16, device=dev)  # chunk-major planes; the blocks ping-pong between xp and gp
+            self.gp = torch.empty(R // 32, M, 64, dtype=torch.int16, device=dev)
+            self.c_pad, self.c_conv = f32(self.pad_cap, A), f32(self.pad_cap, A)
+            C_ = 8 if self.aux_fr else A
+            self._stages, rate = [], 1
+            for i, s_ in enumerate(pl.cfg["upsample_scales"]):
+                rate *= s_
+                last = i == len(pl.up_w) - 1
+                self._stages.append(torch.empty((A + 31) // 32, F * rate, 64, dtype=torch.int16, device=dev) if last and not self.aux_fr else f32(F * rate, C_))
+            if self.aux_fr:
+                g = torch.arange(F, device=dev)
+                self.colour = (g[:, None] % 5 == torch.arange(8, device=dev)[None, :]).to(torch.float32).contiguous()  # the basis of _aux_frame_rate
+                self.kp = ops.planes_empty(M, 32, dev)
+                self.ld_pt = (F + 16 + 31) // 32
+                n = self.ld_pt * 32
+                self.cfull = torch.zeros(16 + n, A, device=dev)  # rows [16, 16 + F) are rewritten by every run, the rest stays zero
+                self.cfull_p = ops.planes_empty(16 + n, A, dev)
+                rows = pl.w_aux_all_p.shape[0]
+                self.pt_a, self.pt_b = ops.planes_empty(rows, n, dev), ops.planes_empty(rows, n, dev)
+                self.c_in = self.cfull[16 : 16 + F]
+            else:
+                self.c_in = f32(F, A)
+            for t_ in (self.xp, self.gp, self.kp if self.aux_fr else self._stages[-1]):
+                assert t_.data_ptr() % 128 == 0
+            self.nbytes = torch.cuda.memory_allocated(dev) - before
+            # the 30 block descriptors: every pointer is static
+            self._layers = []
+            xp, gp = self.xp, self.gp
+            for l, L in enumerate(pl.layers):
+                a = _lib.PwgLayer()
+                a.m, a.r, a.aux, a.ksize, a.dilation, a.first_layer = M, R, A, pl.k, L["dilation"], int(l == 0)
+                a.seg_lo, a.seg_hi = self.maps["seg_lo"].data_ptr(), self.maps["seg_hi"].data_ptr()
+                a.x, a.xp, a.xp_out = None, xp.data_ptr(), gp.data_ptr()
+                a.w_conv_p, a.b_conv, a.w_aux_p = L["w_conv_p"].data_ptr(), L["b_conv"].data_ptr(), L["w_aux_p"].data_ptr()
+                if self.aux_fr:
+                    row0 = l * 2 * R * self.ld_pt * 64
+                    a.kp, a.pt_a, a.pt_b = self.kp.data_ptr(), self.pt_a.data_ptr() + 2 * row0, self.pt_b.data_ptr() + 2 * row0
+                    a.ld_pt, a.hop = self.ld_pt, hop
+                else:
+                    a.cp = self._stages[-1].data_ptr()
+                a.w_os_p, a.b_os, a.skips = L["w_os_p"].data_ptr(), L["b_os"].data_ptr(), self.skips.data_ptr()
+                self._layers.append(a)
+                xp, gp = gp, xp
+            # eager warm-up on an empty batch: the library's one-time setup (dynamic-LDS opt-ins) must not happen inside a capture
+            st = i32(1)
+            self.run(torch.zeros(1, A, device=dev), i32(self.B + 1), st)
+            torch.cuda.current_stream(dev).synchronize()
+
+    def _cascade(self, c):
+        pl, lib, mp = self.plan, _lib.load(), self.maps
+        C_, rate = c.shape[1], 1
+        for i, s_ in enumerate(pl.cfg["upsample_scales"]):
+            out = self._stages[i]
+            as_planes = out.dtype == torch.int16
+            _lib.check(lib.fcl_pwg_upsample_stage(c.data_ptr(), mp["frame_utt"].data_ptr(), mp["utt_off"].data_ptr(), self.frames_cap, rate, s_,
+                                                  pl.up_w[i].data_ptr(), None if as_planes else out.data_ptr(), out.data_ptr() if as_planes else None, C_,
+                                                  1, ops._stream()))
+            c, rate = out, rate * s_
+        return c
+
+    def run(self, mel_rows_cap, utt_frame0_dev, status, seed_dev=None, draw_noise=True):
+        """Enqueue the whole generator + the PCM conversion on the current stream.  mel_rows_cap: [rows, aux] float32 device tensor whose first
+        utt_frame0[B] rows are the batch's packed mel frames (later rows are never read as features); utt_frame0_dev: int32 [B + 1] on the device;
+        status: the pass's int32 status word (FCL_STATUS_VOCODER_CAP / FCL_STATUS_PCM_NONFINITE are OR-ed into it; a word that is already set
+        makes this pass generate nothing); seed_dev: optional int32 device word added to the seed (a graph advances it per replay);
+        draw_noise=False: `self.z` already holds the noise.  Results: self.pcm (int16) and self.wav (float32), live samples [0, self.live[1])."""
+        pl, lib, mp = self.plan, _lib.load(), self.maps
+        if mel_rows_cap.dim() != 2 or mel_rows_cap.shape[1] != pl.A or mel_rows_cap.dtype != torch.float32 or not mel_rows_cap.is_contiguous():
+            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: expected contiguous float32 [rows, %d] mel rows, got %r" % (pl.A, tuple(mel_rows_cap.shape)))
+        if utt_frame0_dev.dtype != torch.int32 or utt_frame0_dev.numel() < self.B + 1 or status.dtype != torch.int32:
+            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: utt_frame0 must hold %d int32 frame starts and status be an int32 word" % (self.B + 1))
+        s, live = ops._stream(), self.live.data_ptr()
+        chk, F, M = _lib.check, self.frames_cap, self.M
+        chk(lib.fcl_pwg_maps_build(utt_frame0_dev.data_ptr(), status.data_ptr(), self.B, F, self.ctx, pl.hop, mp["pad_idx"].data_ptr(), mp["lo"].data_ptr(),
+                                   mp["hi"].data_ptr(), mp["keep"].data_ptr(), mp["frame_utt"].data_ptr(), mp["utt_off"].data_ptr(), mp["seg_lo"].data_ptr(),
+                                   mp["seg_hi"].data_ptr(), live, s))
+        # feature side at frame rate, over the capacity: replicate padding (dead rows zero) + conv_in ('valid' = 'same' on the interior)
+        chk(lib.fcl_pwg_gather_pad(mel_rows_cap.data_ptr(), mel_rows_cap.shape[0], mp["pad_idx"].data_ptr(), live, self.pad_cap, pl.A, self.c_pad.data_ptr(), s))
+        k, cout, cin = pl.conv_in.shape
+        chk(lib.fcl_conv1d_fwd(self.c_pad.data_ptr(), pl.conv_in.data_ptr(), None, mp["lo"].data_ptr(), mp["hi"].data_ptr(), None, self.c_conv.data_ptr(),
+                               self.pad_cap, cin, cout, k, ops.ACT_NONE, s))
+        chk(lib.fcl_gather_rows_fwd(self.c_conv.data_ptr(), mp["keep"].data_ptr(), self.c_in.data_ptr(), None, F, pl.A, s))
+        if self.aux_fr:
+            kc = self._cascade(self.colour)
+            chk(lib.fcl_pwg_aux_coeff(kc.data_ptr(), M, pl.hop, F, self.kp.data_ptr(), s))
+            n, rows = self.ld_pt * 32, pl.w_aux_all_p.shape[0]
+            chk(lib.fcl_pack_planes(self.cfull.data_ptr(), self.cfull.stride(0), self.cfull.shape[0], pl.A, self.cfull_p.data_ptr(), s))
+            chk(lib.fcl_linear_planes_fwd(pl.w_aux_all_p.data_ptr(), pl.w_aux_all_p.shape[1] // 64, self.cfull_p[16:].data_ptr(), None, None, n,
+                                          self.pt_a.data_ptr(), rows, n, pl.A, ops.ACT_NONE, s))
+            chk(lib.fcl_linear_planes_fwd(pl.w_aux_all_p.data_ptr(), pl.w_aux_all_p.shape[1] // 64, self.cfull_p.data_ptr(), None, None, n,
+                                          self.pt_b.data_ptr(), rows, n, pl.A, ops.ACT_NONE, s))
+        else:
+            self._cascade(self.c_in)
+        if draw_noise:
+            chk(lib.fcl_pwg_noise_cap(self.z.data_ptr(), M, self.seed, None if seed_dev is None else seed_dev.data_ptr(), live, s))
+        chk(lib.fcl_pwg_first_conv_cap(self.z.data_ptr(), pl.first_w.data_ptr(), pl.first_b.data_ptr(), self.xp.data_ptr(), M, pl.R, live, s))
+        for a in self._layers:
+            chk(lib.fcl_pwg_layer_cap_fwd(C.byref(a), live, s))
+        chk(lib.fcl_pwg_last_cap_fwd(self.skips.data_ptr(), math.sqrt(1.0 / len(pl.layers)), pl.last_w1p.data_ptr(), pl.last_b1.data_ptr(), pl.last_w2.data_ptr(),
+                                     pl.last_b2, self.wav.data_ptr(), M, pl.S, live, s))
+        chk(lib.fcl_pcm16_fwd(self.wav.data_ptr(), self.pcm.data_ptr(), M, live, status.data_ptr(), s))
+        return self.pcm
+
+
 class ParallelWaveGANGenerator(object):
     """mel -> waveform.  `synthesize(mels)` is the batched entry; `inference(c, x=None)` mirrors the published single-utterance call."""
 
@@ -227,8 +434,9 @@ class ParallelWaveGANGenerator(object):
             mel_rows = torch.cat([torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mels]).contiguous()
             return self.synthesize_packed(mel_rows, lens, noise, seed, return_intermediates)
 
-    def synthesize_packed(self, mel_rows, lens, noise=None, seed=0, return_intermediates=False):
-        """The same on utterances already packed row-wise ([sum T', aux] device tensor, e.g. engine.run's output) with their frame counts."""
+    def synthesize_packed(self, mel_rows, lens, noise=None, seed=0, return_intermediates=False, return_flat=False):
+        """The same on utterances already packed row-wise ([sum T', aux] device tensor, e.g. engine.run's output) with their frame counts.
+        return_flat: also return the one [sum T' * hop] buffer the per-utterance waveforms are slices of (utterances back to back), as the last result."""
         pl, dev = self.plan, self.plan.device
         lib = _lib.load()
         with torch.cuda.device(dev):
@@ -296,8 +504,9 @@ class ParallelWaveGANGenerator(object):
                                             ops._stream()))
             outs = [wav[int(offs[i]) * pl.hop : int(offs[i + 1]) * pl.hop] for i in range(len(lens))]
             if return_intermediates:
-                return outs, dict(z=z, taps=taps, skips=skips, seg=(seg_lo, seg_hi))
-            return outs
+                res = (outs, dict(z=z, taps=taps, skips=skips, seg=(seg_lo, seg_hi)))
+                return res + (wav,) if return_flat else res
+            return (outs, wav) if return_flat else outs
 
     def inference(self, c, x=None):
         """ParallelWaveGANGenerator.inference(c, x): c [T', aux] (x: optional noise [T' * hop]) -> waveform [T' * hop, 1]."""

@@ -40,7 +40,10 @@ enum {
                                    * (decoder_sa_kd.py:739) — the pass produced nothing valid */
     FCL_STATUS_LMAX_CAP = 4,      /* max duration > lmax_cap: the loop would have needed more steps than were launched (nothing was decoded) */
     FCL_STATUS_FRAMES_CAP = 8,    /* sum of durations > frames_cap: the frame-major buffers are too small (nothing was decoded) */
-    FCL_STATUS_ROWS_CAP = 16      /* live rows of a decoder step > the host's bound for that step (rows beyond the bound were not computed) */
+    FCL_STATUS_ROWS_CAP = 16,     /* live rows of a decoder step > the host's bound for that step (rows beyond the bound were not computed) */
+    FCL_STATUS_VOCODER_CAP = 32,  /* fcl_pwg_maps_build: the batch has more frames than the vocoder's frames_cap, or the status word was already set when
+                                   * the vocoder's maps were built: nothing is live, no waveform was generated */
+    FCL_STATUS_PCM_NONFINITE = 64 /* fcl_pcm16_fwd met a NaN / Inf sample (written as 0) */
 };
 
 /* Arithmetic of the MFMA contractions (Linear / Conv1d / LSTM-step GEMMs and the weight-gradient GEMM) launched by the CALLING THREAD:
@@ -767,6 +770,35 @@ int fcl_pwg_layer_fwd(const fcl_pwg_layer_t* a, fcl_stream_t stream);
  * (both unused, may be NULL, for s_ch = 64: one launch that reads skips once). */
 int fcl_pwg_last_fwd(const float* skips, float scale, const uint16_t* w1p, const float* b1, const float* w2, float b2, uint16_t* yp, float* h, float* wav,
                      int64_t m, int s_ch, fcl_stream_t stream);
+
+/* ---- capacity form of the vocoder: the same generator with every buffer, map and grid sized by a CAPACITY (frames_cap mel frames,
+ * frames_cap * hop samples) and the live extent read from the device, so that the synthesis pass's predicted durations never have to reach the
+ * host and the whole chain text -> waveform is capturable.  Restricted to the one-launch block (r = 64, ksize = 3, aux <= 96) and a hop that is a
+ * multiple of 128.  No entry allocates, synchronises or copies; fcl_pwg_layer_cap_fwd opts its kernel into its dynamic LDS on first use, so
+ * call it once outside a capture.
+ * fcl_pwg_maps_build: ONE launch that builds every index map of a batch from the synthesis pass's frame starts utt_frame0 [batch + 1] (device):
+ *      utt_off [batch + 2], frame_utt / keep [frames_cap], pad_idx / lo / hi [frames_cap + 2 * ctx * (batch + 1)], seg_lo / seg_hi
+ *      [frames_cap * hop] and live [4] = {live frames, live samples, live padded rows, utterances with frames}.  On the live extent they are what
+ *      the host builds for the utterances that have frames (an utterance without frames contributes nothing); frames [live, frames_cap) form one
+ *      pseudo-utterance (index `batch`) that owns the rest of every buffer, so every index lies inside its target and dead rows only see dead rows.
+ *      *status != 0 on entry, frame starts that do not ascend from 0, or more than frames_cap frames: live = {0, 0, 0, 0}, FCL_STATUS_VOCODER_CAP is
+ *      OR-ed into *status, the whole capacity becomes the pseudo-utterance.
+ * fcl_pwg_gather_pad: out [pad_cap, c] = mel[pad_idx[j]] for the live padded rows, ZERO for the rest (the synthesis buffer's rows past its total
+ *      are not valid and must not enter: 0 x NaN is NaN in the frame windows next to the live / dead boundary).
+ * fcl_pwg_noise_cap / fcl_pwg_first_conv_cap / fcl_pwg_layer_cap_fwd / fcl_pwg_last_cap_fwd: the exact-size entries' arithmetic on samples
+ *      [0, live[1]) only (a->m / m_cap / n_cap are capacities: buffer strides and grids); the noise seed is seed + *seed_dev (seed_dev may be NULL);
+ *      first_conv writes chunk-major planes.
+ * fcl_pcm16_fwd: pcm[i] = clip(rint((double)wav[i] * 32767), -32768, 32767), ties to even, for i < live[1] (live NULL: i < n_cap); a non-finite
+ *      sample becomes 0 and sets FCL_STATUS_PCM_NONFINITE in *status. */
+int fcl_pwg_maps_build(const int32_t* utt_frame0, uint32_t* status, int batch, int64_t frames_cap, int ctx, int hop, int32_t* pad_idx, int32_t* lo, int32_t* hi,
+                       int32_t* keep, int32_t* frame_utt, int32_t* utt_off, int32_t* seg_lo, int32_t* seg_hi, int32_t* live, fcl_stream_t stream);
+int fcl_pwg_gather_pad(const float* mel, int64_t mel_rows, const int32_t* pad_idx, const int32_t* live, int64_t pad_cap, int c, float* out, fcl_stream_t stream);
+int fcl_pwg_noise_cap(float* z, int64_t n_cap, uint32_t seed, const uint32_t* seed_dev, const int32_t* live, fcl_stream_t stream);
+int fcl_pwg_first_conv_cap(const float* z, const float* w, const float* b, uint16_t* xp, int64_t m_cap, int r, const int32_t* live, fcl_stream_t stream);
+int fcl_pwg_layer_cap_fwd(const fcl_pwg_layer_t* a, const int32_t* live, fcl_stream_t stream);
+int fcl_pwg_last_cap_fwd(const float* skips, float scale, const uint16_t* w1p, const float* b1, const float* w2, float b2, float* wav, int64_t m_cap, int s_ch,
+                         const int32_t* live, fcl_stream_t stream);
+int fcl_pcm16_fwd(const float* wav, int16_t* pcm, int64_t n_cap, const int32_t* live, uint32_t* status, fcl_stream_t stream);
 
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
