@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import max_abs
+from helpers import bf16_to_f32, max_abs, split_planes_np
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,27 +30,6 @@ def dev(a):
 
 def rnd(rng, *shape):
     return rng.standard_normal(shape).astype(np.float32)
-
-
-def bf16_rn(x):
-    """numpy restatement of the device's float -> bf16 conversion (round to nearest even), as the uint16 bit pattern."""
-    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    return ((b + 0x7FFF + ((b >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def bf16_to_f32(h):
-    return (h.astype(np.uint32) << 16).view(np.float32)
-
-
-def split_planes_np(x):
-    """[R, K] float32 -> P32 planes uint16 [R, ceil(K/32), 2, 32] (include/fcl_hip.h: hi = bf16_rn(x), lo = bf16_rn(x - hi), zeros past K)."""
-    r, k = x.shape
-    kp = (k + 31) // 32 * 32
-    xp = np.zeros((r, kp), np.float32)
-    xp[:, :k] = x
-    hi = bf16_rn(xp)
-    lo = bf16_rn(xp - bf16_to_f32(hi))
-    return np.stack([hi.reshape(r, kp // 32, 32), lo.reshape(r, kp // 32, 32)], axis=2)
 
 
 def unpack(planes, rows, cols):

@@ -48,12 +48,32 @@ def run_both(voc, cfg, lens, seed):
 
 
 def test_full_v1_generator_matches_the_oracle(voc):
-    got, want, aux, _ = run_both(voc, None, [5, 1, 3], 0)
+    import math
+
+    import torch.nn.functional as F
+
+    from oracle import pwg_oracle as O
+
+    got, want, aux, (tsd, mels, noise, hop) = run_both(voc, None, [5, 1, 3], 0)
     for g, w in zip(got, want):
         assert g.shape == w.shape
         err = max_abs(g.cpu(), w) / float(w.abs().max())
         print('rel err', err)
         assert err < 1e-3  # relative to the waveform's peak (the closed-form generator's output is small)
+    # the residual stream after every block and the skip sum, every utterance (the one-launch blocks, default geometry)
+    s0 = 0
+    for mel, z in zip(mels, noise):
+        c = F.pad(torch.from_numpy(mel).t().unsqueeze(0), (O.CONFIG["aux_context_window"],) * 2, mode="replicate")
+        with torch.no_grad():
+            _, taps, skips = O.generator_forward(tsd, torch.from_numpy(z).reshape(1, 1, -1), O.upsample(tsd, c), return_taps=True)
+        n = mel.shape[0] * hop
+        for l, t in enumerate(taps):
+            err = max_abs(aux["taps"][l][s0 : s0 + n].cpu(), t[0].t())
+            assert err < 5e-5, (l, err)
+        err = max_abs(aux["skips"][s0 : s0 + n].cpu() * math.sqrt(1.0 / len(taps)), skips[0].t())
+        print('skip sum err', err)
+        assert err < 5e-5
+        s0 += n
 
 
 def test_small_irregular_generator_and_per_layer_taps(voc):
