@@ -95,6 +95,22 @@ class PwgLayer(C.Structure):  # fcl_pwg_layer_t
                           "kp", "pt_a", "pt_b")] + [("ld_pt", C.c_int32), ("hop", C.c_int32)]
 
 
+class HfgConv(C.Structure):  # fcl_hfg_conv_t
+    _fields_ = [("m", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "ksize", "dilation", "rate")] + [("slope", _F)] + [
+        (n, _P) for n in ("xp", "wp", "bias", "frame_utt", "utt_off", "resid", "y", "yp")]
+
+
+class HfgTconv(C.Structure):  # fcl_hfg_tconv_t
+    _fields_ = [("m_in", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "stride", "ksize", "padding", "rate_in")] + [
+        ("slope", _F), ("reserved", C.c_int32)] + [(n, _P) for n in ("xp", "wp", "bias", "frame_utt", "utt_off", "y", "yp")]
+
+
+class HfgUnit(C.Structure):  # fcl_hfg_unit_t
+    _fields_ = [("m", C.c_int64)] + [(n, C.c_int32) for n in ("c", "ksize", "dilation", "rate", "first", "last")] + [
+        ("slope", _F), ("cs_scale", _F), ("csp_slope", _F), ("reserved", C.c_int32)] + [
+        (n, _P) for n in ("xp", "x", "w1p", "b1", "w2p", "b2", "frame_utt", "utt_off", "x_out", "xp_out", "cs", "csp", "tp")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -241,6 +257,10 @@ SIGNATURES = {
     "fcl_pwg_layer_cap_fwd": (_I, [_P, _P, _P]),
     "fcl_pwg_last_cap_fwd": (_I, [_P, _F, _P, _P, _P, _F, _P, C.c_int64, _I, _P, _P]),
     "fcl_pcm16_fwd": (_I, [_P, _P, C.c_int64, _P, _P, _P]),
+    "fcl_hfg_conv_fwd": (_I, [C.POINTER(HfgConv), _P]),
+    "fcl_hfg_tconv_fwd": (_I, [C.POINTER(HfgTconv), _P]),
+    "fcl_hfg_unit_fwd": (_I, [C.POINTER(HfgUnit), _P]),
+    "fcl_hfg_out_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, C.c_int64, _I, _I, _I, _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

@@ -817,6 +817,10 @@ class SpeechRunner(BatchRunner):
             raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: the model writes %d mel channels, the vocoder takes %d" % (plan.hp.odim, gen.plan.A))
         if torch.device(gen.plan.device) != torch.device(plan.device):
             raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: model and vocoder must live on one device")
+        if getattr(gen.plan, "eager_only", False):
+            raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: %s has no capacity form (only the Parallel WaveGAN generator can follow the synthesis pass "
+                                    "inside one graph); use the two-step route (engine.run, then gen.synthesize_packed), as tts.synthesize does"
+                                    % type(gen).__name__)
         self.gen, self.hop, self.seed = gen, int(gen.plan.hop), int(seed)
         with torch.cuda.device(plan.device):
             self.synth = CapacitySynth(gen, batch, int(voc_frames_cap) if voc_frames_cap else caps.frames, seed=seed)

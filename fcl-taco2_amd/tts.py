@@ -98,7 +98,8 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
         ctl_of = lambda chunk: [one] * len(chunk)
     else:
         ctl_of = lambda chunk: None
-    eager_only = bool(getattr(plan, "generic_decoder", False)) or plan.hp.elayers != 1
+    # (a generator without a capacity form -- HiFi-GAN -- keeps every batch on the two-step route, like a model the capacity graph does not cover)
+    eager_only = bool(getattr(plan, "generic_decoder", False)) or plan.hp.elayers != 1 or bool(getattr(gen.plan, "eager_only", False))
     max_buckets = max(1, int(MAX_BUCKETS if max_buckets is None else max_buckets))
     buckets = collections.OrderedDict()
     calibration = None
@@ -325,15 +326,13 @@ def shard_of(utts, nj, job):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .vocoder import PWGPlan, ParallelWaveGANGenerator
-    from .vocoder_decode import generator_config, load_checkpoint
+    from .vocoder_decode import build_generator
 
     torch.set_num_threads(4)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
     dev = "cuda:%d" % (args.job % max(torch.cuda.device_count(), 1))
-    cfg, rate = generator_config(args.vocoder_checkpoint, args.vocoder_config)
     model = build_model(args.model, args.model_conf, args.teacher_config, dev)
-    gen = ParallelWaveGANGenerator(PWGPlan(load_checkpoint(args.vocoder_checkpoint, args.unsafe_pickle), dev, cfg))
+    gen, rate = build_generator(args.vocoder_checkpoint, dev, args.vocoder_config, args.unsafe_pickle)
     mine = shard_of(read_manifest(args.json), args.nj, args.job)
     feats = args.feats_out if args.feats_out is None or args.nj == 1 else "%s.%d" % (args.feats_out, args.job + 1)
     res = synthesize(model, gen, mine, args.outdir, rate, args.batch_size, args.seed, prosody_from_args(args, [u[0] for u in mine]), feats, args.max_buckets)

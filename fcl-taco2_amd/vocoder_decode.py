@@ -1,7 +1,8 @@
 """mel -> waveform driver on MI355X: the step the reference delegates to the external `parallel-wavegan-decode --checkpoint vocoder/PWG/PWG.pkl
 --feats-scp <decode>/feats.scp --outdir <wav dir>` (inference_student.sh:20-23, inference_teacher.sh:20-23, README.md:46).  Same flag names and
-the same outputs (`<outdir>/<utt_id>_gen.wav`, 16-bit PCM at the generator's sampling rate); the generator is fcl_taco2_amd/vocoder.py (published
-architecture, parity unpinned: DESIGN.md §6b).
+the same outputs (`<outdir>/<utt_id>_gen.wav`, 16-bit PCM at the generator's sampling rate); the generator is selected as that tool selects it, by
+`generator_type` of the config.yml: fcl_taco2_amd/vocoder.py (ParallelWaveGANGenerator) or fcl_taco2_amd/hifigan.py (HiFiGANGenerator,
+DESIGN.md §6c), both from the published architecture, parity unpinned.
 
     python -m fcl_taco2_amd.vocoder_decode --checkpoint vocoder/PWG/PWG.pkl --feats-scp exp/student/test/feats.scp --outdir exp/student/test/wav
 
@@ -28,15 +29,13 @@ from .vocoder import CONFIG, PWGPlan, ParallelWaveGANGenerator
 def generator_config(checkpoint, config=None):
     """Generator geometry from the `config.yml` parallel_wavegan keeps beside its checkpoints (`generator_params`); the v1 defaults without one.
     Returns (cfg overrides for PWGPlan, sampling rate)."""
-    path = config or os.path.join(os.path.dirname(os.path.abspath(checkpoint)), "config.yml")
-    if not os.path.exists(path):
-        if config:
-            raise FileNotFoundError(config)
-        return {}, 22050
-    import yaml
+    return _pwg_config_of(_read_config(checkpoint, config))
 
-    with open(path) as f:
-        y = yaml.safe_load(f) or {}
+
+def _pwg_config_of(y):
+    """generator_config on the parsed config.yml (None: no file)"""
+    if y is None:
+        return {}, 22050
     gp = y.get("generator_params", {})
     unsupported = {k: gp[k] for k, dflt in (("in_channels", 1), ("out_channels", 1), ("use_causal_conv", False), ("upsample_net", "ConvInUpsampleNetwork"))
                    if gp.get(k, dflt) != dflt}
@@ -52,6 +51,116 @@ def generator_config(checkpoint, config=None):
     if "upsample_scales" in up:
         cfg["upsample_scales"] = tuple(int(s) for s in up["upsample_scales"])
     return cfg, int(y.get("sampling_rate", 22050))
+
+
+PWG_TYPE, HIFIGAN_TYPE = "ParallelWaveGANGenerator", "HiFiGANGenerator"
+
+
+def _read_config(checkpoint, config=None):
+    """The parsed config.yml beside the checkpoint (or `config`), None without one."""
+    path = config or os.path.join(os.path.dirname(os.path.abspath(checkpoint)), "config.yml")
+    if not os.path.exists(path):
+        if config:
+            raise FileNotFoundError(config)
+        return None
+    import yaml
+
+    with open(path) as f:
+        return yaml.safe_load(f) or {}
+
+
+def generator_type(checkpoint, config=None):
+    """`generator_type` of the config.yml (parallel-wavegan-decode selects the generator class by it); ParallelWaveGANGenerator when the key is
+    absent; None without a config.yml (the state-dict keys then decide: family_of_state_dict)."""
+    return _type_of(_read_config(checkpoint, config))
+
+
+def _type_of(y):
+    return None if y is None else y.get("generator_type", PWG_TYPE)
+
+
+def family_of_state_dict(sd):
+    """Generator family from the state-dict keys: `input_conv.weight*` is HiFi-GAN's, `first_conv.weight*` Parallel WaveGAN's."""
+    if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict) and "generator" in sd["model"]:
+        sd = sd["model"]["generator"]
+    keys = set(sd)
+    if keys & {"input_conv.weight", "input_conv.weight_g", "input_conv.weight_v"}:
+        return HIFIGAN_TYPE
+    if keys & {"first_conv.weight", "first_conv.weight_g", "first_conv.weight_v"}:
+        return PWG_TYPE
+    raise NotImplementedError("fcl-taco2_amd: the state dict holds neither input_conv.weight (HiFiGANGenerator) nor first_conv.weight "
+                              "(ParallelWaveGANGenerator): unknown generator family")
+
+
+def hifigan_config(checkpoint, config=None):
+    """HiFi-GAN geometry from `generator_params` of the config.yml -> (cfg overrides for HiFiGANPlan, sampling rate).  Parameters the kernels do not
+    cover are refused by name (hifigan.config)."""
+    return _hifigan_config_of(_read_config(checkpoint, config))
+
+
+def _hifigan_config_of(y):
+    from . import hifigan
+
+    y = y or {}
+    gp = dict(y.get("generator_params", {}))
+    gp.pop("use_weight_norm", None)  # read from the state dict itself
+    unknown = sorted(k for k in gp if k not in hifigan.CONFIG)
+    if unknown:
+        raise NotImplementedError("fcl-taco2_amd: generator_params %r are not supported on the HIP path" % {k: gp[k] for k in unknown})
+    hifigan.config(gp)
+    return gp, int(y.get("sampling_rate", 22050))
+
+
+def hifigan_config_from_shapes(sd):
+    """Without a config.yml: channels and kernel sizes from the shapes; what the shapes cannot tell is ASSUMED -- upsampling scale = kernel / 2 and
+    dilations (1, 3, 5) per block (as many as the block has convolutions must be 3) -- and logged."""
+    if "model" in sd and "generator" in sd["model"]:
+        sd = sd["model"]["generator"]
+    shape = lambda k: tuple(np.shape(sd[k if k in sd else k + "_v"]))
+    has = lambda k: k in sd or k + "_v" in sd
+    ch, cin, k = shape("input_conv.weight")
+    n = 0
+    while has("upsamples.%d.1.weight" % n):
+        n += 1
+    kus = tuple(shape("upsamples.%d.1.weight" % i)[2] for i in range(n))
+    nb = 0
+    while has("blocks.%d.convs1.0.1.weight" % nb):
+        nb += 1
+    if n == 0 or nb == 0 or nb % n:
+        raise NotImplementedError("fcl-taco2_amd: cannot read a HiFi-GAN geometry from the state dict (%d upsampling layers, %d blocks)" % (n, nb))
+    nk = nb // n
+    krs = tuple(shape("blocks.%d.convs1.0.1.weight" % j)[2] for j in range(nk))
+    nd = 0
+    while has("blocks.0.convs1.%d.1.weight" % nd):
+        nd += 1
+    if nd != 3 or any(ku % 2 for ku in kus):
+        raise NotImplementedError("fcl-taco2_amd: a HiFi-GAN state dict without config.yml is read as scale = kernel / 2 and dilations (1, 3, 5); this one "
+                                  "has %d convolutions per block and upsampling kernels %r" % (nd, kus))
+    cfg = dict(in_channels=int(cin), out_channels=int(shape("output_conv.1.weight")[0]), channels=int(ch), kernel_size=int(k),
+               upsample_scales=tuple(ku // 2 for ku in kus), upsample_kernel_sizes=kus, resblock_kernel_sizes=krs, resblock_dilations=((1, 3, 5),) * nk)
+    logging.warning("no config.yml beside the HiFi-GAN checkpoint: ASSUMING upsample_scales %r (= kernel / 2) and resblock_dilations (1, 3, 5); channels %d, "
+                    "kernel sizes %r / %r are read from the shapes", cfg["upsample_scales"], ch, kus, krs)
+    return cfg, 22050
+
+
+def build_generator(checkpoint, device, config=None, allow_pickle=False):
+    """Generator of a checkpoint + its sampling rate, by `generator_type` of the config.yml (absent / ParallelWaveGANGenerator: vocoder.py;
+    HiFiGANGenerator: hifigan.py; anything else: NotImplementedError naming it) or, without a config.yml, by the state-dict keys."""
+    y = _read_config(checkpoint, config)  # read once: the type and the geometry come from the same parse
+    gtype = _type_of(y)
+    if gtype is not None and gtype not in (PWG_TYPE, HIFIGAN_TYPE):
+        raise NotImplementedError("fcl-taco2_amd: generator_type %r is not supported on the HIP path (%s and %s are)" % (gtype, PWG_TYPE, HIFIGAN_TYPE))
+    sd = load_checkpoint(checkpoint, allow_pickle)
+    from_keys = gtype is None
+    if from_keys:
+        gtype = family_of_state_dict(sd)
+    if gtype == HIFIGAN_TYPE:
+        from .hifigan import HiFiGANGenerator, HiFiGANPlan
+
+        cfg, rate = hifigan_config_from_shapes(sd) if from_keys else _hifigan_config_of(y)
+        return HiFiGANGenerator(HiFiGANPlan(sd, device, cfg)), rate
+    cfg, rate = _pwg_config_of(y)
+    return ParallelWaveGANGenerator(PWGPlan(sd, device, cfg)), rate
 
 
 def load_checkpoint(path, allow_pickle=False):
@@ -176,7 +285,7 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Parallel WaveGAN decoding on MI355X (drop-in for `parallel-wavegan-decode`)")
+    ap = argparse.ArgumentParser(description="Parallel WaveGAN / HiFi-GAN decoding on MI355X (drop-in for `parallel-wavegan-decode`)")
     ap.add_argument("--checkpoint", required=True, help="generator checkpoint ({'model': {'generator': state_dict}} or a bare state_dict)")
     ap.add_argument("--feats-scp", "--scp", dest="feats_scp", required=True, help="Kaldi scp of [T', aux] float matrices (decode.py's <out>.scp)")
     ap.add_argument("--outdir", required=True)
@@ -192,10 +301,9 @@ def main(argv=None):
     torch.set_num_threads(4)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
     dev = "cuda:%d" % (args.job % max(torch.cuda.device_count(), 1))
-    cfg, rate = generator_config(args.checkpoint, args.config)
-    gen = ParallelWaveGANGenerator(PWGPlan(load_checkpoint(args.checkpoint, args.unsafe_pickle), dev, cfg))
+    gen, rate = build_generator(args.checkpoint, dev, args.config, args.unsafe_pickle)
     feats = sorted(kaldi_io.read_scp(args.feats_scp).items())
-    aux = dict(CONFIG, **cfg)["aux_channels"]
+    aux = gen.plan.A
     for uid, m in feats:
         if m.ndim != 2 or m.shape[1] != aux or m.shape[0] < 1:
             raise ValueError("%s: expected a [T', %d] feature matrix, got %r" % (uid, aux, m.shape))

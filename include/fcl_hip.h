@@ -715,7 +715,8 @@ int fcl_prof_collect(fcl_prof_entry_t* out, int max_entries);
  *      kan-bayashi/ParallelWaveGAN generator (v1, LJSpeech: 80 mels, hop 256 = 4*4*4*4, 30 layers / 3 stacks, 64 residual + skip channels,
  *      128 gate channels, kernel 3), restated in oracle/pwg_oracle.py (parity unpinned).  Rows are SAMPLES, time-major, utterances concatenated;
  *      seg_lo / seg_hi [M] give every row the sample range of its utterance (zero padding at utterance edges).  Needs the pre-split operand
- *      path (refused under FCL_PRECISION=0 / FCL_PLANES=0). ------------------------------------------------------------------------------- */
+ *      path (refused under FCL_PRECISION=0 / FCL_PLANES=0).  That tool selects its generator class by `generator_type`: the HiFi-GAN generator
+ *      is the section after this one. ---------------------------------------------------------------------------------------------------- */
 /* One stage of the upsampling network: nearest-neighbour stretch by `scale` + the 1 x (2*scale+1) smoothing convolution w (no bias), per channel.
  * in [frames * rate_in, c] -> out [frames * rate_in * scale, c] fp32 and / or out_p (P32 planes, ceil(c/32) lines per row, zero past c).
  * frame_utt [frames]: utterance of each mel frame; utt_off [n_utt + 1]: first frame of each utterance.  c % 4 == 0; in / out 16-byte aligned. */
@@ -799,6 +800,86 @@ int fcl_pwg_layer_cap_fwd(const fcl_pwg_layer_t* a, const int32_t* live, fcl_str
 int fcl_pwg_last_cap_fwd(const float* skips, float scale, const uint16_t* w1p, const float* b1, const float* w2, float b2, float* wav, int64_t m_cap, int s_ch,
                          const int32_t* live, fcl_stream_t stream);
 int fcl_pcm16_fwd(const float* wav, int16_t* pcm, int64_t n_cap, const int32_t* live, uint32_t* status, fcl_stream_t stream);
+
+/* ---- HiFi-GAN generator (mel -> waveform): the second generator family `parallel-wavegan-decode` (inference_student.sh:20-23) selects by
+ *      `generator_type`.  Published architecture (kan-bayashi/ParallelWaveGAN HiFiGANGenerator, v1 / LJSpeech: 80 mels, 512 channels halved per stage,
+ *      transposed convolutions 8 x 8 x 2 x 2 with kernels 16 / 16 / 4 / 4, residual blocks of kernel 3 / 7 / 11 x dilations 1 / 3 / 5), restated in
+ *      tests/hifigan_ref.py (parity unpinned).  Rows are SAMPLES at the stage's rate, time-major, utterances concatenated, channels contiguous.
+ *      frame_utt [frames] / utt_off [n_utt + 1] (as fcl_pwg_upsample_stage) with `rate` rows per frame give every row its utterance: every
+ *      convolution sees zeros outside it.  P32 convention: a producer writes the fp32 value where a residual needs it and the planes of
+ *      LeakyReLU(value, slope), the next consumer's operand.  bf16x3 on the bf16 MFMA; FCL_GEMM_BF16 = hi planes only.  Refused under
+ *      FCL_PRECISION=0 / FCL_PLANES=0.  No entry allocates, synchronises or copies. ---------------------------------------------------------- */
+/* One Conv1d (input_conv; the building block of residual units wider than 128 channels): v = conv(xp) + bias (+ resid), 'same' zero padding
+ * inside the utterance; y = v (optional), yp = planes of LeakyReLU(v, slope) (optional).  ksize odd <= 11, dilation 1..5, cout % 32 == 0. */
+typedef struct {
+    int64_t m;                  /* rows */
+    int32_t cin, cout;          /* xp / wp carry ceil(cin / 32) lines per row */
+    int32_t ksize, dilation;
+    int32_t rate;               /* rows per frame */
+    float slope;
+    const uint16_t* xp;         /* operand planes [m, cin] */
+    const uint16_t* wp;         /* planes of the taps, tap-major [ksize * cout, cin] (fcl_pack_conv1d_weight + fcl_pack_planes) */
+    const float* bias;          /* [cout] */
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    const float* resid;         /* optional [m, cout] */
+    float* y;                   /* optional [m, cout] */
+    uint16_t* yp;               /* optional planes [m, cout] */
+} fcl_hfg_conv_t;
+int fcl_hfg_conv_fwd(const fcl_hfg_conv_t* a, fcl_stream_t stream);
+/* One upsampling stage in one launch: ConvTranspose1d(cin -> cout, ksize, stride, padding, output_padding = stride % 2) on xp = planes of
+ * LeakyReLU(c) [m_in, cin], computed polyphase: output row n = stride * q + p takes the ksize / stride taps of phase p from the input rows around q
+ * (utterance bounds at the INPUT rate).  Writes y [m_in * stride, cout] and / or yp = planes of LeakyReLU(y, slope).  ksize must be a multiple of
+ * stride and ksize - 2 * padding + stride % 2 == stride (stride x as many rows out as in); other geometries are refused (FCL_ERR_SHAPE).
+ * The tap count ksize / stride (<= 8) is deliberately general: the package's padding rule (stride / 2 + stride % 2) admits ksize = 2 * stride only,
+ * which is what fcl_taco2_amd/hifigan.py accepts, but the entry takes any padding that keeps the length. */
+typedef struct {
+    int64_t m_in;               /* input rows */
+    int32_t cin, cout;          /* multiples of 32 */
+    int32_t stride, ksize, padding;
+    int32_t rate_in;            /* input rows per frame */
+    float slope;
+    int32_t reserved;
+    const uint16_t* xp;
+    const uint16_t* wp;         /* planes of the taps, tap-major [ksize * cout, cin]: the (cin, cout, ksize) weight with its first two dimensions swapped,
+                                 * through fcl_pack_conv1d_weight + fcl_pack_planes */
+    const float* bias;          /* [cout] */
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    float* y;
+    uint16_t* yp;
+} fcl_hfg_tconv_t;
+int fcl_hfg_tconv_fwd(const fcl_hfg_tconv_t* a, fcl_stream_t stream);
+/* One residual unit: xt = conv1(LeakyReLU(x), ksize, dilation); x' = conv2(LeakyReLU(xt), ksize, 1) + x.  ONE launch for c = 32 / 64 / 128 (xt and
+ * its (ksize - 1) / 2-row halo stay in LDS); other multiples of 32 run as one launch per convolution through the workspace tp.  ksize 3 / 5 / 7 / 11,
+ * dilation 1..5.  Writes x_out = x' (optional; may be x) and xp_out = planes of LeakyReLU(x', slope) (optional; NOT xp).  last != 0 (the last unit of
+ * a block): cs = first ? x' * cs_scale : cs + x' * cs_scale, and csp (optional) = planes of LeakyReLU(new cs, csp_slope), the next stage's operand. */
+typedef struct {
+    int64_t m;
+    int32_t c, ksize, dilation;
+    int32_t rate;               /* rows per frame */
+    int32_t first, last;
+    float slope, cs_scale, csp_slope;
+    int32_t reserved;
+    const uint16_t* xp;         /* planes of LeakyReLU(x) */
+    const float* x;             /* [m, c] */
+    const uint16_t* w1p;        /* planes of the taps [ksize * c, c] */
+    const float* b1;
+    const uint16_t* w2p;
+    const float* b2;
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    float* x_out;
+    uint16_t* xp_out;
+    float* cs;                  /* [m, c] */
+    uint16_t* csp;
+    uint16_t* tp;               /* workspace planes [m, c] (c > 128 only) */
+} fcl_hfg_unit_t;
+int fcl_hfg_unit_fwd(const fcl_hfg_unit_t* a, fcl_stream_t stream);
+/* output_conv + tanh: wav [m, cout] = tanh(conv(cp, w, ksize) + b); cp = planes of LeakyReLU(c) [m, c]; w [ksize][cout][c] fp32
+ * (fcl_pack_conv1d_weight); 1 <= cout <= 4. */
+int fcl_hfg_out_fwd(const uint16_t* cp, const float* w, const float* b, const int32_t* frame_utt, const int32_t* utt_off, int rate, float* wav, int64_t m, int c,
+                    int cout, int ksize, fcl_stream_t stream);
 
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
