@@ -261,6 +261,11 @@ SIGNATURES = {
     "fcl_hfg_tconv_fwd": (_I, [C.POINTER(HfgTconv), _P]),
     "fcl_hfg_unit_fwd": (_I, [C.POINTER(HfgUnit), _P]),
     "fcl_hfg_out_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, C.c_int64, _I, _I, _I, _P]),
+    "fcl_hfg_maps_build": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _P, _P]),
+    "fcl_hfg_conv_cap_fwd": (_I, [C.POINTER(HfgConv), _P, _P]),
+    "fcl_hfg_tconv_cap_fwd": (_I, [C.POINTER(HfgTconv), _P, _P]),
+    "fcl_hfg_unit_cap_fwd": (_I, [C.POINTER(HfgUnit), _P, _P]),
+    "fcl_hfg_out_cap_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, C.c_int64, _I, _I, _I, _P, _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

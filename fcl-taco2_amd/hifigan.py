@@ -7,8 +7,9 @@ without weight norm) load here; the loader is strict about names and shapes.
 
 Batched: utterances are concatenated row-major (rows = samples at the stage's rate, channels-last); every convolution and the transposed
 convolutions see zeros outside their own utterance.  The generator is deterministic: `seed` / `noise` are accepted and unused.  No CPU fallback;
-needs the pre-split path (FCL_PRECISION / FCL_PLANES not 0).  No capacity form: engine.SpeechRunner refuses this generator and tts.synthesize takes
-its two-step route for every batch."""
+needs the pre-split path (FCL_PRECISION / FCL_PLANES not 0).  `CapacitySynth` is the capacity form (every buffer sized once, the live extent read
+from the device): what engine.SpeechRunner captures behind the synthesis pass and what tts.synthesize(vocoder_graph=True) runs; without that flag
+tts.synthesize keeps its two-step route for this generator."""
 import ctypes as C
 
 import numpy as np
@@ -99,10 +100,167 @@ def tconv_rule(x, w, b, s, lens):
     return out
 
 
+def capacity_maps_rule(utt_frame0, batch, frames_cap, hop, status=0):
+    """numpy statement of fcl_hfg_maps_build.  utt_frame0 [batch + 1]: frame starts of the utterance slots ([batch] = total); a slot without
+    frames owns no frame.  Frames [live, frames_cap) belong to pseudo-utterance `batch` (utt_off[batch] = live, utt_off[batch + 1] = frames_cap), so
+    every index lies inside its buffer.  An incoming status, starts that do not ascend from 0 or more than frames_cap frames: nothing is live and
+    the whole capacity is the pseudo-utterance; the last two OR STATUS_VOCODER_CAP into a zero status, an incoming status stays as it is.
+    Returns dict(frame_utt [frames_cap], utt_off [batch + 2], live [4] = {frames, samples, 0, utterances with frames}, status, ok)."""
+    off = np.asarray(utt_frame0, dtype=np.int64).reshape(-1)[: batch + 1]
+    if off.shape[0] != batch + 1:
+        raise ValueError("capacity_maps_rule: utt_frame0 must hold batch + 1 = %d frame starts" % (batch + 1))
+    fits = off[0] == 0 and bool(np.all(np.diff(off) >= 0)) and off[batch] <= frames_cap
+    ok = fits and int(status) == 0
+    status_out = int(status) if int(status) != 0 or fits else _lib.STATUS_VOCODER_CAP
+    if not ok:
+        off = np.zeros(batch + 1, dtype=np.int64)
+    live = int(off[batch])
+    fu = np.full(frames_cap, batch, dtype=np.int64)
+    fu[:live] = np.searchsorted(off[:batch], np.arange(live), side="right") - 1  # (equal starts: the last one, i.e. the slot that has frames)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return dict(frame_utt=i32(fu), utt_off=i32(np.concatenate([off, [frames_cap]])), live=i32([live, live * hop, 0, int((np.diff(off) > 0).sum())]),
+                status=status_out, ok=bool(ok))
+
+
+def _stage_geometry(cfg):
+    """[(rows per frame, channels)] of every stage's output"""
+    c = config(cfg)
+    out, rate = [], 1
+    for i, s in enumerate(c["upsample_scales"]):
+        rate *= s
+        out.append((rate, c["channels"] >> (i + 1)))
+    return out
+
+
+def capacity_nbytes(cfg, batch, frames_cap):
+    """Exact byte count of a CapacitySynth's buffers (its `nbytes` adds the allocator's rounding, < 512 B per tensor).  Per capacity frame:
+        7 x max_i(rate_i x C_i) x 4      the ONE set of row buffers c, cpl, xb, cs, pa, pb, csp (fp32 or planes: 4 B per row and channel either way)
+                                         every stage works in -- a stage's seven are dead once the next stage's transposed convolution has read csp
+        + max(rate_i x C_i : C_i wider than 128) x 4     the workspace tp of the one-launch-per-convolution stages (0 without such a stage)
+        + channels x 4 + ceil(in_channels / 32) x 128    input_conv's output planes and the mel's planes
+        + hop x (4 + 2) x out_channels + 4               wav, pcm and frame_utt
+    plus 4 x (batch + 2) + 16 bytes for utt_off and the live record.  v1: 7 x 8192 x 4 = 229 KB of the 241 KB per frame, ~0.94 KB per sample."""
+    c = config(cfg)
+    geo = _stage_geometry(c)
+    hop = geo[-1][0]
+    rows = 7 * max(r * ch for r, ch in geo) * 4
+    tp = max([r * ch for r, ch in geo if ch not in (32, 64, 128)] + [0]) * 4
+    small = c["channels"] * 4 + (c["in_channels"] + 31) // 32 * 128 + hop * 6 * c["out_channels"] + 4
+    return int(frames_cap) * (rows + tp + small) + 4 * (int(batch) + 2) + 16
+
+
+class CapacitySynth(object):
+    """The generator in CAPACITY form (the twin of vocoder.CapacitySynth): every buffer, descriptor and pointer is fixed at construction for `batch`
+    utterance slots and `frames_cap` mel frames; what is live comes from the device (the synthesis pass's frame starts), so `run` derives no host
+    value from the data, allocates nothing and is capturable in a hipGraph behind the synthesis pass (engine.SpeechRunner).  The chain is
+    fcl_hfg_maps_build -> fcl_pack_planes of the capacity mel -> the conv / tconv / unit / out cap launches -> fcl_pcm16_fwd; the cap launches do no
+    work and touch no memory past the live rows, and a live row is computed exactly as `synthesize_packed` computes it on the same packed rows.
+    Memory: capacity_nbytes (the stages share one set of row buffers); `nbytes` is what this instance holds (its tensors, 512-byte granularity)."""
+
+    def __init__(self, gen, batch, frames_cap, seed=0):
+        pl = self.plan = gen.plan
+        self.gen, self.B, self.frames_cap, self.seed = gen, int(batch), int(frames_cap), int(seed) & 0xFFFFFFFF
+        dev = pl.device
+        if pl.out_channels != 1:
+            raise _lib.FclError("fcl-taco2_amd: the capacity form of the HiFi-GAN generator writes mono PCM: out_channels = %d is not supported; use "
+                                "synthesize_packed for this generator" % pl.out_channels)
+        if self.B < 1 or self.B > 1024 or self.frames_cap < 1 or self.frames_cap * pl.hop >= 2 ** 31 - 1:
+            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: 1..1024 utterances and fewer than 2^31 / hop frames expected (got %d, %d)"
+                                % (self.B, self.frames_cap))
+        F, hop = self.frames_cap, pl.hop
+        self.M = F * hop
+        geo = _stage_geometry(pl.cfg)
+        with torch.cuda.device(dev):
+            i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+            self.frame_utt, self.utt_off, self.live = i32(F), i32(self.B + 2), i32(4)
+            self.melp = ops.planes_empty(F, pl.A, dev)
+            self.cp0 = ops.planes_empty(F, pl.input["cout"], dev)
+            width = max(r * ch for r, ch in geo)  # elements per frame of the widest stage
+            c, xb, cs = [torch.empty(F * width, device=dev, dtype=torch.float32) for _ in range(3)]
+            cpl, pa, pb, csp = [torch.empty(F * width * 2, device=dev, dtype=torch.int16) for _ in range(4)]
+            tpw = max([r * ch for r, ch in geo if ch not in (32, 64, 128)] + [0])
+            tp = torch.empty(F * tpw * 2, device=dev, dtype=torch.int16) if tpw else None
+            self.wav = torch.empty(self.M, device=dev, dtype=torch.float32)
+            self.pcm = torch.empty(self.M, device=dev, dtype=torch.int16)
+            self._rows = (c, cpl, xb, cs, pa, pb, csp, tp)
+            for t_ in (self.melp, self.cp0, cpl, pa, pb, csp) + ((tp,) if tp is not None else ()):
+                assert t_.data_ptr() % 128 == 0
+            # what this instance holds: its tensors' storages at the caching allocator's 512-byte granularity (a memory_allocated() difference would
+            # also count the unsplit remainders of whatever pool blocks the allocator happened to hand out)
+            held = (self.frame_utt, self.utt_off, self.live, self.melp, self.cp0, self.wav, self.pcm) + tuple(t_ for t_ in self._rows if t_ is not None)
+            self.nbytes = sum((t_.untyped_storage().nbytes() + 511) // 512 * 512 for t_ in held)
+            # the descriptors of every launch: every pointer is static, m / m_in is the capacity
+            fu, uo = self.frame_utt.data_ptr(), self.utt_off.data_ptr()
+            a = _lib.HfgConv()
+            a.m, a.cin, a.cout, a.ksize, a.dilation, a.rate, a.slope = F, pl.input["cin"], pl.input["cout"], pl.input["k"], 1, 1, pl.slope
+            a.xp, a.wp, a.bias, a.frame_utt, a.utt_off, a.yp = self.melp.data_ptr(), pl.input["wp"].data_ptr(), pl.input["b"].data_ptr(), fu, uo, self.cp0.data_ptr()
+            self._input = a
+            self._stages = []
+            rate, rows, cp = 1, F, self.cp0
+            for si, st in enumerate(pl.stages):
+                last_stage = si == len(pl.stages) - 1
+                tc = _lib.HfgTconv()
+                tc.m_in, tc.cin, tc.cout, tc.stride, tc.ksize, tc.padding, tc.rate_in, tc.slope = rows, st["cin"], st["cout"], st["s"], st["ku"], \
+                    tconv_padding(st["s"])[0], rate, pl.slope
+                rows, rate, Cc = rows * st["s"], rate * st["s"], st["cout"]
+                tc.xp, tc.wp, tc.bias, tc.frame_utt, tc.utt_off, tc.y, tc.yp = cp.data_ptr(), st["wp"].data_ptr(), st["b"].data_ptr(), fu, uo, c.data_ptr(), \
+                    cpl.data_ptr()
+                units, nk = [], len(st["blocks"])
+                for j, blk in enumerate(st["blocks"]):
+                    x_in, xp_in, xp_out = c, cpl, pa
+                    for d, U in enumerate(blk):
+                        last = d == len(blk) - 1
+                        u = _lib.HfgUnit()
+                        u.m, u.c, u.ksize, u.dilation, u.rate, u.first, u.last = rows, Cc, U["k"], U["dilation"], rate, int(j == 0), int(last)
+                        u.slope, u.cs_scale, u.csp_slope = pl.slope, 1.0 / nk, OUT_SLOPE if last_stage else pl.slope
+                        u.xp, u.x, u.w1p, u.b1, u.w2p, u.b2 = xp_in.data_ptr(), x_in.data_ptr(), U["w1p"].data_ptr(), U["b1"].data_ptr(), U["w2p"].data_ptr(), \
+                            U["b2"].data_ptr()
+                        u.frame_utt, u.utt_off = fu, uo
+                        if last:
+                            u.cs, u.csp = cs.data_ptr(), csp.data_ptr() if j == nk - 1 else None
+                        else:
+                            u.x_out, u.xp_out = xb.data_ptr(), xp_out.data_ptr()
+                        u.tp = tp.data_ptr() if Cc not in (32, 64, 128) else None
+                        units.append(u)
+                        x_in, xp_in, xp_out = xb, xp_out, (pb if xp_out is pa else pa)
+                self._stages.append((tc, units))
+                cp = csp
+            self._csp, self._rate = csp, rate
+            # eager warm-up on an empty batch: the library's one-time setup (dynamic-LDS opt-ins) must not happen inside a capture
+            self.run(torch.zeros(1, pl.A, device=dev), i32(self.B + 1), i32(1))
+            torch.cuda.current_stream(dev).synchronize()
+
+    def run(self, mel_rows_cap, utt_frame0_dev, status, seed_dev=None):
+        """Enqueue the whole generator + the PCM conversion on the current stream.  mel_rows_cap: [rows, in_channels] float32 device tensor whose first
+        utt_frame0[B] rows are the batch's packed mel frames (later rows may hold anything, NaN included: their planes are never read);
+        utt_frame0_dev: int32 [B + 1] on the device; status: the pass's int32 status word (FCL_STATUS_VOCODER_CAP / FCL_STATUS_PCM_NONFINITE are
+        OR-ed into it; a word that is already set makes this pass generate nothing); seed_dev: accepted and ignored (the generator draws no noise).
+        Results: self.pcm (int16) and self.wav (float32), live samples [0, self.live[1])."""
+        pl, lib = self.plan, _lib.load()
+        if mel_rows_cap.dim() != 2 or mel_rows_cap.shape[1] != pl.A or mel_rows_cap.dtype != torch.float32 or not mel_rows_cap.is_contiguous():
+            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: expected contiguous float32 [rows, %d] mel rows, got %r" % (pl.A, tuple(mel_rows_cap.shape)))
+        if utt_frame0_dev.dtype != torch.int32 or utt_frame0_dev.numel() < self.B + 1 or status.dtype != torch.int32:
+            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: utt_frame0 must hold %d int32 frame starts and status be an int32 word" % (self.B + 1))
+        s, live, chk = ops._stream(), self.live.data_ptr(), _lib.check
+        chk(lib.fcl_hfg_maps_build(utt_frame0_dev.data_ptr(), status.data_ptr(), self.B, self.frames_cap, pl.hop, self.frame_utt.data_ptr(),
+                                   self.utt_off.data_ptr(), live, s))
+        # (a buffer with fewer rows than the capacity cannot hold more live frames than it has rows: the synthesis pass's own capacity)
+        chk(lib.fcl_pack_planes(mel_rows_cap.data_ptr(), mel_rows_cap.stride(0), min(int(mel_rows_cap.shape[0]), self.frames_cap), pl.A, self.melp.data_ptr(), s))
+        chk(lib.fcl_hfg_conv_cap_fwd(C.byref(self._input), live, s))
+        for tc, units in self._stages:
+            chk(lib.fcl_hfg_tconv_cap_fwd(C.byref(tc), live, s))
+            for u in units:
+                chk(lib.fcl_hfg_unit_cap_fwd(C.byref(u), live, s))
+        chk(lib.fcl_hfg_out_cap_fwd(self._csp.data_ptr(), pl.out_w.data_ptr(), pl.out_b.data_ptr(), self.frame_utt.data_ptr(), self.utt_off.data_ptr(), self._rate,
+                                    self.wav.data_ptr(), self.M, pl.c_last, 1, pl.cfg["kernel_size"], live, s))
+        chk(lib.fcl_pcm16_fwd(self.wav.data_ptr(), self.pcm.data_ptr(), self.M, live, status.data_ptr(), s))
+        return self.pcm
+
+
 class HiFiGANPlan(object):
     """Device-resident, GEMM-ready weights of one generator: tap-major P32 planes of every convolution, packed once."""
 
-    eager_only = True  # no capacity form: tts.synthesize keeps the two-step route, engine.SpeechRunner refuses
+    eager_only = True  # the driver's default route: tts.synthesize takes the two-step route unless vocoder_graph is asked for (CapacitySynth exists)
 
     def __init__(self, state_dict, device, cfg=None):
         if not ops.planes_enabled():
@@ -161,6 +319,10 @@ class HiFiGANGenerator(object):
 
     def __init__(self, plan):
         self.plan = plan
+
+    def capacity_synth(self, batch, frames_cap, seed=0):
+        """The capacity form of this generator for `batch` utterance slots and `frames_cap` mel frames (what engine.SpeechRunner captures)."""
+        return CapacitySynth(self, batch, frames_cap, seed=seed)
 
     def synthesize(self, mels, noise=None, seed=0, return_intermediates=False):
         """mels: list of [T'_i, in_channels] float tensors / arrays -> list of [T'_i * hop] float32 device tensors ([T'_i * hop, out] for out > 1)."""

@@ -14,7 +14,9 @@ runs; a writer thread encodes the wav files.  `--feats-out PREFIX` also writes t
 run can be audited against `decode.py` + `vocoder_decode.py`.
 
 One SpeechRunner holds 1082 bytes per capacity sample (vocoder.CapacitySynth), 10.4 GB at the measured BASELINE configs[4] capacity (64
-utterances of 60 - 100 phonemes, 37 632 frames: DESIGN.md 6b), so few are kept: `--max-buckets` (default 2), least recently used first out."""
+utterances of 60 - 100 phonemes, 37 632 frames: DESIGN.md 6b), so few are kept: `--max-buckets` (default 2), least recently used first out.
+A HiFi-GAN generator takes the two-step route for every batch by default; `--vocoder-graph` puts it on the same one-graph route through its
+capacity form (hifigan.CapacitySynth, ~0.94 KB per capacity sample for v1: DESIGN.md 6c)."""
 import argparse
 import collections
 import logging
@@ -72,10 +74,11 @@ class _Bucket(object):
 
 
 @torch.no_grad()
-def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=None, feats_out=None, max_buckets=None):
+def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=None, feats_out=None, max_buckets=None, vocoder_graph=False):
     """utts: [(utt_id, ids)] or [(utt_id, ids, spemb)].  Writes <outdir>/<utt_id>_gen.wav; returns a dict: samples, seconds, rtf, utterances and
     how many batches took each route (graph_batches, eager_batches, redone_batches; their sum is the number of batches), and `batches`: per batch
-    (route, utterance ids in batch order, vocoder noise seed)."""
+    (route, utterance ids in batch order, vocoder noise seed).  vocoder_graph: a generator whose default route is the two-step one but which has a
+    capacity form (HiFi-GAN: gen.capacity_synth) takes the bucketed one-graph route too; nothing changes for Parallel WaveGAN."""
     from . import engine, ops, vocoder
 
     os.makedirs(outdir, exist_ok=True)
@@ -98,8 +101,10 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
         ctl_of = lambda chunk: [one] * len(chunk)
     else:
         ctl_of = lambda chunk: None
-    # (a generator without a capacity form -- HiFi-GAN -- keeps every batch on the two-step route, like a model the capacity graph does not cover)
-    eager_only = bool(getattr(plan, "generic_decoder", False)) or plan.hp.elayers != 1 or bool(getattr(gen.plan, "eager_only", False))
+    # (a generator whose default route is the two-step one -- HiFi-GAN -- keeps every batch on it, like a model the capacity graph does not cover,
+    # unless the caller asks for the graph route and the generator has a capacity form)
+    gen_eager = bool(getattr(gen.plan, "eager_only", False)) and not (vocoder_graph and hasattr(gen, "capacity_synth"))
+    eager_only = bool(getattr(plan, "generic_decoder", False)) or plan.hp.elayers != 1 or gen_eager
     max_buckets = max(1, int(MAX_BUCKETS if max_buckets is None else max_buckets))
     buckets = collections.OrderedDict()
     calibration = None
@@ -291,7 +296,10 @@ def build_parser():
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--feats-out", default=None, metavar="PREFIX", help="also write the mels as PREFIX.ark / PREFIX.scp")
     ap.add_argument("--batch-size", type=int, default=32)
-    ap.add_argument("--max-buckets", type=int, default=MAX_BUCKETS, help="captured text->waveform graphs kept (each holds ~1.07 KB per capacity sample)")
+    ap.add_argument("--max-buckets", type=int, default=MAX_BUCKETS, help="captured text->waveform graphs kept (each holds ~1.07 KB per capacity sample with "
+                    "Parallel WaveGAN, ~0.94 KB with HiFi-GAN v1)")
+    ap.add_argument("--vocoder-graph", action="store_true", help="HiFi-GAN: run the generator inside the captured text->waveform graph (its capacity form) "
+                    "instead of the two-step route; no effect for Parallel WaveGAN, which always does")
     ap.add_argument("--nj", type=int, default=1, help="number of utterance shards (one process per GPU)")
     ap.add_argument("--job", type=int, default=0, help="this process's shard (0-based)")
     ap.add_argument("--seed", type=int, default=137)
@@ -335,7 +343,8 @@ def main(argv=None):
     gen, rate = build_generator(args.vocoder_checkpoint, dev, args.vocoder_config, args.unsafe_pickle)
     mine = shard_of(read_manifest(args.json), args.nj, args.job)
     feats = args.feats_out if args.feats_out is None or args.nj == 1 else "%s.%d" % (args.feats_out, args.job + 1)
-    res = synthesize(model, gen, mine, args.outdir, rate, args.batch_size, args.seed, prosody_from_args(args, [u[0] for u in mine]), feats, args.max_buckets)
+    res = synthesize(model, gen, mine, args.outdir, rate, args.batch_size, args.seed, prosody_from_args(args, [u[0] for u in mine]), feats, args.max_buckets,
+                     vocoder_graph=args.vocoder_graph)
     logging.info("generated %d utterances, %.1f s of audio in %.2f s (RTF = %.5f); batches: %d graph, %d eager, %d redone", res["utterances"],
                  res["samples"] / float(rate), res["seconds"], res["rtf"], res["graph_batches"], res["eager_batches"], res["redone_batches"])
     return res

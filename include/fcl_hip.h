@@ -881,6 +881,27 @@ int fcl_hfg_unit_fwd(const fcl_hfg_unit_t* a, fcl_stream_t stream);
 int fcl_hfg_out_fwd(const uint16_t* cp, const float* w, const float* b, const int32_t* frame_utt, const int32_t* utt_off, int rate, float* wav, int64_t m, int c,
                     int cout, int ksize, fcl_stream_t stream);
 
+/* ---- capacity form of the HiFi-GAN generator: the same kernels with every buffer and grid sized by a CAPACITY (frames_cap mel frames) and the live
+ * extent read from the device, so that the chain text -> waveform is capturable with this generator too (fcl_taco2_amd/hifigan.py CapacitySynth).
+ * No entry allocates, synchronises or copies; each cap entry opts its kernel into its dynamic LDS on first use, so call it once outside a capture.
+ * fcl_hfg_maps_build: ONE launch that builds frame_utt [frames_cap], utt_off [batch + 2] and live [4] = {live frames, live samples (frames x hop), 0,
+ *      utterances with frames} (the words fcl_pcm16_fwd reads) from the synthesis pass's frame starts utt_frame0 [batch + 1] (device).  A slot without
+ *      frames (utt_frame0[u] == utt_frame0[u + 1]) owns no frame; frames [live, frames_cap) belong to pseudo-utterance `batch` with
+ *      utt_off[batch] = live, utt_off[batch + 1] = frames_cap, so every index lies inside its buffer.  *status != 0 on entry, frame starts that do
+ *      not ascend from 0, or more than frames_cap frames: live = {0, 0, 0, 0} and the whole capacity is the pseudo-utterance; the last two also OR
+ *      FCL_STATUS_VOCODER_CAP into *status, an incoming status is left as it is.  Any hop >= 1; 1 <= batch <= 1024; frames_cap * hop < 2^31.
+ * fcl_hfg_conv_cap_fwd / fcl_hfg_tconv_cap_fwd / fcl_hfg_unit_cap_fwd / fcl_hfg_out_cap_fwd: the exact entries' arguments, checks and arithmetic with
+ *      m / m_in read as the CAPACITY (grid and buffer extent); the rows worked on are live[0] x rate (rate_in), read by every workgroup from the
+ *      device.  A live row is computed exactly as the exact entry computes it at m = live rows on the same buffers; rows at and beyond the live rows
+ *      are neither read nor written in any buffer. */
+int fcl_hfg_maps_build(const int32_t* utt_frame0, uint32_t* status, int batch, int64_t frames_cap, int hop, int32_t* frame_utt, int32_t* utt_off, int32_t* live,
+                       fcl_stream_t stream);
+int fcl_hfg_conv_cap_fwd(const fcl_hfg_conv_t* a, const int32_t* live, fcl_stream_t stream);
+int fcl_hfg_tconv_cap_fwd(const fcl_hfg_tconv_t* a, const int32_t* live, fcl_stream_t stream);
+int fcl_hfg_unit_cap_fwd(const fcl_hfg_unit_t* a, const int32_t* live, fcl_stream_t stream);
+int fcl_hfg_out_cap_fwd(const uint16_t* cp, const float* w, const float* b, const int32_t* frame_utt, const int32_t* utt_off, int rate, float* wav, int64_t m, int c,
+                        int cout, int ksize, const int32_t* live, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,

@@ -7,6 +7,13 @@
 One process, alternating legs, event timers, a synchronise at each batch end.  Prints one JSON line.
 
     python tools/hifigan_ab.py [--batch 64] [--frames-lo 420] [--frames-hi 720] [--repeats 5] [--prof]
+
+--speech: the text -> waveform A/B of this generator instead, under the protocol of tools/speech_ab.py (whose remaining flags follow: --batch,
+--batches, --repeats, --distinct, --t-lo, --t-hi, --alone): leg A BatchRunner -> frames() -> synthesize_packed -> float32 D2H, leg B SpeechRunner on
+hifigan.CapacitySynth -> int16 D2H; wall ms per batch, RTF, host-enqueue ms per batch, and the generator alone in both forms (exact vs capacity)
+from the library's event timers, `blocks_ms` = the residual-unit kernels.
+
+    python tools/hifigan_ab.py --speech [--batch 64] [--batches 20] [--repeats 3]
 """
 import argparse
 import json
@@ -19,6 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def timed(fn, dev):
@@ -30,7 +38,19 @@ def timed(fn, dev):
     return a.elapsed_time(b), out
 
 
+def speech(argv):
+    """the SpeechRunner leg: tools/speech_ab.py with a HiFi-GAN v1 generator (random weights, as the legs above)"""
+    import hifigan_ref as R
+    import speech_ab
+    from fcl_taco2_amd import hifigan
+
+    make = lambda dev: hifigan.HiFiGANGenerator(hifigan.HiFiGANPlan(R.random_state_dict(np.random.RandomState(7), R.V1), dev, R.plan_cfg(R.V1)))
+    speech_ab.main(argv, make_gen=make, blocks_prefix="hfg_unit")
+
+
 def main():
+    if "--speech" in sys.argv[1:]:
+        return speech([a for a in sys.argv[1:] if a != "--speech"])
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--frames-lo", type=int, default=420)

@@ -30,7 +30,9 @@ from fcl_taco2_amd.plan import SynthesisPlan  # noqa: E402
 RATE = 22050.0
 
 
-def main():
+def main(argv=None, make_gen=None, blocks_prefix="pwg_layer"):
+    """make_gen(device) -> generator: another generator family under the same protocol (tools/hifigan_ab.py --speech); blocks_prefix: the launch-record
+    names summed as `blocks_ms` in the generator-alone comparison"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--batches", type=int, default=20)
@@ -40,12 +42,15 @@ def main():
     ap.add_argument("--t-hi", type=int, default=100)
     ap.add_argument("--alone", type=int, default=0, metavar="N", help="only the generator alone, N alternating exact / capacity passes without the "
                     "library's timers: the run to put under `rocprofv3 --kernel-trace --stats` (pwg_layer_pkernel vs pwg_layer_cap_pkernel)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = "cuda:0"
     B, T_cap = args.batch, (args.t_hi + 15) // 16 * 16
     hp = HP.student_hparams()
     plan = SynthesisPlan(SYN.positive_duration_head(SYN.closed_form_state_dict(HP.param_spec(hp))), hp, dev)
-    gen = V.ParallelWaveGANGenerator(V.PWGPlan({k: SYN.closed_form_tensor("pwg." + k, tuple(s)) for k, s in V.param_spec().items()}, dev))
+    if make_gen is not None:
+        gen = make_gen(dev)
+    else:
+        gen = V.ParallelWaveGANGenerator(V.PWGPlan({k: SYN.closed_form_tensor("pwg." + k, tuple(s)) for k, s in V.param_spec().items()}, dev))
     hop = gen.plan.hop
     sets = [SYN.batch_c2(hp.idim, batch=B, t_lo=args.t_lo, t_hi=args.t_hi, seed=1234 + i)[0] for i in range(args.distinct)]
     maps = []
@@ -147,7 +152,7 @@ def main():
             torch.cuda.synchronize()
             p = _lib.prof_collect()
             _lib.prof_enable(False)
-            blocks = sum(v["ms"] for k, v in p.items() if k.startswith("pwg_layer"))
+            blocks = sum(v["ms"] for k, v in p.items() if k.startswith(blocks_prefix))
             alone[form].append(dict(blocks_ms=blocks, all_kernels_ms=sum(v["ms"] for v in p.values())))
     summ = lambda leg, key: [r[key] for r in rows if r["leg"] == leg]
     out = dict(batch=B, phonemes=[args.t_lo, args.t_hi], distinct_batches=len(sets), live_frames=live, frames_cap=caps.frames,
