@@ -84,7 +84,7 @@ struct DecoderWs {
     float *G0, *F0, *pre_a, *pre_b, *h0[2], *c0, *h1[2], *c1, *prev;
     float *h2[2], *c2;  // third cell (fcl_decoder_weights_t.dlayers == 3)
     unsigned short *h0_p[2], *h1_p[2], *pre_p;  // P32 planes of the recurrent states / the prenet output (the LSTM steps' pre-split operands)
-    size_t bytes, state_bytes;                  // state_bytes: h0 .. h1_p, zeroed before the loop
+    size_t bytes, state_bytes;                  // state_bytes: h0 .. prev, zeroed before the generic loop (the shipped structure's loop needs no fill)
 };
 
 // P32 planes are used by the decoder loop when the plan provides them and the widths are whole 32-column lines
@@ -106,8 +106,8 @@ static DecoderWs carve(const fcl_decoder_weights_t* w, int n, void* base) {
     ws.F0 = take(N * w->odim * RF);
     ws.pre_a = take(N * w->p);
     ws.pre_b = take(N * w->p);
-    // what the loop READS before it writes — the states entering step 0 (fp32 and, for the pre-split path, planes) and prev_out — is contiguous, so
-    // one kernel zeroes exactly that; the ping-pong partners are written by step 0 before anything reads them
+    // what the generic loop READS before it writes — the states entering step 0 (fp32 and, for the pre-split path, planes) and prev_out — is contiguous,
+    // so one kernel zeroes exactly that; the ping-pong partners are written by step 0 before anything reads them
     ws.h0[0] = take(N * w->u);
     ws.c0 = take(N * w->u);
     ws.h1[0] = take(N * w->u);
@@ -538,15 +538,16 @@ int fcl_decoder_loop_fwd(const fcl_decoder_weights_t* w, const fcl_decoder_io_t*
     const int N = io->n, C = w->c, P = w->p, U = w->u, O = w->odim;
     DecoderWs ws = carve(w, N, io->workspace);
 
-    // zero recurrent state (h0[2], c0, h1[2], c1 are contiguous) and prev_out
     static const bool planes_on = tunable("PRECISION", 1) != 0 && tunable("PLANES", 1) != 0;
     const bool planes = decoder_planes(w) && io->att_c_p != nullptr && planes_on;
     FCL_REQUIRE(planes || io->att_c, FCL_ERR_INVALID, "decoder_loop_fwd: att_c is required when the P32 path is off");
     FCL_REQUIRE(!io->before_p || planes, FCL_ERR_INVALID, "decoder_loop_fwd: before_p needs the P32 weight planes and att_c_p");
-    {
-        hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, s, ws.h0[0], (long long)(ws.state_bytes / 4));
-        FCL_HIP(hipGetLastError());
-    }
+    // No fill of the recurrent state: step 0 of both layers runs the ZERO-STATE form of the LSTM step (h_in == NULL, the h . W_hh^T term not passed),
+    // which reads neither h nor c and writes c; the first feat_prenet launch has no previous frame (h1 == NULL).  Every later read of a state buffer
+    // is of rows below the HOST's bound of its step, and the step before stored the rows below min(its host bound, its device count): a row in
+    // between is read unwritten, but it is at or beyond the device count of every later step (the counts do not increase), so nothing computed from
+    // it is stored, and no output row of any launch depends on another row.  The same held before for the ping-pong partners h0[1] / h1[1] and
+    // their planes, which no fill ever covered.
     const int ldc = C / 32, ldp = P / 32, ldu = U / 32;  // plane strides in 128-byte lines (planes mode: whole lines)
     auto small_step = [&](int m) { return lstm_step_is_small(m, U); };  // launch_lstm_step's own choice: small steps read the fp32 operands
     // loop-invariant hoists: att_c is constant across steps, so its share of the LSTM-0
@@ -574,8 +575,11 @@ int fcl_decoder_loop_fwd(const fcl_decoder_weights_t* w, const fcl_decoder_io_t*
         // chain, and the line drops from 45 to 38 M frames/s (HISTORY "round 4")
         static const int tile_on = tunable("DEC_TILE", 0), tile_min = tunable("DEC_TILE_MIN_ROWS", 1024);
         if (tile_on && planes && w->stream && decoder_tile_shape_ok(w) && N >= tile_min && io->lmax <= 64 && !io->teacher_ys && !io->tap_prenet && !io->tap_lstm0 &&
-            !io->tap_lstm1 && drop_mode != FCL_DROP_MASK && gemm_mode() != FCL_GEMM_BF16)
+            !io->tap_lstm1 && drop_mode != FCL_DROP_MASK && gemm_mode() != FCL_GEMM_BF16) {
+            hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, s, ws.c0, (long long)((ws.c1 - ws.c0) + (size_t)N * U));  // (it reads c0 / c1 at its step 0)
+            FCL_HIP(hipGetLastError());
             return launch_decoder_tile(w, io, ws.G0, ws.F0, ws.c0, ws.c1, drop_mode, 0, nullptr, nullptr, s);
+        }
     }
     // fcl_decoder_io_t.tail_from: from that step on the rows still live continue in ONE launch of the persistent row-tile kernel, from the loop's own
     // fp32 states -- in a capacity graph the steps beyond the longest duration seen so far then cost one launch in all instead of three each
@@ -617,17 +621,17 @@ int fcl_decoder_loop_fwd(const fcl_decoder_weights_t* w, const fcl_decoder_io_t*
         const bool big = planes && !small_step(n);  // big steps: pre-split operands through the LDS-DMA kernels; their outputs feed the next step's
         const bool next_big = planes && t + 1 < io->lmax && !small_step(io->live_rows_host[t + 1]);
         l0.term[0] = GemmTerm{ws.pre_b, w->w0_pre, P, P, P, 0, w->w0_pre_hi, w->w0_pre_lo};
-        l0.term[1] = GemmTerm{ws.h0[cur], w->w0_hh, U, U, U, 0, w->w0_hh_hi, w->w0_hh_lo};
+        l0.term[1] = GemmTerm{ws.h0[cur], w->w0_hh, U, U, U, 0, w->w0_hh_hi, w->w0_hh_lo};  // (step 0: not passed -- h0 = 0)
         if (big) {
             l0.term[0].Ap = ws.pre_p; l0.term[0].Wp = w->w0_pre_p; l0.term[0].lda_p = l0.term[0].ldw_p = ldp;
             l0.term[1].Ap = ws.h0_p[cur]; l0.term[1].Wp = w->w0_hh_p; l0.term[1].lda_p = l0.term[1].ldw_p = ldu;
             l0.h_out_p = ws.h0_p[cur ^ 1]; l0.ld_hp = ldu;  // read by layer 1 now and by layer 0 of the next step
         }
         l0.term[0].Wff = w->w0_pre_ff; l0.term[1].Wff = w->w0_hh_ff;
-        l0.nterms = 2; l0.M = n; l0.U = U; l0.G = ws.G0; l0.g_row_mul = 1; l0.g_row_add = 0;
+        l0.nterms = t == 0 ? 1 : 2; l0.M = n; l0.U = U; l0.G = ws.G0; l0.g_row_mul = 1; l0.g_row_add = 0;
         l0.m_dev = io->live_rows ? io->live_rows + t : nullptr;
         l0.rank1_w = w->w0_pos; l0.dur = io->dur; l0.step = t;
-        l0.h_in = ws.h0[cur]; l0.h_out = ws.h0[cur ^ 1]; l0.c = ws.c0; l0.zoneout = w->zoneout_rate;
+        l0.h_in = t == 0 ? nullptr : ws.h0[cur]; l0.h_out = ws.h0[cur ^ 1]; l0.c = ws.c0; l0.zoneout = w->zoneout_rate;
         if (io->tap_lstm0) { l0.out2 = io->tap_lstm0; l0.out2_row_base = io->frame_off; l0.out2_row_add = t; l0.ld2 = U; }
         rc = launch_lstm_step(l0, s);
         if (rc) return rc;
@@ -641,9 +645,9 @@ int fcl_decoder_loop_fwd(const fcl_decoder_weights_t* w, const fcl_decoder_io_t*
             if (next_big) { l1.h_out_p = ws.h1_p[cur ^ 1]; l1.ld_hp = ldu; }
         }
         l1.term[0].Wff = w->w1_ih_ff; l1.term[1].Wff = w->w1_hh_ff;
-        l1.nterms = 2; l1.M = n; l1.U = U; l1.bias = w->b1; l1.step = t;
+        l1.nterms = t == 0 ? 1 : 2; l1.M = n; l1.U = U; l1.bias = w->b1; l1.step = t;
         l1.m_dev = l0.m_dev;
-        l1.h_in = ws.h1[cur]; l1.h_out = ws.h1[cur ^ 1]; l1.c = ws.c1; l1.zoneout = w->zoneout_rate;
+        l1.h_in = t == 0 ? nullptr : ws.h1[cur]; l1.h_out = ws.h1[cur ^ 1]; l1.c = ws.c1; l1.zoneout = w->zoneout_rate;
         if (io->tap_lstm1) { l1.out2 = io->tap_lstm1; l1.out2_row_base = io->frame_off; l1.out2_row_add = t; l1.ld2 = U; }
         rc = launch_lstm_step(l1, s);
         if (rc) return rc;

@@ -959,7 +959,8 @@ __global__ __launch_bounds__(512) void feat_prenet_split_f32_kernel(const FeatPr
     }
 }
 
-// PRE: both terms have K = 256 (the student's decoder LSTMs) -> all 2 x 8 weight fragments are requested at kernel entry.
+// PRE: every term has K = 256 (the student's decoder LSTMs: two terms, or the input term alone in the zero-state form of step 0) -> all weight
+// fragments are requested at kernel entry.
 template <bool PRE>
 __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a) {
     // device-driven loops: loads and MFMAs run on the host's row bound, only the final store is limited to the device's live-row count (its scalar
@@ -982,8 +983,10 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     WFrag<1, 8> wf[2];
     if (PRE) {
+        const int nt = a.nterms;  // 2, or 1 (wave-uniform)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {  // W rows g*U + u0.. form fragment tile (g*U + u0)/16 (U % 16 == 0); 8 steps per row tile
+            if (t >= nt) break;
             const size_t fo = (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8;
             const u16* const wh[1] = {a.term[t].Whi + fo};
             const u16* const wl[1] = {a.term[t].Wlo + fo};
@@ -991,6 +994,7 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
+            if (t >= nt) break;
             if (t) __syncthreads();
             load_rowtile_split(A_h, A_lo, 256 + 16, a.term[t].A, a.term[t].lda, 256, m0, M);
             __syncthreads();
@@ -1028,7 +1032,7 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
 
 // The small step in EXACT fp32 with register-resident weights (FCL_PRECISION=0; round 4): the structure of lstm_small_x3_kernel<true> on fragment-major
 // fp32 weights (fcl_gemm_term_t.Wff) and v_mfma_f32_16x16x4_f32, the weight fragment as the A operand (a lane's accumulators: four consecutive units
-// of one row).  Both terms K = 256.
+// of one row).  Every term K = 256: two, or the input term alone in the zero-state form.
 __global__ __launch_bounds__(256) void lstm_small_ff_kernel(const LstmStepArgs a) {
     const int M = a.M, Ms = live_rows_of(a.M, a.m_dev);
     if ((int)blockIdx.y * 16 >= Ms) return;
@@ -1045,13 +1049,16 @@ __global__ __launch_bounds__(256) void lstm_small_ff_kernel(const LstmStepArgs a
     if (evalid) ci = cell_prefetch(a, em, eu);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     WFragF<1, 8> wf[2];
+    const int nt = a.nterms;  // 2, or 1 (wave-uniform)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
+        if (t >= nt) break;
         const float* const w[1] = {a.term[t].Wff + (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8};
         wf[t].load(w);
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
+        if (t >= nt) break;
         if (t) __syncthreads();
         load_rowtile(A_f, LD, a.term[t].A, a.term[t].lda, 256, m0, M);
         __syncthreads();
@@ -1129,11 +1136,17 @@ int launch_lstm_small(const LstmStepArgs& a, hipStream_t s) {
     bool planes = true;
     for (int i = 0; i < a.nterms; ++i) planes = planes && a.term[i].Whi && a.term[i].Wlo && (a.term[i].K & 7) == 0 && a.term[i].ldw == a.term[i].K;
     planes = planes && (a.U & 15) == 0;
+    // the register-resident forms: two K = 256 terms, or the zero-state step's single one (its h . W_hh^T term is dropped, not contracted with zeros)
+    bool pre256 = a.nterms == 2 || (a.nterms == 1 && !a.h_in), ff = true;
+    for (int i = 0; i < a.nterms; ++i) {
+        pre256 = pre256 && a.term[i].K == 256;
+        ff = ff && a.term[i].Wff != nullptr;
+    }
     if (planes) {
         ProfScope ps("lstm_small_kernel/bf16x3", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
-        if (a.nterms == 2 && a.term[0].K == 256 && a.term[1].K == 256) hipLaunchKernelGGL(lstm_small_x3_kernel<true>, grid, dim3(256), 0, s, a);
+        if (pre256) hipLaunchKernelGGL(lstm_small_x3_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(lstm_small_x3_kernel<false>, grid, dim3(256), 0, s, a);
-    } else if (a.nterms == 2 && a.term[0].Wff && a.term[1].Wff && a.term[0].K == 256 && a.term[1].K == 256 && (a.U & 15) == 0) {
+    } else if (pre256 && ff && (a.U & 15) == 0) {
         ProfScope ps("lstm_small_ff_kernel/f32", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
         hipLaunchKernelGGL(lstm_small_ff_kernel, grid, dim3(256), 0, s, a);
     } else {

@@ -478,7 +478,7 @@ template <int WM, int WN, int TM = 1>
 static void launch_lstm_cfg(const LstmStepArgs& a, hipStream_t s, const char* name, double flops) {
     using G = Geo<WM, WN, true, TM>;
     dim3 grid((a.U + 16 * WN - 1) / (16 * WN), (a.M + G::BM - 1) / G::BM);
-    const bool plain = !a.zone_keep_h && !a.row_len;
+    const bool plain = !a.zone_keep_h && !a.row_len && a.h_in;  // (the zero-state form, h_in == NULL, runs in MODE -1, which tests it per launch)
     const int mode = (plain && a.G && a.rank1_w && !a.bias) ? 0 : (plain && a.bias && !a.G && !a.rank1_w) ? 1 : -1;
     char full[64];  // <WM, WN, MODE, PREC, TM> as rocprofv3 prints the instantiation
     const int hi_only = precision() && gemm_mode() == FCL_GEMM_BF16;
@@ -614,7 +614,8 @@ int validate_lstm_step(const LstmStepArgs& a) {
     if (a.M == 0) return 0;
     int rc = check_terms(a.term, a.nterms, 3, false, nullptr);
     if (rc) return rc;
-    FCL_REQUIRE(a.h_in && a.h_out && a.c && a.h_in != a.h_out, FCL_ERR_INVALID, "lstm_step: h_in/h_out/c must be set and h_out must not alias h_in");
+    // h_in == NULL is the zero-state form (previous hidden and cell state are zero, c is write-only): every step kernel has it
+    FCL_REQUIRE(a.h_out && a.c && a.h_in != a.h_out, FCL_ERR_INVALID, "lstm_step: h_out/c must be set and h_out must not alias h_in");
     FCL_REQUIRE(!a.rank1_w || a.dur, FCL_ERR_INVALID, "lstm_step: rank1_w needs dur");
     FCL_REQUIRE((a.zone_keep_h == nullptr) == (a.zone_keep_c == nullptr), FCL_ERR_INVALID, "lstm_step: zoneout masks come in pairs");
     return 0;

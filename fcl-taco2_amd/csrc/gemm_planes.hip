@@ -144,14 +144,17 @@ struct PGeo {
 
 // The shared main loop.  LSTM: tile column c of the wave strip wn is gate (c >> 4) & 3 of unit u0 + wn*16 + (c & 15), i.e. W row g*NU + u
 // (TN must be 4); generic: W row n0 + c.  NU = N (generic) or U.  Returns false in a loader wave (LW > 0), which is done and must return.
-template <int WM, int WN, int TM, int TN, int NST, bool LSTM, int LW, int HI>
+// ROLE: 0 = the wave finds out here whether it loads or computes; 1 / 2 = the caller has branched on it already (LW > 0) and this is a loader / compute
+// wave -- the other role's code, and the accumulators' live range across it, then drop out of that call.
+template <int WM, int WN, int TM, int TN, int NST, bool LSTM, int LW, int HI, int ROLE = 0>
 __device__ __forceinline__ bool pmainloop(const GemmTerm* __restrict__ terms, int nterms, int M, int m0, int n0, int NU, const int* __restrict__ seg_lo,
                                           const int* __restrict__ seg_hi, u8* smem, f32x4 (&acc)[TM][TN], int ksplit_chunks = 0) {
     using G = PGeo<WM, WN, TM, TN, NST, LW>;
     static_assert(!LSTM || TN == 4, "LSTM tiles keep the four gates of a unit in one lane");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool loader = LW > 0 && wave >= G::NW;
+    static_assert(ROLE == 0 || LW > 0, "a role is fixed only where loader waves exist");
+    const bool loader = ROLE == 1 || (ROLE == 0 && LW > 0 && wave >= G::NW);
     const int lw = LW > 0 ? wave - G::NW : wave;  // index among the loading waves
     const int wm = wave / WN, wn = wave % WN;
     int nchunks = 0;
@@ -582,8 +585,12 @@ __global__ __launch_bounds__(64 * (WM * WN + LW), (NST == 2 && WM * WN + LW == 1
     pgemm_epilogue<WN, TM, TN, G::BM, G::BN, G::CTHREADS, G::LDS_BYTES>(a, acc, smem, m0, n0);
 }
 
-// NST = 2 (two ring stages, 64 KB: TWO workgroups per CU, 6 waves per SIMD, <= 80 VGPRs): the epilogue operands are then NOT requested before
-// the K loop (48 VGPRs held across it) but where they are used -- the other workgroup's main loop covers their latency.
+// The fixed synthesis modes (MODE >= 0) SEED the accumulators: a lane's acc[tm][g][r] is exactly the pre-activation of (row, gate g, unit), so it starts
+// from G0 + pos * w_pos (layer 0) or the bias (layer 1) instead of zero -- no register beyond the accumulators themselves, the loads are older than
+// every LDS-DMA piece (the loop's waits cover them), and the epilogue neither loads nor adds them.  MODE -1 (training forms, masks, saved gates, taps)
+// keeps zero accumulators and the additive operands in CellIn.
+// NST = 2 (two ring stages, 64 KB: TWO workgroups per CU, 6 waves per SIMD, <= 80 VGPRs): the old state is then NOT requested before the K loop
+// (16 VGPRs held across it) but where it is used -- the other workgroup's main loop covers the latency.  The zero-state modes (2 / 3) have none.
 template <int WM, int WN, int TM, int NST, int MODE, int LW, int HI>
 __device__ __forceinline__ void plstm_body(const LstmStepArgs& a, u8* smem) {
     using G = PGeo<WM, WN, TM, 4, NST, LW>;
@@ -594,27 +601,44 @@ __device__ __forceinline__ void plstm_body(const LstmStepArgs& a, u8* smem) {
     // count, whose scalar load is then hidden behind the whole K loop
     const int M = a.M, Ms = live_rows_of(a.M, a.m_dev);
     if (m0 >= Ms) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier / LDS-DMA)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    f32x4 acc[TM][4];
+    if (LW > 0 && wave >= G::NW) {  // a loader wave has no cells: LDS-DMA only (branching here keeps the seeds out of its registers)
+        (void)pmainloop<WM, WN, TM, 4, NST, true, LW, HI, 1>(a.term, a.nterms, M, m0, u0, a.U, nullptr, nullptr, smem, acc);
+        return;
+    }
     const int wm = wave / WN, wn = wave % WN;
     const int u = u0 + wn * 16 + (lane & 15);
     const int rq = lane >> 4;
     // epilogue operands (G0 / bias / position / old state) are requested BEFORE the K loop (plain loads: they are older than every LDS-DMA
     // piece, so the counted vmcnt waits of the loop cover them and their latency hides under it)
+    constexpr bool SEED = MODE >= 0;
     constexpr bool PRE = NST != 2;
     CellIn ci[PRE ? TM : 1][4];
     const int uc = min(u, a.U - 1);
-    if (PRE && (LW == 0 || wave < G::NW)) {
+    if (PRE) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ci[tm][r] = cell_prefetch<MODE>(a, min(m0 + (wm * TM + tm) * 16 + rq * 4 + r, M - 1), uc);
+            for (int r = 0; r < 4; ++r) ci[tm][r] = cell_prefetch<MODE, SEED>(a, min(m0 + (wm * TM + tm) * 16 + rq * 4 + r, M - 1), uc);
     }
-    f32x4 acc[TM][4];
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[tm][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (!pmainloop<WM, WN, TM, 4, NST, true, LW, HI>(a.term, a.nterms, M, m0, u0, a.U, nullptr, nullptr, smem, acc)) return;  // loader wave
+    if (SEED) {
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int mc = min(m0 + (wm * TM + tm) * 16 + rq * 4 + r, M - 1);
+                float add[4];
+                cell_seed<MODE>(a, mc, uc, cell_pos<MODE>(a, mc), add);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[tm][j][r] = add[j];
+            }
+    }
+    (void)pmainloop<WM, WN, TM, 4, NST, true, LW, HI, (LW > 0 ? 2 : 0)>(a.term, a.nterms, M, m0, u0, a.U, nullptr, nullptr, smem, acc);
     if (g_plstm_dbg == 1) {
         float sdbg = 0.f;
 #pragma unroll
@@ -640,10 +664,10 @@ __device__ __forceinline__ void plstm_body(const LstmStepArgs& a, u8* smem) {
             if (m < Ms && u < a.U) {  // (cell_math also stores the optional taps / saved gates: live rows only)
                 const float pre[4] = {acc[tm][0][r], acc[tm][1][r], acc[tm][2][r], acc[tm][3][r]};
                 if (PRE) {
-                    cell_math<MODE>(a, m, u, pre, ci[PRE ? tm : 0][r], h_w, c_w);
+                    cell_math<MODE, SEED>(a, m, u, pre, ci[PRE ? tm : 0][r], h_w, c_w);
                 } else {
-                    const CellIn cl = cell_prefetch<MODE>(a, m, u);
-                    cell_math<MODE>(a, m, u, pre, cl, h_w, c_w);
+                    const CellIn cl = cell_prefetch<MODE, SEED>(a, m, u);
+                    cell_math<MODE, SEED>(a, m, u, pre, cl, h_w, c_w);
                 }
             }
             th[rm * LDT + wn * 16 + (lane & 15)] = h_w;
@@ -1038,14 +1062,17 @@ template <int WM, int WN, int TM, int NST, int LW, int HI>
 static int launch_plstm_lw(const LstmStepArgs& a, hipStream_t s, double flops) {
     using G = PGeo<WM, WN, TM, 4, NST, LW>;
     const bool plain = !a.zone_keep_h && !a.row_len && !a.save_gates && !a.out2;  // (MODE >= 0 compiles these options out of the cell code)
-    const int mode = (plain && a.G && a.rank1_w && !a.bias) ? 0 : (plain && a.bias && !a.G && !a.rank1_w) ? 1 : -1;
+    const int layer = (plain && a.G && a.rank1_w && !a.bias) ? 0 : (plain && a.bias && !a.G && !a.rank1_w) ? 1 : -1;
+    const int mode = layer < 0 ? -1 : layer + (a.h_in ? 0 : 2);  // (2 / 3: the zero-state form of 0 / 1; MODE -1 tests h_in at run time)
     dim3 grid((a.U + 16 * WN - 1) / (16 * WN), (a.M + G::BM - 1) / G::BM);
     char full[64];
     snprintf(full, sizeof(full), "plstm_kernel<%d,%d,%d,%d,%d,%d>%s", WM, WN, TM, NST, mode, LW, HI == 2 ? "/f32" : HI ? "/bf16" : "");
-    const void* fn = mode == 0 ? reinterpret_cast<const void*>(plstm_kernel<WM, WN, TM, NST, 0, LW, HI>)
-                   : mode == 1 ? reinterpret_cast<const void*>(plstm_kernel<WM, WN, TM, NST, 1, LW, HI>)
-                               : reinterpret_cast<const void*>(plstm_kernel<WM, WN, TM, NST, -1, LW, HI>);
-    const int rc = ensure_dyn_lds(fn, G::LDS_BYTES);
+    void (*const fn)(const LstmStepArgs) = mode == 0   ? plstm_kernel<WM, WN, TM, NST, 0, LW, HI>
+                                           : mode == 1 ? plstm_kernel<WM, WN, TM, NST, 1, LW, HI>
+                                           : mode == 2 ? plstm_kernel<WM, WN, TM, NST, 2, LW, HI>
+                                           : mode == 3 ? plstm_kernel<WM, WN, TM, NST, 3, LW, HI>
+                                                       : plstm_kernel<WM, WN, TM, NST, -1, LW, HI>;
+    const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(fn), G::LDS_BYTES);
     if (rc) return rc;
     double fill = 0.0;
     {
@@ -1054,9 +1081,7 @@ static int launch_plstm_lw(const LstmStepArgs& a, hipStream_t s, double flops) {
         fill = (double)grid.x * grid.y * (double)nch * (G::BM + G::BN) * 128.0;
     }
     ProfScope ps(full, flops, a.M, s, fill);
-    if (mode == 0) hipLaunchKernelGGL((plstm_kernel<WM, WN, TM, NST, 0, LW, HI>), grid, dim3(G::THREADS), G::LDS_BYTES, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((plstm_kernel<WM, WN, TM, NST, 1, LW, HI>), grid, dim3(G::THREADS), G::LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((plstm_kernel<WM, WN, TM, NST, -1, LW, HI>), grid, dim3(G::THREADS), G::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(fn, grid, dim3(G::THREADS), G::LDS_BYTES, s, a);
     return check_hip(hipGetLastError(), "plstm launch");
 }
 

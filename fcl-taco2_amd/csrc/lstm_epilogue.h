@@ -16,7 +16,7 @@ __device__ __forceinline__ float act_apply(float v, int act) {  // FCL_ACT_*
 
 // everything one (row m, unit u) needs besides the MFMA partial sums, fetched early to hide latency
 struct CellIn {
-    float add[4];  // bias + G + pos*w  per gate
+    float add[4];  // bias + G + pos*w  per gate (unset when the kernel seeded its accumulators with it: cell_seed)
     float h_old, c_old;
     bool live;
 };
@@ -24,27 +24,52 @@ struct CellIn {
 // MODE -1: every optional input tested at run time; MODE 0: decoder layer 0 (G + position, no bias);
 // MODE 1: decoder layer 1 (bias only).  The fixed modes issue their loads unconditionally, so hipcc keeps
 // them all in flight instead of branching + waiting around each one (guide §5 trap (c)).
+// MODE 2 / 3: MODE 0 / 1 in the ZERO-STATE form (fcl_lstm_step_t.h_in == NULL: the previous hidden and cell state are zero): neither h_in nor c is
+// loaded, the cell and the zoneout blend run on old = 0 -- bit for bit what explicit zero buffers give -- and c is write-only.
+__host__ __device__ constexpr bool mode_layer0(int MODE) { return MODE == 0 || MODE == 2; }
+__host__ __device__ constexpr bool mode_layer1(int MODE) { return MODE == 1 || MODE == 3; }
+
+// the position input of row m: step / dur[m] (0 where the step has none)
 template <int MODE = -1>
-__device__ __forceinline__ CellIn cell_prefetch(const LstmStepArgs& a, int m, int u) {
-    CellIn ci;
-    const bool has_bias = MODE < 0 ? a.bias != nullptr : MODE == 1;
-    const bool has_g = MODE < 0 ? a.G != nullptr : MODE == 0;
-    const bool has_pos = MODE < 0 ? a.rank1_w != nullptr : MODE == 0;
+__device__ __forceinline__ float cell_pos(const LstmStepArgs& a, int m) {
+    const bool has_pos = MODE < 0 ? a.rank1_w != nullptr : mode_layer0(MODE);
+    return has_pos ? (float)a.step / (float)a.dur[m] : 0.f;  // reference: arange(d).float() / d  (a reciprocal instead: no measurable gain, r3)
+}
+
+// the additive operands of the four gate pre-activations of (row m, unit u): bias + G + pos * w  (pos = cell_pos of the row)
+template <int MODE = -1>
+__device__ __forceinline__ void cell_seed(const LstmStepArgs& a, int m, int u, float pos, float (&add)[4]) {
+    const bool has_bias = MODE < 0 ? a.bias != nullptr : mode_layer1(MODE);
+    const bool has_g = MODE < 0 ? a.G != nullptr : mode_layer0(MODE);
+    const bool has_pos = MODE < 0 ? a.rank1_w != nullptr : mode_layer0(MODE);
+    if (MODE >= 0) {  // fixed modes: each value is loaded straight into its place (no 0 + x in between, which hipcc may not fold: -0)
+        const float* gr = has_g ? a.G + (size_t)((long long)m * a.g_row_mul + a.g_row_add) * (4 * a.U) : a.bias;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) ci.add[g] = has_bias ? a.bias[g * a.U + u] : 0.f;
-    if (has_g) {
-        const float* gr = a.G + (size_t)((long long)m * a.g_row_mul + a.g_row_add) * (4 * a.U);
+        for (int g = 0; g < 4; ++g) add[g] = gr[g * a.U + u];
+    } else {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) ci.add[g] += gr[g * a.U + u];
+        for (int g = 0; g < 4; ++g) add[g] = has_bias ? a.bias[g * a.U + u] : 0.f;
+        if (has_g) {
+            const float* gr = a.G + (size_t)((long long)m * a.g_row_mul + a.g_row_add) * (4 * a.U);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) add[g] += gr[g * a.U + u];
+        }
     }
     if (has_pos) {
-        const float pos = (float)a.step / (float)a.dur[m];  // reference: arange(d).float() / d  (a reciprocal instead: no measurable gain, r3)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) ci.add[g] += pos * a.rank1_w[g * a.U + u];
+        for (int g = 0; g < 4; ++g) add[g] += pos * a.rank1_w[g * a.U + u];
     }
+}
+
+// SEEDED: the caller has started its accumulators from cell_seed, so only the old state is fetched here
+template <int MODE = -1, bool SEEDED = false>
+__device__ __forceinline__ CellIn cell_prefetch(const LstmStepArgs& a, int m, int u) {
+    CellIn ci;
+    if (!SEEDED) cell_seed<MODE>(a, m, u, cell_pos<MODE>(a, m), ci.add);
+    const bool zero_state = MODE < 0 ? a.h_in == nullptr : MODE >= 2;
     const size_t off = (size_t)m * a.U + u;
-    ci.h_old = a.h_in[off];
-    ci.c_old = a.c[off];
+    ci.h_old = zero_state ? 0.f : a.h_in[off];
+    ci.c_old = zero_state ? 0.f : a.c[off];
     ci.live = a.row_len ? (a.step < a.row_len[m]) : true;
     return ci;
 }
@@ -54,10 +79,10 @@ __device__ __forceinline__ CellIn cell_prefetch(const LstmStepArgs& a, int m, in
 // MODE >= 0 (the launchers pick it only when no train-form mask, no row_len, no saved gates and no out2 tap is set): those options are compiled
 // out -- the element code of the big-tile step is instruction-bound (8 cells per lane, ~150 VALU instructions each with every option tested per
 // cell: ~4 us per workgroup of the 17 us launch, r3 ISA count), and the synthesis loop uses none of them.
-template <int MODE = -1>
+template <int MODE = -1, bool SEEDED = false>
 __device__ __forceinline__ void cell_math(const LstmStepArgs& a, int m, int u, const float (&acc)[4], const CellIn& ci, float& h_w, float& c_w) {
-    const float ig = sigmoid_f(acc[0] + ci.add[0]), fg = sigmoid_f(acc[1] + ci.add[1]);
-    const float gg = tanh_f(acc[2] + ci.add[2]), og = sigmoid_f(acc[3] + ci.add[3]);
+    const float ig = sigmoid_f(SEEDED ? acc[0] : acc[0] + ci.add[0]), fg = sigmoid_f(SEEDED ? acc[1] : acc[1] + ci.add[1]);
+    const float gg = tanh_f(SEEDED ? acc[2] : acc[2] + ci.add[2]), og = sigmoid_f(SEEDED ? acc[3] : acc[3] + ci.add[3]);
     const float c_new = fg * ci.c_old + ig * gg;
     const float h_new = og * tanh_f(c_new);
     const size_t off = (size_t)m * a.U + u;

@@ -264,9 +264,11 @@ typedef struct {
     const float* rank1_w;    /* optional [4U]: + (step / dur[m]) * rank1_w  (the decoder's position input) */
     const int32_t* dur;
     int step;
-    const float* h_in;       /* [M, U] previous hidden state */
+    const float* h_in;       /* [M, U] previous hidden state.  NULL = the ZERO-STATE form: the previous hidden AND cell state are zero; neither h_in nor c
+                              * is read, c is write-only, and the caller passes only the terms whose A operand is non-zero (no h_in . W_hh^T term).
+                              * Bit for bit the result of zero-filled h_in / c and a zero A of the dropped term (a decoder's step 0) */
     float* h_out;            /* [M, U], must not alias h_in */
-    float* c;                /* [M, U] cell state, in place */
+    float* c;                /* [M, U] cell state, in place (write-only in the zero-state form) */
     float zoneout;           /* expectation-form rate (0 = plain LSTMCell) */
     const uint8_t* zone_keep_h; /* optional sampled zoneout masks [M, U] (1 keeps the OLD state), in pairs */
     const uint8_t* zone_keep_c;
