@@ -6,7 +6,10 @@
 2. The fixed synthesis modes of the big-tile kernel start their accumulators from the additive operands (G + position, or the bias): against the
    fp32-operand kernel, which does not, at the bounds of test_gpu_planes.py.
 3. fcl_decoder_loop_fwd has no fill of its recurrent state: the same pass over a workspace of 0xFF bytes (NaN everywhere) and over a zeroed one
-   gives the same finite frames, with host row bounds above the device's live-row counts and across the hand-over into the row-tile kernel."""
+   gives the same finite frames, with host row bounds above the device's live-row counts and across the hand-over into the row-tile kernel.
+
+These claims are kernel against kernel (bit equality, one form against another); tests/test_gpu_lstm_step_f64.py compares every form of the step with
+an independent float64 reference."""
 import ctypes as C
 import os
 import subprocess

@@ -1,6 +1,7 @@
 """-m gpu: the pre-split (P32) operand path — plane packing (bit-exact vs a numpy restatement of the bf16 split), the LDS-DMA GEMM / Conv1d /
 LSTM-step kernels against fp64 references and against the fp32-operand kernels, the plane outputs of every producer, edge shapes (rows and
-columns that do not fill a tile, K that is not a multiple of 32, one-row matrices, ragged conv segments)."""
+columns that do not fill a tile, K that is not a multiple of 32, one-row matrices, ragged conv segments).
+(The LSTM step against an independent float64 reference, every kernel form and option: tests/test_gpu_lstm_step_f64.py.)"""
 import numpy as np
 import pytest
 import torch
