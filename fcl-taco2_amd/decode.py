@@ -10,19 +10,23 @@
     frames / second (stream-synchronised, unlike the reference's unsynchronised clock, tts.py:665-667).
 Differences: utterances are synthesised `--batch-size` at a time (sorted by length), and `--nj/--job` shard the manifest
 by utterance (what `splitjson.py` + one process per split did), one process per GPU, no collective.
+decode() keeps the submit loop (`depth` BatchRunners per length bucket on the shared pass streams); the bucket policy, the capacity sizing and the
+writer thread it shares with tts.py are batching.py's (BucketStore, _grown_caps / _ScaledMaps / widened_caps, Writer).
 """
 import argparse
+import collections
 import importlib
 import json
 import logging
 import os
-import queue
+import sys
 import threading
 import time
 
 import numpy as np
 import torch
 
+from .batching import BucketStore, NullArk, Writer, _grown_caps, _ScaledMaps, chunk_selectors, take, widened_caps  # noqa: F401 (sizing: re-exported)
 from .kaldi_io import ArkScpWriter
 from .prosody import FIELDS as PROSODY_FIELDS, ProsodyControl
 from .sharding import shard_utterances
@@ -134,40 +138,16 @@ class _Pool(object):
             self.slots[j] = [_Slot(self.caps.frames, odim, self.batch, self._slab[(2 * j + q) * w : (2 * j + q + 1) * w]) for q in range(2)]
         return self.runners[j]
 
-
-def _grown_caps(engine, maps, n_rows, scale=1.3):
-    """Capacities for the batches that follow the one whose exact maps are `maps` (they are no longer than it): some slack on every count."""
-    lmax = max(16, int(maps.lmax * 1.5) + 4)
-    bounds = np.full(lmax, 1, dtype=np.int32)
-    live = np.minimum(n_rows, (maps.live_rows.astype(np.float64) * scale).astype(np.int64) + 32)
-    bounds[: maps.lmax] = live
-    bounds[maps.lmax :] = live[-1]
-    bounds = np.maximum.accumulate(bounds[::-1])[::-1].astype(np.int32)  # non-increasing, as the loop requires
-    # the steps past this batch's own longest duration (+ 2) are slack: the rows that do reach them continue in one launch of the row-tile kernel
-    return engine.Caps(lmax, (int(maps.n_frames * scale) + 255) // 256 * 256, bounds, tail_from=maps.lmax + 2)
+    def retire(self):
+        """Before the bucket is dropped: later captures on its pass streams open a fresh shared memory pool.  (A pool whose last graph is destroyed stays
+        in the allocator at use count 0 until its blocks are freed, and a capture into that handle fails the allocator's `use_count > 0` assertion.)"""
+        shared = self.plan.__dict__.get("_decode_cache", {}).get("graph_mempools", {})
+        for j, r in enumerate(self.runners):
+            if r is not None:
+                shared.pop(self.streams[j].cuda_stream, None)
 
 
-class _ScaledMaps(object):
-    """The exact maps of a calibration batch rescaled to another batch's phoneme count (round 6): durations are a per-phoneme quantity, so a
-    later bucket's frame total and live-row profile are the calibrated ones x (its phonemes / the calibrated batch's phonemes); _grown_caps adds the slack
-    and a batch that still overflows is reported by the device and redone eagerly (pool.grow), as before."""
-
-    def __init__(self, maps, n_ph_cal, n_ph):
-        ratio = float(n_ph) / float(max(n_ph_cal, 1))
-        self.lmax = int(maps.lmax)
-        self.live_rows = np.ceil(np.asarray(maps.live_rows, dtype=np.float64) * ratio).astype(np.int64)
-        self.n_frames = int(np.ceil(maps.n_frames * ratio))
-
-
-def widened_caps(engine, maps, old, n_rows):
-    """Capacities of a bucket after one of its batches (exact maps `maps`, from its eager redo) overflowed `old`: more slack on every count, never
-    less than before, and every step may keep every row."""
-    g = _grown_caps(engine, maps, n_rows, scale=1.6)
-    lmax = max(g.lmax, old.lmax)
-    return engine.Caps(lmax, max(g.frames, old.frames), np.full(lmax, n_rows, np.int32), tail_from=g.tail_from)
-
-
-grown_caps, ScaledMaps = _grown_caps, _ScaledMaps  # the capacity sizing shared with the text -> waveform driver (tts.py)
+grown_caps, ScaledMaps = _grown_caps, _ScaledMaps  # (the names bench.py and earlier callers know; the sizing itself lives in batching.py)
 
 
 SHARE_GRAPH_POOLS = os.environ.get("FCL_DECODE_SHARE_POOLS", "1") not in ("", "0")  # the graphs of one pass stream share a memory pool (first call: fewer allocations)
@@ -206,58 +186,23 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
     order = sorted(range(len(utts)), key=lambda i: -len(utts[i][1]))
     dev = next(model.parameters()).device
     plan = model.plan(dev)
-    has_spk = plan.hp.spk_embed_dim is not None
-    if has_spk and any(len(u) < 3 for u in utts):
-        raise ValueError("fcl-taco2_amd: the model has spk_embed_dim=%d: every utterance needs a speaker embedding" % plan.hp.spk_embed_dim)
-    spk_of = (lambda chunk: [u[2] for u in chunk]) if has_spk else (lambda chunk: None)
-    controlled = prosody is not None
-    if isinstance(prosody, dict):  # {utt_id: control}
-        per_utt = {k: ProsodyControl.coerce(v) for k, v in prosody.items()}
-        ctl_of = lambda chunk: [per_utt.get(u[0]) for u in chunk]
-    elif controlled:
-        one = ProsodyControl.coerce(prosody)
-        ctl_of = lambda chunk: [one] * len(chunk)
-    else:
-        ctl_of = lambda chunk: None
+    spk_of, ctl_of, controlled = chunk_selectors(plan, utts, prosody)
     ckey = ("ctl",) if controlled else ()  # controlled graphs and calibrations never replace the uncontrolled ones
     frames = 0
     depth = max(1, int(depth))
     cache = plan.__dict__.setdefault("_decode_cache", {})
     streams = engine.shared_streams(dev, depth)  # the process's pass streams (one pool per device: see engine.shared_streams)
-    import collections
-
-    pools = cache.setdefault(("pools", batch_size, depth) + ckey, collections.OrderedDict())
-    max_buckets = max(1, int(MAX_BUCKETS if max_buckets is None else max_buckets))
     pending = []
-    n_eager = n_graph = n_redo = n_evict = n_est = 0
+    n_eager = n_graph = n_redo = 0
     # dlayers / prenet_layers / elayers other than 2 / 2 / 1 run on the fp32-operand loop with host row counts (fcl_decoder_weights_t.dlayers ...)
     eager_only = bool(getattr(plan, "generic_decoder", False)) or plan.hp.elayers != 1
-
-    # the ark / scp file is written by a worker thread (file writes release the GIL): storage keeps up with the GPU instead of stalling the loop
-    wq = queue.Queue(maxsize=4 * (depth + 1))
-    werr = []
-
-    def writer(w):
-        while True:
-            item = wq.get()
-            if item is None:
-                return
-            chunk, arr, counts, slot = item
-            try:
-                if not werr:
-                    w.write_batch([u[0] for u in chunk], arr[: int(sum(counts))], counts)
-            except Exception as e:  # surfaced by the main thread after the join
-                werr.append(e)
-            finally:
-                if slot is not None:
-                    slot.free.set()
 
     def eager(chunk):
         """Host-round-trip pass (calibration / fallback): exact maps of THIS batch."""
         prep = engine.prepare(plan, [u[1] for u in chunk], spembs=spk_of(chunk), prosody=ctl_of(chunk))
         mel, utt_frames, inter = engine.run(plan, prep, ops.DROP_RNG, seed=int(torch.randint(0, 2 ** 31 - 1, (1,)).item()), return_intermediates=True)
         arr = mel.cpu().numpy()
-        wq.put((chunk, arr, list(utt_frames), None))
+        wr.put((chunk, arr, list(utt_frames)))
         return int(arr.shape[0]), inter["maps"]
 
     def harvest(item):
@@ -272,25 +217,27 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
             return got
         f0 = slot.f0.numpy()
         total = int(f0[len(chunk)])
-        wq.put((chunk, slot.mel.numpy()[:total], [int(v) for v in np.diff(f0[: len(chunk) + 1])], slot))
+        wr.put((chunk, slot.mel.numpy()[:total], [int(v) for v in np.diff(f0[: len(chunk) + 1])]), slot.free)
         return total
 
-    class _Discard(dict):  # out_prefix None: synthesis + device-to-host hand-over only (benchmarks)
-        def __enter__(self):
-            return self
+    def drain(pool):
+        """The store is about to drop the bucket: its batches in flight are harvested, the writer thread is done with its pinned landing buffers."""
+        nonlocal frames
+        for it in take(pending, lambda p: p[0] is pool):
+            frames += harvest(it)
+        for sl in [x for pair in pool.slots if pair for x in pair]:
+            sl.free.wait()
+        pool.retire()
 
-        def __exit__(self, *exc):
-            return False
-
-        def __setitem__(self, k, v):
-            pass
-
-        def write_batch(self, keys, mats, counts):
-            pass
-
-    with (ArkScpWriter(out_prefix) if out_prefix is not None else _Discard()) as w, torch.cuda.device(dev):
-        th = threading.Thread(target=writer, args=(w,), daemon=True)
-        th.start()
+    # the pools and the calibration -- [(exact maps, phoneme count)] of the first eagerly calibrated batch of this model -- stay with the plan; `bi` in
+    # make is the batch the loop below is at when the policy asks for a bucket
+    store = BucketStore(engine, batch_size, lambda t_cap, caps: _Pool(plan, batch_size, t_cap, caps, streams, seed + 31 * bi, controlled), drain,
+                        MAX_BUCKETS if max_buckets is None else max_buckets, ESTIMATE_CAPS,
+                        cache.setdefault(("pools", batch_size, depth) + ckey, collections.OrderedDict()), cache.setdefault(("calibration", batch_size) + ckey, []),
+                        sizing=sys.modules[__name__])
+    # the ark / scp file is written by a worker thread: out_prefix None = synthesis + device-to-host hand-over only (benchmarks)
+    with (ArkScpWriter(out_prefix) if out_prefix is not None else NullArk()) as w, torch.cuda.device(dev):
+        wr = Writer(lambda it: w.write_batch([u[0] for u in it[0]], it[1][: int(sum(it[2]))], it[2]), 4 * (depth + 1))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         try:
@@ -302,50 +249,17 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
                     n_eager += 1
                     continue
                 t_cap = (max(len(u[1]) for u in chunk) + 15) // 16 * 16
-                pool = pools.get(t_cap)
-                if pool is not None:
-                    pools.move_to_end(t_cap)
-                if pool is not None and pool.grow is not None:  # a batch overflowed this bucket: drain it, widen the capacities, capture anew
-                    for it in [p_ for p_ in pending if p_[0] is pool]:
-                        pending.remove(it)
-                        frames += harvest(it)
-                    caps = widened_caps(engine, pool.grow, pool.caps, batch_size * t_cap)
-                    pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, caps, streams, seed + 31 * bi, controlled)
-                cal = cache.get(("calibration", batch_size) + ckey)  # (exact maps, phoneme count) of the first eagerly calibrated batch of this model
-                if pool is None and cal is not None and ESTIMATE_CAPS:
-                    # a later bucket: capacities ESTIMATED from the phoneme count (no eager batch, no host round trip); the batch itself goes through the graph below
-                    est = _ScaledMaps(cal[0], cal[1], sum(len(u[1]) for u in chunk))
-                    pool = pools[t_cap] = _Pool(plan, batch_size, t_cap, _grown_caps(engine, est, batch_size * t_cap), streams, seed + 31 * bi, controlled)
-                    n_est += 1
-                    while len(pools) > max_buckets:
-                        old_cap, old_pool = next(iter(pools.items()))
-                        for it in [p_ for p_ in pending if p_[0] is old_pool]:
-                            pending.remove(it)
-                            frames += harvest(it)
-                        for sl in [x for pair in old_pool.slots if pair for x in pair]:
-                            sl.free.wait()
-                        del pools[old_cap]
-                        n_evict += 1
+                n_ph = sum(len(u[1]) for u in chunk)
+                pool = store.get(t_cap, n_ph)
                 if pool is None:  # first batch of the bucket: eager pass = its result + the bucket's calibration
                     got, maps = eager(chunk)
                     frames += got
                     n_eager += 1
-                    cache.setdefault(("calibration", batch_size) + ckey, (maps, sum(len(u[1]) for u in chunk)))
-                    pools[t_cap] = _Pool(plan, batch_size, t_cap, _grown_caps(engine, maps, batch_size * t_cap), streams, seed + 31 * bi, controlled)
-                    while len(pools) > max_buckets:  # least recently used bucket out: its batches in flight are harvested first
-                        old_cap, old_pool = next(iter(pools.items()))
-                        for it in [p_ for p_ in pending if p_[0] is old_pool]:
-                            pending.remove(it)
-                            frames += harvest(it)
-                        for sl in [x for pair in old_pool.slots if pair for x in pair]:
-                            sl.free.wait()  # the writer thread still reads the pinned landing buffers it was handed
-                        del pools[old_cap]
-                        n_evict += 1
+                    store.calibrated(t_cap, maps, n_ph)
                     continue
                 j = pool.next % len(streams)
                 pool.next += 1
-                for it in [p_ for p_ in pending if p_[1] == j]:  # stream j's previous batch (of any bucket) must have left the runner's static buffers
-                    pending.remove(it)
+                for it in take(pending, lambda p: p[1] == j):  # stream j's previous batch (of any bucket) must have left the runner's static buffers
                     frames += harvest(it)
                 r = pool.runner(j)
                 slot = pool.slots[j][(pool.next // len(streams)) % 2]
@@ -376,22 +290,19 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
             # graphs already launched keep copying into the pinned landing buffers: wait for the device, hand the slots back, and let the
             # writer finish what it was given -- then the ark is closed by the `with` and the error propagates
             torch.cuda.synchronize()
-            for it in pending:
+            for it in take(pending):
                 it[0].runners[it[1]].status.zero_()
                 it[3].free.set()
-            del pending[:]
             raise
         finally:
-            wq.put(None)
-            th.join()
+            wr.join()
             if not keep_graphs:
                 release_graphs(plan)
         secs = time.perf_counter() - t0
-        if werr:
-            raise werr[0]
+        wr.close()  # the writer's first error, if it had one
     if stats is not None:
-        stats.update(device_seconds=dev_secs, eager_batches=n_eager, graph_batches=n_graph, redone_batches=n_redo, buckets=len(pools), evicted_buckets=n_evict,
-                     estimated_buckets=n_est)
+        stats.update(device_seconds=dev_secs, eager_batches=n_eager, graph_batches=n_graph, redone_batches=n_redo, buckets=len(store.buckets),
+                     evicted_buckets=store.evicted, estimated_buckets=store.estimated)
     return frames, secs
 
 

@@ -157,7 +157,7 @@ class Caps(object):
     def for_batches(host_maps, slack_steps=0, frame_round=256):
         """Exact capacities of a KNOWN set of batches (their host-built maps): steps = the longest duration (+ slack_steps), frames = the largest
         total rounded up to `frame_round`, per-step row bounds = the maximum over the batches.  This is the best case -- what bench.py's headline
-        line uses for the four batches it feeds; a driver that cannot know its batches in advance calibrates with slack (decode._grown_caps)."""
+        line uses for the four batches it feeds; a driver that cannot know its batches in advance calibrates with slack (batching._grown_caps)."""
         lmax = max(m.lmax for m in host_maps) + int(slack_steps)
         bounds = np.ones(lmax, dtype=np.int32)
         for m in host_maps:

@@ -6,11 +6,11 @@
 
 Writes `<outdir>/<utt_id>_gen.wav` (16-bit PCM mono at the vocoder config's sampling rate), what the two-step recipe writes.  Utterances are
 sorted by length and bucketed by padded phoneme count like decode.py; every bucket keeps one engine.SpeechRunner (synthesis with predicted
-durations -> capacity vocoder -> int16 PCM in a single hipGraph; the durations never reach the host).  Capacities are sized the way decode.py
-does it: the first batch runs through the two-step route (synthesis, frame counts on the host, exact-size vocoder), which both produces its
+durations -> capacity vocoder -> int16 PCM in a single hipGraph; the durations never reach the host).  Capacities follow the bucket policy
+decode.py follows too (batching.BucketStore): the first batch runs through the two-step route (synthesis, frame counts on the host, exact-size vocoder), which both produces its
 audio and calibrates; later buckets are estimated from their phoneme counts; a batch that overflows a capacity is reported by the device, redone
 through the two-step route, and its bucket grows.  The int16 PCM travels through pinned staging on a placed copy stream while the next batch
-runs; a writer thread encodes the wav files.  `--feats-out PREFIX` also writes the mels the waveforms were made from as PREFIX.ark/.scp, so a
+runs; a writer thread (batching.Writer) encodes the wav files.  `--feats-out PREFIX` also writes the mels the waveforms were made from as PREFIX.ark/.scp, so a
 run can be audited against `decode.py` + `vocoder_decode.py`.
 
 One SpeechRunner holds 1082 bytes per capacity sample (vocoder.CapacitySynth), 10.4 GB at the measured BASELINE configs[4] capacity (64
@@ -18,10 +18,8 @@ utterances of 60 - 100 phonemes, 37 632 frames: DESIGN.md 6b), so few are kept: 
 A HiFi-GAN generator takes the two-step route for every batch by default; `--vocoder-graph` puts it on the same one-graph route through its
 capacity form (hifigan.CapacitySynth, ~0.94 KB per capacity sample for v1: DESIGN.md 6c)."""
 import argparse
-import collections
 import logging
 import os
-import queue
 import threading
 import time
 import wave
@@ -29,9 +27,9 @@ import wave
 import numpy as np
 import torch
 
-from .decode import ScaledMaps, add_prosody_arguments, build_model, grown_caps, prosody_from_args, read_manifest, widened_caps
+from .batching import BucketStore, NullArk, Writer, chunk_selectors, take
+from .decode import add_prosody_arguments, build_model, prosody_from_args, read_manifest
 from .kaldi_io import ArkScpWriter
-from .prosody import ProsodyControl
 from .sharding import shard_utterances
 
 MAX_BUCKETS = 2
@@ -88,47 +86,20 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
     hop, odim = gen.plan.hop, int(plan.hp.odim)
     if odim != gen.plan.A:
         raise ValueError("fcl-taco2_amd: the model writes %d mel channels, the vocoder takes %d" % (odim, gen.plan.A))
-    has_spk = plan.hp.spk_embed_dim is not None
-    if has_spk and any(len(u) < 3 for u in utts):
-        raise ValueError("fcl-taco2_amd: the model has spk_embed_dim=%d: every utterance needs a speaker embedding" % plan.hp.spk_embed_dim)
-    spk_of = (lambda chunk: [u[2] for u in chunk]) if has_spk else (lambda chunk: None)
-    controlled = prosody is not None
-    if isinstance(prosody, dict):
-        per_utt = {k: ProsodyControl.coerce(v) for k, v in prosody.items()}
-        ctl_of = lambda chunk: [per_utt.get(u[0]) for u in chunk]
-    elif controlled:
-        one = ProsodyControl.coerce(prosody)
-        ctl_of = lambda chunk: [one] * len(chunk)
-    else:
-        ctl_of = lambda chunk: None
+    spk_of, ctl_of, controlled = chunk_selectors(plan, utts, prosody)
     # (a generator whose default route is the two-step one -- HiFi-GAN -- keeps every batch on it, like a model the capacity graph does not cover,
     # unless the caller asks for the graph route and the generator has a capacity form)
     gen_eager = bool(getattr(gen.plan, "eager_only", False)) and not (vocoder_graph and hasattr(gen, "capacity_synth"))
     eager_only = bool(getattr(plan, "generic_decoder", False)) or plan.hp.elayers != 1 or gen_eager
-    max_buckets = max(1, int(MAX_BUCKETS if max_buckets is None else max_buckets))
-    buckets = collections.OrderedDict()
-    calibration = None
     counts = dict(graph_batches=0, eager_batches=0, redone_batches=0)
     routes = {}  # batch number -> (route, utterance ids, vocoder noise seed): what an audit needs to redo a batch from its mels
-    wq, werr = queue.Queue(maxsize=8), []
 
-    def writer(ark):
-        while True:
-            item = wq.get()
-            if item is None:
-                return
-            chunk, pcm, offs, mel, frames, done = item
-            try:
-                if not werr:
-                    for i, u in enumerate(chunk):
-                        write_pcm_wav(os.path.join(outdir, u[0] + "_gen.wav"), pcm[offs[i] : offs[i + 1]], rate)
-                    if ark is not None:
-                        ark.write_batch([u[0] for u in chunk], mel[: int(sum(frames))], frames)
-            except Exception as e:  # surfaced by the main thread after the join
-                werr.append(e)
-            finally:
-                if done is not None:
-                    done.set()
+    def write(item):
+        chunk, pcm, offs, mel, frames = item
+        for i, u in enumerate(chunk):
+            write_pcm_wav(os.path.join(outdir, u[0] + "_gen.wav"), pcm[offs[i] : offs[i + 1]], rate)
+        if mel is not None:
+            ark.write_batch([u[0] for u in chunk], mel[: int(sum(frames))], frames)
 
     def two_step(chunk, k):
         """Synthesis with the host round trip, then the exact-size vocoder: calibration of a bucket and the redo route."""
@@ -141,7 +112,7 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
         n = sum(frames) * hop
         host = vocoder.pcm16(flat)
         offs = np.concatenate([[0], np.cumsum(frames)]) * hop
-        wq.put((chunk, host, offs, mel.cpu().numpy() if feats_out else None, frames, None))
+        wr.put((chunk, host, offs, mel.cpu().numpy() if feats_out else None, frames))
         return n, inter["maps"]
 
     def harvest(item):
@@ -157,33 +128,28 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
             return got
         f0 = slot["f0"].numpy().astype(np.int64)
         frames = [int(v) for v in np.diff(f0[: len(chunk) + 1])]
-        wq.put((chunk, slot["pcm"].numpy(), f0 * hop, slot["mel"].numpy() if feats_out else None, frames, slot["free"]))
+        wr.put((chunk, slot["pcm"].numpy(), f0 * hop, slot["mel"].numpy() if feats_out else None, frames), slot["free"])
         return int(f0[len(chunk)]) * hop
 
-    def new_bucket(t_cap, caps):
+    def make(t_cap, caps):
         vocoder_frames_cap(caps.frames, hop)
-        buckets[t_cap] = _Bucket(t_cap, caps)
-        while len(buckets) > max_buckets:  # least recently used bucket out: its batches in flight are harvested first
-            old_cap, old = next(iter(buckets.items()))
-            drain(old)
-            del buckets[old_cap]
-        return buckets[t_cap]
+        return _Bucket(t_cap, caps)
 
     pending, samples = [], 0
 
     def drain(b):
         nonlocal samples
-        for it in [p for p in pending if p[0] is b]:
-            pending.remove(it)
+        for it in take(pending, lambda p: p[0] is b):
             samples += harvest(it)
         for sl in (b.slots or []):
             sl["free"].wait()
 
-    with (ArkScpWriter(feats_out) if feats_out else _NoArk()) as ark, torch.cuda.device(dev):
-        th = threading.Thread(target=writer, args=(ark if feats_out else None,), daemon=True)
-        th.start()
+    # the buckets and the calibration of the run (the first batch's exact maps) live for this call only
+    store = BucketStore(engine, batch_size, make, drain, MAX_BUCKETS if max_buckets is None else max_buckets)
+    with (ArkScpWriter(feats_out) if feats_out else NullArk()) as ark, torch.cuda.device(dev):
         main_stream = engine.shared_streams(dev, 1)[0]
         copy_stream = ops.stream_apart([main_stream], device=dev) if os.environ.get("FCL_PLACE_STREAMS", "1") != "0" else torch.cuda.Stream(device=dev)
+        wr = Writer(write, 8)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         try:
@@ -193,23 +159,13 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
                     samples += two_step(chunk, k)[0]
                     counts["eager_batches"] += 1
                     continue
-                b = buckets.get(t_cap)
-                if b is not None:
-                    buckets.move_to_end(t_cap)
-                    if b.grow is not None:  # a batch overflowed this bucket: drain it, widen the capacities, capture anew
-                        drain(b)
-                        del buckets[t_cap]
-                        b.runner = None
-                        b = new_bucket(t_cap, widened_caps(engine, b.grow, b.caps, batch_size * t_cap))
-                elif calibration is not None:  # a later bucket: capacities estimated from the phoneme count, no eager batch
-                    est = ScaledMaps(calibration[0], calibration[1], sum(len(u[1]) for u in chunk))
-                    b = new_bucket(t_cap, grown_caps(engine, est, batch_size * t_cap))
-                else:  # the first batch of the run: the two-step route = its audio + the calibration
+                n_ph = sum(len(u[1]) for u in chunk)
+                b = store.get(t_cap, n_ph)
+                if b is None:  # the first batch of the run: the two-step route = its audio + the calibration
                     got, maps = two_step(chunk, k)
                     samples += got
                     counts["eager_batches"] += 1
-                    calibration = (maps, sum(len(u[1]) for u in chunk))
-                    new_bucket(t_cap, grown_caps(engine, maps, batch_size * t_cap))
+                    store.calibrated(t_cap, maps, n_ph)
                     continue
                 if b.runner is None:
                     b.runner = engine.SpeechRunner(plan, gen, batch_size, t_cap, b.caps, forced=False, stream=main_stream, seed=seed + 31 * k,
@@ -224,8 +180,7 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
                 r = b.runner
                 slot = b.slots[b.next % 2]
                 b.next += 1
-                for it in [p for p in pending if p[2] is slot]:  # this landing area's previous batch
-                    pending.remove(it)
+                for it in take(pending, lambda p: p[2] is slot):  # this landing area's previous batch
                     samples += harvest(it)
                 slot["free"].wait()
                 slot["free"].clear()
@@ -263,26 +218,15 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
             torch.cuda.synchronize()
         except BaseException:
             torch.cuda.synchronize()
-            for it in pending:
+            for it in take(pending):
                 it[2]["free"].set()
-            del pending[:]
             raise
         finally:
-            wq.put(None)
-            th.join()
+            wr.join()
         secs = time.perf_counter() - t0
-        if werr:
-            raise werr[0]
+        wr.close()  # the writer's first error, if it had one
     audio = samples / float(rate)
     return dict(samples=int(samples), seconds=secs, rtf=secs / max(audio, 1e-9), utterances=len(utts), batches=[routes[k] for k in sorted(routes)], **counts)
-
-
-class _NoArk(object):
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
 
 
 def build_parser():

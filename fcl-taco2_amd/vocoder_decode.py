@@ -13,8 +13,6 @@ utterance (one process per GPU, no collective), like decode.py.
 import argparse
 import logging
 import os
-import queue
-import threading
 import time
 import wave
 
@@ -22,6 +20,7 @@ import numpy as np
 import torch
 
 from . import kaldi_io, ops
+from .batching import Writer
 from .sharding import shard_utterances
 from .vocoder import CONFIG, PWGPlan, ParallelWaveGANGenerator
 
@@ -217,23 +216,12 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
     dev = gen.plan.device
     hop = gen.plan.hop
     batches = make_batches([m.shape[0] for _, m in feats], batch_frames)
-    wq, werr = queue.Queue(maxsize=depth + 1), []
 
-    def writer():
-        try:
-            while True:
-                item = wq.get()
-                if item is None:
-                    return
-                for uid, wav in item:
-                    write_wav(os.path.join(outdir, uid + "_gen.wav"), wav, rate)
-        except Exception as e:  # surfaced by the main thread
-            werr.append(e)
-            while wq.get() is not None:
-                pass
+    def write(items):
+        for uid, wav in items:
+            write_wav(os.path.join(outdir, uid + "_gen.wav"), wav, rate)
 
-    th = threading.Thread(target=writer, daemon=True)
-    th.start()
+    wr = Writer(write, depth + 1)
     with torch.cuda.device(dev):  # the copies' queue on a compute pipe apart from the generator's stream (ops.stream_apart: fcl_hip.h "Compute pipes")
         copy_stream = ops.stream_apart([torch.cuda.current_stream(dev)], device=dev) if os.environ.get("FCL_PLACE_STREAMS", "1") != "0" else torch.cuda.Stream(device=dev)
     slots = [None] * (depth + 1)  # pinned staging, one per batch in flight
@@ -248,39 +236,39 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
         for uid, n in zip(ids, lens):
             items.append((uid, arr[s : s + n * hop].copy()))
             s += n * hop
-        wq.put(items)
+        wr.put(items)
         return s
 
-    with torch.cuda.device(dev):
-        for bi, idx in enumerate(batches):
-            mels = [feats[i][1] for i in idx]
-            lens = [int(m.shape[0]) for m in mels]
-            packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(mels), dtype=np.float32)).to(dev, non_blocking=True)
-            wavs = gen.synthesize_packed(packed, lens, seed=seed + bi)
-            n = sum(lens) * hop
-            flat = wavs[0]._base if wavs[0]._base is not None else wavs[0]  # the batch's waveforms are views into one buffer
-            j = bi % (depth + 1)
-            if slots[j] is None or slots[j].numel() < n:
-                slots[j] = torch.empty(max(n, 1 << 20), dtype=torch.float32, pin_memory=True)
-            done = torch.cuda.Event()
-            done.record()
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(done)
-                host = slots[j][:n]
-                host.copy_(flat[:n], non_blocking=True)
-                flat.record_stream(copy_stream)
-                ev = torch.cuda.Event()
-                ev.record()
-            pending.append(([feats[i][0] for i in idx], lens, host, ev))
-            while len(pending) > depth:
+    try:
+        with torch.cuda.device(dev):
+            for bi, idx in enumerate(batches):
+                mels = [feats[i][1] for i in idx]
+                lens = [int(m.shape[0]) for m in mels]
+                packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(mels), dtype=np.float32)).to(dev, non_blocking=True)
+                wavs = gen.synthesize_packed(packed, lens, seed=seed + bi)
+                n = sum(lens) * hop
+                flat = wavs[0]._base if wavs[0]._base is not None else wavs[0]  # the batch's waveforms are views into one buffer
+                j = bi % (depth + 1)
+                if slots[j] is None or slots[j].numel() < n:
+                    slots[j] = torch.empty(max(n, 1 << 20), dtype=torch.float32, pin_memory=True)
+                done = torch.cuda.Event()
+                done.record()
+                with torch.cuda.stream(copy_stream):
+                    copy_stream.wait_event(done)
+                    host = slots[j][:n]
+                    host.copy_(flat[:n], non_blocking=True)
+                    flat.record_stream(copy_stream)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                pending.append(([feats[i][0] for i in idx], lens, host, ev))
+                while len(pending) > depth:
+                    total += harvest(pending.pop(0))
+            while pending:
                 total += harvest(pending.pop(0))
-        while pending:
-            total += harvest(pending.pop(0))
-    wq.put(None)
-    th.join()
+    finally:  # the thread is joined also when synthesis fails
+        wr.join()
     torch.cuda.synchronize()
-    if werr:
-        raise werr[0]
+    wr.close()  # the writer's first error, if it had one
     return total, time.perf_counter() - t0
 
 

@@ -351,6 +351,35 @@ def test_decode_driver_estimates_later_buckets_capacities_from_phoneme_counts(tm
         assert max_abs(mels2[uid], mels[uid]) < 2e-5
 
 
+def test_decode_driver_evicts_least_recently_used_buckets(tmp_path):
+    """max_buckets=1 with three length buckets: every new bucket evicts the one before it -- its batch in flight is harvested and its pinned landing
+    buffers are waited for first -- and no utterance is lost or altered on the way.  The calibration stays with the plan: a second call on the same
+    model estimates every bucket and runs no eager batch."""
+    from fcl_taco2_amd import decode as D, engine
+    from fcl_taco2_amd.kaldi_io import read_scp
+
+    S, T = HP.student_hparams(dropout_rate=0.0), HP.teacher_hparams()
+    model = SYN.build_model("student", S, T, DEV).eval()
+    sd = SYN.positive_duration_head(SYN.closed_form_state_dict(HP.param_spec(S, T, True)))
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    model = model.to(DEV).eval()
+    rng = np.random.RandomState(9)
+    utts = [("u%03d" % i, rng.randint(1, S.idim, size=int(n)).astype(np.int64)) for i, n in enumerate(list(rng.randint(50, 64, 8)) + list(rng.randint(34, 48, 8)) +
+                                                                                                      list(rng.randint(18, 32, 8)))]
+    st = {}
+    frames, _ = D.decode(model, utts, str(tmp_path / "v"), batch_size=4, depth=2, stats=st, max_buckets=1)
+    assert st["eager_batches"] == 1 and st["estimated_buckets"] == 2 and st["evicted_buckets"] == 2 and st["buckets"] == 1 and st["redone_batches"] == 0, st
+    mels = read_scp(str(tmp_path / "v.scp"))
+    assert sorted(mels) == sorted(u for u, _ in utts) and frames == sum(m.shape[0] for m in mels.values())
+    plan = model.plan()
+    for uid, x in utts[::5]:
+        ref = engine.synthesize(plan, [x])[0]
+        assert mels[uid].shape == tuple(ref.shape) and max_abs(mels[uid], ref) < 2e-5
+    st2 = {}
+    frames2, _ = D.decode(model, utts, str(tmp_path / "w"), batch_size=4, depth=2, stats=st2, max_buckets=1)
+    assert st2["eager_batches"] == 0 and frames2 == frames, st2
+
+
 def test_grouped_predictor_launches_equal_the_per_predictor_path():
     """plan.PredictorGroup: the duration / pitch / energy predictors (one geometry in the shipped recipes) as ONE launch per layer -- a Conv1d with
     the stacked output channels, grouped LayerNorms, a grouped Conv1d, grouped LayerNorm + head -- against one launch per predictor and layer:
