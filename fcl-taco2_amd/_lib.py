@@ -111,6 +111,11 @@ class HfgUnit(C.Structure):  # fcl_hfg_unit_t
         (n, _P) for n in ("xp", "x", "w1p", "b1", "w2p", "b2", "frame_utt", "utt_off", "x_out", "xp_out", "cs", "csp", "tp")]
 
 
+class GriffinLim(C.Structure):  # fcl_gl_t
+    _fields_ = [("frames", C.c_int64), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_utt", C.c_int32), ("momentum", _F)] + [
+        (n, _P) for n in ("window", "twiddle", "frame_utt", "utt_off", "utt_seed", "s", "p", "fr", "y", "c_prev", "c_out", "u_out")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -266,6 +271,11 @@ SIGNATURES = {
     "fcl_hfg_tconv_cap_fwd": (_I, [C.POINTER(HfgTconv), _P, _P]),
     "fcl_hfg_unit_cap_fwd": (_I, [C.POINTER(HfgUnit), _P, _P]),
     "fcl_hfg_out_cap_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, C.c_int64, _I, _I, _I, _P, _P]),
+    "fcl_gl_mel2lin_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
+    "fcl_gl_phase_init": (_I, [C.POINTER(GriffinLim), _P]),
+    "fcl_gl_synth_fwd": (_I, [C.POINTER(GriffinLim), _P]),
+    "fcl_gl_ola_fwd": (_I, [C.POINTER(GriffinLim), _P]),
+    "fcl_gl_analysis_fwd": (_I, [C.POINTER(GriffinLim), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

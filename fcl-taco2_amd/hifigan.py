@@ -320,6 +320,10 @@ class HiFiGANGenerator(object):
     def __init__(self, plan):
         self.plan = plan
 
+    def samples_of(self, frames):
+        """samples of an utterance of `frames` mel frames"""
+        return int(frames) * self.plan.hop
+
     def capacity_synth(self, batch, frames_cap, seed=0):
         """The capacity form of this generator for `batch` utterance slots and `frames_cap` mel frames (what engine.SpeechRunner captures)."""
         return CapacitySynth(self, batch, frames_cap, seed=seed)

@@ -16,7 +16,9 @@ run can be audited against `decode.py` + `vocoder_decode.py`.
 One SpeechRunner holds 1082 bytes per capacity sample (vocoder.CapacitySynth), 10.4 GB at the measured BASELINE configs[4] capacity (64
 utterances of 60 - 100 phonemes, 37 632 frames: DESIGN.md 6b), so few are kept: `--max-buckets` (default 2), least recently used first out.
 A HiFi-GAN generator takes the two-step route for every batch by default; `--vocoder-graph` puts it on the same one-graph route through its
-capacity form (hifigan.CapacitySynth, ~0.94 KB per capacity sample for v1: DESIGN.md 6c)."""
+capacity form (hifigan.CapacitySynth, ~0.94 KB per capacity sample for v1: DESIGN.md 6c).  `--griffin-lim` instead of `--vocoder-checkpoint` needs no
+trained generator (griffinlim.py); it has no capacity form, every batch takes the two-step route, and an utterance of T' frames gives
+hop * (T' - 1) samples."""
 import argparse
 import logging
 import os
@@ -108,10 +110,12 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
         frames = [int(f) for f in frames]
         nseed = (seed + 104729 * k) & 0xFFFFFFFF
         routes[k] = ("two-step", [u[0] for u in chunk], nseed)
+        if hasattr(gen, "check_lens"):  # Griffin-Lim: an utterance too short for its reflection is refused by id
+            gen.check_lens(frames, [u[0] for u in chunk])
         _, flat = gen.synthesize_packed(mel, frames, seed=nseed, return_flat=True)
-        n = sum(frames) * hop
+        offs = np.concatenate([[0], np.cumsum([gen.samples_of(f) for f in frames])])  # (frames x hop; hop x (frames - 1) for Griffin-Lim)
+        n = int(offs[-1])
         host = vocoder.pcm16(flat)
-        offs = np.concatenate([[0], np.cumsum(frames)]) * hop
         wr.put((chunk, host, offs, mel.cpu().numpy() if feats_out else None, frames))
         return n, inter["maps"]
 
@@ -230,12 +234,17 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
 
 
 def build_parser():
+    from . import griffinlim
+
     ap = argparse.ArgumentParser(prog="fcl_taco2_amd.tts", description="FCL-taco2 text -> waveform on MI355X in one process (synthesis + Parallel WaveGAN)")
     ap.add_argument("--model", required=True)
     ap.add_argument("--model-conf", required=True)
     ap.add_argument("--teacher-config", default=None, help="model.json of the teacher (student checkpoints trained with KD projections)")
     ap.add_argument("--json", required=True, help="data.json manifest (phoneme ids per utterance)")
-    ap.add_argument("--vocoder-checkpoint", required=True, help="generator checkpoint ({'model': {'generator': state_dict}} or a bare state_dict)")
+    ap.add_argument("--vocoder-checkpoint", default=None, help="generator checkpoint ({'model': {'generator': state_dict}} or a bare state_dict); this or "
+                    "--griffin-lim")
+    ap.add_argument("--griffin-lim", action="store_true", help="no vocoder checkpoint: pseudo-inverse mel filterbank + Griffin-Lim (exclusive with "
+                    "--vocoder-checkpoint; every batch takes the two-step route)")
     ap.add_argument("--vocoder-config", default=None, help="parallel_wavegan config.yml (default: next to the checkpoint; v1 geometry without one)")
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--feats-out", default=None, metavar="PREFIX", help="also write the mels as PREFIX.ark / PREFIX.scp")
@@ -251,13 +260,17 @@ def build_parser():
     ap.add_argument("--unsafe-pickle", action="store_true", help="allow the full unpickler for vocoder checkpoints that weights_only=True rejects (runs code "
                     "embedded in the file: trusted checkpoints only)")
     add_prosody_arguments(ap)
+    griffinlim.add_arguments(ap)
     return ap
 
 
 def parse_args(argv=None):
     """Parses and checks everything that can be checked before the first device call; flag errors end in ap.error (SystemExit 2)."""
+    from . import griffinlim
+
     ap = build_parser()
     args = ap.parse_args(argv)
+    griffinlim.check_arguments(ap, args, args.vocoder_checkpoint)
     if args.batch_size < 1:
         ap.error("--batch-size must be at least 1")
     if args.nj < 1 or not 0 <= args.job < args.nj:
@@ -284,7 +297,12 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
     dev = "cuda:%d" % (args.job % max(torch.cuda.device_count(), 1))
     model = build_model(args.model, args.model_conf, args.teacher_config, dev)
-    gen, rate = build_generator(args.vocoder_checkpoint, dev, args.vocoder_config, args.unsafe_pickle)
+    if args.griffin_lim:
+        from . import griffinlim
+
+        gen, rate = griffinlim.from_args(args, dev, n_mels=int(model.plan(dev).hp.odim))
+    else:
+        gen, rate = build_generator(args.vocoder_checkpoint, dev, args.vocoder_config, args.unsafe_pickle)
     mine = shard_of(read_manifest(args.json), args.nj, args.job)
     feats = args.feats_out if args.feats_out is None or args.nj == 1 else "%s.%d" % (args.feats_out, args.job + 1)
     res = synthesize(model, gen, mine, args.outdir, rate, args.batch_size, args.seed, prosody_from_args(args, [u[0] for u in mine]), feats, args.max_buckets,

@@ -332,6 +332,10 @@ class ParallelWaveGANGenerator(object):
         self._maps_cache = {}
 
     # ---- integer index maps of a batch shape (host-built once per tuple of utterance lengths, cached) -------------------------------------------
+    def samples_of(self, frames):
+        """samples of an utterance of `frames` mel frames"""
+        return int(frames) * self.plan.hop
+
     def _maps(self, lens):
         key = tuple(lens)
         hit = self._maps_cache.get(key)

@@ -2,7 +2,9 @@
 --feats-scp <decode>/feats.scp --outdir <wav dir>` (inference_student.sh:20-23, inference_teacher.sh:20-23, README.md:46).  Same flag names and
 the same outputs (`<outdir>/<utt_id>_gen.wav`, 16-bit PCM at the generator's sampling rate); the generator is selected as that tool selects it, by
 `generator_type` of the config.yml: fcl_taco2_amd/vocoder.py (ParallelWaveGANGenerator) or fcl_taco2_amd/hifigan.py (HiFiGANGenerator,
-DESIGN.md §6c), both from the published architecture, parity unpinned.
+DESIGN.md §6c), both from the published architecture, parity unpinned.  `--griffin-lim` instead of `--checkpoint` needs no trained generator
+(fcl_taco2_amd/griffinlim.py): de-normalise with `--mel-stats`, pseudo-inverse mel filterbank, Griffin-Lim; an utterance of T' frames
+then gives hop * (T' - 1) samples.
 
     python -m fcl_taco2_amd.vocoder_decode --checkpoint vocoder/PWG/PWG.pkl --feats-scp exp/student/test/feats.scp --outdir exp/student/test/wav
 
@@ -214,7 +216,7 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
     """feats: list of (utt_id, [T', aux] float32 array).  Writes <outdir>/<utt_id>_gen.wav; returns (samples, seconds)."""
     os.makedirs(outdir, exist_ok=True)
     dev = gen.plan.device
-    hop = gen.plan.hop
+    samples_of = gen.samples_of  # per-utterance sample counts are the generator's (frames x hop; hop x (frames - 1) for Griffin-Lim)
     batches = make_batches([m.shape[0] for _, m in feats], batch_frames)
 
     def write(items):
@@ -234,8 +236,8 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
         arr = host.numpy()
         items, s = [], 0
         for uid, n in zip(ids, lens):
-            items.append((uid, arr[s : s + n * hop].copy()))
-            s += n * hop
+            items.append((uid, arr[s : s + samples_of(n)].copy()))
+            s += samples_of(n)
         wr.put(items)
         return s
 
@@ -246,7 +248,7 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
                 lens = [int(m.shape[0]) for m in mels]
                 packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(mels), dtype=np.float32)).to(dev, non_blocking=True)
                 wavs = gen.synthesize_packed(packed, lens, seed=seed + bi)
-                n = sum(lens) * hop
+                n = sum(samples_of(m) for m in lens)
                 flat = wavs[0]._base if wavs[0]._base is not None else wavs[0]  # the batch's waveforms are views into one buffer
                 j = bi % (depth + 1)
                 if slots[j] is None or slots[j].numel() < n:
@@ -272,25 +274,51 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
     return total, time.perf_counter() - t0
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="Parallel WaveGAN / HiFi-GAN decoding on MI355X (drop-in for `parallel-wavegan-decode`)")
-    ap.add_argument("--checkpoint", required=True, help="generator checkpoint ({'model': {'generator': state_dict}} or a bare state_dict)")
+def build_parser():
+    from . import griffinlim
+
+    ap = argparse.ArgumentParser(prog="fcl_taco2_amd.vocoder_decode",
+                                 description="Parallel WaveGAN / HiFi-GAN / Griffin-Lim decoding on MI355X (drop-in for `parallel-wavegan-decode`)")
+    ap.add_argument("--checkpoint", default=None, help="generator checkpoint ({'model': {'generator': state_dict}} or a bare state_dict); this or --griffin-lim")
+    ap.add_argument("--griffin-lim", action="store_true", help="no checkpoint: pseudo-inverse mel filterbank + Griffin-Lim (exclusive with --checkpoint)")
     ap.add_argument("--feats-scp", "--scp", dest="feats_scp", required=True, help="Kaldi scp of [T', aux] float matrices (decode.py's <out>.scp)")
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--config", default=None, help="parallel_wavegan config.yml (default: next to the checkpoint; v1 geometry without one)")
     ap.add_argument("--batch-frames", type=int, default=51200, help="mel frames per GPU batch")
     ap.add_argument("--nj", type=int, default=1, help="number of utterance shards (one process per GPU)")
     ap.add_argument("--job", type=int, default=0, help="this process's shard (0-based)")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the device noise")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the device noise (Griffin-Lim: of the initial phase)")
     ap.add_argument("--verbose", type=int, default=1)
     ap.add_argument("--unsafe-pickle", action="store_true", help="allow the full unpickler for checkpoints that weights_only=True rejects (runs code "
                     "embedded in the file: trusted checkpoints only)")
+    griffinlim.add_arguments(ap)
+    return ap
+
+
+def parse_args(argv=None):
+    """Parses and checks what can be checked before the first device call; flag errors end in ap.error (SystemExit 2)."""
+    from . import griffinlim
+
+    ap = build_parser()
     args = ap.parse_args(argv)
+    griffinlim.check_arguments(ap, args, args.checkpoint)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     torch.set_num_threads(4)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
     dev = "cuda:%d" % (args.job % max(torch.cuda.device_count(), 1))
-    gen, rate = build_generator(args.checkpoint, dev, args.config, args.unsafe_pickle)
     feats = sorted(kaldi_io.read_scp(args.feats_scp).items())
+    if args.griffin_lim:
+        from . import griffinlim
+
+        # (utterances too short for the reflection are refused by id before the first device call)
+        griffinlim.check_lens([m.shape[0] for _, m in feats], args.n_fft, args.hop, [uid for uid, _ in feats])
+        gen, rate = griffinlim.from_args(args, dev, n_mels=int(feats[0][1].shape[1]) if feats and feats[0][1].ndim == 2 and args.mel_basis is None else 80)
+    else:
+        gen, rate = build_generator(args.checkpoint, dev, args.config, args.unsafe_pickle)
     aux = gen.plan.A
     for uid, m in feats:
         if m.ndim != 2 or m.shape[1] != aux or m.shape[0] < 1:

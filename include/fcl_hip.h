@@ -904,6 +904,56 @@ int fcl_hfg_unit_cap_fwd(const fcl_hfg_unit_t* a, const int32_t* live, fcl_strea
 int fcl_hfg_out_cap_fwd(const uint16_t* cp, const float* w, const float* b, const int32_t* frame_utt, const int32_t* utt_off, int rate, float* wav, int64_t m, int c,
                         int cout, int ksize, const int32_t* live, fcl_stream_t stream);
 
+/* ---- Griffin-Lim vocoder: mel -> waveform without a trained generator (fcl_taco2_amd/griffinlim.py; restated in float64 numpy in
+ *      tests/griffinlim_ref.py).  The library links no FFT: csrc/griffinlim.hip holds an LDS-resident real FFT (complex FFT of n_fft / 2 points + split).
+ * Inputs: packed mel rows [frames, n_mels] (normalised log10 mel, utterances concatenated), frames per utterance T_u, optional mel_stats [2, n_mels]
+ *      (mean, std), and fs, n_fft, hop, win_length, fmin, fmax, n_iter, momentum, seed.  F = n_fft / 2 + 1 bins.
+ * Mel to linear:  lm = mel * (std + 1e-8) + mean (identity without stats);  m = 10^lm;  S = max(1e-10, m @ pinv(B)^T) [frames, F].  B is the Slaney-style
+ *      mel filterbank (triangles on the Slaney mel scale, area normalisation 2 / (f_hi - f_lo)); the package builds B and pinv(B) in float64 numpy and
+ *      uploads pinv(B)^T [n_mels, F] as float32.
+ * Window: periodic Hann of win_length, zero-padded centred to n_fft.
+ * STFT per utterance: reflect-pad n_fft / 2 on both sides; frame t starts at t * hop of the padded signal; times the window; real FFT.  A signal of
+ *      hop (T - 1) samples gives T frames.
+ * ISTFT: per frame the inverse real FFT (imaginary parts of the DC and Nyquist bins ignored) times the window, overlap-added into n_fft + hop (T - 1)
+ *      samples, divided by the window-sum-square where that exceeds FLT_MIN (left undivided elsewhere), n_fft / 2 samples dropped at both ends:
+ *      hop (T - 1) samples, NOT T * hop.
+ * Iteration: P = exp(2 pi i u), C_prev = 0; n_iter times { y = istft(S P); C = stft(y); A = C - momentum / (1 + momentum) C_prev; P = A / (|A| + 1e-16);
+ *      C_prev = C }; the result is istft(S P).  momentum 0 is the classic form (no C_prev).
+ * Initial phase: u [T, F] of utterance i from counter hashes, h(x) = the library's hash_u32 (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *      x *= 0x846ca68b; x ^= x >> 16, uint32):  u = (h(h(utt_seed[i] ^ h(t + 0x9E3779B9)) ^ (k * 0x85EBCA6B)) >> 8) * 2^-24 for local frame t and bin k
+ *      (numpy twin: griffinlim.phase_uniforms).  utt_seed is a device array, so a batch equals its per-utterance runs with the same seeds.
+ * Supported: n_fft 512 / 1024 / 2048, 1 <= hop <= n_fft / 2, win_length <= n_fft, and (refused by the package, by utterance, before any device call)
+ *      T_u >= n_fft / (2 hop) + 2, so that the reflection is a single one; the kernels clamp and stay inside their buffers for any T_u >= 1.
+ * Buffers of a batch: s [frames, F] float, p / c_prev / c_out [frames, F] complex (float pairs), fr [frames, n_fft] float, y [hop (frames - n_utt)] float:
+ *      utterance i (frames utt_off[i] .. utt_off[i + 1]) owns the samples from hop (utt_off[i] - i).  frame_utt [frames] / utt_off [n_utt + 1] as
+ *      fcl_hfg_*.  window [n_fft]; twiddle [n_fft] complex, W^k = exp(-2 pi i k / n_fft), computed in double.  No entry allocates, synchronises or copies.
+ * fcl_gl_mel2lin_fwd: the mel-to-linear step (mel_stats optional; n_mels <= 256).
+ * fcl_gl_phase_init:  p = exp(2 pi i u) from utt_seed; u_out (optional, [frames, F] float) receives u itself.
+ * fcl_gl_synth_fwd:   fr = irfft(s p) x window.        fcl_gl_ola_fwd: y from fr (a gather in fixed frame order, no atomics).
+ * fcl_gl_analysis_fwd: C = stft(y); the phase update into p (and c_prev, which momentum != 0 requires); c_out (optional) receives C. */
+typedef struct {
+    int64_t frames;
+    int32_t n_fft, hop, n_utt;
+    float momentum;
+    const float* window;
+    const float* twiddle;
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    const uint32_t* utt_seed;
+    const float* s;
+    float* p;
+    float* fr;
+    float* y;
+    float* c_prev;
+    float* c_out;
+    float* u_out;
+} fcl_gl_t;
+int fcl_gl_mel2lin_fwd(const float* mel, const float* mel_stats, const float* pinv_t, float* s, int64_t frames, int n_mels, int bins, fcl_stream_t stream);
+int fcl_gl_phase_init(const fcl_gl_t* a, fcl_stream_t stream);
+int fcl_gl_synth_fwd(const fcl_gl_t* a, fcl_stream_t stream);
+int fcl_gl_ola_fwd(const fcl_gl_t* a, fcl_stream_t stream);
+int fcl_gl_analysis_fwd(const fcl_gl_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
