@@ -797,8 +797,8 @@ class BatchRunner(object):
 
 class SpeechRunner(BatchRunner):
     """Text -> waveform in ONE captured graph per batch: a BatchRunner whose graph continues, on the same stream (a chain, no parallel branches),
-    into the capacity form of the vocoder (vocoder.CapacitySynth, or hifigan.CapacitySynth for a generator that offers `capacity_synth`: device-built
-    index maps, live-extent launches) and the PCM conversion.  The
+    into the capacity form of the vocoder (`gen.capacity_synth`: vocoder.CapacitySynth or hifigan.CapacitySynth, device-built index maps,
+    live-extent launches) and the PCM conversion.  The
     durations -- predicted (forced=False, the default here), forced, or prosody-controlled -- never reach the host: the vocoder takes the pass's
     device frame starts, and both stages report into the runner's one status word.
 
@@ -812,21 +812,18 @@ class SpeechRunner(BatchRunner):
 
     def __init__(self, plan, gen, batch, t_cap, caps, voc_frames_cap=None, forced=False, stream=None, dropout_mode=ops.DROP_RNG, seed=0, depth=3,
                  pack_outputs=False, mempool=None, controls=False):
-        from .vocoder import CapacitySynth  # (vocoder.py imports nothing from here)
-
         if int(plan.hp.odim) != int(gen.plan.A):
             raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: the model writes %d mel channels, the vocoder takes %d" % (plan.hp.odim, gen.plan.A))
         if torch.device(gen.plan.device) != torch.device(plan.device):
             raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: model and vocoder must live on one device")
-        if not hasattr(gen, "capacity_synth") and getattr(gen.plan, "eager_only", False):
+        if not hasattr(gen, "capacity_synth"):
             raise ops._lib.FclError("fcl-taco2_amd: SpeechRunner: %s has no capacity form (only the Parallel WaveGAN generator can follow the synthesis pass "
                                     "inside one graph); use the two-step route (engine.run, then gen.synthesize_packed), as tts.synthesize does"
                                     % type(gen).__name__)
         self.gen, self.hop, self.seed = gen, int(gen.plan.hop), int(seed)
         with torch.cuda.device(plan.device):
             frames_cap = int(voc_frames_cap) if voc_frames_cap else caps.frames
-            # (a generator family with a capacity form of its own offers it -- hifigan.CapacitySynth; the same surface either way)
-            self.synth = gen.capacity_synth(batch, frames_cap, seed=seed) if hasattr(gen, "capacity_synth") else CapacitySynth(gen, batch, frames_cap, seed=seed)
+            self.synth = gen.capacity_synth(batch, frames_cap, seed=seed)  # vocoder.CapacitySynth or hifigan.CapacitySynth: the same surface
         BatchRunner.__init__(self, plan, batch, t_cap, caps, forced=forced, stream=stream, dropout_mode=dropout_mode, seed=seed, depth=depth,
                              pack_outputs=pack_outputs, mempool=mempool, controls=controls, tail=SpeechRunner._vocoder_tail)
         self.pcm, self.live = self.synth.pcm, self.synth.live

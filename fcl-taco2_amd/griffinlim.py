@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .vocoder import Generator
 
 DEFAULTS = dict(fs=22050, n_fft=1024, hop=256, win_length=None, n_mels=80, fmin=80.0, fmax=7600.0, n_iter=64, momentum=0.99)  # preprocess.py's analysis
 N_FFTS = (512, 1024, 2048)
@@ -200,11 +201,8 @@ def launch_analysis(pl, mp, y, P, c_prev=None, c_out=None, momentum=0.0):
     _lib.check(_lib.load().fcl_gl_analysis_fwd(C.byref(_args(pl, mp, momentum, y=y, p=P, c_prev=c_prev, c_out=c_out)), ops._stream()))
 
 
-class GriffinLim(object):
-    """mel -> waveform.  `synthesize(mels)` is the batched entry; `inference(c)` mirrors the generators' single-utterance call."""
-
-    def __init__(self, plan):
-        self.plan = plan
+class GriffinLim(Generator):
+    """Griffin-Lim on a GriffinLimPlan, with the generators' surface (`synthesize(..., phase0=)` passes the initial phase on)."""
 
     def samples_of(self, frames):
         """samples of an utterance of `frames` mel frames: hop * (frames - 1)"""
@@ -230,26 +228,13 @@ class GriffinLim(object):
             launch_ola(pl, mp, fr, flat)
         return flat
 
-    def synthesize(self, mels, noise=None, seed=0, return_intermediates=False, phase0=None):
-        """mels: list of [T'_i, n_mels] float tensors / arrays -> list of [hop * (T'_i - 1)] float32 device tensors."""
-        dev = self.plan.device
-        with torch.cuda.device(dev):
-            lens = [int(m.shape[0]) for m in mels]
-            mel_rows = torch.cat([torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mels]).contiguous()
-            return self.synthesize_packed(mel_rows, lens, noise, seed, return_intermediates, phase0=phase0)
-
     def synthesize_packed(self, mel_rows, lens, noise=None, seed=0, return_intermediates=False, return_flat=False, phase0=None, n_iter=None, ids=None):
         """The same on utterances already packed row-wise ([sum T', n_mels] device tensor) with their frame counts.  Utterance i draws its initial
         phase from seed + i, so a batch equals its per-utterance runs with the same seeds; phase0 ([sum T', F] complex64) replaces the draw.  `noise`
         is accepted and unused.  return_intermediates: also dict(S, P) (the magnitudes and the last phase).  return_flat: also the one buffer the
         waveforms are slices of (utterances back to back)."""
         pl, dev = self.plan, self.plan.device
-        lens = [int(n) for n in lens]
-        if not lens or min(lens) < 1:
-            raise _lib.FclError("fcl-taco2_amd: empty mel")
-        check_lens(lens, pl.n_fft, pl.hop, ids)
-        if mel_rows.dim() != 2 or mel_rows.shape[1] != pl.A or mel_rows.shape[0] != sum(lens):
-            raise _lib.FclError("fcl-taco2_amd: expected [%d, %d] mel rows, got %r" % (sum(lens), pl.A, tuple(mel_rows.shape)))
+        lens = self._packed_lens(mel_rows, lens, ids)
         if sum(lens) * pl.n_fft >= 2 ** 31 - 1:
             raise _lib.FclError("fcl-taco2_amd: more than 2^31 / n_fft frames in one Griffin-Lim batch")
         with torch.cuda.device(dev):
@@ -269,16 +254,7 @@ class GriffinLim(object):
             flat = self.iterate(mp, S, P, n_iter)
             so = (mp.frame_off - np.arange(mp.n_utt + 1)) * pl.hop
             outs = [flat[int(so[i]) : int(so[i + 1])] for i in range(mp.n_utt)]
-            res = (outs,)
-            if return_intermediates:
-                res += (dict(S=S, P=P, lens=lens),)
-            if return_flat:
-                res += (flat,)
-            return res[0] if len(res) == 1 else res
-
-    def inference(self, c, x=None):
-        """c [T', n_mels] -> waveform [hop * (T' - 1), 1]"""
-        return self.synthesize([c])[0].reshape(-1, 1)
+            return self._results(outs, dict(S=S, P=P, lens=lens), flat, return_intermediates, return_flat)
 
 
 def add_arguments(ap):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .vocoder import fold_weight_norm
+from .vocoder import Generator, check_capacity, check_run_args, fold_weight_norm
 
 CONFIG = dict(in_channels=80, out_channels=1, channels=512, kernel_size=7, upsample_scales=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
               resblock_kernel_sizes=(3, 7, 11), resblock_dilations=((1, 3, 5), (1, 3, 5), (1, 3, 5)), use_additional_convs=True, bias=True,
@@ -149,12 +149,69 @@ def capacity_nbytes(cfg, batch, frames_cap):
     return int(frames_cap) * (rows + tp + small) + 4 * (int(batch) + 2) + 16
 
 
+def build_chain(pl, F, fu, uo, melp, cp0, rows_of, y0=None):
+    """The descriptors of every launch on F frames, once for the exact form (synthesize_packed) and the capacity form (CapacitySynth).  fu, uo:
+    pointers of frame_utt / utt_off; melp, cp0: planes of the mel and of input_conv's output (y0: its fp32 output, where wanted);
+    rows_of(rows, channels) -> the row buffers (c, cpl, xb, cs, pa, pb, csp, tp) a stage works in (fp32 c, xb, cs, the others planes; tp only
+    read for a width outside 32 / 64 / 128).  The transposed convolution writes c / cpl; the units of a block ping-pong from there through
+    xb / pa / pb, the block's last unit adds into cs and the stage's last one writes csp, the planes the next stage (or output_conv) reads.
+    Returns (input conv, [(tconv, units)], csp, rows per frame of csp)."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = _lib.HfgConv()
+    a.m, a.cin, a.cout, a.ksize, a.dilation, a.rate, a.slope = F, pl.input["cin"], pl.input["cout"], pl.input["k"], 1, 1, pl.slope
+    a.xp, a.wp, a.bias, a.frame_utt, a.utt_off, a.y, a.yp = ptr(melp), ptr(pl.input["wp"]), ptr(pl.input["b"]), fu, uo, ptr(y0), ptr(cp0)
+    stages, rate, rows, cp = [], 1, F, cp0
+    for si, st in enumerate(pl.stages):
+        tc = _lib.HfgTconv()
+        tc.m_in, tc.cin, tc.cout, tc.stride, tc.ksize, tc.padding, tc.rate_in, tc.slope = rows, st["cin"], st["cout"], st["s"], st["ku"], \
+            tconv_padding(st["s"])[0], rate, pl.slope
+        rows, rate, Cc = rows * st["s"], rate * st["s"], st["cout"]
+        c, cpl, xb, cs, pa, pb, csp, tp = rows_of(rows, Cc)
+        tc.xp, tc.wp, tc.bias, tc.frame_utt, tc.utt_off, tc.y, tc.yp = ptr(cp), ptr(st["wp"]), ptr(st["b"]), fu, uo, ptr(c), ptr(cpl)
+        units, nk = [], len(st["blocks"])
+        for j, blk in enumerate(st["blocks"]):
+            x_in, xp_in, xp_out = c, cpl, pa
+            for d, U in enumerate(blk):
+                last = d == len(blk) - 1
+                u = _lib.HfgUnit()
+                u.m, u.c, u.ksize, u.dilation, u.rate, u.first, u.last = rows, Cc, U["k"], U["dilation"], rate, int(j == 0), int(last)
+                u.slope, u.cs_scale, u.csp_slope = pl.slope, 1.0 / nk, OUT_SLOPE if si == len(pl.stages) - 1 else pl.slope
+                u.xp, u.x, u.w1p, u.b1, u.w2p, u.b2 = ptr(xp_in), ptr(x_in), ptr(U["w1p"]), ptr(U["b1"]), ptr(U["w2p"]), ptr(U["b2"])
+                u.frame_utt, u.utt_off = fu, uo
+                if last:
+                    u.cs, u.csp = ptr(cs), ptr(csp) if j == nk - 1 else None
+                else:
+                    u.x_out, u.xp_out = ptr(xb), ptr(xp_out)
+                u.tp = ptr(tp) if Cc not in (32, 64, 128) else None
+                units.append(u)
+                x_in, xp_in, xp_out = xb, xp_out, (pb if xp_out is pa else pa)
+        stages.append((tc, units))
+        cp = csp
+    return a, stages, cp, rate
+
+
+def enqueue_chain(pl, chain, wav, M, oc, s, live=None):
+    """Every launch of build_chain's descriptors, then output_conv into wav [M, oc]: the exact entries, or with `live` (the pointer of a capacity
+    form's live record) the cap entries, which do no work past the live rows."""
+    lib, chk, cap = _lib.load(), _lib.check, () if live is None else (live,)
+    conv, tconv, unit, out = (lib.fcl_hfg_conv_fwd, lib.fcl_hfg_tconv_fwd, lib.fcl_hfg_unit_fwd, lib.fcl_hfg_out_fwd) if live is None else (
+        lib.fcl_hfg_conv_cap_fwd, lib.fcl_hfg_tconv_cap_fwd, lib.fcl_hfg_unit_cap_fwd, lib.fcl_hfg_out_cap_fwd)
+    a, stages, csp, rate = chain
+    chk(conv(C.byref(a), *cap, s))
+    for tc, units in stages:
+        chk(tconv(C.byref(tc), *cap, s))
+        for u in units:
+            chk(unit(C.byref(u), *cap, s))
+    chk(out(csp.data_ptr(), pl.out_w.data_ptr(), pl.out_b.data_ptr(), a.frame_utt, a.utt_off, rate, wav.data_ptr(), M, pl.c_last, oc, pl.cfg["kernel_size"], *cap, s))
+
+
 class CapacitySynth(object):
-    """The generator in CAPACITY form (the twin of vocoder.CapacitySynth): every buffer, descriptor and pointer is fixed at construction for `batch`
+    """The generator in CAPACITY form (the surface of vocoder.CapacitySynth): every buffer, descriptor and pointer is fixed at construction for `batch`
     utterance slots and `frames_cap` mel frames; what is live comes from the device (the synthesis pass's frame starts), so `run` derives no host
     value from the data, allocates nothing and is capturable in a hipGraph behind the synthesis pass (engine.SpeechRunner).  The chain is
     fcl_hfg_maps_build -> fcl_pack_planes of the capacity mel -> the conv / tconv / unit / out cap launches -> fcl_pcm16_fwd; the cap launches do no
-    work and touch no memory past the live rows, and a live row is computed exactly as `synthesize_packed` computes it on the same packed rows.
+    work and touch no memory past the live rows, and a live row is computed exactly as `synthesize_packed` computes it on the same packed rows:
+    both run build_chain's descriptors through enqueue_chain, here on the one shared set of row buffers.
     Memory: capacity_nbytes (the stages share one set of row buffers); `nbytes` is what this instance holds (its tensors, 512-byte granularity)."""
 
     def __init__(self, gen, batch, frames_cap, seed=0):
@@ -164,9 +221,7 @@ class CapacitySynth(object):
         if pl.out_channels != 1:
             raise _lib.FclError("fcl-taco2_amd: the capacity form of the HiFi-GAN generator writes mono PCM: out_channels = %d is not supported; use "
                                 "synthesize_packed for this generator" % pl.out_channels)
-        if self.B < 1 or self.B > 1024 or self.frames_cap < 1 or self.frames_cap * pl.hop >= 2 ** 31 - 1:
-            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: 1..1024 utterances and fewer than 2^31 / hop frames expected (got %d, %d)"
-                                % (self.B, self.frames_cap))
+        check_capacity(self.B, self.frames_cap, pl.hop)
         F, hop = self.frames_cap, pl.hop
         self.M = F * hop
         geo = _stage_geometry(pl.cfg)
@@ -190,42 +245,7 @@ class CapacitySynth(object):
             held = (self.frame_utt, self.utt_off, self.live, self.melp, self.cp0, self.wav, self.pcm) + tuple(t_ for t_ in self._rows if t_ is not None)
             self.nbytes = sum((t_.untyped_storage().nbytes() + 511) // 512 * 512 for t_ in held)
             # the descriptors of every launch: every pointer is static, m / m_in is the capacity
-            fu, uo = self.frame_utt.data_ptr(), self.utt_off.data_ptr()
-            a = _lib.HfgConv()
-            a.m, a.cin, a.cout, a.ksize, a.dilation, a.rate, a.slope = F, pl.input["cin"], pl.input["cout"], pl.input["k"], 1, 1, pl.slope
-            a.xp, a.wp, a.bias, a.frame_utt, a.utt_off, a.yp = self.melp.data_ptr(), pl.input["wp"].data_ptr(), pl.input["b"].data_ptr(), fu, uo, self.cp0.data_ptr()
-            self._input = a
-            self._stages = []
-            rate, rows, cp = 1, F, self.cp0
-            for si, st in enumerate(pl.stages):
-                last_stage = si == len(pl.stages) - 1
-                tc = _lib.HfgTconv()
-                tc.m_in, tc.cin, tc.cout, tc.stride, tc.ksize, tc.padding, tc.rate_in, tc.slope = rows, st["cin"], st["cout"], st["s"], st["ku"], \
-                    tconv_padding(st["s"])[0], rate, pl.slope
-                rows, rate, Cc = rows * st["s"], rate * st["s"], st["cout"]
-                tc.xp, tc.wp, tc.bias, tc.frame_utt, tc.utt_off, tc.y, tc.yp = cp.data_ptr(), st["wp"].data_ptr(), st["b"].data_ptr(), fu, uo, c.data_ptr(), \
-                    cpl.data_ptr()
-                units, nk = [], len(st["blocks"])
-                for j, blk in enumerate(st["blocks"]):
-                    x_in, xp_in, xp_out = c, cpl, pa
-                    for d, U in enumerate(blk):
-                        last = d == len(blk) - 1
-                        u = _lib.HfgUnit()
-                        u.m, u.c, u.ksize, u.dilation, u.rate, u.first, u.last = rows, Cc, U["k"], U["dilation"], rate, int(j == 0), int(last)
-                        u.slope, u.cs_scale, u.csp_slope = pl.slope, 1.0 / nk, OUT_SLOPE if last_stage else pl.slope
-                        u.xp, u.x, u.w1p, u.b1, u.w2p, u.b2 = xp_in.data_ptr(), x_in.data_ptr(), U["w1p"].data_ptr(), U["b1"].data_ptr(), U["w2p"].data_ptr(), \
-                            U["b2"].data_ptr()
-                        u.frame_utt, u.utt_off = fu, uo
-                        if last:
-                            u.cs, u.csp = cs.data_ptr(), csp.data_ptr() if j == nk - 1 else None
-                        else:
-                            u.x_out, u.xp_out = xb.data_ptr(), xp_out.data_ptr()
-                        u.tp = tp.data_ptr() if Cc not in (32, 64, 128) else None
-                        units.append(u)
-                        x_in, xp_in, xp_out = xb, xp_out, (pb if xp_out is pa else pa)
-                self._stages.append((tc, units))
-                cp = csp
-            self._csp, self._rate = csp, rate
+            self._chain = build_chain(pl, F, self.frame_utt.data_ptr(), self.utt_off.data_ptr(), self.melp, self.cp0, lambda rows, ch: self._rows)
             # eager warm-up on an empty batch: the library's one-time setup (dynamic-LDS opt-ins) must not happen inside a capture
             self.run(torch.zeros(1, pl.A, device=dev), i32(self.B + 1), i32(1))
             torch.cuda.current_stream(dev).synchronize()
@@ -237,22 +257,13 @@ class CapacitySynth(object):
         OR-ed into it; a word that is already set makes this pass generate nothing); seed_dev: accepted and ignored (the generator draws no noise).
         Results: self.pcm (int16) and self.wav (float32), live samples [0, self.live[1])."""
         pl, lib = self.plan, _lib.load()
-        if mel_rows_cap.dim() != 2 or mel_rows_cap.shape[1] != pl.A or mel_rows_cap.dtype != torch.float32 or not mel_rows_cap.is_contiguous():
-            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: expected contiguous float32 [rows, %d] mel rows, got %r" % (pl.A, tuple(mel_rows_cap.shape)))
-        if utt_frame0_dev.dtype != torch.int32 or utt_frame0_dev.numel() < self.B + 1 or status.dtype != torch.int32:
-            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: utt_frame0 must hold %d int32 frame starts and status be an int32 word" % (self.B + 1))
+        check_run_args(mel_rows_cap, utt_frame0_dev, status, pl.A, self.B)
         s, live, chk = ops._stream(), self.live.data_ptr(), _lib.check
         chk(lib.fcl_hfg_maps_build(utt_frame0_dev.data_ptr(), status.data_ptr(), self.B, self.frames_cap, pl.hop, self.frame_utt.data_ptr(),
                                    self.utt_off.data_ptr(), live, s))
         # (a buffer with fewer rows than the capacity cannot hold more live frames than it has rows: the synthesis pass's own capacity)
         chk(lib.fcl_pack_planes(mel_rows_cap.data_ptr(), mel_rows_cap.stride(0), min(int(mel_rows_cap.shape[0]), self.frames_cap), pl.A, self.melp.data_ptr(), s))
-        chk(lib.fcl_hfg_conv_cap_fwd(C.byref(self._input), live, s))
-        for tc, units in self._stages:
-            chk(lib.fcl_hfg_tconv_cap_fwd(C.byref(tc), live, s))
-            for u in units:
-                chk(lib.fcl_hfg_unit_cap_fwd(C.byref(u), live, s))
-        chk(lib.fcl_hfg_out_cap_fwd(self._csp.data_ptr(), pl.out_w.data_ptr(), pl.out_b.data_ptr(), self.frame_utt.data_ptr(), self.utt_off.data_ptr(), self._rate,
-                                    self.wav.data_ptr(), self.M, pl.c_last, 1, pl.cfg["kernel_size"], live, s))
+        enqueue_chain(pl, self._chain, self.wav, self.M, 1, s, live)
         chk(lib.fcl_pcm16_fwd(self.wav.data_ptr(), self.pcm.data_ptr(), self.M, live, status.data_ptr(), s))
         return self.pcm
 
@@ -314,106 +325,42 @@ def check_state_dict(sd, cfg):
         raise _lib.FclError("fcl-taco2_amd: HiFi-GAN generator state_dict holds %s, which the configured geometry does not use" % extra[0])
 
 
-class HiFiGANGenerator(object):
-    """mel -> waveform.  `synthesize(mels)` is the batched entry; `inference(c)` mirrors the published single-utterance call."""
-
-    def __init__(self, plan):
-        self.plan = plan
-
-    def samples_of(self, frames):
-        """samples of an utterance of `frames` mel frames"""
-        return int(frames) * self.plan.hop
+class HiFiGANGenerator(Generator):
+    """The HiFi-GAN generator on a HiFiGANPlan."""
 
     def capacity_synth(self, batch, frames_cap, seed=0):
         """The capacity form of this generator for `batch` utterance slots and `frames_cap` mel frames (what engine.SpeechRunner captures)."""
         return CapacitySynth(self, batch, frames_cap, seed=seed)
 
-    def synthesize(self, mels, noise=None, seed=0, return_intermediates=False):
-        """mels: list of [T'_i, in_channels] float tensors / arrays -> list of [T'_i * hop] float32 device tensors ([T'_i * hop, out] for out > 1)."""
-        dev = self.plan.device
-        with torch.cuda.device(dev):
-            lens = [int(m.shape[0]) for m in mels]
-            mel_rows = torch.cat([torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mels]).contiguous()
-            return self.synthesize_packed(mel_rows, lens, noise, seed, return_intermediates)
-
     def synthesize_packed(self, mel_rows, lens, noise=None, seed=0, return_intermediates=False, return_flat=False):
-        """The same on utterances already packed row-wise ([sum T', in_channels] device tensor) with their frame counts.  return_intermediates: also a
-        dict with `taps` = [input_conv's output, every stage's output c] (fp32).  return_flat: also the one buffer the waveforms are slices of."""
+        """Utterances packed row-wise ([sum T', in_channels] device tensor) with their frame counts -> list of [T'_i * hop] float32 device tensors
+        ([T'_i * hop, out] for out > 1).  return_intermediates: also a dict with `taps` = [input_conv's output, every stage's output c] (fp32).
+        return_flat: also the one buffer the waveforms are slices of."""
         pl, dev = self.plan, self.plan.device
-        lib = _lib.load()
         with torch.cuda.device(dev):
-            lens = [int(n) for n in lens]
-            if not lens or min(lens) < 1:
-                raise _lib.FclError("fcl-taco2_amd: empty mel")
-            if mel_rows.dim() != 2 or mel_rows.shape[1] != pl.A or mel_rows.shape[0] != sum(lens):
-                raise _lib.FclError("fcl-taco2_amd: expected [%d, %d] mel rows, got %r" % (sum(lens), pl.A, tuple(mel_rows.shape)))
+            lens = self._packed_lens(mel_rows, lens)
             F = sum(lens)
             if F * pl.hop >= 2 ** 30:
                 raise _lib.FclError("fcl-taco2_amd: more than 2^30 samples in one vocoder batch")
             offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
             frame_utt = torch.from_numpy(np.repeat(np.arange(len(lens)), lens).astype(np.int32)).to(dev)
             utt_off = torch.from_numpy(offs.astype(np.int32)).to(dev)
-            fu, uo, s_ = frame_utt.data_ptr(), utt_off.data_ptr(), ops._stream()
             f32 = lambda r, c: torch.empty(r, c, device=dev, dtype=torch.float32)
-            taps = []
+            held = []  # every stage's own row buffers, alive until the launches are enqueued
+
+            def rows_of(rows, ch):  # (c, cpl, xb, cs, pa, pb, csp, tp) at the stage's size
+                pe = lambda: ops.planes_empty(rows, ch, dev)
+                held.append((f32(rows, ch), pe(), f32(rows, ch), f32(rows, ch), pe(), pe(), pe(), pe() if ch not in (32, 64, 128) else None))
+                return held[-1]
+
             melp = ops.pack_planes(mel_rows.to(torch.float32).contiguous())
-            a = _lib.HfgConv()
-            a.m, a.cin, a.cout, a.ksize, a.dilation, a.rate, a.slope = F, pl.input["cin"], pl.input["cout"], pl.input["k"], 1, 1, pl.slope
-            a.xp, a.wp, a.bias, a.frame_utt, a.utt_off = melp.data_ptr(), pl.input["wp"].data_ptr(), pl.input["b"].data_ptr(), fu, uo
-            cp = ops.planes_empty(F, a.cout, dev)
-            a.yp = cp.data_ptr()
-            if return_intermediates:
-                c0 = f32(F, a.cout)
-                a.y = c0.data_ptr()
-                taps.append(c0)
-            _lib.check(lib.fcl_hfg_conv_fwd(C.byref(a), s_))
-            rate, rows = 1, F
-            for si, st in enumerate(pl.stages):
-                last_stage = si == len(pl.stages) - 1
-                tc = _lib.HfgTconv()
-                tc.m_in, tc.cin, tc.cout, tc.stride, tc.ksize, tc.padding, tc.rate_in, tc.slope = rows, st["cin"], st["cout"], st["s"], st["ku"], \
-                    tconv_padding(st["s"])[0], rate, pl.slope
-                rows, rate, Cc = rows * st["s"], rate * st["s"], st["cout"]
-                c, cpl = f32(rows, Cc), ops.planes_empty(rows, Cc, dev)
-                tc.xp, tc.wp, tc.bias, tc.frame_utt, tc.utt_off, tc.y, tc.yp = cp.data_ptr(), st["wp"].data_ptr(), st["b"].data_ptr(), fu, uo, c.data_ptr(), \
-                    cpl.data_ptr()
-                _lib.check(lib.fcl_hfg_tconv_fwd(C.byref(tc), s_))
-                xb, cs = f32(rows, Cc), f32(rows, Cc)
-                pa, pb, csp = ops.planes_empty(rows, Cc, dev), ops.planes_empty(rows, Cc, dev), ops.planes_empty(rows, Cc, dev)
-                tp = ops.planes_empty(rows, Cc, dev) if Cc not in (32, 64, 128) else None
-                nk = len(st["blocks"])
-                for j, units in enumerate(st["blocks"]):
-                    x_in, xp_in, xp_out = c, cpl, pa
-                    for d, U in enumerate(units):
-                        last = d == len(units) - 1
-                        u = _lib.HfgUnit()
-                        u.m, u.c, u.ksize, u.dilation, u.rate, u.first, u.last = rows, Cc, U["k"], U["dilation"], rate, int(j == 0), int(last)
-                        u.slope, u.cs_scale, u.csp_slope = pl.slope, 1.0 / nk, OUT_SLOPE if last_stage else pl.slope
-                        u.xp, u.x, u.w1p, u.b1, u.w2p, u.b2 = xp_in.data_ptr(), x_in.data_ptr(), U["w1p"].data_ptr(), U["b1"].data_ptr(), U["w2p"].data_ptr(), \
-                            U["b2"].data_ptr()
-                        u.frame_utt, u.utt_off = fu, uo
-                        if last:
-                            u.cs, u.csp = cs.data_ptr(), csp.data_ptr() if j == nk - 1 else None
-                        else:
-                            u.x_out, u.xp_out = xb.data_ptr(), xp_out.data_ptr()
-                        u.tp = None if tp is None else tp.data_ptr()
-                        _lib.check(lib.fcl_hfg_unit_fwd(C.byref(u), s_))
-                        x_in, xp_in, xp_out = xb, xp_out, (pb if xp_out is pa else pa)
-                cp = csp
-                if return_intermediates:
-                    taps.append(cs)
-            M, oc = rows, pl.out_channels
+            cp0 = ops.planes_empty(F, pl.input["cout"], dev)
+            c0 = f32(F, pl.input["cout"]) if return_intermediates else None
+            chain = build_chain(pl, F, frame_utt.data_ptr(), utt_off.data_ptr(), melp, cp0, rows_of, c0)
+            M, oc = F * pl.hop, pl.out_channels
             flat = torch.empty(M * oc, device=dev, dtype=torch.float32)  # the per-utterance waveforms are slices of this one buffer
-            _lib.check(lib.fcl_hfg_out_fwd(cp.data_ptr(), pl.out_w.data_ptr(), pl.out_b.data_ptr(), fu, uo, rate, flat.data_ptr(), M, pl.c_last, oc,
-                                           pl.cfg["kernel_size"], s_))
+            enqueue_chain(pl, chain, flat, M, oc, ops._stream())
             outs = [flat[int(offs[i]) * pl.hop * oc : int(offs[i + 1]) * pl.hop * oc] for i in range(len(lens))]
             if oc > 1:
                 outs = [o.reshape(-1, oc) for o in outs]
-            if return_intermediates:
-                res = (outs, dict(taps=taps, lens=lens))
-                return res + (flat,) if return_flat else res
-            return (outs, flat) if return_flat else outs
-
-    def inference(self, c, x=None):
-        """HiFiGANGenerator.inference(c): c [T', in_channels] -> waveform [T' * hop, out_channels]."""
-        return self.synthesize([c])[0].reshape(-1, self.plan.out_channels)
+            return self._results(outs, dict(taps=[c0] + [b[3] for b in held], lens=lens), flat, return_intermediates, return_flat)

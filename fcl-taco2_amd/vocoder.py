@@ -180,6 +180,90 @@ def capacity_maps_rule(utt_frame0, frames_cap, ctx, hop, status=0):
                 seg_hi=i32(offx[su + 1] * hop), live=i32([live, live * hop, live_pad, int(has.sum())]), ok=ok)
 
 
+def check_capacity(batch, frames_cap, hop):
+    """The range of a capacity form's `batch` utterance slots and `frames_cap` mel frames"""
+    if batch < 1 or batch > 1024 or frames_cap < 1 or frames_cap * hop >= 2 ** 31 - 1:
+        raise _lib.FclError("fcl-taco2_amd: capacity vocoder: 1..1024 utterances and fewer than 2^31 / hop frames expected (got %d, %d)" % (batch, frames_cap))
+
+
+def check_run_args(mel_rows_cap, utt_frame0_dev, status, aux, batch):
+    """What a capacity form's `run` refuses"""
+    if mel_rows_cap.dim() != 2 or mel_rows_cap.shape[1] != aux or mel_rows_cap.dtype != torch.float32 or not mel_rows_cap.is_contiguous():
+        raise _lib.FclError("fcl-taco2_amd: capacity vocoder: expected contiguous float32 [rows, %d] mel rows, got %r" % (aux, tuple(mel_rows_cap.shape)))
+    if utt_frame0_dev.dtype != torch.int32 or utt_frame0_dev.numel() < batch + 1 or status.dtype != torch.int32:
+        raise _lib.FclError("fcl-taco2_amd: capacity vocoder: utt_frame0 must hold %d int32 frame starts and status be an int32 word" % (batch + 1))
+
+
+# ---- the launch chain, once for the exact form (synthesize_packed: buffers of the batch's size, allocated per call) and the capacity form
+# (CapacitySynth: buffers of the capacity, allocated once).  Nothing below allocates or reads a device value back.
+def cascade(pl, c, frame_utt, utt_off, frames, chunk_major, outs):
+    """The 4 x (stretch + smoothing) stages on c [frames, C] (C % 4 == 0) into `outs`, one buffer per stage: fp32 [frames * rate, C], or int16 for
+    the planes of that stage's result.  Returns the last one."""
+    lib, C_, rate = _lib.load(), c.shape[1], 1
+    for s, w, out in zip(pl.cfg["upsample_scales"], pl.up_w, outs):
+        as_planes = out.dtype == torch.int16
+        _lib.check(lib.fcl_pwg_upsample_stage(c.data_ptr(), frame_utt.data_ptr(), utt_off.data_ptr(), frames, rate, s, w.data_ptr(),
+                                              None if as_planes else out.data_ptr(), out.data_ptr() if as_planes else None, C_, int(chunk_major),
+                                              ops._stream()))
+        c, rate = out, rate * s
+    return c
+
+
+def cascade_outs(pl, frames, C_, dev, want_planes):
+    """A buffer per stage for `cascade` on [frames, C_]: fp32, the last one the planes of the result where wanted"""
+    rows = [frames * int(r) for r in np.cumprod(pl.cfg["upsample_scales"])]
+    return [torch.empty(r, C_, device=dev) for r in rows[:-1]] + [ops.planes_empty(rows[-1], C_, dev) if want_planes else torch.empty(rows[-1], C_, device=dev)]
+
+
+def colour_basis(g):
+    """e[g][c] = (g mod 5 == c), [frames, 8], of the frame numbers g: the upsampling network's response to it gives the coefficients of the
+    frame-rate auxiliary term"""
+    return (g[:, None] % 5 == torch.arange(8, device=g.device)[None, :]).to(torch.float32).contiguous()
+
+
+def aux_term(pl, colour, frame_utt, utt_off, frames, chunk_major, stages, kp, cfull, cfull_p, pt_a, pt_b):
+    """The auxiliary term of every block at frame rate (fcl_pwg_layer_t.kp): the upsampling network is linear and a sample of frame f sees frames
+    f-2 .. f+2 only, so conv1x1_aux(upsample(c))[m] = sum_g k[m][g] (W_aux c_in[g]).  k (-> kp, coefficient lines [M]) is the network's response,
+    utterance edges included, to the colour basis; cfull holds c_in in rows [16, 16 + frames) of zeros, and the projections W_aux c_in^T of all
+    blocks are gate-row major over frames: line q of pt_a = frames [32q, 32q + 32), of pt_b = frames [32q - 16, 32q + 16)."""
+    lib, s = _lib.load(), ops._stream()
+    kc = cascade(pl, colour, frame_utt, utt_off, frames, chunk_major, stages)
+    _lib.check(lib.fcl_pwg_aux_coeff(kc.data_ptr(), frames * pl.hop, pl.hop, frames, kp.data_ptr(), s))
+    n, rows, w = cfull.shape[0] - 16, pl.w_aux_all_p.shape[0], pl.w_aux_all_p
+    _lib.check(lib.fcl_pack_planes(cfull.data_ptr(), cfull.stride(0), cfull.shape[0], pl.A, cfull_p.data_ptr(), s))
+    for src, pt in ((cfull_p[16:], pt_a), (cfull_p, pt_b)):
+        _lib.check(lib.fcl_linear_planes_fwd(w.data_ptr(), w.shape[1] // 64, src.data_ptr(), None, None, n, pt.data_ptr(), rows, n, pl.A, ops.ACT_NONE, s))
+
+
+def layer_chain(pl, M, seg_lo, seg_hi, xp, gp, skips, aux, x=None, unfused=None):
+    """The descriptors of the residual blocks on M rows.  aux: (kp, pt_a, pt_b, ld_pt) of the frame-rate auxiliary term, or the planes cp of the
+    upsampled features.  The one-launch blocks ping-pong between xp and gp; unfused = (z, o) workspaces selects the three-launch block, which
+    updates fp32 x and xp in place and keeps the gate's planes in gp."""
+    layers, R = [], pl.R
+    p_in, p_out = xp.data_ptr(), gp.data_ptr()
+    for l, L in enumerate(pl.layers):
+        a = _lib.PwgLayer()
+        a.m, a.r, a.aux, a.ksize, a.dilation, a.first_layer = M, R, pl.A, pl.k, L["dilation"], int(l == 0)
+        a.seg_lo, a.seg_hi = seg_lo, seg_hi
+        a.x, a.xp = None if x is None else x.data_ptr(), p_in
+        a.w_conv_p, a.b_conv, a.w_aux_p = L["w_conv_p"].data_ptr(), L["b_conv"].data_ptr(), L["w_aux_p"].data_ptr()
+        if isinstance(aux, tuple):
+            kp, pt_a, pt_b, ld_pt = aux
+            row0 = l * 2 * R * ld_pt * 64  # this block's gate rows of the stacked projection (int16 elements)
+            a.kp, a.pt_a, a.pt_b = kp.data_ptr(), pt_a.data_ptr() + 2 * row0, pt_b.data_ptr() + 2 * row0
+            a.ld_pt, a.hop = ld_pt, pl.hop
+        else:
+            a.cp = aux.data_ptr()
+        a.w_os_p, a.b_os, a.skips = L["w_os_p"].data_ptr(), L["b_os"].data_ptr(), skips.data_ptr()
+        if unfused is None:
+            a.xp_out = p_out
+            p_in, p_out = p_out, p_in
+        else:
+            a.z, a.gp, a.o = unfused[0].data_ptr(), p_out, unfused[1].data_ptr()
+        layers.append(a)
+    return layers
+
+
 class CapacitySynth(object):
     """The generator in CAPACITY form: every buffer, index map and grid is sized once for `batch` utterance slots and `frames_cap` mel frames; what is
     live comes from the device (the synthesis pass's frame starts), so `run` derives no host value from the data, allocates nothing and is
@@ -203,9 +287,7 @@ class CapacitySynth(object):
                                 "channels, FCL_PWG_FUSED not 0) and a hop that is a multiple of 128; use synthesize_packed for this generator")
         if not aux_frame_rate(pl) and pl.A <= 64:
             raise _lib.FclError("fcl-taco2_amd: the capacity vocoder from upsampled planes (FCL_PWG_AUX_FRAME_RATE=0) needs more than 64 auxiliary channels")
-        if self.B < 1 or self.B > 1024 or self.frames_cap < 1 or self.frames_cap * pl.hop >= 2 ** 31 - 1:
-            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: 1..1024 utterances and fewer than 2^31 / hop frames expected (got %d, %d)"
-                                % (self.B, self.frames_cap))
+        check_capacity(self.B, self.frames_cap, pl.hop)
         self.ctx = ctx = int(pl.cfg["aux_context_window"])
         self.aux_fr = aux_frame_rate(pl)
         F, R, A, hop = self.frames_cap, pl.R, pl.A, pl.hop
@@ -223,15 +305,10 @@ class CapacitySynth(object):
             self.xp = torch.empty(R // 32, M, 64, dtype=torch.int16, device=dev)  # chunk-major planes; the blocks ping-pong between xp and gp
             self.gp = torch.empty(R // 32, M, 64, dtype=torch.int16, device=dev)
             self.c_pad, self.c_conv = f32(self.pad_cap, A), f32(self.pad_cap, A)
-            C_ = 8 if self.aux_fr else A
-            self._stages, rate = [], 1
-            for i, s_ in enumerate(pl.cfg["upsample_scales"]):
-                rate *= s_
-                last = i == len(pl.up_w) - 1
-                self._stages.append(torch.empty((A + 31) // 32, F * rate, 64, dtype=torch.int16, device=dev) if last and not self.aux_fr else f32(F * rate, C_))
+            self._stages = cascade_outs(pl, F, 8, dev, False) if self.aux_fr else cascade_outs(pl, F, A, dev, True)  # (chunk-major planes)
             if self.aux_fr:
-                g = torch.arange(F, device=dev)
-                self.colour = (g[:, None] % 5 == torch.arange(8, device=dev)[None, :]).to(torch.float32).contiguous()  # the basis of _aux_frame_rate
+                g = torch.arange(F, device=dev)  # (alive until `nbytes` is read below, which has always counted it)
+                self.colour = colour_basis(g)
                 self.kp = ops.planes_empty(M, 32, dev)
                 self.ld_pt = (F + 16 + 31) // 32
                 n = self.ld_pt * 32
@@ -245,40 +322,16 @@ class CapacitySynth(object):
             for t_ in (self.xp, self.gp, self.kp if self.aux_fr else self._stages[-1]):
                 assert t_.data_ptr() % 128 == 0
             self.nbytes = torch.cuda.memory_allocated(dev) - before
-            # the 30 block descriptors: every pointer is static
-            self._layers = []
-            xp, gp = self.xp, self.gp
-            for l, L in enumerate(pl.layers):
-                a = _lib.PwgLayer()
-                a.m, a.r, a.aux, a.ksize, a.dilation, a.first_layer = M, R, A, pl.k, L["dilation"], int(l == 0)
-                a.seg_lo, a.seg_hi = self.maps["seg_lo"].data_ptr(), self.maps["seg_hi"].data_ptr()
-                a.x, a.xp, a.xp_out = None, xp.data_ptr(), gp.data_ptr()
-                a.w_conv_p, a.b_conv, a.w_aux_p = L["w_conv_p"].data_ptr(), L["b_conv"].data_ptr(), L["w_aux_p"].data_ptr()
-                if self.aux_fr:
-                    row0 = l * 2 * R * self.ld_pt * 64
-                    a.kp, a.pt_a, a.pt_b = self.kp.data_ptr(), self.pt_a.data_ptr() + 2 * row0, self.pt_b.data_ptr() + 2 * row0
-                    a.ld_pt, a.hop = self.ld_pt, hop
-                else:
-                    a.cp = self._stages[-1].data_ptr()
-                a.w_os_p, a.b_os, a.skips = L["w_os_p"].data_ptr(), L["b_os"].data_ptr(), self.skips.data_ptr()
-                self._layers.append(a)
-                xp, gp = gp, xp
+            # the block descriptors: every pointer is static
+            self._layers = layer_chain(pl, M, self.maps["seg_lo"].data_ptr(), self.maps["seg_hi"].data_ptr(), self.xp, self.gp, self.skips,
+                                       (self.kp, self.pt_a, self.pt_b, self.ld_pt) if self.aux_fr else self._stages[-1])
             # eager warm-up on an empty batch: the library's one-time setup (dynamic-LDS opt-ins) must not happen inside a capture
             st = i32(1)
             self.run(torch.zeros(1, A, device=dev), i32(self.B + 1), st)
             torch.cuda.current_stream(dev).synchronize()
 
     def _cascade(self, c):
-        pl, lib, mp = self.plan, _lib.load(), self.maps
-        C_, rate = c.shape[1], 1
-        for i, s_ in enumerate(pl.cfg["upsample_scales"]):
-            out = self._stages[i]
-            as_planes = out.dtype == torch.int16
-            _lib.check(lib.fcl_pwg_upsample_stage(c.data_ptr(), mp["frame_utt"].data_ptr(), mp["utt_off"].data_ptr(), self.frames_cap, rate, s_,
-                                                  pl.up_w[i].data_ptr(), None if as_planes else out.data_ptr(), out.data_ptr() if as_planes else None, C_,
-                                                  1, ops._stream()))
-            c, rate = out, rate * s_
-        return c
+        return cascade(self.plan, c, self.maps["frame_utt"], self.maps["utt_off"], self.frames_cap, True, self._stages)
 
     def run(self, mel_rows_cap, utt_frame0_dev, status, seed_dev=None, draw_noise=True):
         """Enqueue the whole generator + the PCM conversion on the current stream.  mel_rows_cap: [rows, aux] float32 device tensor whose first
@@ -287,10 +340,7 @@ class CapacitySynth(object):
         makes this pass generate nothing); seed_dev: optional int32 device word added to the seed (a graph advances it per replay);
         draw_noise=False: `self.z` already holds the noise.  Results: self.pcm (int16) and self.wav (float32), live samples [0, self.live[1])."""
         pl, lib, mp = self.plan, _lib.load(), self.maps
-        if mel_rows_cap.dim() != 2 or mel_rows_cap.shape[1] != pl.A or mel_rows_cap.dtype != torch.float32 or not mel_rows_cap.is_contiguous():
-            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: expected contiguous float32 [rows, %d] mel rows, got %r" % (pl.A, tuple(mel_rows_cap.shape)))
-        if utt_frame0_dev.dtype != torch.int32 or utt_frame0_dev.numel() < self.B + 1 or status.dtype != torch.int32:
-            raise _lib.FclError("fcl-taco2_amd: capacity vocoder: utt_frame0 must hold %d int32 frame starts and status be an int32 word" % (self.B + 1))
+        check_run_args(mel_rows_cap, utt_frame0_dev, status, pl.A, self.B)
         s, live = ops._stream(), self.live.data_ptr()
         chk, F, M = _lib.check, self.frames_cap, self.M
         chk(lib.fcl_pwg_maps_build(utt_frame0_dev.data_ptr(), status.data_ptr(), self.B, F, self.ctx, pl.hop, mp["pad_idx"].data_ptr(), mp["lo"].data_ptr(),
@@ -303,14 +353,7 @@ class CapacitySynth(object):
                                self.pad_cap, cin, cout, k, ops.ACT_NONE, s))
         chk(lib.fcl_gather_rows_fwd(self.c_conv.data_ptr(), mp["keep"].data_ptr(), self.c_in.data_ptr(), None, F, pl.A, s))
         if self.aux_fr:
-            kc = self._cascade(self.colour)
-            chk(lib.fcl_pwg_aux_coeff(kc.data_ptr(), M, pl.hop, F, self.kp.data_ptr(), s))
-            n, rows = self.ld_pt * 32, pl.w_aux_all_p.shape[0]
-            chk(lib.fcl_pack_planes(self.cfull.data_ptr(), self.cfull.stride(0), self.cfull.shape[0], pl.A, self.cfull_p.data_ptr(), s))
-            chk(lib.fcl_linear_planes_fwd(pl.w_aux_all_p.data_ptr(), pl.w_aux_all_p.shape[1] // 64, self.cfull_p[16:].data_ptr(), None, None, n,
-                                          self.pt_a.data_ptr(), rows, n, pl.A, ops.ACT_NONE, s))
-            chk(lib.fcl_linear_planes_fwd(pl.w_aux_all_p.data_ptr(), pl.w_aux_all_p.shape[1] // 64, self.cfull_p.data_ptr(), None, None, n,
-                                          self.pt_b.data_ptr(), rows, n, pl.A, ops.ACT_NONE, s))
+            aux_term(pl, self.colour, mp["frame_utt"], mp["utt_off"], F, True, self._stages, self.kp, self.cfull, self.cfull_p, self.pt_a, self.pt_b)
         else:
             self._cascade(self.c_in)
         if draw_noise:
@@ -324,18 +367,61 @@ class CapacitySynth(object):
         return self.pcm
 
 
-class ParallelWaveGANGenerator(object):
-    """mel -> waveform.  `synthesize(mels)` is the batched entry; `inference(c, x=None)` mirrors the published single-utterance call."""
+class Generator(object):
+    """What the vocoder families share: mel -> waveform.  `synthesize(mels)` is the batched entry, `synthesize_packed` (the family's own) takes
+    utterances already packed row-wise, `inference(c, x=None)` mirrors the published single-utterance call."""
 
     def __init__(self, plan):
         self.plan = plan
-        self._maps_cache = {}
 
-    # ---- integer index maps of a batch shape (host-built once per tuple of utterance lengths, cached) -------------------------------------------
     def samples_of(self, frames):
         """samples of an utterance of `frames` mel frames"""
         return int(frames) * self.plan.hop
 
+    def check_lens(self, lens, ids=None):
+        """a family's own refusal of utterance lengths (none here)"""
+
+    def synthesize(self, mels, noise=None, seed=0, return_intermediates=False, **kw):
+        """mels: list of [T'_i, aux] float tensors / arrays.  noise: optional list of [T'_i * hop] arrays for a family that draws noise (else drawn
+        on the device from `seed`).  Returns a list of float32 device tensors, samples_of(T'_i) samples each ([samples, out] for out > 1)."""
+        dev = self.plan.device
+        with torch.cuda.device(dev):
+            lens = [int(m.shape[0]) for m in mels]
+            mel_rows = torch.cat([torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mels]).contiguous()
+            return self.synthesize_packed(mel_rows, lens, noise, seed, return_intermediates, **kw)
+
+    def inference(self, c, x=None):
+        """c [T', aux] (x: optional noise [T' * hop]) -> waveform [samples, out_channels]."""
+        return self.synthesize([c], None if x is None else [x])[0].reshape(-1, getattr(self.plan, "out_channels", 1))
+
+    def _packed_lens(self, mel_rows, lens, ids=None):
+        """the frame counts as ints, after what every synthesize_packed refuses"""
+        lens = [int(n) for n in lens]
+        if not lens or min(lens) < 1:
+            raise _lib.FclError("fcl-taco2_amd: empty mel")
+        self.check_lens(lens, ids)
+        if mel_rows.dim() != 2 or mel_rows.shape[1] != self.plan.A or mel_rows.shape[0] != sum(lens):
+            raise _lib.FclError("fcl-taco2_amd: expected [%d, %d] mel rows, got %r" % (sum(lens), self.plan.A, tuple(mel_rows.shape)))
+        return lens
+
+    @staticmethod
+    def _results(outs, intermediates, flat, return_intermediates, return_flat):
+        res = (outs,) + ((intermediates,) if return_intermediates else ()) + ((flat,) if return_flat else ())
+        return res[0] if len(res) == 1 else res
+
+
+class ParallelWaveGANGenerator(Generator):
+    """The Parallel WaveGAN generator on a PWGPlan."""
+
+    def __init__(self, plan):
+        Generator.__init__(self, plan)
+        self._maps_cache = {}
+
+    def capacity_synth(self, batch, frames_cap, seed=0):
+        """The capacity form of this generator for `batch` utterance slots and `frames_cap` mel frames (what engine.SpeechRunner captures)."""
+        return CapacitySynth(self, batch, frames_cap, seed=seed)
+
+    # ---- integer index maps of a batch shape (host-built once per tuple of utterance lengths, cached) -------------------------------------------
     def _maps(self, lens):
         key = tuple(lens)
         hit = self._maps_cache.get(key)
@@ -384,59 +470,26 @@ class ParallelWaveGANGenerator(object):
 
     def _cascade(self, c, mp, want_planes, chunk_major=False):
         """The 4 x (stretch + smoothing) stages on c [frames, C] (C % 4 == 0): planes of the result (want_planes) or the fp32 result."""
-        pl, dev = self.plan, self.plan.device
-        C_ = c.shape[1]
         frames = int(mp["offs"][-1])
-        rate, lib = 1, _lib.load()
-        n_st = len(pl.up_w)
-        for i, s in enumerate(pl.cfg["upsample_scales"]):
-            last = i == n_st - 1
-            rows = frames * rate * s
-            as_planes = last and want_planes
-            out = ops.planes_empty(rows, C_, dev) if as_planes else torch.empty(rows, C_, device=dev)
-            _lib.check(lib.fcl_pwg_upsample_stage(c.data_ptr(), mp["frame_utt"].data_ptr(), mp["utt_off"].data_ptr(), frames, rate, s, pl.up_w[i].data_ptr(),
-                                                  None if as_planes else out.data_ptr(), out.data_ptr() if as_planes else None, C_, int(chunk_major),
-                                                  ops._stream()))
-            c, rate = out, rate * s
-        return c
+        return cascade(self.plan, c, mp["frame_utt"], mp["utt_off"], frames, chunk_major, cascade_outs(self.plan, frames, c.shape[1], self.plan.device, want_planes))
 
     def _upsample(self, mel_rows, mp, chunk_major):
         return self._cascade(self._conv_in(mel_rows, mp), mp, True, chunk_major)
 
     def _aux_frame_rate(self, mel_rows, mp):
-        """The auxiliary term of every block at frame rate (fcl_pwg_layer_t.kp): the upsampling network is linear and a sample of frame f sees
-        frames f-2 .. f+2 only, so conv1x1_aux(upsample(c))[m] = sum_g k[m][g] (W_aux c_in[g]).  Returns (coefficient lines [M], planes of W_aux c_in^T
-        for all blocks in the two window alignments, lines per row)."""
+        """The operands of aux_term at the batch's size.  Returns (coefficient lines [M], planes of W_aux c_in^T for all blocks in the two window
+        alignments, lines per row)."""
         pl, dev = self.plan, self.plan.device
-        lib = _lib.load()
         frames = int(mp["offs"][-1])
-        M = frames * pl.hop
-        # k: response of the upsampling network (utterance edges included) to the colour basis e[g][c] = (g mod 5 == c)
-        g = torch.arange(frames, device=dev)
-        e = (g[:, None] % 5 == torch.arange(8, device=dev)[None, :]).to(torch.float32).contiguous()
-        kc = self._cascade(e, mp, False)
-        kp = ops.planes_empty(M, 32, dev)
-        _lib.check(lib.fcl_pwg_aux_coeff(kc.data_ptr(), M, pl.hop, frames, kp.data_ptr(), ops._stream()))
-        # projected features, gate-row major over frames: line q of pt_a = frames [32q, 32q + 32), of pt_b = frames [32q - 16, 32q + 16)
+        e, stages = colour_basis(torch.arange(frames, device=dev)), cascade_outs(pl, frames, 8, dev, False)
+        kp = ops.planes_empty(frames * pl.hop, 32, dev)
         ld_pt = (frames + 16 + 31) // 32
-        n = ld_pt * 32
+        n, rows = ld_pt * 32, pl.w_aux_all_p.shape[0]
         cfull = torch.zeros(16 + n, pl.A, device=dev)
         cfull[16 : 16 + frames] = self._conv_in(mel_rows, mp)
-        cfull_p = ops.pack_planes(cfull)
-        rows = pl.w_aux_all_p.shape[0]
-        pt_a = ops.linear_planes(pl.w_aux_all_p, cfull_p[16:], n, pl.A, want_f32=False, want_planes=True)[1]
-        pt_b = ops.linear_planes(pl.w_aux_all_p, cfull_p, n, pl.A, want_f32=False, want_planes=True)[1]
-        assert pt_a.shape == (rows, ld_pt * 64)
+        cfull_p, pt_a, pt_b = ops.planes_empty(16 + n, pl.A, dev), ops.planes_empty(rows, n, dev), ops.planes_empty(rows, n, dev)
+        aux_term(pl, e, mp["frame_utt"], mp["utt_off"], frames, False, stages, kp, cfull, cfull_p, pt_a, pt_b)
         return kp, pt_a, pt_b, ld_pt
-
-    def synthesize(self, mels, noise=None, seed=0, return_intermediates=False):
-        """mels: list of [T'_i, aux] float tensors / arrays.  noise: optional list of [T'_i * hop] arrays (else drawn on the device from `seed`).
-        Returns a list of [T'_i * hop] float32 device tensors."""
-        dev = self.plan.device
-        with torch.cuda.device(dev):
-            lens = [int(m.shape[0]) for m in mels]
-            mel_rows = torch.cat([torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mels]).contiguous()
-            return self.synthesize_packed(mel_rows, lens, noise, seed, return_intermediates)
 
     def synthesize_packed(self, mel_rows, lens, noise=None, seed=0, return_intermediates=False, return_flat=False):
         """The same on utterances already packed row-wise ([sum T', aux] device tensor, e.g. engine.run's output) with their frame counts.
@@ -444,23 +497,15 @@ class ParallelWaveGANGenerator(object):
         pl, dev = self.plan, self.plan.device
         lib = _lib.load()
         with torch.cuda.device(dev):
-            lens = [int(n) for n in lens]
-            if not lens or min(lens) < 1:
-                raise _lib.FclError("fcl-taco2_amd: empty mel")
-            if mel_rows.dim() != 2 or mel_rows.shape[1] != pl.A or mel_rows.shape[0] != sum(lens):
-                raise _lib.FclError("fcl-taco2_amd: expected [%d, %d] mel rows, got %r" % (sum(lens), pl.A, tuple(mel_rows.shape)))
+            lens = self._packed_lens(mel_rows, lens)
             if sum(lens) * pl.hop >= 2 ** 31:  # before any int32 index map is built or any kernel launched with the overflowing sizes
                 raise _lib.FclError("fcl-taco2_amd: more than 2^31 samples in one vocoder batch")
             mp = self._maps(lens)
             offs = mp["offs"]
             M, R = int(offs[-1]) * pl.hop, pl.R
             fused = fused_block(pl)
-            aux_fr = aux_frame_rate(pl)
-            if aux_fr:
-                cp = None
-                kp, pt_a, pt_b, ld_pt = self._aux_frame_rate(mel_rows, mp)
-            else:
-                cp = self._upsample(mel_rows, mp, fused)  # the one-launch block reads chunk-major planes (contiguous rows per 32-column chunk)
+            # the one-launch block reads chunk-major planes of the upsampled features (contiguous rows per 32-column chunk)
+            aux = self._aux_frame_rate(mel_rows, mp) if aux_frame_rate(pl) else self._upsample(mel_rows, mp, fused)
             if noise is None:
                 z = torch.empty(M, device=dev)
                 _lib.check(lib.fcl_pwg_noise(z.data_ptr(), M, seed & 0xFFFFFFFF, ops._stream()))
@@ -476,27 +521,9 @@ class ParallelWaveGANGenerator(object):
                                               M, R, int(fused), ops._stream()))
             skips = torch.empty(M, R, device=dev)
             gp = ops.planes_empty(M, R, dev)  # unfused: the gate's planes; fused: the second x buffer (blocks ping-pong between xp and gp)
-            zbuf = obuf = None
-            if not fused:
-                zbuf, obuf = torch.empty(M, 2 * R, device=dev), torch.empty(M, 2 * R, device=dev)
+            unfused = None if fused else (torch.empty(M, 2 * R, device=dev), torch.empty(M, 2 * R, device=dev))
             taps = []
-            for l, L in enumerate(pl.layers):
-                a = _lib.PwgLayer()
-                a.m, a.r, a.aux, a.ksize, a.dilation, a.first_layer = M, R, pl.A, pl.k, L["dilation"], int(l == 0)
-                a.seg_lo, a.seg_hi = seg_lo.data_ptr(), seg_hi.data_ptr()
-                a.x, a.xp = None if x is None else x.data_ptr(), xp.data_ptr()
-                a.w_conv_p, a.b_conv, a.w_aux_p = L["w_conv_p"].data_ptr(), L["b_conv"].data_ptr(), L["w_aux_p"].data_ptr()
-                if aux_fr:
-                    row0 = l * 2 * R * ld_pt * 64  # this block's gate rows of the stacked projection (int16 elements)
-                    a.kp, a.pt_a, a.pt_b = kp.data_ptr(), pt_a.data_ptr() + 2 * row0, pt_b.data_ptr() + 2 * row0
-                    a.ld_pt, a.hop = ld_pt, pl.hop
-                else:
-                    a.cp = cp.data_ptr()
-                a.w_os_p, a.b_os, a.skips = L["w_os_p"].data_ptr(), L["b_os"].data_ptr(), skips.data_ptr()
-                if fused:
-                    a.xp_out = gp.data_ptr()
-                else:
-                    a.z, a.gp, a.o = zbuf.data_ptr(), gp.data_ptr(), obuf.data_ptr()
+            for a in layer_chain(pl, M, seg_lo.data_ptr(), seg_hi.data_ptr(), xp, gp, skips, aux, x, unfused):
                 _lib.check(lib.fcl_pwg_layer_fwd(C.byref(a), ops._stream()))
                 if fused:
                     xp, gp = gp, xp
@@ -507,11 +534,4 @@ class ParallelWaveGANGenerator(object):
                                             pl.last_w2.data_ptr(), pl.last_b2, gp.data_ptr(), None if x is None else x.data_ptr(), wav.data_ptr(), M, pl.S,
                                             ops._stream()))
             outs = [wav[int(offs[i]) * pl.hop : int(offs[i + 1]) * pl.hop] for i in range(len(lens))]
-            if return_intermediates:
-                res = (outs, dict(z=z, taps=taps, skips=skips, seg=(seg_lo, seg_hi)))
-                return res + (wav,) if return_flat else res
-            return (outs, wav) if return_flat else outs
-
-    def inference(self, c, x=None):
-        """ParallelWaveGANGenerator.inference(c, x): c [T', aux] (x: optional noise [T' * hop]) -> waveform [T' * hop, 1]."""
-        return self.synthesize([c], None if x is None else [x])[0].reshape(-1, 1)
+            return self._results(outs, dict(z=z, taps=taps, skips=skips, seg=(seg_lo, seg_hi)), wav, return_intermediates, return_flat)

@@ -247,9 +247,8 @@ def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):
                 mels = [feats[i][1] for i in idx]
                 lens = [int(m.shape[0]) for m in mels]
                 packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(mels), dtype=np.float32)).to(dev, non_blocking=True)
-                wavs = gen.synthesize_packed(packed, lens, seed=seed + bi)
+                _, flat = gen.synthesize_packed(packed, lens, seed=seed + bi, return_flat=True)  # the batch's waveforms are views into this one buffer
                 n = sum(samples_of(m) for m in lens)
-                flat = wavs[0]._base if wavs[0]._base is not None else wavs[0]  # the batch's waveforms are views into one buffer
                 j = bi % (depth + 1)
                 if slots[j] is None or slots[j].numel() < n:
                     slots[j] = torch.empty(max(n, 1 << 20), dtype=torch.float32, pin_memory=True)

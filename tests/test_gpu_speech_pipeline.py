@@ -314,13 +314,16 @@ def test_speech_runner_one_graph_text_to_pcm(voc, gen):
 
 
 def test_replay_has_no_host_round_trip():
-    """Review aid kept as a test: SpeechRunner adds no replay() of its own, and BatchRunner.replay / CapacitySynth.run hold no synchronising call."""
+    """Review aid kept as a test: SpeechRunner adds no replay() of its own, and BatchRunner.replay, both CapacitySynth.run and every shared function
+    they enqueue through hold no synchronising call and no allocation (the chain builders allocate for the exact form: __init__ and
+    synthesize_packed call them, run does not)."""
     import inspect
 
-    from fcl_taco2_amd import engine, vocoder
+    from fcl_taco2_amd import engine, hifigan, vocoder
 
     assert engine.SpeechRunner.replay is engine.BatchRunner.replay
-    for fn in (engine.BatchRunner.replay, vocoder.CapacitySynth.run, vocoder.CapacitySynth._cascade, engine.SpeechRunner._vocoder_tail):
+    for fn in (engine.BatchRunner.replay, vocoder.CapacitySynth.run, vocoder.CapacitySynth._cascade, vocoder.check_run_args, vocoder.cascade,
+               vocoder.aux_term, hifigan.CapacitySynth.run, hifigan.enqueue_chain, engine.SpeechRunner._vocoder_tail):
         src = inspect.getsource(fn)
         for word in (".item()", ".cpu()", "synchronize", "torch.empty", "torch.zeros", ".to("):
             assert word not in src, (fn.__name__, word)

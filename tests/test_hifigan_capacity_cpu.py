@@ -299,3 +299,66 @@ def test_vocoder_graph_flag_defaults_off():
     assert tts.parse_args(base).vocoder_graph is False
     assert tts.parse_args(base + ["--vocoder-graph"]).vocoder_graph is True
     assert hifigan.HiFiGANPlan.eager_only is True and hasattr(hifigan.HiFiGANGenerator, "capacity_synth")
+
+
+def test_descriptor_chain_is_one_for_both_forms():
+    """hifigan.build_chain on a stub plan of CPU tensors, once with buffers of every stage's own (synthesize_packed) and once with one shared set
+    (CapacitySynth): the scalars against a table written out here, the pointers against the buffers each launch has to read and write."""
+    import types
+
+    import torch
+
+    from fcl_taco2_amd import hifigan
+
+    t = lambda: torch.empty(8)
+    unit = lambda k, d: dict(k=k, dilation=d, w1p=t(), b1=t(), w2p=t(), b2=t())
+    blocks = lambda: [[unit(3, 1), unit(3, 3)], [unit(5, 1)]]  # a block of two units and a block whose one unit is first and last
+    pl = types.SimpleNamespace(slope=0.1, input=dict(wp=t(), b=t(), k=7, cin=80, cout=512), stages=[
+        dict(s=2, ku=4, cin=512, cout=256, wp=t(), b=t(), blocks=blocks()),  # 256 wide: the workspace tp is needed
+        dict(s=4, ku=8, cin=256, cout=64, wp=t(), b=t(), blocks=blocks())])  # 64 wide: it is not
+    F, fu, uo = 5, 1 << 20, 1 << 21
+    f32 = lambda x: C.c_float(x).value
+    #                 m_in cin  cout stride ksize padding rate_in
+    want_tconv = [(5, 512, 256, 2, 4, 1, 1), (10, 256, 64, 4, 8, 2, 2)]
+    #             m   c    ksize dilation rate first last cs_scale csp_slope
+    want_units = [[(10, 256, 3, 1, 2, 1, 0, 0.5, 0.1), (10, 256, 3, 3, 2, 1, 1, 0.5, 0.1), (10, 256, 5, 1, 2, 0, 1, 0.5, 0.1)],
+                  [(40, 64, 3, 1, 8, 1, 0, 0.5, 0.01), (40, 64, 3, 3, 8, 1, 1, 0.5, 0.01), (40, 64, 5, 1, 8, 0, 1, 0.5, 0.01)]]
+    tconv_fields = ("m_in", "cin", "cout", "stride", "ksize", "padding", "rate_in")
+    unit_fields = ("m", "c", "ksize", "dilation", "rate", "first", "last", "cs_scale", "csp_slope")
+    scalars = []
+    for shared in (False, True):
+        melp, cp0, handed = t(), t(), []
+        one_set = tuple(t() for _ in range(8))
+
+        def rows_of(rows, ch):
+            handed.append(one_set if shared else tuple(t() for _ in range(7)) + ((t(),) if ch not in (32, 64, 128) else (None,)))
+            return handed[-1]
+
+        a, stages, csp, rate = hifigan.build_chain(pl, F, fu, uo, melp, cp0, rows_of)
+        assert (a.m, a.cin, a.cout, a.ksize, a.dilation, a.rate, a.slope) == (5, 80, 512, 7, 1, 1, f32(0.1))
+        assert (a.xp, a.wp, a.bias, a.frame_utt, a.utt_off, a.y, a.yp, a.resid) == (melp.data_ptr(), pl.input["wp"].data_ptr(), pl.input["b"].data_ptr(), fu,
+                                                                                      uo, None, cp0.data_ptr(), None)
+        assert len(stages) == len(handed) == 2 and rate == 8 and csp is handed[-1][6]
+        got, read = [], cp0  # `read`: the planes the next transposed convolution reads
+        for (tc, units), st, bufs, wt, wu in zip(stages, pl.stages, handed, want_tconv, want_units):
+            c, cpl, xb, cs, pa, pb, csp_, tp = [None if b is None else b.data_ptr() for b in bufs]
+            assert tuple(getattr(tc, f) for f in tconv_fields) == wt and tc.slope == f32(0.1)
+            assert (tc.xp, tc.wp, tc.bias, tc.frame_utt, tc.utt_off, tc.y, tc.yp) == (read.data_ptr(), st["wp"].data_ptr(), st["b"].data_ptr(), fu, uo, c, cpl)
+            assert [tuple(getattr(u, f) for f in unit_fields) for u in units] == [w[:7] + (f32(w[7]), f32(w[8])) for w in wu]
+            it = iter(units)
+            for j, blk in enumerate(st["blocks"]):
+                x, xp = c, cpl  # what the transposed convolution wrote; then what the unit before wrote
+                for d, U in enumerate(blk):
+                    u = next(it)
+                    assert (u.x, u.xp) == (x, xp) and (u.frame_utt, u.utt_off, u.slope) == (fu, uo, f32(0.1))
+                    assert (u.w1p, u.b1, u.w2p, u.b2) == tuple(U[k].data_ptr() for k in ("w1p", "b1", "w2p", "b2"))
+                    if d == len(blk) - 1:
+                        assert (u.x_out, u.xp_out, u.cs) == (None, None, cs) and u.csp == (csp_ if j == len(st["blocks"]) - 1 else None)
+                    else:
+                        assert (u.x_out, u.xp_out, u.cs, u.csp) == (xb, pa if d % 2 == 0 else pb, None, None)
+                        x, xp = u.x_out, u.xp_out
+                    assert u.tp == (tp if st["cout"] not in (32, 64, 128) else None) and (u.tp is None) == (st["cout"] == 64)
+            got.append([tuple(getattr(tc, f) for f in tconv_fields)] + [tuple(getattr(u, f) for f in unit_fields) for u in units])
+            read = bufs[6]
+        scalars.append(got)
+    assert scalars[0] == scalars[1]

@@ -260,3 +260,43 @@ def test_capacity_synth_needs_a_device_plan():
     from fcl_taco2_amd import engine
 
     assert issubclass(engine.SpeechRunner, engine.BatchRunner) and callable(V.CapacitySynth)
+
+
+def test_layer_descriptors_are_one_chain_for_every_route():
+    """vocoder.layer_chain on a stub plan of CPU tensors: the frame-rate and the upsampled-planes auxiliary operands of the one-launch block (the
+    capacity form and the exact one build the same list), and the unfused operands only the exact form uses."""
+    import types
+
+    import torch
+
+    from fcl_taco2_amd import vocoder as V
+
+    t = lambda: torch.empty(8)
+    dil = [1, 2, 4, 8]
+    pl = types.SimpleNamespace(R=64, A=80, k=3, hop=256, layers=[dict(dilation=d, w_conv_p=t(), b_conv=t(), w_aux_p=t(), w_os_p=t(), b_os=t()) for d in dil])
+    M, lo, hi, ld_pt = 1280, 1 << 20, 1 << 21, 3
+    xp, gp, skips, kp, pt_a, pt_b, cp, x, z, o = [t() for _ in range(10)]
+    p = lambda b: b.data_ptr()
+
+    def common(layers):
+        assert len(layers) == 4
+        for l, (a, L) in enumerate(zip(layers, pl.layers)):
+            assert (a.m, a.r, a.aux, a.ksize, a.dilation, a.first_layer) == (M, 64, 80, 3, dil[l], int(l == 0))
+            assert (a.seg_lo, a.seg_hi, a.skips) == (lo, hi, p(skips))
+            assert (a.w_conv_p, a.b_conv, a.w_aux_p, a.w_os_p, a.b_os) == tuple(p(L[k]) for k in ("w_conv_p", "b_conv", "w_aux_p", "w_os_p", "b_os"))
+
+    for aux in ((kp, pt_a, pt_b, ld_pt), cp):  # the one-launch block: x lives in planes only and ping-pongs between xp and gp
+        layers = V.layer_chain(pl, M, lo, hi, xp, gp, skips, aux)
+        common(layers)
+        for l, a in enumerate(layers):
+            assert (a.xp, a.xp_out) == ((p(xp), p(gp)) if l % 2 == 0 else (p(gp), p(xp)))
+            assert (a.x, a.z, a.gp, a.o) == (None, None, None, None)
+            if aux is cp:
+                assert (a.cp, a.kp, a.pt_a, a.pt_b, a.ld_pt, a.hop) == (p(cp), None, None, None, 0, 0)
+            else:
+                step = 2 * (l * 2 * 64 * ld_pt * 64)  # bytes: this block's 2R gate rows of ld_pt lines of 64 int16
+                assert (a.cp, a.kp, a.pt_a, a.pt_b, a.ld_pt, a.hop) == (None, p(kp), p(pt_a) + step, p(pt_b) + step, ld_pt, 256)
+    layers = V.layer_chain(pl, M, lo, hi, xp, gp, skips, cp, x, (z, o))  # three launches per block: fp32 x and its planes updated in place
+    common(layers)
+    for a in layers:
+        assert (a.x, a.xp, a.xp_out, a.z, a.gp, a.o, a.cp, a.kp) == (p(x), p(xp), None, p(z), p(gp), p(o), p(cp), None)
