@@ -16,7 +16,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------------------
 // C[n, k] += sum_{m in slice} A[m, n] * B[m + shift, k].  Tile 64(n) x 64(k) per workgroup, M walked in 32-row chunks;

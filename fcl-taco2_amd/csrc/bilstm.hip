@@ -18,7 +18,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 
 // MAPS: the launch carries one more workgroup column (blockIdx.x == B): its first workgroup builds the row / frame maps of the batch
@@ -323,7 +322,6 @@ __global__ __launch_bounds__(4 * H) void bilstm_bptt_persistent_kernel(BilstmBwd
 // matrix), 32 r-slices x 16 k-groups; dh[k] = sum over the 32 r-slices: reduce-scatter over 8 lanes, row_ror:8, and a swizzle across the two rows of
 // the 32-lane group.  The sum lands in the lane that owns unit k's cell backward (lanes j & 31 < 8: 16 per wave, all eight waves), so dh never leaves
 // registers; operands of the coming step are prefetched; the gate-row gradients go to everybody through a double-buffered LDS vector: one barrier per step.
-template <int DUMMY = 0>
 __global__ __launch_bounds__(512) void bilstm_bptt_ksplit_kernel(BilstmBwd a, const int* __restrict__ lens, int T) {
     constexpr int H = 128;
     __shared__ __attribute__((aligned(16))) float dg_s[2][4 * H];
@@ -428,12 +426,11 @@ __device__ __forceinline__ bool group_barrier(const GroupSync& gs, int group, un
     return ok_s != 0;
 }
 
-template <int H, bool SAVE>
+template <bool SAVE>
 __global__ __launch_bounds__(512) void bilstm_group_kernel(const float* __restrict__ gx_f, const float* __restrict__ gx_r, const float* __restrict__ whh_f,
                                                            const float* __restrict__ whh_r, const int* __restrict__ lens, float* __restrict__ out, int T,
                                                            float* __restrict__ hbuf /* [groups][2][H] */, GroupSync gs, BilstmSave sv) {
-    static_assert(H == 256, "4 workgroups x 64 units x 2 K-halves");
-    constexpr int P = H / 64;
+    constexpr int H = 256, P = H / 64;  // 4 workgroups x 64 units x 2 K-halves
     __shared__ __attribute__((aligned(16))) float h_s[H];
     __shared__ float g_s[2][256];
     const int p = blockIdx.x % P, group = blockIdx.x / P;  // group = b * 2 + dir
@@ -495,11 +492,9 @@ __global__ __launch_bounds__(512) void bilstm_group_kernel(const float* __restri
 
 // reverse pass, same grouping: workgroup p does the cell backward of its 64 units, then its 256 gate rows' share of dh = dgates . W_hh for ALL H columns
 // (thread (k, rh): 128 weights W_hh[rows of half rh, k] from the transposed matrix); the P partial vectors are exchanged and summed per unit slice.
-template <int H>
 __global__ __launch_bounds__(512) void bilstm_bptt_group_kernel(BilstmBwd a, const int* __restrict__ lens, int T, float* __restrict__ part /* [groups][2][P][H] */,
                                                                 GroupSync gs) {
-    static_assert(H == 256, "4 workgroups x 64 units");
-    constexpr int P = H / 64;
+    constexpr int H = 256, P = H / 64;  // 4 workgroups x 64 units
     __shared__ __attribute__((aligned(16))) float dg_s[256];  // this workgroup's gate-row gradients, (gate, unit-in-slice) order
     __shared__ float p_s[2][H];
     const int p = blockIdx.x % P, group = blockIdx.x / P;
@@ -842,8 +837,8 @@ bool launch_bilstm_group(const float* gx_f, const float* gx_r, const float* whh_
         return true;
     }
     ProfScope ps(sv ? "bilstm_group_kernel<256>/train" : "bilstm_group_kernel<256>", 2.0 * 2 * B * (double)T * 4 * H * H, (double)B * T, s);
-    if (sv) hipLaunchKernelGGL((bilstm_group_kernel<256, true>), grid, dim3(512), 0, s, gx_f, gx_r, whh_f, whh_r, lens, out, T, hbuf, gs, *sv);
-    else hipLaunchKernelGGL((bilstm_group_kernel<256, false>), grid, dim3(512), 0, s, gx_f, gx_r, whh_f, whh_r, lens, out, T, hbuf, gs, BilstmSave());
+    if (sv) hipLaunchKernelGGL(bilstm_group_kernel<true>, grid, dim3(512), 0, s, gx_f, gx_r, whh_f, whh_r, lens, out, T, hbuf, gs, *sv);
+    else hipLaunchKernelGGL(bilstm_group_kernel<false>, grid, dim3(512), 0, s, gx_f, gx_r, whh_f, whh_r, lens, out, T, hbuf, gs, BilstmSave());
     return true;
 }
 
@@ -861,7 +856,7 @@ bool launch_bilstm_bptt_group(const BilstmBwd& a, const int* lens, int B, int T,
         return true;
     }
     ProfScope ps("bilstm_bptt_group_kernel<256>", 2.0 * 2 * B * (double)T * 4 * H * H, (double)B * T, s);
-    hipLaunchKernelGGL((bilstm_bptt_group_kernel<256>), dim3(2 * B * 4), dim3(512), 0, s, a, lens, T, part, gs);
+    hipLaunchKernelGGL(bilstm_bptt_group_kernel, dim3(2 * B * 4), dim3(512), 0, s, a, lens, T, part, gs);
     return true;
 }
 
@@ -892,9 +887,9 @@ bool launch_bilstm_train_persistent(const float* gx_f, const float* gx_r, const 
 bool launch_bilstm_bptt_persistent(const BilstmBwd& a, const int* lens, int B, int T, int H, hipStream_t s) {
     dim3 grid(B, 2);
     if (H != 8 && H != 16 && H != 32 && H != 64 && H != 128) return false;
-    if (H == 128 && ks_claims_simd(bilstm_bptt_ksplit_kernel<0>, "bilstm_bptt_ksplit_kernel<0>")) {
+    if (H == 128 && ks_claims_simd(bilstm_bptt_ksplit_kernel, "bilstm_bptt_ksplit_kernel")) {
         ProfScope ps("bilstm_bptt_ksplit_kernel", 2.0 * 2 * B * (double)T * 4 * H * H, (double)B * T, s);
-        hipLaunchKernelGGL((bilstm_bptt_ksplit_kernel<0>), grid, dim3(512), 0, s, a, lens, T);
+        hipLaunchKernelGGL(bilstm_bptt_ksplit_kernel, grid, dim3(512), 0, s, a, lens, T);
         return true;
     }
     ProfScope ps("bilstm_bptt_persistent_kernel", 2.0 * 2 * B * (double)T * 4 * H * H, (double)B * T, s);

@@ -14,7 +14,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // acc[t] = A_l[16 x K] . W_t[16 rows x K]^T for NT column tiles that share the A fragments.
 // A_l: LDS, row stride lda_l floats.  wrow[t] = &W[(n_t + r16) * ldw] — ALWAYS a valid row (callers clamp the row
@@ -113,14 +112,22 @@ __device__ __forceinline__ float drop_apply(float v, int mode, const uint8_t* ke
     return v;
 }
 
-__global__ __launch_bounds__(512) void feat_prenet_kernel(const FeatPrenetArgs a) {
-    // rows of this launch: the host's counts, or -- device-driven loop -- the smaller of the host's bounds and the device's live counts
-    // device-driven loops: LOADS and the MFMA chains use the host's row bounds (rows between the device count and the bound hold stale but finite state);
-    // only the STORES are limited to the device's live-row counts -- their scalar loads are then off the kernel's critical path (first use: an epilogue)
-    const int M_feat = a.M_feat, M_pre = a.M_pre;
-    const int Ms_feat = (a.live && a.t_prev >= 0) ? min(a.M_feat, a.live[a.t_prev]) : a.M_feat, Ms_pre = a.live ? min(a.M_pre, a.live[a.t_cur]) : a.M_pre;
+// Row bounds of a feat/prenet launch.  LOADS and the MFMA chains use the host's bounds a.M_feat / a.M_pre; the STORES are limited to Ms_feat / Ms_pre: the
+// host's counts, or -- device-driven loop -- the smaller of the host's bounds and the device's live counts (rows between the two hold stale but finite
+// state; the counts' scalar loads are off the kernel's critical path: first use in an epilogue).  Reports a live count above the host's bound in
+// a.status; false = this workgroup's `rows` rows lie beyond the live rows (uniform per workgroup, before any barrier): the kernel returns at once.
+__device__ __forceinline__ bool feat_prenet_rows(const FeatPrenetArgs& a, int rows, int& Ms_feat, int& Ms_pre) {
+    Ms_feat = (a.live && a.t_prev >= 0) ? min(a.M_feat, a.live[a.t_prev]) : a.M_feat;
+    Ms_pre = a.live ? min(a.M_pre, a.live[a.t_cur]) : a.M_pre;
     if (a.live && a.w0 && blockIdx.x == 0 && threadIdx.x == 0 && a.live[a.t_cur] > a.M_pre) atomicOr(a.status, (unsigned int)FCL_STATUS_ROWS_CAP);
-    if ((int)blockIdx.x * (16) >= (a.h1 ? Ms_feat : Ms_pre)) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier)
+    if ((int)blockIdx.x * rows >= (a.h1 ? Ms_feat : Ms_pre)) return false;
+    return true;
+}
+
+__global__ __launch_bounds__(512) void feat_prenet_kernel(const FeatPrenetArgs a) {
+    const int M_feat = a.M_feat, M_pre = a.M_pre;
+    int Ms_feat, Ms_pre;
+    if (!feat_prenet_rows(a, 16, Ms_feat, Ms_pre)) return;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int ldU = a.U + 4, ldO = a.O + 4, ldP = a.P + 4;
     float* A1 = smem;            // [16, U]  h1 tile
@@ -222,9 +229,6 @@ __global__ __launch_bounds__(512) void feat_prenet_kernel(const FeatPrenetArgs a
 // bf16x3 variants of the two small-tile kernels: activations are split (hi/lo bf16 planes) when they enter LDS,
 // weights arrive pre-split (fcl_split_bf16 at plan time) and stream from L2 straight into 16x16x32 bf16 MFMA fragments:
 // 3 MFMAs of 16 cycles per 32-k step instead of 8 fp32 MFMAs of 32 cycles, same fp32 accumulators and epilogues.
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
 __device__ __forceinline__ void split1(float x, u16& hi, u16& lo) {
     const __bf16 h = (__bf16)x;
     hi = __builtin_bit_cast(u16, h);
@@ -292,8 +296,6 @@ struct WFrag {
                 lo[t][st] = *reinterpret_cast<const s16x8*>(flo[t] + st * 512);
             }
     }
-    // CHECK = false: the LDS rows hold NS * 32 valid (or zero-padded) elements, so no lane needs masking and the loop is branch-free
-    template <bool CHECK = true>
     __device__ __forceinline__ void mma(const u16* Ah, const u16* Al, int ldk, int K, int r16, int kq, f32x4 (&out)[NT]) const {
         f32x4 acc[NT];
 #pragma unroll
@@ -303,7 +305,7 @@ struct WFrag {
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
             s16x8 a_hi = {0, 0, 0, 0, 0, 0, 0, 0}, a_lo = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (!CHECK || st * 32 + kq * 8 < K) {
+            if (st * 32 + kq * 8 < K) {
                 a_hi = *reinterpret_cast<const s16x8*>(ah + st * 32);
                 a_lo = *reinterpret_cast<const s16x8*>(al + st * 32);
             }
@@ -334,20 +336,14 @@ __device__ __forceinline__ void load_rowtile_split(u16* Ah, u16* Al, int ldk, co
     }
 }
 
-// Workgroup barrier for data exchanged through LDS only: LDS accesses retired (lgkmcnt), then s_barrier.  Unlike __syncthreads() it leaves
-// global loads in flight (vmcnt untouched) — the register-resident weight fragments requested ahead of their phase.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// SU/SO/SP = compile-time 32-k step counts of U/O/P (weights preloaded into registers); 0 = generic streaming loops.
-template <int SU, int SO, int SP>
+// The streaming bf16x3 form, for the shapes feat_prenet_split_kernel does not cover: any U / O / P (multiples of 8), every wave walking its column
+// tiles' weight fragments from L2 one 32-k step ahead of the MFMAs (rowtile_mma_x3).
 __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArgs a) {
-    // rows of this launch: the host's counts, or -- device-driven loop -- the smaller of the host's bounds and the device's live counts
-    // device-driven loops: LOADS and the MFMA chains use the host's row bounds (rows between the device count and the bound hold stale but finite state);
-    // only the STORES are limited to the device's live-row counts -- their scalar loads are then off the kernel's critical path (first use: an epilogue)
     const int M_feat = a.M_feat, M_pre = a.M_pre;
+    // feat_prenet_rows, spelled out: through the helper this kernel (alone) compiles to a different schedule
     const int Ms_feat = (a.live && a.t_prev >= 0) ? min(a.M_feat, a.live[a.t_prev]) : a.M_feat, Ms_pre = a.live ? min(a.M_pre, a.live[a.t_cur]) : a.M_pre;
     if (a.live && a.w0 && blockIdx.x == 0 && threadIdx.x == 0 && a.live[a.t_cur] > a.M_pre) atomicOr(a.status, (unsigned int)FCL_STATUS_ROWS_CAP);
-    if ((int)blockIdx.x * (16) >= (a.h1 ? Ms_feat : Ms_pre)) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier)
+    if ((int)blockIdx.x * (16) >= (a.h1 ? Ms_feat : Ms_pre)) return;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int ldU = a.U + 8, ldO = a.O + 8, ldP = a.P + 8;  // bf16 elements per plane row
     u16* A1h = reinterpret_cast<u16*>(smem);
@@ -363,12 +359,8 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
     const unsigned int sbump = a.seed_dev ? *a.seed_dev * 0x9E3779B9u : 0u;
     const unsigned int seed0 = hash_u32(a.seed0 + sbump), seed1 = hash_u32(a.seed1 + sbump);
 
-    constexpr bool PRE = SU > 0;
-    // weight fragments for the prenet layers are requested first thing: they are consumed two barriers later
-    WFrag<2, PRE ? SO : 1> f0;
-    WFrag<2, PRE ? SP : 1> f1;
     const bool has_pre = a.w0 && m0 < M_pre;
-    const int ptile = wave, ptile2 = wave + nwaves;  // P/16 <= 2*nwaves is checked by the launcher for the PRE path
+    const int ptile = wave, ptile2 = wave + nwaves;  // this wave's column tiles in the first pass of the prenet layers' tile loops
     const int nsU = (a.U + 31) >> 5, nsO = (a.O + 31) >> 5, nsP = (a.P + 31) >> 5, ptmax = ((a.P + 15) >> 4) - 1;
     const size_t lane8 = (size_t)lane * 8;
     auto frag = [&](const u16* base, int tile, int ns) { return base + (size_t)tile * ns * 512 + lane8; };
@@ -383,18 +375,8 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
             pb1[tt] = a.b1[nc];
         }
     }
-    if (PRE && has_pre) {
-        const u16* const wh0[2] = {frag(a.w0_hi, ptile, nsO), frag(a.w0_hi, min(ptile2, ptmax), nsO)};
-        const u16* const wl0[2] = {frag(a.w0_lo, ptile, nsO), frag(a.w0_lo, min(ptile2, ptmax), nsO)};
-        f0.load(wh0, wl0);
-    }
     if (a.h1) {
-        WFrag<1, PRE ? SU : 1> ff;
-        if (PRE && wave * 16 < a.O) {
-            const u16* const wh[1] = {frag(a.wf_hi, wave, nsU)};
-            const u16* const wl[1] = {frag(a.wf_lo, wave, nsU)};
-            ff.load(wh, wl);
-        }
+        f32x4 accv[1];
         load_rowtile_split(A1h, A1l, ldU, a.h1, a.U, a.U, m0, M_feat);
         __syncthreads();
         if (a.dbg_phase == 1) return;
@@ -410,9 +392,7 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
                 f0v[r] = a.F0[(size_t)mc * a.O + ncc];
                 fo[r] = a.frame_off[mc];
             }
-            f32x4 accv[1];
-            if (PRE) ff.mma(A1h, A1l, ldU, a.U, r16, kq, accv);
-            else rowtile_mma_x3<1>(A1h, A1l, ldU, wh, wl, a.U, r16, kq, accv);
+            rowtile_mma_x3<1>(A1h, A1l, ldU, wh, wl, a.U, r16, kq, accv);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = rq * 4 + r, m = m0 + row;
@@ -436,12 +416,7 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
         for (int i = threadIdx.x; i < 16 * ldO; i += blockDim.x) { A2h[i] = 0; A2l[i] = 0; }  // prev_out = 0 at t = 0
     }
     if (!has_pre || a.dbg_phase == 2) return;
-    if (PRE) {  // layer-1 fragments: in flight while layer 0 computes
-        const u16* const wh1[2] = {frag(a.w1_hi, ptile, nsP), frag(a.w1_hi, min(ptile2, ptmax), nsP)};
-        const u16* const wl1[2] = {frag(a.w1_lo, ptile, nsP), frag(a.w1_lo, min(ptile2, ptmax), nsP)};
-        f1.load(wh1, wl1);
-    }
-    lds_barrier();  // NOT __syncthreads(): its vmcnt(0) would park every wave until the 32 fragment loads just issued have landed
+    lds_barrier();  // NOT __syncthreads(): its vmcnt(0) would wait for the prefetched biases, which nothing needs before an epilogue
     if (a.teacher_in) {
         load_rowtile_split(A2h, A2l, ldO, a.teacher_in, a.teacher_ld, a.O, m0, M_pre);
         __syncthreads();
@@ -451,8 +426,7 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
         const u16* const wh[2] = {frag(a.w0_hi, tile, nsO), frag(a.w0_hi, min(tile2, ptmax), nsO)};
         const u16* const wl[2] = {frag(a.w0_lo, tile, nsO), frag(a.w0_lo, min(tile2, ptmax), nsO)};
         f32x4 accv[2];
-        if (PRE) f0.mma(A2h, A2l, ldO, a.O, r16, kq, accv);
-        else rowtile_mma_x3<2>(A2h, A2l, ldO, wh, wl, a.O, r16, kq, accv);
+        rowtile_mma_x3<2>(A2h, A2l, ldO, wh, wl, a.O, r16, kq, accv);
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             const int nc = (tt ? tile2 : tile) * 16 + col;
@@ -475,8 +449,7 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
         const u16* const wh[2] = {frag(a.w1_hi, tile, nsP), frag(a.w1_hi, min(tile2, ptmax), nsP)};
         const u16* const wl[2] = {frag(a.w1_lo, tile, nsP), frag(a.w1_lo, min(tile2, ptmax), nsP)};
         f32x4 accv[2];
-        if (PRE) f1.mma(A3h, A3l, ldP, a.P, r16, kq, accv);
-        else rowtile_mma_x3<2>(A3h, A3l, ldP, wh, wl, a.P, r16, kq, accv);
+        rowtile_mma_x3<2>(A3h, A3l, ldP, wh, wl, a.P, r16, kq, accv);
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             const int nc = (tt ? tile2 : tile) * 16 + col;
@@ -497,20 +470,15 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
     }
 }
 
-// ---- round 4: the same chain with TRANSPOSED accumulators and (optionally) prenet layer 1's columns split over NS workgroups per row tile.
-// Where the round-3 kernel's (feat_prenet_fast_kernel, deleted in round 5) 14 us went (r4 phase stamps, 2 400 rows: launch floor 3.6, feat_out +2.5..3.4, layer 0 +3.0..3.5, layer 1 +3.6..3.9):
-// not into the weight stream alone -- a first column-split form that only cut the fragments per workgroup from 442 to 245 KB ran exactly as long --
-// but into the per-ELEMENT epilogues.  With the activations as the MFMA's A operand a lane ends up with ONE column of FOUR rows: every finished
-// element then costs its own bias / mask load, its own counter hash, its own fp32 -> (hi, lo) split, two 2-byte LDS stores and up to five scattered
-// 2- / 4-byte global stores with 64-bit address arithmetic: ~30 VALU + ~5 memory instructions per element, 16 - 32 elements per lane and phase, two
-// waves per SIMD.  Swapping the operands (weights as A, activations as B: the same fragments, the same products in the same order, D^T instead of D)
-// gives a lane FOUR CONSECUTIVE COLUMNS of ONE row: one float4 bias / F0 load, one 4-byte mask load, two hashes (16 bits per decision), one packed
-// split (v_cvt_pk_bf16_f32), two 8-byte LDS stores = the next layer's operand, and 8- / 16-byte global stores (the P32 line's hi and lo halves,
-// the fp32 frame) -- about a quarter of the instructions.
-// Column split NS (gridDim.y): a workgroup owns 16 RT rows x 256 / NS columns of layer 1 and recomputes feat_out and layer 0 for its rows (61 k of
-// the 127 k weights): 82 + 98 + 262 / NS KB of fragments per workgroup, NS x the workgroups; split 0 alone stores feat_out.  NS = 1: no split.
-// The layer-1 operand tile re-uses the h1 tile's LDS (96 KB at RT = 4).  All fragments are requested at entry (layer 1's once the h1 staging
-// registers are free); no __syncthreads (its vmcnt(0) would wait for every fragment before the first phase).
+// ---- the same chain for the student's shape (U = P = 256, 64 < O <= 96) with every weight fragment register-resident and TRANSPOSED accumulators.
+// With the activations as the MFMA's A operand a lane ends up with ONE column of FOUR rows, and every finished element costs its own bias / mask
+// load, counter hash, fp32 -> (hi, lo) split, two 2-byte LDS stores and up to five scattered global stores.  Swapping the operands (weights as A,
+// activations as B: the same fragments, the same products in the same order, D^T instead of D) gives a lane FOUR CONSECUTIVE COLUMNS of ONE row: one
+// float4 bias / F0 load, one 4-byte mask load, two hashes (16 bits per decision), one packed split, two 8-byte LDS stores = the next layer's
+// operand, and 8- / 16-byte global stores -- about a quarter of the instructions.
+// A workgroup owns RT row tiles of 16 rows and all 256 columns (82 + 98 + 262 KB of fragments).  The layer-1 operand tile re-uses the h1 tile's LDS
+// (96 KB at RT = 4).  The h1 rows, then feat_out's and layer 0's fragments are requested at entry, layer 1's once feat_out's registers are free; no
+// __syncthreads (its vmcnt(0) would wait for every fragment before the first phase).
 // RNG mode draws a different (equally distributed) stream than the other feat/prenet kernels: 16 bits of a counter hash per decision instead of 24.
 __device__ __forceinline__ void p32_store4(unsigned short* __restrict__ p, int ld, long long m, int n, uint2 hi, uint2 lo) {
     unsigned short* line = p + ((size_t)m * ld + (n >> 5)) * 64 + (n & 31);
@@ -540,13 +508,12 @@ __device__ __forceinline__ void mma_t(const WFrag<NT, NS_>& w, const u16* Ah, co
     for (int t = 0; t < NT; ++t) out[t] = acc[t];
 }
 
-template <int DROP, int RT, int NS>
+template <int DROP, int RT>
 __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenetArgs a) {
-    constexpr int SU = 8, SO = 3, SP = 8, U = 256, OP = 96, P = 256, CT = 16 / NS, NW1 = CT < 8 ? CT : 8, T1 = CT / NW1;
-    static_assert(NS == 1 || NS == 2 || NS == 4 || NS == 8, "layer-1 column split");
+    constexpr int SU = 8, SO = 3, SP = 8, U = 256, OP = 96, P = 256;
     const int M_feat = a.M_feat, M_pre = a.M_pre;
     const int Ms_feat = (a.live && a.t_prev >= 0) ? min(a.M_feat, a.live[a.t_prev]) : a.M_feat, Ms_pre = a.live ? min(a.M_pre, a.live[a.t_cur]) : a.M_pre;
-    const int split = blockIdx.y;
+    const int split = blockIdx.y;  // 0: the grid is one workgroup deep (the tests on it are what is left of a column split of layer 1 over gridDim.y)
     if (a.live && a.w0 && blockIdx.x == 0 && split == 0 && threadIdx.x == 0 && a.live[a.t_cur] > a.M_pre) atomicOr(a.status, (unsigned int)FCL_STATUS_ROWS_CAP);
     if ((int)blockIdx.x * (16 * RT) >= (a.h1 ? Ms_feat : Ms_pre)) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier)
     constexpr int ldU = U + 16, ldO = OP + 16, ldP = P + 16, ROWS = 16 * RT;
@@ -564,13 +531,12 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
     const int r16 = lane & 15, kq = lane >> 4;   // operand fragments: row / column r16, k-group kq
     const int arow = lane & 15, cq = lane >> 4;  // transposed accumulators: activation row arow, columns cq * 4 .. cq * 4 + 3 of the column tile
     const bool has_feat = a.h1 != nullptr, has_pre = a.w0 != nullptr && m0 < M_pre;
-    if (!has_pre && split != 0) return;  // feat-only launch (after the last step): one workgroup per row tile does it
+    if (!has_pre && split != 0) return;
     const bool feat_wave = has_feat && wave * 16 < O;
-    const bool l1_wave = has_pre && wave >= 8 - NW1;
     const size_t lane8 = (size_t)lane * 8;
     auto frag = [&](const u16* base, int tile, int ns) { return base + (size_t)tile * ns * 512 + lane8; };
-    const int t0 = wave, t1 = wave + 8;                   // this wave's layer-0 column tiles
-    const int c1 = split * CT + (wave - (8 - NW1)) * T1;  // first of this wave's T1 layer-1 column tiles (l1_wave only)
+    const int t0 = wave, t1 = wave + 8;  // this wave's layer-0 column tiles
+    const int c1 = split * 16 + wave * 2;  // first of this wave's two layer-1 column tiles
 
     // ---- phase 0 operands first (loads return in order: the first wait then covers the h1 rows alone) ---------------------------------------
     constexpr int HV = RT * 2;  // float4 loads of h1 per thread: ROWS x 64 float4 over 512 threads
@@ -590,7 +556,7 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
     // ---- weight fragments and epilogue operands of phases 1 and 2, requested now ------------------------------------------------------------------
     WFrag<1, SU> ff;
     WFrag<2, SO> f0;
-    WFrag<T1, SP> f1;
+    WFrag<2, SP> f1;
     const int fnc = wave * 16 + cq * 4;  // feat_out columns fnc .. fnc + 3 of this lane (whole groups of four: O % 4 == 0)
     f32x4 f0v[RT];
     int fo[RT];
@@ -616,8 +582,8 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         seed0 = hash_u32(a.seed0 + sbump);
         seed1 = hash_u32(a.seed1 + sbump);
     }
-    f32x4 pb0[2], pb1[T1];
-    unsigned int k0[RT][2], k1[RT][T1];
+    f32x4 pb0[2], pb1[2];
+    unsigned int k0[RT][2], k1[RT][2];
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) pb0[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (has_feat) asm volatile("s_barrier" ::: "memory");  // (feat_out's fragments are queued before anybody's layer-0 fragments)
@@ -650,22 +616,21 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             *reinterpret_cast<uint2*>(A1l + r * ldU + c) = l;
         }
     }
-    // layer-1 fragments: requested once the h1 staging registers are free (they are consumed last; the stream behind feat_out / layer 0 is
-    // unbroken) -- NS = 1 (all 16 column tiles: 128 VGPRs of fragments): once feat_out's fragments are dead too, i.e. after phase 1
+    // layer-1 fragments (all 16 column tiles: 128 VGPRs) and epilogue operands: requested after phase 1, once feat_out's fragments are dead
 #pragma unroll
-    for (int tt = 0; tt < T1; ++tt) pb1[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int tt = 0; tt < 2; ++tt) pb1[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto request_l1 = [&]() {
-        if (l1_wave) {
-            const u16* wh1[T1];
-            const u16* wl1[T1];
+        if (has_pre) {
+            const u16* wh1[2];
+            const u16* wl1[2];
 #pragma unroll
-            for (int tt = 0; tt < T1; ++tt) {
+            for (int tt = 0; tt < 2; ++tt) {
                 wh1[tt] = frag(a.w1_hi, c1 + tt, SP);
                 wl1[tt] = frag(a.w1_lo, c1 + tt, SP);
             }
             f1.load(wh1, wl1);
 #pragma unroll
-            for (int tt = 0; tt < T1; ++tt) {
+            for (int tt = 0; tt < 2; ++tt) {
                 const int nc = (c1 + tt) * 16 + cq * 4;
                 pb1[tt] = *reinterpret_cast<const f32x4*>(a.b1 + nc);
                 if (DROP == 1) {
@@ -675,13 +640,9 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             }
         }
     };
-    if (NS > 1) {
-        asm volatile("s_barrier" ::: "memory");  // (layer 0's fragments are queued before anybody's layer-1 fragments)
-        request_l1();
-    }
     lds_barrier();
     if (a.dbg_phase == 1) return;
-    // ---- phase 1: H8 feat_out of the previous step (+ H10 scatter by split 0) -----------------------------------------------------------------
+    // ---- phase 1: H8 feat_out of the previous step (+ H10 scatter) ---------------------------------------------------------------------------
     if (feat_wave) {
 #pragma unroll
         for (int q = 0; q < RT; ++q) {
@@ -720,14 +681,14 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         }
     }
     if (!has_pre || a.dbg_phase == 2) return;
-    if (NS == 1) request_l1();
+    request_l1();
     lds_barrier();
     if (a.teacher_in) {  // teacher forcing: prenet input is y_{t-1}, not the decoder's own output
 #pragma unroll
         for (int q = 0; q < RT; ++q) load_rowtile_split(A2h + q * 16 * ldO, A2l + q * 16 * ldO, ldO, a.teacher_in, a.teacher_ld, O, m0 + q * 16, M_pre);
         lds_barrier();
     }
-    // ---- phase 2: H6 prenet layer 0 (all 256 columns; recomputed by every column split) ----------------------------------------------------------
+    // ---- phase 2: H6 prenet layer 0 -> LDS (over the h1 tile) ----------------------------------------------------------------------------------
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
         f32x4 accv[2];
@@ -747,16 +708,16 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         }
     }
     lds_barrier();
-    if (a.dbg_phase == 3 || !l1_wave) return;
-    // ---- phase 3: H6 prenet layer 1, this split's columns -> global (+ KD tap, + P32 planes) --------------------------------------------------
+    if (a.dbg_phase == 3) return;
+    // ---- phase 3: H6 prenet layer 1 -> global (+ KD tap, + P32 planes) --------------------------------------------------------------------------
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
-        f32x4 accv[T1];
-        mma_t<T1, SP>(f1, A3h + q * 16 * ldP, A3l + q * 16 * ldP, ldP, r16, kq, accv);
+        f32x4 accv[2];
+        mma_t<2, SP>(f1, A3h + q * 16 * ldP, A3l + q * 16 * ldP, ldP, r16, kq, accv);
         const int m = m0 + q * 16 + arow;
         if (m >= Ms_pre) continue;
 #pragma unroll
-        for (int tt = 0; tt < T1; ++tt) {
+        for (int tt = 0; tt < 2; ++tt) {
             const int nc = (c1 + tt) * 16 + cq * 4;
             f32x4 v = accv[tt] + pb1[tt];
 #pragma unroll
@@ -775,7 +736,7 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
 
 
 // The same launch in EXACT fp32 (FCL_PRECISION=0; round 4): v_mfma_f32_16x16x4_f32 on fragment-major fp32 weights (fcl_pack_frag_f32), one row tile per
-// workgroup, no column split.  Same structure as feat_prenet_split_kernel -- every weight fragment register-resident (a lane's two float4 per tile and
+// workgroup.  Same structure as feat_prenet_split_kernel -- every weight fragment register-resident (a lane's two float4 per tile and
 // 32-k step are exactly the bytes of its hi + lo pair), transposed accumulators (the weight fragment is the MFMA's A operand), vector epilogues,
 // three phases chained through LDS -- with fp32 tiles in LDS instead of split planes.  Replaces feat_prenet_kernel (weights re-streamed from L2 at
 // every k-step: 19.2 us per launch at 2 400 rows, the largest item of the exact-mode pass) where the shape is covered.
@@ -819,9 +780,8 @@ template <int DROP>
 __global__ __launch_bounds__(512) void feat_prenet_split_f32_kernel(const FeatPrenetArgs a) {
     constexpr int SU = 8, SO = 3, SP = 8, U = 256, OP = 96, P = 256;
     const int M_feat = a.M_feat, M_pre = a.M_pre;
-    const int Ms_feat = (a.live && a.t_prev >= 0) ? min(a.M_feat, a.live[a.t_prev]) : a.M_feat, Ms_pre = a.live ? min(a.M_pre, a.live[a.t_cur]) : a.M_pre;
-    if (a.live && a.w0 && blockIdx.x == 0 && threadIdx.x == 0 && a.live[a.t_cur] > a.M_pre) atomicOr(a.status, (unsigned int)FCL_STATUS_ROWS_CAP);
-    if ((int)blockIdx.x * 16 >= (a.h1 ? Ms_feat : Ms_pre)) return;
+    int Ms_feat, Ms_pre;
+    if (!feat_prenet_rows(a, 16, Ms_feat, Ms_pre)) return;
     constexpr int ldU = U + 8, ldO = OP + 8, ldP = P + 8;  // floats: rows 32 bytes apart modulo the 256-byte bank period, as the plane tiles are
     static_assert(ldU == ldP, "the layer-1 operand tile re-uses the h1 tile's LDS");
     extern __shared__ __attribute__((aligned(16))) float fpf_lds[];
@@ -959,6 +919,26 @@ __global__ __launch_bounds__(512) void feat_prenet_split_f32_kernel(const FeatPr
     }
 }
 
+// Tail of the small LSTM steps with prefetched cell operands: wave g's accumulators (gate g of the tile's 16 rows x 16 units) go to LDS, then thread
+// (row, unit) of the workgroup collects its four gate pre-activations and runs the cell.  units_in_lane: the accumulator layout -- false: four rows
+// (hi * 4 ..) of unit lo, the activations being the MFMA's A operand (x3 form); true: four units (hi * 4 ..) of row lo, the weight fragment being the
+// A operand (ff form).  valid: the thread's (m, u) exists; rows from Ms on are beyond the live rows and not stored.
+__device__ __forceinline__ void gates_to_cell(const LstmStepArgs& a, int g, int lane, const f32x4& acc, bool units_in_lane, int m, int u, bool valid, int Ms,
+                                              const CellIn& ci) {
+    __shared__ float g_l[4][16][17];
+    const int lo = lane & 15, hi = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (units_in_lane) g_l[g][lo][hi * 4 + i] = acc[i];
+        else g_l[g][hi * 4 + i][lo] = acc[i];
+    }
+    __syncthreads();
+    if (!valid || m >= Ms) return;
+    const int row = threadIdx.x >> 4, uc = threadIdx.x & 15;
+    const float pre[4] = {g_l[0][row][uc], g_l[1][row][uc], g_l[2][row][uc], g_l[3][row][uc]};
+    cell_finish(a, m, u, pre, ci);
+}
+
 // PRE: every term has K = 256 (the student's decoder LSTMs: two terms, or the input term alone in the zero-state form of step 0) -> all weight
 // fragments are requested at kernel entry.
 template <bool PRE>
@@ -970,7 +950,6 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
     constexpr int KC = 512;
     __shared__ __attribute__((aligned(16))) u16 A_h[16 * (KC + 16)];  // row stride = 2 (mod 4) sixteen-byte slots: conflict-free fragment reads
     __shared__ __attribute__((aligned(16))) u16 A_lo[16 * (KC + 16)];
-    __shared__ float g_l[4][16][17];
     const int m0 = blockIdx.y * 16, u0 = blockIdx.x * 16;
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int r16 = lane & 15, kq = lane >> 4;
@@ -1018,15 +997,7 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
             acc += part[0];
         }
     }
-    {
-        const int col = lane & 15, rq = lane >> 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) g_l[g][rq * 4 + r][col] = acc[r];
-    }
-    __syncthreads();
-    if (!evalid || em >= Ms) return;
-    const float pre[4] = {g_l[0][erow][euc], g_l[1][erow][euc], g_l[2][erow][euc], g_l[3][erow][euc]};
-    cell_finish(a, em, eu, pre, ci);
+    gates_to_cell(a, g, lane, acc, false, em, eu, evalid, Ms, ci);
 }
 
 
@@ -1038,7 +1009,6 @@ __global__ __launch_bounds__(256) void lstm_small_ff_kernel(const LstmStepArgs a
     if ((int)blockIdx.y * 16 >= Ms) return;
     constexpr int LD = 256 + 8;
     __shared__ __attribute__((aligned(16))) float A_f[16 * LD];
-    __shared__ float g_l[4][16][17];
     const int m0 = blockIdx.y * 16, u0 = blockIdx.x * 16;
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int r16 = lane & 15, kq = lane >> 4;
@@ -1066,15 +1036,7 @@ __global__ __launch_bounds__(256) void lstm_small_ff_kernel(const LstmStepArgs a
         mma_tf<1, 8>(wf[t], A_f, LD, r16, kq, part);
         acc += part[0];
     }
-    {
-        const int arow = lane & 15, cq = lane >> 4;  // accumulators: row arow, units cq * 4 .. + 3 of the tile
-#pragma unroll
-        for (int i = 0; i < 4; ++i) g_l[g][arow][cq * 4 + i] = acc[i];
-    }
-    __syncthreads();
-    if (!evalid || em >= Ms) return;
-    const float pre[4] = {g_l[0][erow][euc], g_l[1][erow][euc], g_l[2][erow][euc], g_l[3][erow][euc]};
-    cell_finish(a, em, eu, pre, ci);
+    gates_to_cell(a, g, lane, acc, true, em, eu, evalid, Ms, ci);
 }
 
 // ---- small-M LSTM step: wave g owns gate g of 16 units x 16 rows ------------------------------------
@@ -1111,7 +1073,7 @@ __device__ __forceinline__ void lstm_small_body(const LstmStepArgs& a) {
         for (int r = 0; r < 4; ++r) g_l[g][rq * 4 + r][col] = acc[r];
     }
     __syncthreads();
-    // cell epilogue: thread -> (row, unit)
+    // cell epilogue: thread -> (row, unit); the cell operands are fetched HERE, for the live cells only (not gates_to_cell's prefetched form)
     const int row = threadIdx.x >> 4, uc = threadIdx.x & 15;
     const int m = m0 + row, uu = u0 + uc;
     if (m >= Ms || uu >= a.U) return;
@@ -1130,8 +1092,7 @@ __global__ __launch_bounds__(256) void lstm_small_pair_kernel(const LstmStepArgs
 }
 
 int launch_lstm_small(const LstmStepArgs& a, hipStream_t s) {
-    double ksum = 0;
-    for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
+    const double fl = lstm_step_flops(a);
     dim3 grid((a.U + 15) / 16, (a.M + 15) / 16);
     bool planes = true;
     for (int i = 0; i < a.nterms; ++i) planes = planes && a.term[i].Whi && a.term[i].Wlo && (a.term[i].K & 7) == 0 && a.term[i].ldw == a.term[i].K;
@@ -1143,26 +1104,21 @@ int launch_lstm_small(const LstmStepArgs& a, hipStream_t s) {
         ff = ff && a.term[i].Wff != nullptr;
     }
     if (planes) {
-        ProfScope ps("lstm_small_kernel/bf16x3", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
+        ProfScope ps("lstm_small_kernel/bf16x3", fl, a.M, s);
         if (pre256) hipLaunchKernelGGL(lstm_small_x3_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(lstm_small_x3_kernel<false>, grid, dim3(256), 0, s, a);
     } else if (pre256 && ff && (a.U & 15) == 0) {
-        ProfScope ps("lstm_small_ff_kernel/f32", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
+        ProfScope ps("lstm_small_ff_kernel/f32", fl, a.M, s);
         hipLaunchKernelGGL(lstm_small_ff_kernel, grid, dim3(256), 0, s, a);
     } else {
-        ProfScope ps("lstm_small_kernel", 2.0 * a.M * 4.0 * a.U * ksum, a.M, s);
+        ProfScope ps("lstm_small_kernel", fl, a.M, s);
         hipLaunchKernelGGL(lstm_small_kernel, grid, dim3(256), 0, s, a);
     }
     return check_hip(hipGetLastError(), "lstm_small launch");
 }
 
 int launch_lstm_small_pair(const LstmStepArgs& a0, const LstmStepArgs& a1, hipStream_t s) {
-    double fl = 0;
-    for (const LstmStepArgs* a : {&a0, &a1}) {
-        double ksum = 0;
-        for (int i = 0; i < a->nterms; ++i) ksum += a->term[i].K;
-        fl += 2.0 * a->M * 4.0 * a->U * ksum;
-    }
+    const double fl = lstm_step_flops(a0) + lstm_step_flops(a1);
     const int mmax = a0.M > a1.M ? a0.M : a1.M;  // (tiles beyond a problem's own rows exit at once)
     dim3 grid((a0.U + 15) / 16, (mmax + 15) / 16, 2);
     ProfScope ps("lstm_small_pair_kernel", fl, a0.M + a1.M, s);
@@ -1182,25 +1138,25 @@ int launch_lstm_small_pair_any(const LstmStepArgs& a0, const LstmStepArgs& a1, h
     return launch_lstm_small_pair(a0, a1, s);
 }
 
-// round 4: feat_prenet_split_kernel (transposed accumulators: vectorised epilogues; optional column split of layer 1).  Measured on one box, 2 400 live
-// rows, rocprofv3 durations: the round-3 kernel (RT = 2) 14.1 us; this one at (NS, RT) = (1, 1) 9.5, (1, 2) 11.9, (2, 2) 10.2, (2, 1) 9.6, (4, 1) 17
-// (600 workgroups x 245 KB: the L2 -> CU traffic of a launch, not the per-workgroup stream, is what a split costs).  The 4-stream bench line does not move
-// with any of them (44.5 - 45.7 M frames/s for all, same box): with four passes in flight the pass is bound by the sum of workgroup-time, which RT = 1
-// doubles while it halves the latency.  Launched with no split (NS = 1) and one row tile per workgroup (lowest single-pass latency: 339 -> 269 us of a
-// 1.38 ms eager pass) below 4 096 rows, two above.
+// One of a kernel's three dropout forms (FCL_DROP_*: none, mask, rng), opted in for `lds` bytes of dynamic LDS and launched on 512 threads.
+static int launch_fp_drop(const void* const (&fn)[3], int drop_mode, dim3 grid, size_t lds, const FeatPrenetArgs& a, hipStream_t s) {
+    const void* f = fn[drop_mode == 1 || drop_mode == 2 ? drop_mode : 0];
+    const int rc = ensure_dyn_lds(f, (int)lds);
+    if (rc) return rc;
+    void* args[] = {const_cast<FeatPrenetArgs*>(&a)};
+    return check_hip(hipLaunchKernel(f, grid, dim3(512), args, lds, s), "feat_prenet launch");
+}
+
+// feat_prenet_split_kernel with RT row tiles per workgroup.  Measured on one box, 2 400 live rows, rocprofv3 durations: the kernel it replaced (RT = 2)
+// 14.1 us; this one at RT = 1 9.5, at RT = 2 11.9.  The 4-stream bench line does not move with either (44.5 - 45.7 M frames/s, same box): with four
+// passes in flight the pass is bound by the sum of workgroup-time, which RT = 1 doubles while it halves the latency.  Launched with one row tile per
+// workgroup (lowest single-pass latency: 339 -> 269 us of a 1.38 ms eager pass) below 4 096 rows, two above.
 template <int RT>
 static int launch_feat_prenet_split(const FeatPrenetArgs& a, int rows, hipStream_t s) {
     constexpr size_t lds_s = 2 * sizeof(unsigned short) * 16 * RT * ((256 + 16) + (96 + 16));
-    const dim3 g((rows + 16 * RT - 1) / (16 * RT), 1), b(512);
-    const void* fn = a.drop_mode == 1   ? reinterpret_cast<const void*>(feat_prenet_split_kernel<1, RT, 1>)
-                     : a.drop_mode == 2 ? reinterpret_cast<const void*>(feat_prenet_split_kernel<2, RT, 1>)
-                                        : reinterpret_cast<const void*>(feat_prenet_split_kernel<0, RT, 1>);
-    const int rc = ensure_dyn_lds(fn, (int)lds_s);
-    if (rc) return rc;
-    if (a.drop_mode == 1) hipLaunchKernelGGL((feat_prenet_split_kernel<1, RT, 1>), g, b, lds_s, s, a);
-    else if (a.drop_mode == 2) hipLaunchKernelGGL((feat_prenet_split_kernel<2, RT, 1>), g, b, lds_s, s, a);
-    else hipLaunchKernelGGL((feat_prenet_split_kernel<0, RT, 1>), g, b, lds_s, s, a);
-    return 0;
+    static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_split_kernel<0, RT>), reinterpret_cast<const void*>(feat_prenet_split_kernel<1, RT>),
+                                      reinterpret_cast<const void*>(feat_prenet_split_kernel<2, RT>)};
+    return launch_fp_drop(fn, a.drop_mode, dim3((rows + 16 * RT - 1) / (16 * RT), 1), lds_s, a, s);
 }
 
 int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
@@ -1225,7 +1181,7 @@ int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
     if (planes) {
         const size_t lds3 = 2 * sizeof(unsigned short) * 16 * ((size_t)(a.U + 8) + (a.O + 8) + (a.P + 8));
         {
-            const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(feat_prenet_x3_kernel<0, 0, 0>), 160 * 1024);
+            const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(feat_prenet_x3_kernel), 160 * 1024);
             if (rc) return rc;
         }
         ProfScope ps("feat_prenet_kernel/bf16x3", fl, rows, s);
@@ -1233,22 +1189,17 @@ int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
             const int rc = rows >= 4096 ? launch_feat_prenet_split<2>(a, rows, s) : launch_feat_prenet_split<1>(a, rows, s);
             if (rc) return rc;
         } else {
-            hipLaunchKernelGGL((feat_prenet_x3_kernel<0, 0, 0>), dim3((rows + 15) / 16), dim3(512), lds3, s, a);
+            hipLaunchKernelGGL(feat_prenet_x3_kernel, dim3((rows + 15) / 16), dim3(512), lds3, s, a);
         }
     } else if (a.wf_ff && a.w0_ff && a.w1_ff && a.U == 256 && a.P == 256 && a.O > 64 && a.O <= 96 && !a.teacher_in && !a.pre_out_p && !a.before_p &&
                (!a.w0 || a.pre_out)) {
         // exact-fp32 mode with fragment-major fp32 weights: the register-resident form (19.2 -> ~9 us per launch at 2 400 rows)
         ProfScope ps("feat_prenet_split_kernel/f32", fl, rows, s);
         constexpr size_t lds_f = sizeof(float) * 16 * ((256 + 8) + (96 + 8));
-        const dim3 g((rows + 15) / 16), b(512);
-        const void* fn = a.drop_mode == 1   ? reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<1>)
-                         : a.drop_mode == 2 ? reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<2>)
-                                            : reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<0>);
-        const int rc = ensure_dyn_lds(fn, (int)lds_f);
+        static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<0>), reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<1>),
+                                          reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<2>)};
+        const int rc = launch_fp_drop(fn, a.drop_mode, dim3((rows + 15) / 16), lds_f, a, s);
         if (rc) return rc;
-        if (a.drop_mode == 1) hipLaunchKernelGGL(feat_prenet_split_f32_kernel<1>, g, b, lds_f, s, a);
-        else if (a.drop_mode == 2) hipLaunchKernelGGL(feat_prenet_split_f32_kernel<2>, g, b, lds_f, s, a);
-        else hipLaunchKernelGGL(feat_prenet_split_f32_kernel<0>, g, b, lds_f, s, a);
     } else {
         ProfScope ps("feat_prenet_kernel", fl, rows, s);
         hipLaunchKernelGGL(feat_prenet_kernel, dim3((rows + 15) / 16), dim3(512), lds, s, a);

@@ -22,9 +22,7 @@
 
 namespace fcl {
 
-typedef unsigned short u16;
 typedef unsigned char u8;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
@@ -57,7 +55,6 @@ struct DecTileArgs {
 __device__ __forceinline__ void glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)l, 16, 0, 0); }
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void slot_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // stream slot index (inside a step) at which a phase starts
 struct DtPhases {
@@ -182,10 +179,10 @@ __global__ __launch_bounds__(64 * (8 + DT_NL)) void decoder_tile_kernel(const De
     auto gemm_phase = [&](const u8* buf, int nch, f32x4 (&acc)[2], auto&& hook, bool hooked) {
         acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < nch; ++c) {
-            slot_barrier();
+            lds_barrier();
             if (hooked && c == 0) {
                 hook();
-                slot_barrier();
+                lds_barrier();
             }
             s16x8 ah[2], al[2], wh, wl;
             read_a(buf, c, ah, al);
@@ -199,11 +196,11 @@ __global__ __launch_bounds__(64 * (8 + DT_NL)) void decoder_tile_kernel(const De
             s16x8 ah[2], al[2];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                slot_barrier();
+                lds_barrier();
                 if (g == 0) {
                     if (hooked && c == 0) {
                         hook();
-                        slot_barrier();
+                        lds_barrier();
                     }
                     read_a(c < 8 ? bufA : bufB, c & 7, ah, al);
                 }

@@ -20,7 +20,6 @@
 namespace fcl {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DW_BM = 32;  // contraction rows per chunk (one 16x16x32 MFMA step)
 

@@ -106,6 +106,14 @@ struct GemmArgs {
 // ---- fused LSTM step (gemm_f32.hip / decoder_step.hip): the argument block is the public fcl_lstm_step_t ----------
 typedef fcl_lstm_step_t LstmStepArgs;
 
+// summed contraction length of a multi-term problem, and the flops of an LSTM step (four gates of U units per row): the launchers' ProfScope figures
+static inline double terms_ksum(const GemmTerm* t, int n) {
+    double ksum = 0;
+    for (int i = 0; i < n; ++i) ksum += t[i].K;
+    return ksum;
+}
+static inline double lstm_step_flops(const LstmStepArgs& a) { return 2.0 * a.M * 4.0 * a.U * terms_ksum(a.term, a.nterms); }
+
 // ---- profiling hook (capi.hip) ----------------------------------------------------------------------
 extern bool g_prof_on;
 void prof_begin(const char* name, double flops, double rows, hipStream_t s, double fill_bytes = 0.0);
@@ -174,12 +182,13 @@ int launch_lstm_cell_bwd(const float* gates, const float* c_old, const float* c_
 __device__ __forceinline__ int live_rows_of(int m_host, const int* m_dev) { return m_dev ? min(m_host, *m_dev) : m_host; }
 
 // ---- bf16x3 operand split shared by the big-tile GEMMs (gemm_f32.hip) and the weight-gradient GEMM (backward.hip) ------------------
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16;
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void split4(const f32x4_t v, uint2& hi, uint2& lo) {
+__device__ __forceinline__ void split4(const f32x4 v, uint2& hi, uint2& lo) {
     const unsigned h01 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){v[0], v[1]}, bf16x2_t));
     const unsigned h23 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){v[2], v[3]}, bf16x2_t));
     const float r0 = v[0] - __builtin_bit_cast(float, h01 << 16), r1 = v[1] - __builtin_bit_cast(float, h01 & 0xFFFF0000u);
@@ -251,6 +260,10 @@ int tunable(const char* name, int dflt);  // FCL_<NAME> environment override, re
 int ensure_dyn_lds(const void* func, int bytes);
 
 
+// Workgroup barrier for data exchanged through LDS only: LDS accesses retired (lgkmcnt), then s_barrier.  Unlike __syncthreads() it leaves
+// global loads in flight (vmcnt untouched) -- weight fragments, tiles or epilogue operands requested ahead of the phase that consumes them.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // wave-uniform read of word k of a small device record (e.g. the capacity vocoder's live record, fcl_pwg_maps_build): a uniform address in the
 // constant address space becomes ONE scalar load per wave, and the value lives in an SGPR (no vector register, no per-lane load)
 __device__ __forceinline__ int uniform_word(const int* rec, int k) {
@@ -268,7 +281,7 @@ __host__ __device__ static inline unsigned int hash_u32(unsigned int x) {
 // dropout of four consecutive columns n .. n + 3 of row m (DROP: 0 none, 1 mask bytes, 2 counter hash: 16 bits per decision; idx = m * N + n) --
 // shared by feat_prenet_split_kernel (decoder_step.hip) and decoder_tile_kernel (decoder_tile.hip): the same (seed, row, column) draws the same bits
 template <int DROP>
-__device__ __forceinline__ f32x4_t drop4(f32x4_t v, unsigned int keep4, unsigned int idx, unsigned int seed, unsigned int thr16, float scale) {
+__device__ __forceinline__ f32x4 drop4(f32x4 v, unsigned int keep4, unsigned int idx, unsigned int seed, unsigned int thr16, float scale) {
     if (DROP == 1) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = ((keep4 >> (8 * r)) & 0xFFu) ? v[r] * scale : 0.f;

@@ -16,7 +16,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct LossBatch {
     fcl_loss_term_t t[FCL_LOSS_MAX_TERMS];

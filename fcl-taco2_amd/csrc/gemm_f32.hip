@@ -20,7 +20,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef FCL_BK
 #define FCL_BK 32
@@ -463,10 +462,8 @@ static void launch_gemm_cfg(const GemmArgs& a, hipStream_t s, const char* name, 
     snprintf(full, sizeof(full), "gemm_kernel<%d,%d,%d,%d>%s", WM, WN, precision() ? 1 : 0, TM, b.hi_only ? "/bf16" : precision() ? "/bf16x3" : "");
     static const int shapes = tunable("PROF_SHAPES", 0);  // developer aid: the profile records split by shape (M x N x sum K)
     if (shapes && g_prof_on) {
-        long long ks = 0;
-        for (int i = 0; i < a.nterms; ++i) ks += a.term[i].K;
         const size_t l = strlen(full);
-        snprintf(full + l, sizeof(full) - l, " %dx%dx%lld", a.M, a.N, ks);
+        snprintf(full + l, sizeof(full) - l, " %dx%dx%lld", a.M, a.N, (long long)terms_ksum(a.term, a.nterms));
     }
     (void)name;
     ProfScope ps(full, flops, a.M, s);
@@ -563,9 +560,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
         return launch_gemm_planes(b, s);
     }
     for (int i = 0; i < a.nterms; ++i) FCL_REQUIRE(a.term[i].A && a.term[i].W, FCL_ERR_INVALID, "gemm: term %d has no fp32 operands for the fp32-operand kernels", i);
-    double ksum = 0;
-    for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
-    const double flops = 2.0 * a.M * (double)a.N * ksum;
+    const double flops = 2.0 * a.M * (double)a.N * terms_ksum(a.term, a.nterms);
     const GemmTerm& t0 = a.term[0];
     static const int smallm = tunable("GEMM_SMALLM", 256);  // (r3: 64 -> 256; the BPTT steps with 65 - 256 live rows ran 34 us each on one lonely 64-row tile per 16 columns)
     if (a.M <= smallm && a.nterms == 1 && t0.shift == 0 && !a.seg_lo && !a.rank1_a && !a.C0 && a.act == FCL_ACT_NONE && a.drop_mode == 0 && !a.keep &&
@@ -639,9 +634,7 @@ int launch_lstm_step(const LstmStepArgs& a, hipStream_t s) {
         ExactScope sc;
         return launch_lstm_planes(b, s);
     }
-    double ksum = 0;
-    for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
-    const double flops = 2.0 * a.M * 4.0 * a.U * ksum;
+    const double flops = lstm_step_flops(a);
     const long long wg64 = (long long)((a.M + 63) / 64) * ((a.U + 15) / 16);
     if (a.U >= 32 && (long long)((a.M + 63) / 64) * ((a.U + 31) / 32) >= tm2_min_wg()) {
         launch_lstm_cfg<2, 2, 2>(a, s, "lstm_step_kernel<2,2,tm2>", flops);

@@ -21,8 +21,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 typedef unsigned char u8;
 
 __device__ __attribute__((aligned(128))) unsigned int g_zero_line[32];  // 128 bytes of zeros (static device memory is zero-initialised)
@@ -127,13 +125,13 @@ __device__ __forceinline__ void pchunk_mma(const u8* sb, int a_hi, int a_lo, int
     }
 }
 
-// LW = 0: every wave loads its share of a chunk and computes.  LW = 2: two extra LOADER waves per workgroup do nothing but the LDS-DMA of all row
-// groups (and the counted waits), the WM x WN compute waves nothing but fragment reads and MFMAs; one barrier per chunk joins them.  A wave that
-// issues its own global_load_lds cannot issue MFMAs meanwhile (in-order issue), so with ~1 workgroup per CU the two phases used to alternate.
-template <int WM, int WN, int TM, int TN, int NST, int LW = 0>
+// LW (2 or 4) extra LOADER waves per workgroup do nothing but the LDS-DMA of all row groups (and the counted waits), the WM x WN compute waves
+// nothing but fragment reads and MFMAs; one barrier per chunk joins them.  A wave that issues its own global_load_lds cannot issue MFMAs meanwhile
+// (in-order issue), so with ~1 workgroup per CU the two phases would alternate if every wave did both.
+template <int WM, int WN, int TM, int TN, int NST, int LW>
 struct PGeo {
     static constexpr int BM = 16 * WM * TM, BN = 16 * WN * TN, NW = WM * WN, THREADS = 64 * (NW + LW), CTHREADS = 64 * NW;
-    static constexpr int NL = LW > 0 ? LW : NW;                              // waves that issue LDS-DMA
+    static constexpr int NL = LW;                                            // waves that issue LDS-DMA
     static constexpr int GA = BM / 8 / NL, GB = BN / 8 / NL, GPW = GA + GB;  // LDS-DMA row groups (8 rows = 1 KB) per loading wave per chunk
     static constexpr int STAGE = (BM + BN) * 128;
     static constexpr int LDS_BYTES = NST * STAGE;
@@ -143,8 +141,8 @@ struct PGeo {
 };
 
 // The shared main loop.  LSTM: tile column c of the wave strip wn is gate (c >> 4) & 3 of unit u0 + wn*16 + (c & 15), i.e. W row g*NU + u
-// (TN must be 4); generic: W row n0 + c.  NU = N (generic) or U.  Returns false in a loader wave (LW > 0), which is done and must return.
-// ROLE: 0 = the wave finds out here whether it loads or computes; 1 / 2 = the caller has branched on it already (LW > 0) and this is a loader / compute
+// (TN must be 4); generic: W row n0 + c.  NU = N (generic) or U.  Returns false in a loader wave, which is done and must return.
+// ROLE: 0 = the wave finds out here whether it loads or computes; 1 / 2 = the caller has branched on it already and this is a loader / compute
 // wave -- the other role's code, and the accumulators' live range across it, then drop out of that call.
 template <int WM, int WN, int TM, int TN, int NST, bool LSTM, int LW, int HI, int ROLE = 0>
 __device__ __forceinline__ bool pmainloop(const GemmTerm* __restrict__ terms, int nterms, int M, int m0, int n0, int NU, const int* __restrict__ seg_lo,
@@ -153,9 +151,8 @@ __device__ __forceinline__ bool pmainloop(const GemmTerm* __restrict__ terms, in
     static_assert(!LSTM || TN == 4, "LSTM tiles keep the four gates of a unit in one lane");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    static_assert(ROLE == 0 || LW > 0, "a role is fixed only where loader waves exist");
-    const bool loader = ROLE == 1 || (ROLE == 0 && LW > 0 && wave >= G::NW);
-    const int lw = LW > 0 ? wave - G::NW : wave;  // index among the loading waves
+    const bool loader = ROLE == 1 || (ROLE == 0 && wave >= G::NW);
+    const int lw = wave - G::NW;  // index among the loading waves
     const int wm = wave / WN, wn = wave % WN;
     int nchunks = 0;
     for (int t = 0; t < nterms; ++t) nchunks += (terms[t].K + 31) >> 5;
@@ -165,7 +162,7 @@ __device__ __forceinline__ bool pmainloop(const GemmTerm* __restrict__ terms, in
         nchunks = max(0, min(ksplit_chunks, nchunks - kskip));
     }
 
-    if (LW == 0 || loader) {
+    if (loader) {
         // ---- loader coordinates: group g = j*NL + lw covers rows g*8 .. g*8+7 of its region; lane -> (row = lane >> 3, LDS piece = lane & 7)
         const unsigned coff = (unsigned)(((lane & 7) ^ (((lw & 1) << 2) | (lane >> 4))) * 16);  // SOURCE piece for this lane's LDS slot
         const u8* zline = reinterpret_cast<const u8*>(g_zero_line) + coff;
@@ -245,47 +242,23 @@ __device__ __forceinline__ bool pmainloop(const GemmTerm* __restrict__ terms, in
         for (int p = 0; p < NST - 1; ++p) {
             if (issued < nchunks) { issue(p); ++issued; }
         }
-        if (LW > 0) {  // loader wave: waits + barriers + refills only
-            int is = NST - 1;
-            for (int i = 0; i < nchunks; ++i) {
-                const int left = nchunks - 1 - i;
-                if (NST == 2) wait_vm<0>();  // two stages: only the chunk consumed next is in flight
-                else if (NST >= 4 && left >= 2) wait_vm<2 * G::GPW>();
-                else if (left >= 1) wait_vm<G::GPW>();
-                else wait_vm<0>();
-                asm volatile("s_barrier" ::: "memory");
-                if (left >= NST - 1) {
-                    issue(is);
-                    is = is + 1 == NST ? 0 : is + 1;
-                }
-            }
-            return false;
-        }
-        // ---- LW == 0: the same waves also compute
-        const int r16 = lane & 15, kq = lane >> 4;
-        const int sw = r16 >> 1;
-        const int a_hi = (wm * TM * 16 + r16) * 128 + ((kq ^ sw) << 4);
-        const int a_lo = (wm * TM * 16 + r16) * 128 + (((4 + kq) ^ sw) << 4);
-        const int b_hi = G::BM * 128 + (wn * TN * 16 + r16) * 128 + ((kq ^ sw) << 4);
-        const int b_lo = G::BM * 128 + (wn * TN * 16 + r16) * 128 + (((4 + kq) ^ sw) << 4);
-        int cs = 0, is = NST - 1;
-        for (int i = 0; i < nchunks; ++i) {  // chunk i is consumed while chunks i+1 .. i+NST-2 stay in flight and chunk i+NST-1 is issued
+        // waits + barriers + refills only: chunk i is consumed while chunks i+1 .. i+NST-2 stay in flight and chunk i+NST-1 is issued
+        int is = NST - 1;
+        for (int i = 0; i < nchunks; ++i) {
             const int left = nchunks - 1 - i;
-            if (NST == 2) wait_vm<0>();
+            if (NST == 2) wait_vm<0>();  // two stages: only the chunk consumed next is in flight
             else if (NST >= 4 && left >= 2) wait_vm<2 * G::GPW>();
             else if (left >= 1) wait_vm<G::GPW>();
             else wait_vm<0>();
-            asm volatile("s_barrier" ::: "memory");  // chunk i has landed for every wave; every wave is done reading the buffer refilled now
+            asm volatile("s_barrier" ::: "memory");  // chunk i has landed; every compute wave is done reading the buffer refilled now
             if (left >= NST - 1) {
                 issue(is);
                 is = is + 1 == NST ? 0 : is + 1;
             }
-            pchunk_mma<TM, TN, HI>(smem + cs * G::STAGE, a_hi, a_lo, b_hi, b_lo, acc);
-            cs = cs + 1 == NST ? 0 : cs + 1;
         }
-        return true;
+        return false;
     }
-    // ---- compute wave of a loader-specialised workgroup
+    // ---- compute wave
     {
         const int r16 = lane & 15, kq = lane >> 4;
         const int sw = r16 >> 1;
@@ -603,7 +576,7 @@ __device__ __forceinline__ void plstm_body(const LstmStepArgs& a, u8* smem) {
     if (m0 >= Ms) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier / LDS-DMA)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     f32x4 acc[TM][4];
-    if (LW > 0 && wave >= G::NW) {  // a loader wave has no cells: LDS-DMA only (branching here keeps the seeds out of its registers)
+    if (wave >= G::NW) {  // a loader wave has no cells: LDS-DMA only (branching here keeps the seeds out of its registers)
         (void)pmainloop<WM, WN, TM, 4, NST, true, LW, HI, 1>(a.term, a.nterms, M, m0, u0, a.U, nullptr, nullptr, smem, acc);
         return;
     }
@@ -638,7 +611,7 @@ __device__ __forceinline__ void plstm_body(const LstmStepArgs& a, u8* smem) {
                 for (int j = 0; j < 4; ++j) acc[tm][j][r] = add[j];
             }
     }
-    (void)pmainloop<WM, WN, TM, 4, NST, true, LW, HI, (LW > 0 ? 2 : 0)>(a.term, a.nterms, M, m0, u0, a.U, nullptr, nullptr, smem, acc);
+    (void)pmainloop<WM, WN, TM, 4, NST, true, LW, HI, 2>(a.term, a.nterms, M, m0, u0, a.U, nullptr, nullptr, smem, acc);
     if (g_plstm_dbg == 1) {
         float sdbg = 0.f;
 #pragma unroll
@@ -755,10 +728,8 @@ static int launch_pgemm_lw(const GemmArgs& a, hipStream_t s, double flops) {
     snprintf(full, sizeof(full), "pgemm_kernel<%d,%d,%d,%d,%d,%d>%s%s", WM, WN, TM, TN, NST, LW, HI == 2 ? "/f32" : HI ? "/bf16" : "", a.accumulate ? "/dW" : "");
     static const int shapes = tunable("PROF_SHAPES", 0);  // developer aid: the profile records split by shape (M x N x sum K)
     if (shapes && g_prof_on) {
-        long long ks = 0;
-        for (int i = 0; i < a.nterms; ++i) ks += a.term[i].K;
         const size_t l = strlen(full);
-        snprintf(full + l, sizeof(full) - l, " %dx%dx%lld", a.M, a.N, ks);
+        snprintf(full + l, sizeof(full) - l, " %dx%dx%lld", a.M, a.N, (long long)terms_ksum(a.term, a.nterms));
     }
     double fill = 0.0;  // LDS-DMA bytes of the launch: every tile streams (BM + BN) 128-byte lines per 32-k chunk of every term
     {
@@ -808,10 +779,10 @@ static int launch_pgemm_cfg(const GemmArgs& a, hipStream_t s, double flops) {
 // k taps read it at row offsets -pad .. +pad; only the W chunk changes per step: (BM + 16 + k * BN) * 128 B per channel chunk instead of
 // k * (BM + BN) * 128 B (-39 % for k = 5, 64 x 64 tiles).  Utterance edges: a row outside the segment of the OUTPUT row it contributes to is
 // zeroed per lane at fragment-read time (one shared tile serves rows of two utterances when a tile straddles a boundary).
-template <int WM, int WN, int TM, int TN, int NL_ = 2, int NSTW_ = 3>
+template <int WM, int WN, int TM, int TN>
 struct CGeo {
-    static constexpr int BM = 16 * WM * TM, BN = 16 * WN * TN, NW = WM * WN, NL = NL_, THREADS = 64 * (NW + NL), CTHREADS = 64 * NW;
-    static constexpr int HALO = NL_ == 4 ? 16 : 8, AROWS = BM + 2 * HALO, A_BYTES = AROWS * 128, W_BYTES = BN * 128, NSTW = NSTW_;  // W ring stages (2: 68 KB for the 128 x 128 tile -> two workgroups per CU)
+    static constexpr int BM = 16 * WM * TM, BN = 16 * WN * TN, NW = WM * WN, NL = 2, THREADS = 64 * (NW + NL), CTHREADS = 64 * NW;  // NL loader waves
+    static constexpr int HALO = 8, AROWS = BM + 2 * HALO, A_BYTES = AROWS * 128, W_BYTES = BN * 128, NSTW = 3;  // NSTW: W ring stages (two bundles ahead)
     static constexpr int LDS_BYTES = 2 * A_BYTES + NSTW * W_BYTES;
     static constexpr int GAH = AROWS / 8 / NL, GB = BN / 8 / NL;
     static_assert((AROWS / 8) % NL == 0 && (BN / 8) % NL == 0, "tile rows must split evenly over the loader waves");
@@ -821,9 +792,9 @@ struct CGeo {
 // HI: 0 = bf16x3 planes, 1 = the hi planes alone (autocast), 2 (round 5) = EXACT fp32 lines (FCL_PRECISION=0: a row-major fp32 activation / the
 // tap-major fp32 weights ARE 128-byte lines of 32 floats, see pchunk_mma<HI = 2>): the exact mode's convolutions used to run as k-term GEMMs that
 // re-fetch the input tile for every tap
-template <int WM, int WN, int TM, int TN, int HI, int NL, int NSTW = 3>
-__global__ __launch_bounds__(64 * (WM * WN + NL)) void pconv_kernel(const GemmArgs a) {
-    using G = CGeo<WM, WN, TM, TN, NL, NSTW>;
+template <int WM, int WN, int TM, int TN, int HI>
+__global__ __launch_bounds__((CGeo<WM, WN, TM, TN>::THREADS)) void pconv_kernel(const GemmArgs a) {
+    using G = CGeo<WM, WN, TM, TN>;
     extern __shared__ __attribute__((aligned(1024))) u8 smem[];
     int bx, by;
     xcd_tile_p(bx, by);
@@ -879,14 +850,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void pconv_kernel(const GemmAr
             if (++ij == k) { ij = 0; ++ic; }
         };
         issue();
-        if (G::NSTW == 2) {  // two W stages: one bundle ahead (the other workgroup on the CU covers the exposed DMA latency)
-            for (int s = 0; s < S; ++s) {
-                wait_vm<0>();
-                asm volatile("s_barrier" ::: "memory");
-                if (s + 1 < S) issue();
-            }
-            return;
-        }
         if (S > 1) issue();
         for (int s = 0; s < S; ++s) {
             // everything but the newest bundle (step s + 1) has landed; that bundle carries an A tile when s + 1 opens a chunk
@@ -1000,32 +963,29 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void pconv_kernel(const GemmAr
 // feed, 39.2 vs 39.6 M frames/s over three runs each: one bundle ahead exposes the W latency of a 5-tap step)
 template <int WM, int WN, int TM, int TN>
 static int launch_pconv_cfg(const GemmArgs& a, hipStream_t s, double flops) {
-    constexpr int NL = 2;
-    using G = CGeo<WM, WN, TM, TN, NL>;
+    using G = CGeo<WM, WN, TM, TN>;
     const bool hi = gemm_mode() == FCL_GEMM_BF16;
-    const void* fn = hi ? reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 1, NL>) : reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 0, NL>);
+    const void* fn = hi ? reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 1>) : reinterpret_cast<const void*>(pconv_kernel<WM, WN, TM, TN, 0>);
     const int rc = ensure_dyn_lds(fn, G::LDS_BYTES);
     if (rc) return rc;
     const int ncols = a.Yp ? max(a.N, a.ldyp * 32) : a.N;
     const int groups = (a.g_a || a.g_w || a.g_y || a.g_yp) ? max(1, a.nblk) : 1;  // (nblk carries the group count of a grouped Conv1d)
     dim3 grid((ncols + G::BN - 1) / G::BN, (a.M + G::BM - 1) / G::BM, groups);
     char full[48];
-    snprintf(full, sizeof(full), "pconv_kernel<%d,%d,%d,%d,%d>%s", WM, WN, TM, TN, NL, hi ? "/bf16" : "");
+    snprintf(full, sizeof(full), "pconv_kernel<%d,%d,%d,%d,%d>%s", WM, WN, TM, TN, G::NL, hi ? "/bf16" : "");
     // LDS-DMA bytes: per 32-channel chunk of the input a tile streams its row window once (BM + halo rows) and one BN-row weight slab per tap
     const double fill = (double)grid.x * grid.y * grid.z * (double)((a.term[0].K + 31) >> 5) * ((double)G::AROWS + (double)a.conv_k * G::BN) * 128.0;
     ProfScope ps(full, flops, a.M, s, fill);
     static const int dbg = tunable("PGEMM_DBG", 0);
     GemmArgs b = a;
     b.dbg_phase = dbg;
-    if (hi) hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 1, NL>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
-    else hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 0, NL>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
+    if (hi) hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 1>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
+    else hipLaunchKernelGGL((pconv_kernel<WM, WN, TM, TN, 0>), grid, dim3(G::THREADS), G::LDS_BYTES, s, b);
     return check_hip(hipGetLastError(), "pconv launch");
 }
 
 int launch_gemm_planes(const GemmArgs& a, hipStream_t s) {
-    double ksum = 0;
-    for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
-    const double flops = 2.0 * a.M * (double)a.N * ksum;
+    const double flops = 2.0 * a.M * (double)a.N * terms_ksum(a.term, a.nterms);
     const long long t64x128 = (long long)((a.M + 63) / 64) * ((a.N + 127) / 128);
     const long long t128x128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
     // measured on MI355X (tools/probe/planes_gemm_probe): 8-wave 128 x 128 tiles where they still give >= ~150 workgroups, 64 x 128 with three
@@ -1095,9 +1055,7 @@ static int launch_plstm_cfg(const LstmStepArgs& a, hipStream_t s, double flops) 
 int launch_lstm_planes(const LstmStepArgs& a, hipStream_t s) {
     FCL_REQUIRE(!a.h_out_p || ((a.U & 31) == 0 && a.ld_hp * 32 >= a.U && (reinterpret_cast<uintptr_t>(a.h_out_p) & 127u) == 0), FCL_ERR_SHAPE,
                 "lstm_step: h_out_p needs U %% 32 == 0, ld_hp >= U / 32 and a 128-byte aligned buffer");
-    double ksum = 0;
-    for (int i = 0; i < a.nterms; ++i) ksum += a.term[i].K;
-    const double flops = 2.0 * a.M * 4.0 * a.U * ksum;
+    const double flops = lstm_step_flops(a);
     const long long t128 = (long long)((a.M + 127) / 128) * ((a.U + 31) / 32);
     const long long t64 = (long long)((a.M + 63) / 64) * ((a.U + 31) / 32);
     // thresholds as tunables (r3, 4 passes in flight, B = 32: 64-row tiles everywhere -- two workgroups per CU, also from different streams -- are +1.5 ...
@@ -1158,12 +1116,7 @@ int launch_lstm_planes_pair(const LstmStepArgs& a0, const LstmStepArgs& a1, hipS
     for (const LstmStepArgs* a : {&a0, &a1})
         if (a->h_out_p && !((a->U & 31) == 0 && a->ld_hp * 32 >= a->U && (reinterpret_cast<uintptr_t>(a->h_out_p) & 127u) == 0)) return 0;
     *handled = true;
-    double flops = 0;
-    for (const LstmStepArgs* a : {&a0, &a1}) {
-        double ksum = 0;
-        for (int i = 0; i < a->nterms; ++i) ksum += a->term[i].K;
-        flops += 2.0 * a->M * 4.0 * a->U * ksum;
-    }
+    const double flops = lstm_step_flops(a0) + lstm_step_flops(a1);
     const int M = a0.M > a1.M ? a0.M : a1.M, U = a0.U;
     const bool hi = gemm_mode() == FCL_GEMM_BF16;
     // the training-side thresholds of launch_lstm_planes on the larger of the two row counts (both problems share one tile shape)
@@ -1199,10 +1152,6 @@ __device__ __forceinline__ float pwg_gate(float a, float b) {
 
 void* g_debug_ptr = nullptr;
 
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, i.e. it would wait for the epilogue operands prefetched
-// from global memory right after the main loop (their latency is meant to hide behind the gate and phase 2)
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 struct PwgFusedArgs {
     GemmTerm term[4];
     int nterms, M;
@@ -1219,17 +1168,16 @@ struct PwgFusedArgs {
     int dbg;  // developer timing aid (FCL_PWG_DBG): 1 / 2 / 3 = return after the main loop / the gate / phase 2 (results are then garbage)
 };
 
-// WM = 4: 128-row tiles, W_os resident in LDS (160 KB, one workgroup per CU); WM = 2: 64-row tiles, W_os fragments straight from L2 into
-// registers, everything else inside the 72 KB ring (two workgroups per CU: one's epilogue overlaps the other's main loop).
-template <int WM, int NST, bool HI>
-__global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgFusedArgs a) {
-    using G = PGeo<WM, 2, 2, 4, NST, 2>;
-    constexpr int TM = 2, TN = 4, WN = 2, BM = G::BM;
-    constexpr bool WLDS = WM == 4 && NST == 3;
+// 128-row tiles, 3-deep ring, W_os resident in LDS (160 KB, one workgroup per CU).
+using PwgGeo = PGeo<4, 2, 2, 4, 3, 2>;
+template <bool HI>
+__global__ __launch_bounds__(PwgGeo::THREADS) void pwg_layer_kernel(const PwgFusedArgs a) {
+    using G = PwgGeo;
+    constexpr int WM = 4, TM = 2, TN = 4, WN = 2, NST = 3, BM = G::BM;
     constexpr int LDT = 132, ZT_BYTES = BM * LDT * 4;
-    constexpr int WOS = G::LDS_BYTES;                                          // WLDS only: 32 KB after the ring
-    constexpr int GA = WLDS ? WOS + 32768 : (ZT_BYTES + 1023) / 1024 * 1024;    // gate planes: after W_os, or inside the ring behind the staging tile
-    static_assert(G::BN == 128 && ZT_BYTES <= G::LDS_BYTES && (WLDS || GA + BM * 256 <= G::LDS_BYTES), "tile geometry");
+    constexpr int WOS = G::LDS_BYTES;  // W_os: 32 KB after the ring
+    constexpr int GA = WOS + 32768;    // gate planes: after W_os
+    static_assert(G::BN == 128 && ZT_BYTES <= G::LDS_BYTES, "tile geometry");
     extern __shared__ __attribute__((aligned(1024))) u8 smem[];
     int bx, by;
     xcd_tile_p(bx, by);
@@ -1237,7 +1185,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #define PWG_STAMP(k) do { if (a.ts && tid == 0) a.ts[(size_t)by * 8 + (k)] = (long long)wall_clock64(); } while (0)
     PWG_STAMP(0);
-    if (WLDS && wave < G::NW) {  // W_os [128, 64] planes -> LDS, two 16 KB chunks in the ring's layout (piece p of row n at slot p ^ ((n >> 1) & 7))
+    if (wave < G::NW) {  // W_os [128, 64] planes -> LDS, two 16 KB chunks in the ring's layout (piece p of row n at slot p ^ ((n >> 1) & 7))
         for (int i = tid; i < 2048; i += G::CTHREADS) {
             const int n = i >> 4, c = (i >> 3) & 1, p = i & 7;
             const uint4 v = *reinterpret_cast<const uint4*>(a.w_os_p + ((size_t)(n * 2 + c) * 64 + p * 8));
@@ -1263,17 +1211,6 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
     const int wm = wave / WN, wn = wave % WN;
     const int col = lane & 15, rq = lane >> 4;
     const int r16 = lane & 15, kq = lane >> 4, sw = r16 >> 1;
-    s16x8 wh[2][TN], wl[2][TN];
-    if (!WLDS) {  // phase-2 B fragments (W_os rows wn*64 + tn*16 + r16, chunk c, pieces kq / 4 + kq): requested now, consumed after the gate
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-                const u16* w = a.w_os_p + ((size_t)((wn * TN + tn) * 16 + r16) * 2 + c) * 64 + kq * 8;
-                wh[c][tn] = *reinterpret_cast<const s16x8*>(w);
-                if (!HI) wl[c][tn] = *reinterpret_cast<const s16x8*>(w + 32);
-            }
-    }
     // final-epilogue operands (the old x planes and the skip accumulator of this thread's items) are requested NOW: their latency hides behind the
     // gate and phase 2
     constexpr int ITEMS = BM * 8 / G::CTHREADS;
@@ -1302,7 +1239,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
         if (acc[0][0][0] == 12345.f) a.skips[0] = 1.f;
         return;
     }
-    lds_sync();  // every compute wave is done with the ring
+    lds_barrier();  // every compute wave is done with the ring
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -1312,7 +1249,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
 #pragma unroll
             for (int r = 0; r < 4; ++r) zt[((wm * TM + tm) * 16 + rq * 4 + r) * LDT + cn] = acc[tm][tn][r] + b;
         }
-    lds_sync();
+    lds_barrier();
     PWG_STAMP(6);
     for (int i = tid; i < BM * 8; i += G::CTHREADS) {  // gate: 8 columns per item -> one hi and one lo piece of the A planes
         const int r = i >> 3, p = i & 7, c0 = p * 8;
@@ -1332,7 +1269,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
         *reinterpret_cast<uint4*>(base + ((piece ^ sws) << 4)) = make_uint4(h0.x, h0.y, h1.x, h1.y);
         *reinterpret_cast<uint4*>(base + (((4 + piece) ^ sws) << 4)) = make_uint4(l0.x, l0.y, l1.x, l1.y);
     }
-    lds_sync();
+    lds_barrier();
     PWG_STAMP(3);
     if (a.dbg == 2) return;
 #pragma unroll
@@ -1343,27 +1280,8 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
         const int ar = (wm * TM * 16 + r16) * 128, br = (wn * TN * 16 + r16) * 128;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            if constexpr (WLDS) {
-                pchunk_mma<TM, TN, HI>(smem, GA + c * (BM * 128) + ar + ((kq ^ sw) << 4), GA + c * (BM * 128) + ar + (((4 + kq) ^ sw) << 4),
-                                       WOS + c * 16384 + br + ((kq ^ sw) << 4), WOS + c * 16384 + br + (((4 + kq) ^ sw) << 4), acc);
-            } else {
-                s16x8 ah[TM], al[TM];
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm) {
-                    ah[tm] = *reinterpret_cast<const s16x8*>(smem + GA + c * (BM * 128) + ar + tm * 2048 + ((kq ^ sw) << 4));
-                    if (!HI) al[tm] = *reinterpret_cast<const s16x8*>(smem + GA + c * (BM * 128) + ar + tm * 2048 + (((4 + kq) ^ sw) << 4));
-                }
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn) {
-                        if (!HI) {
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[tm], wh[c][tn], acc[tm][tn], 0, 0, 0);
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[tm], wl[c][tn], acc[tm][tn], 0, 0, 0);
-                        }
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[tm], wh[c][tn], acc[tm][tn], 0, 0, 0);
-                    }
-            }
+            pchunk_mma<TM, TN, HI>(smem, GA + c * (BM * 128) + ar + ((kq ^ sw) << 4), GA + c * (BM * 128) + ar + (((4 + kq) ^ sw) << 4),
+                                   WOS + c * 16384 + br + ((kq ^ sw) << 4), WOS + c * 16384 + br + (((4 + kq) ^ sw) << 4), acc);
         }
     }
     PWG_STAMP(4);
@@ -1371,8 +1289,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
         if (acc[0][0][0] == 12345.f) a.skips[0] = 1.f;
         return;
     }
-    if (!WLDS) lds_sync();  // GA sits in the ring next to the staging tile's rows: everyone has read its fragments before o is staged
-    // (WLDS: zt is free since the gate pass, phase 2 reads GA / WOS only)
+    // (zt is free since the gate pass, phase 2 reads GA / WOS only: no barrier before o is staged)
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -1382,7 +1299,7 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
 #pragma unroll
             for (int r = 0; r < 4; ++r) zt[((wm * TM + tm) * 16 + rq * 4 + r) * LDT + cn] = acc[tm][tn][r] + b;
         }
-    lds_sync();
+    lds_barrier();
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int i = tid + it * G::CTHREADS, r = i >> 3, c0 = (i & 7) * 8;
@@ -1420,9 +1337,10 @@ __global__ __launch_bounds__(64 * (WM * 2 + 2)) void pwg_layer_kernel(const PwgF
 // read it.  LDS: ring 96 KB | W_os 32 KB | gate planes / o staging 32 KB.
 // AUXF: the auxiliary term at frame rate -- 3 x 2 + 1 chunks per tile instead of 3 x 2 + 3, the last one (coefficient lines x a 32-frame window of
 // the projected features) with a W tile that depends on the tile's frame.
-template <bool HI, int LW, bool AUXF>
+using PwgPGeo = PGeo<4, 2, 2, 4, 3, 4>;  // 4 loader waves over 2: 151.9 -> 145.1 ms per 30 blocks
+template <bool HI, bool AUXF>
 __device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int ntiles) {
-    using G = PGeo<4, 2, 2, 4, 3, LW>;
+    using G = PwgPGeo;
     constexpr int TM = 2, TN = 4, WN = 2, BM = 128, NST = 3, NCH = AUXF ? 7 : 9;
     constexpr int WOS = G::LDS_BYTES, GA = WOS + 32768;
     static_assert(G::BM == BM && G::BN == 128 && G::STAGE == 32768, "tile geometry");
@@ -1618,7 +1536,7 @@ __device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int
                     *reinterpret_cast<u16*>(line + (((k >> 3) ^ sws) << 4)) = __builtin_bit_cast(u16, gh);
                     if (!HI) *reinterpret_cast<u16*>(line + (((4 + (k >> 3)) ^ sws) << 4)) = __builtin_bit_cast(u16, (__bf16)(g - (float)gh));
                 }
-        lds_sync();  // B1: g complete
+        lds_barrier();  // B1: g complete
         PWG_PSTAMP(2);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -1631,7 +1549,7 @@ __device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int
                 pchunk_mma<TM, TN, HI>(smem, GA + c * 16384 + ar + ((kq ^ sw) << 4), GA + c * 16384 + ar + (((4 + kq) ^ sw) << 4),
                                        WOS + c * 16384 + br + ((kq ^ sw) << 4), WOS + c * 16384 + br + (((4 + kq) ^ sw) << 4), acc);
         }
-        lds_sync();  // B2: every wave has read its g fragments; the buffer becomes the staging tile of o
+        lds_barrier();  // B2: every wave has read its g fragments; the buffer becomes the staging tile of o
         PWG_PSTAMP(3);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -1644,7 +1562,7 @@ __device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int
                         for (int r = 0; r < 4; ++r)
                             ot[((wm & 1) * 32 + tm * 16 + rq * 4 + r) * 128 + (((wn * TN + tn) * 16 + col) ^ (rq << 4))] = acc[tm][tn][r] + bo[tn];
             }
-            lds_sync();  // B3 / B5
+            lds_barrier();  // B3 / B5
             {
                 const int rl = tid >> 3, c0 = (tid & 7) * 8, m = m0 + h * 64 + rl;
                 if (m < a.M) {
@@ -1672,7 +1590,7 @@ __device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int
                     *reinterpret_cast<f32x4*>(sk + 4) = ps1[h] + k1;
                 }
             }
-            if (h == 0) lds_sync();  // B4: half 0 has been read out
+            if (h == 0) lds_barrier();  // B4: half 0 has been read out
         }
         PWG_PSTAMP(4);
 #undef PWG_PSTAMP
@@ -1681,29 +1599,29 @@ __device__ __forceinline__ void pwg_layer_pbody(const PwgFusedArgs& a, const int
     }
 }
 
-template <bool HI, int LW, bool AUXF>
-__global__ __launch_bounds__(64 * (8 + LW)) void pwg_layer_pkernel(const PwgFusedArgs a, const int ntiles) {
-    pwg_layer_pbody<HI, LW, AUXF>(a, ntiles);
+template <bool HI, bool AUXF>
+__global__ __launch_bounds__(PwgPGeo::THREADS) void pwg_layer_pkernel(const PwgFusedArgs a, const int ntiles) {
+    pwg_layer_pbody<HI, AUXF>(a, ntiles);
 }
 
 // capacity form (fcl_pwg_layer_cap_fwd; live = {frames, samples, ...} of fcl_pwg_maps_build, one scalar load per wave): a.M, the chunk strides and the grid are those of the CAPACITY; the tiles that are walked are those of the
 // live samples, read from the device.  live is a multiple of hop, hence of 128: every live tile is a full tile, as in an exact-size call.
-template <bool HI, int LW, bool AUXF>
-__global__ __launch_bounds__(64 * (8 + LW)) void pwg_layer_cap_pkernel(const PwgFusedArgs a, const int* __restrict__ live) {
+template <bool HI, bool AUXF>
+__global__ __launch_bounds__(PwgPGeo::THREADS) void pwg_layer_cap_pkernel(const PwgFusedArgs a, const int* __restrict__ live) {
     const int ntiles = (min(uniform_word(live, 1), a.M) + 127) >> 7;
-    pwg_layer_pbody<HI, LW, AUXF>(a, ntiles);
+    pwg_layer_pbody<HI, AUXF>(a, ntiles);
 }
 
-template <int WM, int NST, bool HI>
+template <bool HI>
 static int launch_pwg_cfg(const PwgFusedArgs& a, long long m, double flops, hipStream_t s) {
-    using G = PGeo<WM, 2, 2, 4, NST, 2>;
-    constexpr int LDS = G::LDS_BYTES + ((WM == 4 && NST == 3) ? 2 * 32768 : 0);
-    auto k = pwg_layer_kernel<WM, NST, HI>;
+    using G = PwgGeo;
+    constexpr int LDS = G::LDS_BYTES + 2 * 32768;
+    auto k = pwg_layer_kernel<HI>;
     const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k), LDS);
     if (rc) return rc;
     dim3 grid(1, (unsigned)((m + G::BM - 1) / G::BM));
     char full[48];
-    snprintf(full, sizeof(full), "pwg_layer_kernel<%d,%d>%s", WM, NST, HI ? "/bf16" : "");
+    snprintf(full, sizeof(full), "pwg_layer_kernel<4,3>%s", HI ? "/bf16" : "");
     ProfScope ps(full, flops, (int)m, s);
     hipLaunchKernelGGL(k, grid, dim3(G::THREADS), LDS, s, a);
     return check_hip(hipGetLastError(), "pwg_layer launch");
@@ -1750,11 +1668,10 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s, const int* l
     FCL_REQUIRE(!live || (!dbg && exp_terms <= 0 && !want_ts && (auxf || L.aux > 64)), FCL_ERR_SHAPE,
                 "pwg_layer_cap_fwd: the capacity form runs on the persistent kernel only (frame-rate auxiliary term, or 64 < aux <= 96; no developer switches)");
     if (!dbg && exp_terms <= 0 && (auxf || L.aux > 64)) {  // (the persistent kernel is written for 3 x 2 + 3 chunks: r = 64, ksize = 3, 64 < aux <= 96)
-        constexpr int LDS = PGeo<4, 2, 2, 4, 3, 2>::LDS_BYTES + 2 * 32768;
-        constexpr int lwv = 4;  // 4 loader waves over 2: 151.9 -> 145.1 ms per 30 blocks
+        constexpr int LDS = PwgPGeo::LDS_BYTES + 2 * 32768;
         typedef void (*kern_t)(const PwgFusedArgs, const int);
-        static const kern_t table[2][2] = {{pwg_layer_pkernel<false, lwv, false>, pwg_layer_pkernel<false, lwv, true>},
-                                           {pwg_layer_pkernel<true, lwv, false>, pwg_layer_pkernel<true, lwv, true>}};
+        static const kern_t table[2][2] = {{pwg_layer_pkernel<false, false>, pwg_layer_pkernel<false, true>},
+                                           {pwg_layer_pkernel<true, false>, pwg_layer_pkernel<true, true>}};
         const kern_t fn = table[hi ? 1 : 0][auxf ? 1 : 0];
         const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(fn), LDS);
         if (rc) return rc;
@@ -1765,22 +1682,22 @@ int launch_pwg_layer_fused(const fcl_pwg_layer_t& L, hipStream_t s, const int* l
         int nwg = std::min(ntiles, wg_per_cu > 0 ? wg_per_cu : cus);
         if (live) {  // the grid is the capacity's; workgroups without a live tile exit at once
             typedef void (*ckern_t)(const PwgFusedArgs, const int*);
-            static const ckern_t ctable[2][2] = {{pwg_layer_cap_pkernel<false, lwv, false>, pwg_layer_cap_pkernel<false, lwv, true>},
-                                                 {pwg_layer_cap_pkernel<true, lwv, false>, pwg_layer_cap_pkernel<true, lwv, true>}};
+            static const ckern_t ctable[2][2] = {{pwg_layer_cap_pkernel<false, false>, pwg_layer_cap_pkernel<false, true>},
+                                                 {pwg_layer_cap_pkernel<true, false>, pwg_layer_cap_pkernel<true, true>}};
             const ckern_t cfn = ctable[hi ? 1 : 0][auxf ? 1 : 0];
             const int rcc = ensure_dyn_lds(reinterpret_cast<const void*>(cfn), LDS);
             if (rcc) return rcc;
             ProfScope ps(hi ? "pwg_layer_cap_pkernel/bf16" : "pwg_layer_cap_pkernel", flops, (int)L.m, s);
-            hipLaunchKernelGGL(cfn, dim3((unsigned)nwg), dim3(64 * (8 + lwv)), LDS, s, a, live);
+            hipLaunchKernelGGL(cfn, dim3((unsigned)nwg), dim3(PwgPGeo::THREADS), LDS, s, a, live);
             return check_hip(hipGetLastError(), "pwg_layer capacity launch");
         }
         ProfScope ps(hi ? "pwg_layer_pkernel/bf16" : "pwg_layer_pkernel", flops, (int)L.m, s);
-        hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(64 * (8 + lwv)), LDS, s, a, ntiles);
+        hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(PwgPGeo::THREADS), LDS, s, a, ntiles);
         return check_hip(hipGetLastError(), "pwg_layer persistent launch");
     }
     // measured on MI355X, 64 x 800 frames, ms per layer: 128-row tiles + 3-deep ring + W_os in LDS 7.07; the same with a 4-deep ring and W_os
     // fragments from L2 8.4 (the main loop alone is 4.05 either way: not bound by bytes in flight); 64-row tiles, two workgroups per CU 7.5
-    return hi ? launch_pwg_cfg<4, 3, true>(a, L.m, flops, s) : launch_pwg_cfg<4, 3, false>(a, L.m, flops, s);
+    return hi ? launch_pwg_cfg<true>(a, L.m, flops, s) : launch_pwg_cfg<false>(a, L.m, flops, s);
 }
 
 // ---- the generator's last_conv_layers in one launch: wav[m] = relu(relu(skips[m] * scale) W1^T + b1) . w2 + b2  (64 skip channels).
@@ -1818,7 +1735,7 @@ __device__ __forceinline__ void pwg_last_body(u8* smem, const float* __restrict_
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int i = tid + 256 * j, row = i >> 4, c4 = (i & 15) * 4, k = c4 & 31;
-            f32x4_t y;
+            f32x4 y;
 #pragma unroll
             for (int e = 0; e < 4; ++e) y[e] = fmaxf(v[j][e] * scale, 0.f);
             uint2 h, l;

@@ -13,11 +13,11 @@
     int lo[TM], hi[TM];
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) hfg_bounds(a.frame_utt, a.utt_off, a.rate, a.m, t0 + (wm * TM + tm) * 16 + r16, lo[tm], hi[tm]);
-    f32x4_t acc[TM][TN];
+    f32x4 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads();
     for (int j = 0; j < a.kr; ++j) {
         const int shift = (j - h2) * a.dil;
@@ -39,7 +39,7 @@
             const int col = n0 + tn * 16 + (lane & 15);
             const float b = a.b1[col];
             const int c = col >> 5, piece = (col & 31) >> 3, el = (col & 7) * 2;
-            f32x4_t v;  // this lane's four rows of the column, split by the one split every producer uses (what the two-launch form writes to tp)
+            f32x4 v;  // this lane's four rows of the column, split by the one split every producer uses (what the two-launch form writes to tp)
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = hfg_lrelu(acc[tm][tn][r] + b, a.slope);
             uint2 h, l;
@@ -52,7 +52,7 @@
                 *reinterpret_cast<u16*>(line + ((piece ^ sw) << 4) + el) = (u16)(hw[r >> 1] >> ((r & 1) * 16));
                 if (!HI) *reinterpret_cast<u16*>(line + (((4 + piece) ^ sw) << 4) + el) = (u16)(lw[r >> 1] >> ((r & 1) * 16));
             }
-            acc[tm][tn] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            acc[tm][tn] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) hfg_bounds(a.frame_utt, a.utt_off, a.rate, a.m, m0 + (wm * TM + tm) * 16 + r16, lo[tm], hi[tm]);
@@ -84,5 +84,5 @@
     for (int i = tid; i < BM * (C / 4); i += 256) {
         const int r = i / (C / 4), c4 = (i - r * (C / 4)) * 4;
         if (m0 + r >= a.m) continue;
-        hfg_store4(a.e, m0 + r, C, c4, *reinterpret_cast<const f32x4_t*>(zt + r * LDT + c4));
+        hfg_store4(a.e, m0 + r, C, c4, *reinterpret_cast<const f32x4*>(zt + r * LDT + c4));
     }

@@ -22,7 +22,6 @@
 
 namespace fcl {
 
-typedef unsigned short u16;
 typedef unsigned char u8;
 
 __device__ __forceinline__ float hfg_lrelu(float v, float s) { return v >= 0.f ? v : v * s; }
@@ -53,7 +52,7 @@ __device__ __forceinline__ void hfg_load_tile(const u16* __restrict__ xp, int ld
 // zeros), B rows n, n + 16, .. of the weight planes at wl (this lane's row and k-quarter).  Row tiles at or beyond tm_end are skipped.
 template <int TM, int TN, bool HI>
 __device__ __forceinline__ void hfg_tap(const u8* tile, int nrows, int nl, const int (&arow)[TM], unsigned okmask, int tm_end, const u16* __restrict__ wl, int ldw,
-                                        int kq, f32x4_t (&acc)[TM][TN]) {
+                                        int kq, f32x4 (&acc)[TM][TN]) {
     const s16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int c = 0; c < nl; ++c) {
         s16x8 bh[TN], bl[TN];
@@ -98,13 +97,13 @@ struct HfgEpi {
     float csp_slope;
 };
 
-__device__ __forceinline__ void hfg_store4(const HfgEpi& e, long long n, int C, int col, f32x4_t v) {
+__device__ __forceinline__ void hfg_store4(const HfgEpi& e, long long n, int C, int col, f32x4 v) {
     const size_t o = (size_t)n * C + col;
     const size_t po = ((size_t)n * (C >> 5) + (col >> 5)) * 64 + (col & 31);
-    if (e.resid) v += *reinterpret_cast<const f32x4_t*>(e.resid + o);
-    if (e.y) *reinterpret_cast<f32x4_t*>(e.y + o) = v;
+    if (e.resid) v += *reinterpret_cast<const f32x4*>(e.resid + o);
+    if (e.y) *reinterpret_cast<f32x4*>(e.y + o) = v;
     if (e.yp) {
-        f32x4_t a;
+        f32x4 a;
 #pragma unroll
         for (int i = 0; i < 4; ++i) a[i] = hfg_lrelu(v[i], e.slope);
         uint2 h, l;
@@ -113,11 +112,11 @@ __device__ __forceinline__ void hfg_store4(const HfgEpi& e, long long n, int C, 
         *reinterpret_cast<uint2*>(e.yp + po + 32) = l;
     }
     if (e.cs) {
-        f32x4_t s = v * e.cs_scale;
-        if (!e.first) s += *reinterpret_cast<const f32x4_t*>(e.cs + o);
-        *reinterpret_cast<f32x4_t*>(e.cs + o) = s;
+        f32x4 s = v * e.cs_scale;
+        if (!e.first) s += *reinterpret_cast<const f32x4*>(e.cs + o);
+        *reinterpret_cast<f32x4*>(e.cs + o) = s;
         if (e.csp) {
-            f32x4_t a;
+            f32x4 a;
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[i] = hfg_lrelu(s[i], e.csp_slope);
             uint2 h, l;
@@ -169,11 +168,11 @@ __device__ __forceinline__ void hfg_conv_body(const HfgConvArgs& a, u8* smem) {
     float* zt = reinterpret_cast<float*>(smem);
     for (int n_pass = 0; n_pass < a.cout; n_pass += PW) {
         const int n0 = n_pass + wn * TN * 16;
-        f32x4_t acc[TM][TN];
+        f32x4 acc[TM][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int l0 = 0; l0 < a.ldx; l0 += 4) {
             const int nl = min(4, a.ldx - l0);
             __syncthreads();
@@ -208,7 +207,7 @@ __device__ __forceinline__ void hfg_conv_body(const HfgConvArgs& a, u8* smem) {
             const int r = i / (PW / 4), c4 = (i - r * (PW / 4)) * 4;
             if (q0 + r >= a.m_in) continue;
             const long long n = TC ? (long long)(q0 + r) * a.stride + phase : (long long)(q0 + r);
-            hfg_store4(a.e, n, a.cout, n_pass + c4, *reinterpret_cast<const f32x4_t*>(zt + r * LDT + c4));
+            hfg_store4(a.e, n, a.cout, n_pass + c4, *reinterpret_cast<const f32x4*>(zt + r * LDT + c4));
         }
     }
 }

@@ -6,7 +6,6 @@
 
 namespace fcl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- plan-time packing ----------------------------------------------------------------------------
 __global__ void pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ out,

@@ -14,7 +14,6 @@
 
 namespace fcl {
 
-typedef unsigned short u16;
 
 // ---- one stage of UpsampleNetwork: Stretch2d(scale, nearest) + Conv2d(1, 1, (1, 2*scale+1), padding (0, scale), no bias), per channel.
 // in: [frames * rate_in rows, C]; out: [frames * rate_in * scale rows, C] (fp32 and / or planes with ldp lines per row, zero past C).
@@ -33,7 +32,7 @@ __global__ __launch_bounds__(256) void pwg_upsample_stage_kernel(const float* __
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long r = i / cq;
         const int c = (int)(i - r * cq) * 4;
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         if (c < C) {
             const int u = frame_utt[r / rate_out];
             const long long lo = (long long)utt_off[u] * rate_out, hi = (long long)utt_off[u + 1] * rate_out;
@@ -49,11 +48,11 @@ __global__ __launch_bounds__(256) void pwg_upsample_stage_kernel(const float* __
             for (int d = 0; d < 3; ++d) {
                 const long long ri = i0 + d - 1;
                 if (k[d] != 0.f && ri >= 0 && ri < rows_in) {
-                    const f32x4_t v = *reinterpret_cast<const f32x4_t*>(in + ri * C + c);
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(in + ri * C + c);
                     acc += k[d] * v;
                 }
             }
-            if (out) *reinterpret_cast<f32x4_t*>(out + r * C + c) = acc;
+            if (out) *reinterpret_cast<f32x4*>(out + r * C + c) = acc;
         }
         if (out_p) {
             uint2 h, l;
@@ -74,8 +73,8 @@ __global__ __launch_bounds__(256) void pwg_first_conv_kernel(const float* __rest
         const long long m = i / rq;
         const int ch = (int)(i - m * rq) * 4;
         const float zm = z[m];
-        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(w + ch) * zm + *reinterpret_cast<const f32x4_t*>(b + ch);
-        if (x) *reinterpret_cast<f32x4_t*>(x + m * R + ch) = v;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(w + ch) * zm + *reinterpret_cast<const f32x4*>(b + ch);
+        if (x) *reinterpret_cast<f32x4*>(x + m * R + ch) = v;
         uint2 h, l;
         split4(v, h, l);
         u16* line = chunk_major ? xp + ((size_t)(ch >> 5) * M + m) * 64 + (ch & 31) : xp + ((size_t)m * (R >> 5) + (ch >> 5)) * 64 + (ch & 31);
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(256) void pwg_aux_coeff_kernel(const float* __restr
         const long long f = m / hop;
         const int r = (int)(f & 31);
         const long long w0 = (r >= 2 && r <= 29) ? (f >> 5) * 32 : ((f + 16) >> 5) * 32 - 16;
-        const f32x4_t k03 = *reinterpret_cast<const f32x4_t*>(kc + m * 8);
+        const f32x4 k03 = *reinterpret_cast<const f32x4*>(kc + m * 8);
         const float k4 = kc[m * 8 + 4];
         const float kv[5] = {k03[0], k03[1], k03[2], k03[3], k4};
         unsigned hw[16], lw[16];  // 32 columns, two bf16 per word
@@ -296,12 +295,12 @@ __global__ __launch_bounds__(256) void pwg_gather_pad_kernel(const float* __rest
     const long long total = (long long)pad_cap * cq;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(i / cq), c = (int)(i - (long long)j * cq) * 4;
-        f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (j < live_pad) {
             const int src = pad_idx[j];
-            if ((unsigned)src < (unsigned)mel_rows) v = *reinterpret_cast<const f32x4_t*>(mel + (size_t)src * C + c);
+            if ((unsigned)src < (unsigned)mel_rows) v = *reinterpret_cast<const f32x4*>(mel + (size_t)src * C + c);
         }
-        *reinterpret_cast<f32x4_t*>(out + (size_t)j * C + c) = v;
+        *reinterpret_cast<f32x4*>(out + (size_t)j * C + c) = v;
     }
 }
 
@@ -321,7 +320,7 @@ __global__ __launch_bounds__(256) void pwg_first_conv_cap_kernel(const float* __
         const long long m = i / rq;
         const int ch = (int)(i - m * rq) * 4;
         const float zm = z[m];
-        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(w + ch) * zm + *reinterpret_cast<const f32x4_t*>(b + ch);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(w + ch) * zm + *reinterpret_cast<const f32x4*>(b + ch);
         uint2 h, l;
         split4(v, h, l);
         u16* line = xp + ((size_t)(ch >> 5) * m_cap + m) * 64 + (ch & 31);
@@ -340,7 +339,7 @@ __global__ __launch_bounds__(256) void pwg_pcm16_kernel(const float* __restrict_
         const long long i = q * 4;
         short o[4] = {0, 0, 0, 0};
         if (i + 4 <= n) {
-            const f32x4_t v = *reinterpret_cast<const f32x4_t*>(wav + i);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(wav + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float x = v[e];
