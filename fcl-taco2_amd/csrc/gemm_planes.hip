@@ -406,10 +406,11 @@ __device__ __forceinline__ void pgemm_epilogue(const GemmArgs& a_, f32x4 (&acc)[
     if (a.dbg_phase == 2) return;  // developer timing aid: no write-out
     const int rows = RP ? BM : min(BM, a_M - m0);  // staging rows to write out; RP: staging row rm holds tile row (rm & ~15) + rho16(rm & 15)
     auto trow = [&](int rm) { return RP ? (rm & ~15) + rho16(rm & 15) : rm; };
-    if (a.bn_ws) {  // BatchNorm statistics of the staged outputs (GemmArgs::bn_ws): rows past M and columns past N are staged as zeros
+    // (96-column tiles have no whole number of threads per column: launch_gemm_planes never hands them a launch with bn_ws)
+    if constexpr (CTHREADS % BN == 0) if (a.bn_ws) {  // BatchNorm statistics of the staged outputs (GemmArgs::bn_ws): rows past M and columns past N are staged as zeros
         __shared__ int bn_last;
         constexpr int RG = CTHREADS / BN;  // row groups: RG threads per column
-        static_assert(CTHREADS % BN == 0 && RG >= 1, "one or more whole threads per tile column");
+        static_assert(RG >= 1, "one or more whole threads per tile column");
         const int cn = threadIdx.x % BN, rg = threadIdx.x / BN, n = n0 + cn;
         double sm = 0.0, sq = 0.0;
         for (int rm = rg; rm < BM; rm += RG) {
@@ -783,7 +784,11 @@ template <int WM, int WN, int TM, int TN>
 struct CGeo {
     static constexpr int BM = 16 * WM * TM, BN = 16 * WN * TN, NW = WM * WN, NL = 2, THREADS = 64 * (NW + NL), CTHREADS = 64 * NW;  // NL loader waves
     static constexpr int HALO = 8, AROWS = BM + 2 * HALO, A_BYTES = AROWS * 128, W_BYTES = BN * 128, NSTW = 3;  // NSTW: W ring stages (two bundles ahead)
-    static constexpr int LDS_BYTES = 2 * A_BYTES + NSTW * W_BYTES;
+    // the epilogue stages the finished BM x BN tile as fp32 over the idle ring: the 256-row tiles' staging tile (132 KB at 128 columns) is larger than their
+    // ring (116 KB), so the allocation is the larger of the two; every tile of up to 128 rows stages inside its ring as before
+    static constexpr int RING_BYTES = 2 * A_BYTES + NSTW * W_BYTES, STAGING_BYTES = BM * (BN + 4) * 4;
+    static constexpr int LDS_BYTES = RING_BYTES > STAGING_BYTES ? RING_BYTES : STAGING_BYTES;
+    static_assert(LDS_BYTES <= 160 * 1024, "one CU's LDS");
     static constexpr int GAH = AROWS / 8 / NL, GB = BN / 8 / NL;
     static_assert((AROWS / 8) % NL == 0 && (BN / 8) % NL == 0, "tile rows must split evenly over the loader waves");
     static_assert(GAH + GB <= 60, "s_waitcnt vmcnt is a 6-bit field");
@@ -1000,6 +1005,25 @@ int launch_gemm_planes(const GemmArgs& a, hipStream_t s) {
         // (round 6: 150 -> 60 -- the 128-row stencil wherever it has 60 tiles: +0.4 ... +1.0 % on the four-pass line in three same-box scans, everything else flat:
         // profiles/r6_tile_sweep.log, r6_tunable_scan_synth_pconv.log)
         static const int cbig_min = tunable("PCONV_BIG_MIN", 60);
+        // TALL tiles (256 rows, TM = 4): the ring steps of a tile stream the layer's whole weight set whatever the tile's height, so twice the rows per
+        // workgroup halve the weight fill per output row and cut the CU-time of the layer by a third.  96-COLUMN tiles (TN = 3): 64 < N <= 96
+        // (the last postnet layer: 80 mel bins) as ONE column tile instead of two 64-column tiles.  Both only with the plain epilogue (bias, activation,
+        // residual, fp32 / planes out); same products in the same order per output element: bit-identical results.
+        //   FCL_PCONV_TALL_MIN: 256-row tiles for launches with at least so many of them; 0 (default) = never -- measured on the four-pass line at 40
+        //   (the postnet: 98 tiles) -0.5 %, at 20 (the encoder / predictor convolutions too) -2 % (profiles/r7_pconv_tall_ab.log, r7_pconv_tall_scan.log)
+        //   FCL_PCONV_N96_MIN: the 128 x 96 tile from so many 128-row tiles on (0 = never); 60 as FCL_PCONV_BIG_MIN: +1.2 / +1.3 % on two boxes, every run above every run
+        //   of the parent (same log)
+        static const int tall_min = tunable("PCONV_TALL_MIN", 0), n96_min = tunable("PCONV_N96_MIN", 60);
+        const bool plain_ep = !a.bn_ws && !a.loss_t && !a.Y2 && a.drop_mode == 0 && !a.rank1_a && !a.C0 && !(a.g_a || a.g_w || a.g_y || a.g_yp);
+        if (plain_ep) {
+            const long long rt256 = (a.M + 255) / 256, rt128 = (a.M + 127) / 128;
+            if (a.N > 64 && a.N <= 96) {
+                if (tall_min > 0 && rt256 >= tall_min) return launch_pconv_cfg<4, 2, 4, 3>(a, s, flops);
+                if (n96_min > 0 && rt128 >= n96_min) return launch_pconv_cfg<4, 2, 2, 3>(a, s, flops);
+            } else if (tall_min > 0 && a.N >= 128 && rt256 * ((a.N + 127) / 128) >= tall_min) {
+                return launch_pconv_cfg<4, 2, 4, 4>(a, s, flops);
+            }
+        }
         if (t128x128 >= cbig_min && a.N >= 128) return launch_pconv_cfg<4, 2, 2, 4>(a, s, flops);
         if (t64x128 >= 250 && a.N >= 96) return launch_pconv_cfg<2, 2, 2, 4>(a, s, flops);
         return launch_pconv_cfg<2, 2, 2, 2>(a, s, flops);
