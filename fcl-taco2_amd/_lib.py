@@ -116,6 +116,11 @@ class GriffinLim(C.Structure):  # fcl_gl_t
         (n, _P) for n in ("window", "twiddle", "frame_utt", "utt_off", "utt_seed", "s", "p", "fr", "y", "c_prev", "c_out", "u_out")]
 
 
+class Features(C.Structure):  # fcl_fx_t
+    _fields_ = [("frames", C.c_int64), ("samples", C.c_int64)] + [(n, C.c_int32) for n in ("n_fft", "hop", "n_utt", "n_mels", "nnz", "reserved")] + [
+        (n, _P) for n in ("x", "smp_off", "frame_utt", "utt_off", "window", "twiddle", "fb_lo", "fb_off", "fb_w", "mel_stats", "mel", "energy", "mag_out")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -276,6 +281,8 @@ SIGNATURES = {
     "fcl_gl_synth_fwd": (_I, [C.POINTER(GriffinLim), _P]),
     "fcl_gl_ola_fwd": (_I, [C.POINTER(GriffinLim), _P]),
     "fcl_gl_analysis_fwd": (_I, [C.POINTER(GriffinLim), _P]),
+    "fcl_fx_logmel_fwd": (_I, [C.POINTER(Features), _P]),
+    "fcl_fx_segment_mean_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

@@ -1,6 +1,7 @@
 """Host-side batching shared by the pipelined drivers (decode.py, tts.py, vocoder_decode.py): the capacity sizing of a length bucket, the bucket
 policy (BucketStore: calibrate once, estimate later buckets, widen after an overflow, keep the least recently used ones), the writer thread, and the
-per-chunk selection helpers.  No device call and no torch in here: the drivers keep their submit loops and hand in what differs (how a bucket is
+per-chunk selection helpers, and the frame-count packing of the drivers that take whole utterances (make_batches: vocoder_decode.py,
+extract_features.py).  No device call and no torch in here: the drivers keep their submit loops and hand in what differs (how a bucket is
 made, how its batches in flight are harvested), so the policy runs on the CPU with fakes (tests/test_batching.py)."""
 import collections
 import queue
@@ -91,6 +92,21 @@ class BucketStore(object):
             del self.buckets[old_cap]
             self.evicted += 1
         return b
+
+
+def make_batches(lengths, batch_frames):
+    """Indices sorted by length (longest first), cut into batches of at most `batch_frames` frames (at least one utterance each)."""
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])
+    out, cur, tot = [], [], 0
+    for i in order:
+        if cur and tot + lengths[i] > batch_frames:
+            out.append(cur)
+            cur, tot = [], 0
+        cur.append(i)
+        tot += lengths[i]
+    if cur:
+        out.append(cur)
+    return out
 
 
 class Writer(object):

@@ -257,6 +257,16 @@ class GriffinLim(Generator):
             return self._results(outs, dict(S=S, P=P, lens=lens), flat, return_intermediates, return_flat)
 
 
+def add_analysis_arguments(g):
+    """The analysis flags alone (the feature-extraction driver takes these without the Griffin-Lim ones)"""
+    g.add_argument("--fs", type=int, default=DEFAULTS["fs"], help="sampling rate")
+    g.add_argument("--n-fft", type=int, default=DEFAULTS["n_fft"])
+    g.add_argument("--hop", type=int, default=DEFAULTS["hop"])
+    g.add_argument("--win-length", type=int, default=None, help="window length (default: n_fft)")
+    g.add_argument("--fmin", type=float, default=DEFAULTS["fmin"])
+    g.add_argument("--fmax", type=float, default=DEFAULTS["fmax"])
+
+
 def add_arguments(ap):
     """The drivers' Griffin-Lim flags; the analysis flags default to the reference's preprocess.py."""
     g = ap.add_argument_group("Griffin-Lim (no vocoder checkpoint)")
@@ -264,12 +274,7 @@ def add_arguments(ap):
     g.add_argument("--mel-basis", default=None, metavar="FILE.npy", help="[n_mels, n_fft / 2 + 1] mel filterbank replacing the built Slaney one")
     g.add_argument("--gl-iters", type=int, default=DEFAULTS["n_iter"], help="Griffin-Lim iterations")
     g.add_argument("--gl-momentum", type=float, default=DEFAULTS["momentum"], help="momentum of the fast Griffin-Lim update (0: the classic form)")
-    g.add_argument("--fs", type=int, default=DEFAULTS["fs"], help="sampling rate")
-    g.add_argument("--n-fft", type=int, default=DEFAULTS["n_fft"])
-    g.add_argument("--hop", type=int, default=DEFAULTS["hop"])
-    g.add_argument("--win-length", type=int, default=None, help="window length (default: n_fft)")
-    g.add_argument("--fmin", type=float, default=DEFAULTS["fmin"])
-    g.add_argument("--fmax", type=float, default=DEFAULTS["fmax"])
+    add_analysis_arguments(g)
 
 
 def check_arguments(ap, args, checkpoint):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import kaldi_io, ops
-from .batching import Writer
+from .batching import Writer, make_batches  # noqa: F401  (make_batches: also this module's name for it)
 from .sharding import shard_utterances
 from .vocoder import CONFIG, PWGPlan, ParallelWaveGANGenerator
 
@@ -195,21 +195,6 @@ def write_wav(path, samples, rate):
         w.setsampwidth(2)
         w.setframerate(rate)
         w.writeframes(pcm.tobytes())
-
-
-def make_batches(lengths, batch_frames):
-    """Indices sorted by length (longest first), cut into batches of at most `batch_frames` frames (at least one utterance each)."""
-    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])
-    out, cur, tot = [], [], 0
-    for i in order:
-        if cur and tot + lengths[i] > batch_frames:
-            out.append(cur)
-            cur, tot = [], 0
-        cur.append(i)
-        tot += lengths[i]
-    if cur:
-        out.append(cur)
-    return out
 
 
 def decode(gen, feats, outdir, rate, batch_frames=51200, seed=0, depth=2):

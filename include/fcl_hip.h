@@ -954,6 +954,46 @@ int fcl_gl_synth_fwd(const fcl_gl_t* a, fcl_stream_t stream);
 int fcl_gl_ola_fwd(const fcl_gl_t* a, fcl_stream_t stream);
 int fcl_gl_analysis_fwd(const fcl_gl_t* a, fcl_stream_t stream);
 
+/* ---- Feature extraction: waveform -> log-mel rows, frame energy and phoneme-level means (fcl_taco2_amd/features.py; restated in float64
+ *      numpy in tests/features_ref.py).  The forward half of the Griffin-Lim block above, on the same LDS-resident FFT (csrc/gl_fft.h), same window,
+ *      twiddle table and filterbank B.
+ * Inputs: x, the utterances' float samples back to back; utterance u owns the samples smp_off[u] .. smp_off[u + 1] (L_u of them, any length that is
+ *      at least n_fft / 2 + 1, so that the reflection at either end is a single one) and the T_u = L_u / hop + 1 (integer division) frames
+ *      utt_off[u] .. utt_off[u + 1]; frame_utt [frames] / utt_off [n_utt + 1] as fcl_gl_*.
+ * Frame t of an utterance: samples q = t * hop + n - n_fft / 2, n < n_fft, with q < 0 -> -q and q >= L -> 2 (L - 1) - q (reflect padding); times the
+ *      window; real FFT X[k], k <= n_fft / 2 (imaginary parts of the DC and Nyquist bins zero).
+ * S[k] = |X[k]|  (to mag_out [frames, n_fft / 2 + 1] when that pointer is given: tests and diagnostics; otherwise the magnitudes stay in LDS).
+ * energy[f] = sqrt(sum_k S[k]^2), summed in a fixed order (no atomics).
+ * mel[f, c] = log10(max(1e-10, sum_k S[k] B[c, k])); with mel_stats ([2, n_mels]: mean, std) then (v - mean[c]) / (std[c] + 1e-8).  B arrives in banded
+ *      form: row c is zero outside the bins fb_lo[c] .. fb_lo[c] + (fb_off[c + 1] - fb_off[c]) and holds fb_w[fb_off[c] .. fb_off[c + 1]) there
+ *      (fb_lo [n_mels], fb_off [n_mels + 1], fb_w [nnz]); the sum runs in ascending k.  n_mels <= 256.
+ * A batch is bit for bit its per-utterance runs.  Supported: n_fft 512 / 1024 / 2048, 1 <= hop <= n_fft / 2; window and twiddle 8-byte aligned;
+ *      frames x max(n_fft / 2 + 1, n_mels) and samples (the length of x) below 2^31.  Shorter utterances are refused by the package, by id, before any
+ *      device call; the kernel clamps and stays inside x for any L_u >= 1.  No entry allocates, synchronises or copies.
+ * fcl_fx_segment_mean_fwd: out[p] = the mean of v over the frames of phoneme p in ascending frame order, 0 for an empty set.  Phoneme p of utterance
+ *      u = ph_utt[p] (phonemes ph_off[u] .. ph_off[u + 1]) owns the frames [a, a + dur[p]), a = utt_off[u] + the sum of dur over the utterance's
+ *      earlier phonemes, cut at utt_off[u + 1].  nonzero_only != 0: only frames with mask[frame] != 0 count (phoneme-level log F0 over voiced frames). */
+typedef struct {
+    int64_t frames, samples;
+    int32_t n_fft, hop, n_utt, n_mels, nnz, reserved;
+    const float* x;
+    const int32_t* smp_off;
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    const float* window;
+    const float* twiddle;
+    const int32_t* fb_lo;
+    const int32_t* fb_off;
+    const float* fb_w;
+    const float* mel_stats;
+    float* mel;
+    float* energy;
+    float* mag_out;
+} fcl_fx_t;
+int fcl_fx_logmel_fwd(const fcl_fx_t* a, fcl_stream_t stream);
+int fcl_fx_segment_mean_fwd(const float* v, const float* mask, const int32_t* dur, const int32_t* ph_utt, const int32_t* ph_off, const int32_t* utt_off,
+                            float* out, int64_t n_ph, int n_utt, int64_t frames, int nonzero_only, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
