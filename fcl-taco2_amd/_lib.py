@@ -121,6 +121,11 @@ class Features(C.Structure):  # fcl_fx_t
         (n, _P) for n in ("x", "smp_off", "frame_utt", "utt_off", "window", "twiddle", "fb_lo", "fb_off", "fb_w", "mel_stats", "mel", "energy", "mag_out")]
 
 
+class Pitch(C.Structure):  # fcl_px_t
+    _fields_ = [("frames", C.c_int64), ("samples", C.c_int64)] + [(n, C.c_int32) for n in ("n", "hop", "n_utt", "tau_min", "tau_max", "reserved")] + [
+        ("fs", _F), ("threshold", _F)] + [(n, _P) for n in ("x", "smp_off", "frame_utt", "utt_off", "f0", "cmnd_out", "tau_out")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -283,6 +288,8 @@ SIGNATURES = {
     "fcl_gl_analysis_fwd": (_I, [C.POINTER(GriffinLim), _P]),
     "fcl_fx_logmel_fwd": (_I, [C.POINTER(Features), _P]),
     "fcl_fx_segment_mean_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
+    "fcl_px_yin_fwd": (_I, [C.POINTER(Pitch), _P]),
+    "fcl_px_short_run_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

@@ -1,21 +1,25 @@
 """wav -> training features driver on MI355X: the acoustic half of the reference's preprocessing step (log10 mel, frame energy, phoneme-level
 means, mean / std normalisation), written from the contract in include/fcl_hip.h "Feature extraction" and DESIGN.md §6e on fcl_taco2_amd/features.py.
 
-    python -m fcl_taco2_amd.extract_features --wav-dir wavs --feature-root feats --durations-dir durations --f0-dir f0 --train-list train.txt
+    python -m fcl_taco2_amd.extract_features --wav-dir wavs --feature-root feats --durations-dir durations --track-f0 --train-list train.txt
 
 Reads 16-bit PCM mono wavs at `--fs` (standard library `wave`; samples / 32768; no resampler), batches them by frame count, and writes under
 `--feature-root`:
     mels-ori/<utt>.npy  [T, n_mels] float32 log10 mel, T = samples // hop + 1
     en-ori/<utt>.npy    [T] frame energy ||S||_2; with --durations-dir [P] phoneme-level means, and
     durations_MFA/<utt>.npy  [P] the durations with the last entry adjusted so that they sum to T
-    f0-ori/<utt>.npy    [P] with --f0-dir (frame-level F0 tracks in Hz from any external tracker, 0 = unvoiced, truncated to T, zero-padded when
-                        shorter): phoneme-level means of log F0 over voiced frames, 0 for a phoneme without one
+    f0-ori/<utt>.npy    [P] with --track-f0 (the YIN tracker of fcl_taco2_amd/pitch.py, DESIGN.md §6f, on the batch's samples already on the device;
+                        --f0-floor / --f0-ceil / --f0-threshold / --f0-min-voiced / --f0-frame-length) or --f0-dir (frame-level F0 tracks in Hz
+                        from any other tracker, 0 = unvoiced, truncated to T, zero-padded when shorter): phoneme-level means of log F0 over
+                        voiced frames, 0 for a phoneme without one.  --f0-frames-out DIR also writes the tracker's frame-level tracks, <utt>.npy
+                        [T] float32 Hz: fed back through --f0-dir they reproduce f0-ori/ bit for bit
 With `--train-list` (utterance ids, one per line) the mean and population standard deviation over the listed utterances are accumulated in float64
 (F0: non-zero entries only) and written as mel_stats.npy [2, n_mels] and f0_en_stats.npy [f0_mean, f0_std, en_mean, en_std] (en_stats.npy
 [en_mean, en_std] without F0), and every utterance is normalised with them, (v - mean) / (std + 1e-8), into mels/ [T, n_mels], en/ [P, 1]
 ([T, 1] without --durations-dir) and f0/ [P, 1] (unvoiced phonemes stay 0): with durations_MFA/, the files a training manifest's input1 / input4 /
 input3 / input2 point at.
-Out of scope: F0 tracking, TextGrid parsing (durations come as .npy), writing the json manifests, resampling.
+Out of scope: parity with the reference's third-party F0 tracker (DIO + StoneMask), tracking across frames, TextGrid parsing (durations come as
+.npy), writing the json manifests, resampling.
 """
 import argparse
 import logging
@@ -26,7 +30,7 @@ import wave
 import numpy as np
 import torch
 
-from . import features, griffinlim
+from . import features, griffinlim, pitch
 from .batching import Writer, make_batches
 
 
@@ -111,15 +115,20 @@ def fit_track(f0, T):
     return np.concatenate([f0, np.zeros(T - len(f0), np.float32)])
 
 
-def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None):
-    """utts: [(utt_id, path)].  Writes the -ori files under root; returns the ids in input order."""
+def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None, tracker=None, f0_frames_out=None):
+    """utts: [(utt_id, path)].  Writes the -ori files under root; returns the ids in input order.  tracker (a pitch.PitchTracker on fx's hop and
+    sampling rate) takes the place of f0_dir's tracks; f0_frames_out: a directory for its frame-level tracks."""
     pl = fx.plan
     sub = lambda d: os.path.join(root, d)
-    for d in ["mels-ori", "en-ori"] + (["durations_MFA"] if durations_dir else []) + (["f0-ori"] if f0_dir else []):
+    for d in ["mels-ori", "en-ori"] + (["durations_MFA"] if durations_dir else []) + (["f0-ori"] if f0_dir or tracker else []):
         os.makedirs(sub(d), exist_ok=True)
+    if f0_frames_out:
+        os.makedirs(f0_frames_out, exist_ok=True)
     ids, paths = [u for u, _ in utts], dict(utts)
     n_samples = [wav_samples(paths[u], pl.fs) for u in ids]  # headers only: the samples are read batch by batch
     fx.check_lens(n_samples, ids)  # refused by id before the first device call
+    if tracker is not None:
+        tracker.check_lens(n_samples, ids)
     frame_lens = [fx.frames_of(n) for n in n_samples]
 
     def write(items):
@@ -131,14 +140,22 @@ def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None)
         for idx in make_batches(frame_lens, batch_frames):
             bid = [ids[i] for i in idx]
             waves = [read_wav(paths[u], pl.fs) for u in bid]
-            mel, energy, T = fx.extract_packed(np.concatenate(waves), [len(w) for w in waves], ids=bid)
+            if tracker is None:
+                mel, energy, T = fx.extract_packed(np.concatenate(waves), [len(w) for w in waves], ids=bid)
+            else:  # one upload and one set of maps for the mel launch and the tracker's two
+                lens = [len(w) for w in waves]
+                x = torch.from_numpy(np.concatenate(waves)).to(pl.device)
+                mp = features.Maps(lens, pl.hop, pl.device)
+                mel, energy, T = fx.extract_packed(x, lens, ids=bid, maps=mp)
+                f0 = tracker.track_packed(x, lens, ids=bid, maps=mp)[0].cpu().numpy()
             if durations_dir:
                 durs = [np.load(os.path.join(durations_dir, u + ".npy")) for u in bid]
                 en, durs = fx.phoneme_means(energy, T, durs, ids=bid)
                 en = en.cpu().numpy()
                 ph = np.concatenate([[0], np.cumsum([len(d) for d in durs])])
-                if f0_dir:
-                    f0 = np.concatenate([fit_track(np.load(os.path.join(f0_dir, u + ".npy")), t) for u, t in zip(bid, T)])
+                if f0_dir or tracker is not None:
+                    if tracker is None:
+                        f0 = np.concatenate([fit_track(np.load(os.path.join(f0_dir, u + ".npy")), t) for u, t in zip(bid, T)])
                     lf0, _ = fx.phoneme_means(log_f0(f0), T, durs, mask=f0, ids=bid)
                     lf0 = lf0.cpu().numpy()
             mel, energy = mel.cpu().numpy(), energy.cpu().numpy()
@@ -149,10 +166,12 @@ def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None)
                 if durations_dir:
                     items.append((os.path.join(sub("en-ori"), u + ".npy"), en[ph[j] : ph[j + 1]].copy()))
                     items.append((os.path.join(sub("durations_MFA"), u + ".npy"), durs[j]))
-                    if f0_dir:
+                    if f0_dir or tracker is not None:
                         items.append((os.path.join(sub("f0-ori"), u + ".npy"), lf0[ph[j] : ph[j + 1]].copy()))
                 else:
                     items.append((os.path.join(sub("en-ori"), u + ".npy"), energy[fo[j] : fo[j + 1]].copy()))
+                if f0_frames_out:
+                    items.append((os.path.join(f0_frames_out, u + ".npy"), f0[fo[j] : fo[j + 1]].copy()))
             wr.put(items)
     finally:
         wr.join()
@@ -201,6 +220,8 @@ def build_parser():
     ap.add_argument("--feature-root", required=True, metavar="DIR")
     ap.add_argument("--durations-dir", default=None, metavar="DIR", help="<utt>.npy integer phoneme durations in frames: energy (and F0) become phoneme-level")
     ap.add_argument("--f0-dir", default=None, metavar="DIR", help="<utt>.npy frame-level F0 in Hz (0 = unvoiced) from an external tracker; needs --durations-dir")
+    ap.add_argument("--track-f0", action="store_true", help="track F0 on the GPU (YIN) in place of --f0-dir; needs --durations-dir")
+    ap.add_argument("--f0-frames-out", default=None, metavar="DIR", help="with --track-f0: also write the frame-level tracks <utt>.npy [T] float32 Hz")
     ap.add_argument("--train-list", default=None, metavar="FILE", help="utterance ids (one per line) the statistics are taken over; writes the normalised files")
     ap.add_argument("--batch-frames", type=int, default=51200, help="frames per GPU batch")
     ap.add_argument("--n-mels", type=int, default=griffinlim.DEFAULTS["n_mels"])
@@ -209,6 +230,7 @@ def build_parser():
     g = ap.add_argument_group("analysis (the defaults are the reference's preprocessing)")
     g.add_argument("--mel-basis", default=None, metavar="FILE.npy", help="[n_mels, n_fft / 2 + 1] mel filterbank replacing the built Slaney one")
     griffinlim.add_analysis_arguments(g)
+    pitch.add_pitch_arguments(ap.add_argument_group("F0 tracking (--track-f0; the defaults are the range of the reference's tracker)"))
     return ap
 
 
@@ -218,6 +240,12 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.f0_dir and not args.durations_dir:
         ap.error("--f0-dir needs --durations-dir (F0 is written as phoneme-level means)")
+    if args.track_f0 and args.f0_dir:
+        ap.error("--track-f0 and --f0-dir are mutually exclusive (one source of F0)")
+    if args.track_f0 and not args.durations_dir:
+        ap.error("--track-f0 needs --durations-dir (F0 is written as phoneme-level means)")
+    if args.f0_frames_out and not args.track_f0:
+        ap.error("--f0-frames-out needs --track-f0 (it writes the tracker's frame-level tracks)")
     if args.batch_frames < 1:
         ap.error("--batch-frames must be positive")
     for flag, d in (("--wav-dir", args.wav_dir), ("--durations-dir", args.durations_dir), ("--f0-dir", args.f0_dir)):
@@ -230,6 +258,8 @@ def parse_args(argv=None):
         griffinlim.check_config(args.n_fft, args.hop, args.n_fft if args.win_length is None else args.win_length, args.n_mels, args.fs, args.fmin, args.fmax)
     except (NotImplementedError, ValueError) as e:
         ap.error(str(e))
+    if args.track_f0:
+        pitch.check_arguments(ap, args)
     return args
 
 
@@ -243,9 +273,11 @@ def main(argv=None):
             train_ids = [ln.strip() for ln in f if ln.strip()]
     t0 = time.perf_counter()
     fx = features.from_args(args, args.device)
-    ids = extract(fx, utts, args.feature_root, args.batch_frames, args.durations_dir, args.f0_dir)
+    tracker = pitch.from_args(args, args.device) if args.track_f0 else None
+    ids = extract(fx, utts, args.feature_root, args.batch_frames, args.durations_dir, args.f0_dir, tracker, args.f0_frames_out)
     torch.cuda.synchronize()
-    stats = normalise_all(args.feature_root, ids, train_ids, bool(args.durations_dir), bool(args.f0_dir)) if train_ids is not None else None
+    have_f0 = bool(args.f0_dir) or args.track_f0
+    stats = normalise_all(args.feature_root, ids, train_ids, bool(args.durations_dir), have_f0) if train_ids is not None else None
     logging.info("extracted %d utterances in %.2f s", len(ids), time.perf_counter() - t0)
     return ids, stats
 

@@ -164,9 +164,10 @@ class FeatureExtractor(object):
     def check_lens(self, lens, ids=None):
         check_lens(lens, self.plan.n_fft, ids)
 
-    def extract_packed(self, wave, lens, return_magnitudes=False, ids=None):
+    def extract_packed(self, wave, lens, return_magnitudes=False, ids=None, maps=None):
         """wave: the utterances' samples back to back ([sum L] float32, device tensor or array), lens: samples per utterance ->
-        (mel_rows [sum T, n_mels], energy [sum T], frame_lens) (+ the magnitudes [sum T, F] with return_magnitudes): ONE launch."""
+        (mel_rows [sum T, n_mels], energy [sum T], frame_lens) (+ the magnitudes [sum T, F] with return_magnitudes): ONE launch.  maps: the batch's
+        Maps when the caller has built them already (pitch.PitchTracker.track_packed takes the same ones)."""
         pl, dev = self.plan, self.plan.device
         lens = [int(n) for n in lens]
         self.check_lens(lens, ids)
@@ -174,7 +175,9 @@ class FeatureExtractor(object):
             x = torch.as_tensor(wave).to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
             if x.numel() != sum(lens):
                 raise _lib.FclError("fcl-taco2_amd: features: the packed waveform has %d samples, lens sum to %d" % (x.numel(), sum(lens)))
-            mp = Maps(lens, pl.hop, dev)
+            mp = Maps(lens, pl.hop, dev) if maps is None else maps
+            if mp.sample_lens != lens:
+                raise _lib.FclError("fcl-taco2_amd: features: the maps passed in belong to another batch")
             if mp.samples >= 2 ** 31 - 1 or mp.frames * max(pl.bins, pl.A) >= 2 ** 31 - 1:
                 raise _lib.FclError("fcl-taco2_amd: more than 2^31 samples or frames x bins in one feature batch")
             mel = torch.empty(mp.frames, pl.A, device=dev, dtype=torch.float32)

@@ -994,6 +994,44 @@ int fcl_fx_logmel_fwd(const fcl_fx_t* a, fcl_stream_t stream);
 int fcl_fx_segment_mean_fwd(const float* v, const float* mask, const int32_t* dur, const int32_t* ph_utt, const int32_t* ph_off, const int32_t* utt_off,
                             float* out, int64_t n_ph, int n_utt, int64_t frames, int nonzero_only, fcl_stream_t stream);
 
+/* ---- F0 tracking: waveform -> frame-level F0 in Hz, 0 = unvoiced (fcl_taco2_amd/pitch.py; restated in float64 numpy in
+ *      tests/pitch_ref.py).  YIN (de Cheveigne & Kawahara 2002) steps 1 - 5 on the frame grid of the feature extraction above, so that a track has
+ *      exactly the T frames of the utterance's mel rows.
+ * Inputs: x / smp_off / frame_utt / utt_off as fcl_fx_*; utterance u has L_u samples and T_u = L_u / hop + 1 frames and needs L_u >= n / 2 + 1.
+ * Frame t: samples q = t * hop + j - n / 2, j < n, with q < 0 -> -q and q >= L -> 2 (L - 1) - q; NO window.  n (512 or 1024) is the pitch frame
+ *      length, W = n / 2 the integration length.
+ * Difference function, 0 <= tau <= tau_max + 1:  d(tau) = sum_{j < W} (x[j] - x[j + tau])^2  (= e(0) + e(tau) - 2 c(tau), e(tau) = sum_{j < W}
+ *      x[j + tau]^2, c(tau) = sum_{j < W} x[j] x[j + tau]).  tau_min = floor(fs / f0_ceil), tau_max = ceil(fs / f0_floor); 2 <= tau_min < tau_max <= n / 2 - 1.
+ *      The kernel sums the squared differences directly, in a fixed order, so that the error of d(tau) is relative to d(tau) itself.
+ * Cumulative-mean normalisation:  d'(0) = 1;  d'(tau) = d(tau) tau / sum_{j = 1 .. tau} d(j), and 1 where that sum is 0 (digital silence).  The sum
+ *      runs over ascending j in a fixed order (blocks of 8 lags in ascending j, the block totals in ascending block order); no atomics.
+ * Pick: the smallest tau in [tau_min, tau_max] with d'(tau) < threshold (a float; the package's default 0.1); from there tau + 1 while tau < tau_max and
+ *      d'(tau + 1) < d'(tau).  No such tau: the frame is unvoiced, F0 = 0 (tau_out 0).
+ * Parabola: a, b, c = d'(tau - 1), d'(tau), d'(tau + 1); delta = (a - c) / (2 (a - 2 b + c)) clamped to [-1/2, 1/2], 0 when the denominator is <= 0;
+ *      F0 = fs / (tau + delta).
+ * cmnd_out (optional, [frames, tau_max + 2] float: d'(0 .. tau_max + 1)) and tau_out (optional, [frames] int32: the picked integer lag) reach memory
+ *      only when given: tests and diagnostics.
+ * fcl_px_short_run_fwd: f0_out[f] = f0_in[f], but 0 where f lies in a run of non-zero frames shorter than min_voiced (>= 1; 1 keeps everything); a run
+ *      ends at its utterance's first and last frame, so runs never join across utterances.  f0_out must not be f0_in.
+ * A batch is bit for bit its per-utterance runs.  frames x (tau_max + 2) and samples below 2^31.  Shorter utterances and a tau range outside the
+ *      frame are refused by the package before any device call; the kernels clamp every index read from a device table and stay inside their
+ *      buffers for any L_u >= 1.  No entry allocates, synchronises or copies. */
+typedef struct {
+    int64_t frames, samples;
+    int32_t n, hop, n_utt, tau_min, tau_max, reserved;
+    float fs, threshold;
+    const float* x;
+    const int32_t* smp_off;
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    float* f0;
+    float* cmnd_out;
+    int32_t* tau_out;
+} fcl_px_t;
+int fcl_px_yin_fwd(const fcl_px_t* a, fcl_stream_t stream);
+int fcl_px_short_run_fwd(const float* f0_in, const int32_t* frame_utt, const int32_t* utt_off, float* f0_out, int64_t frames, int n_utt, int min_voiced,
+                         fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
