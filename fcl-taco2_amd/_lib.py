@@ -126,6 +126,11 @@ class Pitch(C.Structure):  # fcl_px_t
         ("fs", _F), ("threshold", _F)] + [(n, _P) for n in ("x", "smp_off", "frame_utt", "utt_off", "f0", "cmnd_out", "tau_out")]
 
 
+class Resample(C.Structure):  # fcl_rs_t
+    _fields_ = [("samples_in", C.c_int64), ("samples_out", C.c_int64)] + [(n, C.c_int32) for n in ("l", "m", "k", "n_utt", "max_out", "reserved")] + [
+        (n, _P) for n in ("x", "smp_off_in", "smp_off_out", "table", "y")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -290,6 +295,7 @@ SIGNATURES = {
     "fcl_fx_segment_mean_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     "fcl_px_yin_fwd": (_I, [C.POINTER(Pitch), _P]),
     "fcl_px_short_run_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
+    "fcl_rs_resample_fwd": (_I, [C.POINTER(Resample), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

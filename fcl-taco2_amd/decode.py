@@ -79,7 +79,9 @@ def read_manifest(json_path):
     utts = []
     for k, v in js.items():
         ids = np.array(list(map(int, v["output"][0]["tokenid"].split())), dtype=np.int64)
-        if len(v.get("input", [])) > 1 and "feat" in v["input"][1]:  # speaker embedding: `--use-speaker-embedding` data (tts.py:327-332, 285-287)
+        # speaker embedding: `--use-speaker-embedding` data (tts.py:327-332, 285-287).  A preprocessing manifest's input[1] is the durations file
+        # (filetype "npy", manifest.py): no embedding
+        if len(v.get("input", [])) > 1 and "feat" in v["input"][1] and v["input"][1].get("filetype") != "npy":
             from .kaldi_io import read_vec
 
             path, off = v["input"][1]["feat"].rsplit(":", 1)

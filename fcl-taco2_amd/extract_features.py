@@ -3,8 +3,9 @@ means, mean / std normalisation), written from the contract in include/fcl_hip.h
 
     python -m fcl_taco2_amd.extract_features --wav-dir wavs --feature-root feats --durations-dir durations --track-f0 --train-list train.txt
 
-Reads 16-bit PCM mono wavs at `--fs` (standard library `wave`; samples / 32768; no resampler), batches them by frame count, and writes under
-`--feature-root`:
+Reads 16-bit PCM mono wavs at `--fs` (standard library `wave`; samples / 32768), batches them by frame count, and writes under `--feature-root`.  A wav
+at another rate is refused unless `--resample` is given; it is then uploaded at its own rate and resampled on the device (fcl_taco2_amd/resample.py,
+DESIGN.md §6g) in front of the mel launch and the tracker:
     mels-ori/<utt>.npy  [T, n_mels] float32 log10 mel, T = samples // hop + 1
     en-ori/<utt>.npy    [T] frame energy ||S||_2; with --durations-dir [P] phoneme-level means, and
     durations_MFA/<utt>.npy  [P] the durations with the last entry adjusted so that they sum to T
@@ -18,8 +19,8 @@ With `--train-list` (utterance ids, one per line) the mean and population standa
 [en_mean, en_std] without F0), and every utterance is normalised with them, (v - mean) / (std + 1e-8), into mels/ [T, n_mels], en/ [P, 1]
 ([T, 1] without --durations-dir) and f0/ [P, 1] (unvoiced phonemes stay 0): with durations_MFA/, the files a training manifest's input1 / input4 /
 input3 / input2 point at.
-Out of scope: parity with the reference's third-party F0 tracker (DIO + StoneMask), tracking across frames, TextGrid parsing (durations come as
-.npy), writing the json manifests, resampling.
+TextGrid parsing, the symbol table, the split and the json manifests are fcl_taco2_amd/preprocess.py, which calls extract() and normalise_all() here.
+Out of scope: parity with the reference's third-party F0 tracker (DIO + StoneMask) and resampler, tracking across frames.
 """
 import argparse
 import logging
@@ -30,7 +31,7 @@ import wave
 import numpy as np
 import torch
 
-from . import features, griffinlim, pitch
+from . import features, griffinlim, pitch, resample
 from .batching import Writer, make_batches
 
 
@@ -39,7 +40,7 @@ def _check_header(f, path, fs):
         raise ValueError("%s: %d-byte samples; only 16-bit PCM is read" % (path, f.getsampwidth()))
     if f.getnchannels() != 1:
         raise ValueError("%s: %d channels; only mono is read" % (path, f.getnchannels()))
-    if f.getframerate() != fs:
+    if fs is not None and f.getframerate() != fs:
         raise ValueError("%s: sampling rate %d, --fs is %d (there is no resampler)" % (path, f.getframerate(), fs))
 
 
@@ -48,6 +49,13 @@ def wav_samples(path, fs):
     with wave.open(path, "rb") as f:
         _check_header(f, path, fs)
         return f.getnframes()
+
+
+def wav_rate_and_samples(path):
+    """(sampling rate, sample count) from the header alone, for a driver that resamples (the other refusals of read_wav)"""
+    with wave.open(path, "rb") as f:
+        _check_header(f, path, None)
+        return f.getframerate(), f.getnframes()
 
 
 def read_wav(path, fs):
@@ -115,9 +123,20 @@ def fit_track(f0, T):
     return np.concatenate([f0, np.zeros(T - len(f0), np.float32)])
 
 
-def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None, tracker=None, f0_frames_out=None):
+def _by_rate(idx, rates):
+    """a batch's indices split into runs of one sampling rate, in first-seen order (files of different rates cannot share a packed launch)"""
+    if rates is None:
+        return [(idx, None)]
+    groups = {}
+    for i in idx:
+        groups.setdefault(rates[i], []).append(i)
+    return [(g, r) for r, g in groups.items()]
+
+
+def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None, tracker=None, f0_frames_out=None, resampler_for=None):
     """utts: [(utt_id, path)].  Writes the -ori files under root; returns the ids in input order.  tracker (a pitch.PitchTracker on fx's hop and
-    sampling rate) takes the place of f0_dir's tracks; f0_frames_out: a directory for its frame-level tracks."""
+    sampling rate) takes the place of f0_dir's tracks; f0_frames_out: a directory for its frame-level tracks.  resampler_for (input rate -> a
+    resample.Resampler to fx's rate, e.g. a resample.ResamplerCache): wavs at another rate are resampled on the device instead of refused."""
     pl = fx.plan
     sub = lambda d: os.path.join(root, d)
     for d in ["mels-ori", "en-ori"] + (["durations_MFA"] if durations_dir else []) + (["f0-ori"] if f0_dir or tracker else []):
@@ -125,7 +144,19 @@ def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None,
     if f0_frames_out:
         os.makedirs(f0_frames_out, exist_ok=True)
     ids, paths = [u for u, _ in utts], dict(utts)
-    n_samples = [wav_samples(paths[u], pl.fs) for u in ids]  # headers only: the samples are read batch by batch
+    rates = None
+    if resampler_for is None:
+        n_samples = [wav_samples(paths[u], pl.fs) for u in ids]  # headers only: the samples are read batch by batch
+    else:  # the sample counts after resampling, in integers from the header's
+        rates, n_samples = [], []
+        for u in ids:
+            rate, n = wav_rate_and_samples(paths[u])
+            try:
+                L, M, _ = resample.check_rates(rate, pl.fs)
+            except (NotImplementedError, ValueError) as e:
+                raise type(e)("%s: %s" % (paths[u], e))
+            rates.append(rate)
+            n_samples.append(resample.out_samples(n, L, M))
     fx.check_lens(n_samples, ids)  # refused by id before the first device call
     if tracker is not None:
         tracker.check_lens(n_samples, ids)
@@ -137,14 +168,19 @@ def extract(fx, utts, root, batch_frames=51200, durations_dir=None, f0_dir=None,
 
     wr = Writer(write, 4)
     try:
-        for idx in make_batches(frame_lens, batch_frames):
+        for idx, rate in (g for b in make_batches(frame_lens, batch_frames) for g in _by_rate(b, rates)):
             bid = [ids[i] for i in idx]
-            waves = [read_wav(paths[u], pl.fs) for u in bid]
-            if tracker is None:
-                mel, energy, T = fx.extract_packed(np.concatenate(waves), [len(w) for w in waves], ids=bid)
-            else:  # one upload and one set of maps for the mel launch and the tracker's two
-                lens = [len(w) for w in waves]
+            waves = [read_wav(paths[u], pl.fs if rate is None else rate) for u in bid]
+            lens = [len(w) for w in waves]
+            if rate is not None and rate != pl.fs:  # uploaded at its own rate, resampled on the device
+                x, lens = resampler_for(rate).resample_packed(torch.from_numpy(np.concatenate(waves)).to(pl.device), lens, ids=bid)
+            elif tracker is None:
+                x = np.concatenate(waves)
+            else:
                 x = torch.from_numpy(np.concatenate(waves)).to(pl.device)
+            if tracker is None:
+                mel, energy, T = fx.extract_packed(x, lens, ids=bid)
+            else:  # one upload and one set of maps for the mel launch and the tracker's two
                 mp = features.Maps(lens, pl.hop, pl.device)
                 mel, energy, T = fx.extract_packed(x, lens, ids=bid, maps=mp)
                 f0 = tracker.track_packed(x, lens, ids=bid, maps=mp)[0].cpu().numpy()
@@ -223,6 +259,7 @@ def build_parser():
     ap.add_argument("--track-f0", action="store_true", help="track F0 on the GPU (YIN) in place of --f0-dir; needs --durations-dir")
     ap.add_argument("--f0-frames-out", default=None, metavar="DIR", help="with --track-f0: also write the frame-level tracks <utt>.npy [T] float32 Hz")
     ap.add_argument("--train-list", default=None, metavar="FILE", help="utterance ids (one per line) the statistics are taken over; writes the normalised files")
+    ap.add_argument("--resample", action="store_true", help="resample wavs whose rate is not --fs on the GPU instead of refusing them")
     ap.add_argument("--batch-frames", type=int, default=51200, help="frames per GPU batch")
     ap.add_argument("--n-mels", type=int, default=griffinlim.DEFAULTS["n_mels"])
     ap.add_argument("--device", default="cuda:0")
@@ -274,7 +311,8 @@ def main(argv=None):
     t0 = time.perf_counter()
     fx = features.from_args(args, args.device)
     tracker = pitch.from_args(args, args.device) if args.track_f0 else None
-    ids = extract(fx, utts, args.feature_root, args.batch_frames, args.durations_dir, args.f0_dir, tracker, args.f0_frames_out)
+    resampler_for = resample.ResamplerCache(args.device, args.fs) if args.resample else None
+    ids = extract(fx, utts, args.feature_root, args.batch_frames, args.durations_dir, args.f0_dir, tracker, args.f0_frames_out, resampler_for)
     torch.cuda.synchronize()
     have_f0 = bool(args.f0_dir) or args.track_f0
     stats = normalise_all(args.feature_root, ids, train_ids, bool(args.durations_dir), have_f0) if train_ids is not None else None

@@ -1032,6 +1032,35 @@ int fcl_px_yin_fwd(const fcl_px_t* a, fcl_stream_t stream);
 int fcl_px_short_run_fwd(const float* f0_in, const int32_t* frame_utt, const int32_t* utt_off, float* f0_out, int64_t frames, int n_utt, int min_voiced,
                          fcl_stream_t stream);
 
+/* ---- Resampling: waveform at fs_in -> waveform at fs_out, band-limited (fcl_taco2_amd/resample.py; restated in float64 numpy in
+ *      tests/resample_ref.py).  A Kaiser-windowed sinc evaluated exactly at the L phases of the rational ratio, in front of the two blocks above.
+ * fs_out / fs_in = L / M in lowest terms, s = min(1, L / M).  Z = 64 zero crossings, rho = 0.9475937167399596, beta = 14.769656459379492.
+ * h(tau) = s rho sinc(s rho tau) I0(beta sqrt(1 - u^2)) / I0(beta), u = s tau / Z; h = 0 for |u| >= 1; sinc(v) = sin(pi v) / (pi v).
+ * Utterance u owns the input samples smp_off_in[u] .. smp_off_in[u + 1] of x (n_in of them) and the output samples smp_off_out[u] ..
+ *      smp_off_out[u + 1] of y; the package sizes the latter as n_out = (n_in L) / M (integer division).
+ * Output t of an utterance: n = (t M) / L, p = (t M) mod L (64-bit integers), y[t] = sum_{j = -K .. K} c[p][j] x[n - j], c[p][j] = h(j + p / L),
+ *      K = ceil(Z / s); samples outside [0, n_in) count as zero.  The sum is one float32 fma chain in ascending j; no atomics and no order that
+ *      depends on the batch: a batch is bit for bit its per-utterance runs.
+ * table: the coefficients, built in float64 on the host and rounded to float32, TRANSPOSED: table[(j + K) L + p] = c[p][j]  ([2 K + 1][L] floats).
+ * One launch: a workgroup owns a tile of consecutive outputs of one utterance (grid: tiles of the longest utterance x n_utt), stages the input span
+ *      of the tile (zero-filled past either end of the utterance) in LDS once and reads every product's sample from there.  Where a tile holds whole
+ *      periods of L outputs its threads take them in the order of their phase p, so that a wave reads consecutive floats of a table row.
+ * max_out: the largest n_out of the batch (it sizes the grid; an utterance whose table entry says more is cut there).
+ * Supported: L, M >= 1 and coprime, K >= 1, n_utt <= 65535, samples_in and samples_out below 2^31, and an input span of 64 outputs that fits the
+ *      48 KB of LDS the kernel stages in: 64 M / L + 2 K + 2 <= 12288 (ratios down to 1 / 64).  The package refuses L > 1024 and tables above 4 MB
+ *      before any device call.  The kernel clamps every offset it reads from a device table and stays inside x and y for any table.
+ *      n_utt == 0 or max_out == 0: nothing is launched.  No entry allocates, synchronises or copies. */
+typedef struct {
+    int64_t samples_in, samples_out;
+    int32_t l, m, k, n_utt, max_out, reserved;
+    const float* x;
+    const int32_t* smp_off_in;
+    const int32_t* smp_off_out;
+    const float* table;
+    float* y;
+} fcl_rs_t;
+int fcl_rs_resample_fwd(const fcl_rs_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
