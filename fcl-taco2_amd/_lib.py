@@ -131,6 +131,12 @@ class Resample(C.Structure):  # fcl_rs_t
         (n, _P) for n in ("x", "smp_off_in", "smp_off_out", "table", "y")]
 
 
+class Evaluate(C.Structure):  # fcl_ev_t
+    _fields_ = [(n, C.c_int64) for n in ("frames_a", "frames_b", "cells", "path_rows")] + [(n, C.c_int32) for n in ("n_pairs", "d", "max_ta", "max_tb")] + [
+        (n, _P) for n in ("a", "b", "a_off", "b_off", "cell_off", "path_off", "workspace")] + [("workspace_bytes", _Z)] + [
+        (n, _P) for n in ("path", "path_len", "cost", "pitch_a", "pitch_b", "counts", "sums")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -296,6 +302,10 @@ SIGNATURES = {
     "fcl_px_yin_fwd": (_I, [C.POINTER(Pitch), _P]),
     "fcl_px_short_run_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
     "fcl_rs_resample_fwd": (_I, [C.POINTER(Resample), _P]),
+    "fcl_ev_dtw_workspace_bytes": (_Z, [C.c_int64, _I]),
+    "fcl_ev_cepstra_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
+    "fcl_ev_dtw_fwd": (_I, [C.POINTER(Evaluate), _P]),
+    "fcl_ev_path_pitch_fwd": (_I, [C.POINTER(Evaluate), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

@@ -1061,6 +1061,58 @@ typedef struct {
 } fcl_rs_t;
 int fcl_rs_resample_fwd(const fcl_rs_t* a, fcl_stream_t stream);
 
+/* ---- Evaluation: mel-cepstral distortion and F0 error over a dynamic-time-warping path (fcl_taco2_amd/metrics.py, evaluate.py; restated
+ *      in float64 numpy in tests/evaluate_ref.py).  Two utterances of Ta and Tb frames are compared on the frame grid of the blocks above.
+ * Cepstra (fcl_ev_cepstra_fwd): for a frame's log10-mel vector L[0 .. N), N = n_mels:  c_k = ln10 sqrt(2 / N) sum_m L[m] cos(pi k (m + 1/2) / N),
+ *      k = 1 .. D; c_0 is left out; 1 <= D <= min(N - 1, 40), N <= 256.  table [D][N] and bias [D] are built in float64 on the host and uploaded as
+ *      float32: row k - 1 of table is ln10 sqrt(2 / N) cos(pi k (m + 1/2) / N), times (std[m] + 1e-8) where the rows are normalised mels; bias is then
+ *      sum_m table_raw[k][m] mean[m], and zero for raw rows.  x [frames][N] -> c [frames][D]:  c = (sum_m table[k][m] x[m]) + bias[k], the sum ONE
+ *      float32 fma chain in ascending m from 0, the bias added last.  The table is staged in LDS.
+ * Local distance:  d(i, j) = sqrt(sum_k (a_i[k] - b_j[k])^2), from the differences, one float32 fma chain in ascending k.
+ * DTW (fcl_ev_dtw_fwd), symmetric steps, unit weights:  C(0, 0) = d(0, 0);  C(i, j) = d(i, j) + min(C(i - 1, j - 1), C(i - 1, j), C(i, j - 1)),
+ *      predecessors outside the matrix do not count.  Ties: the diagonal wins; (i - 1, j) replaces it only when strictly smaller; (i, j - 1)
+ *      replaces the winner only when strictly smaller.  The path is backtracked from (Ta - 1, Tb - 1) to (0, 0) and written in forward order as
+ *      (i, j) pairs; its length n satisfies max(Ta, Tb) <= n <= Ta + Tb - 1.  cost = C(Ta - 1, Tb - 1);  MCD_dB = (10 sqrt 2 / ln 10) cost / n (host).
+ * Pitch (fcl_ev_path_pitch_fwd): pitch_a [frames_a] / pitch_b [frames_b] hold cents above 1 Hz, p = 1200 log2 f0, 0 (or anything not > 0) for an
+ *      unvoiced frame.  Over the path cells: n_vv counts both voiced, n_vuv exactly one voiced, S = sum_vv (p_a - p_b)^2, each thread over the
+ *      cells t, t + 256, ... in ascending order, then a fixed tree.  counts [n_pairs][2] = (n_vv, n_vuv), sums [n_pairs] = S.
+ *      F0_RMSE_cents = sqrt(S / n_vv) (NaN for n_vv = 0) and VUV_error = n_vuv / n are formed on the host.
+ * A batch of pairs is packed: pair p owns the rows a_off[p] .. a_off[p + 1] of a (Ta of them; pitch_a likewise), b_off likewise of b, the
+ *      back-pointer cells cell_off[p] .. cell_off[p + 1] (cumulative Ta Tb, int64) of the workspace and the rows path_off[p] .. path_off[p + 1]
+ *      (cumulative Ta + Tb - 1) of path [path_rows][2]; rows of a pair's path slice past its length are set to -1.  frames_a, frames_b, cells and
+ *      path_rows are the totals the tables end at.  One workgroup per pair, no atomics and no reduction whose order depends on the batch: a batch
+ *      is bit for bit its per-pair runs (path, path_len, cost, counts, sums).
+ * Workspace: fcl_ev_dtw_workspace_bytes(total_cells, n_pairs) bytes; its layout is the library's own (one back-pointer per cell).
+ * Supported: 1 <= Ta, Tb <= 4096 (max_ta, max_tb: the batch's largest), n_pairs <= 65535, 1 <= D <= 40.  The kernels clamp every offset they read
+ *      from a device table and every index they read from the workspace or the path; a pair whose slices are smaller than its lengths need is
+ *      skipped (path_len 0, cost NaN).  Whatever the inputs hold, non-finite values included, the path written is a valid warping path and every
+ *      store stays inside the pair's slices.  Each entry validates before any HIP call: a null pointer FCL_ERR_INVALID; D, a length or a count out of
+ *      range FCL_ERR_SHAPE; a workspace that is too small FCL_ERR_WORKSPACE; n_pairs == 0 (frames == 0): nothing is launched.  No entry allocates,
+ *      synchronises or copies. */
+typedef struct {
+    int64_t frames_a, frames_b, cells, path_rows;
+    int32_t n_pairs, d, max_ta, max_tb;
+    const float* a;
+    const float* b;
+    const int32_t* a_off;
+    const int32_t* b_off;
+    const int64_t* cell_off;
+    const int32_t* path_off;
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* path;
+    int32_t* path_len;
+    float* cost;
+    const float* pitch_a;
+    const float* pitch_b;
+    int32_t* counts;
+    float* sums;
+} fcl_ev_t;
+size_t fcl_ev_dtw_workspace_bytes(int64_t total_cells, int n_pairs);
+int fcl_ev_cepstra_fwd(const float* x, const float* table, const float* bias, float* c, int64_t frames, int n_mels, int d, fcl_stream_t stream);
+int fcl_ev_dtw_fwd(const fcl_ev_t* a, fcl_stream_t stream);
+int fcl_ev_path_pitch_fwd(const fcl_ev_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
