@@ -287,11 +287,12 @@ __device__ __forceinline__ void rowtile_mma_x3(const u16* Ah, const u16* Al, int
 template <int NT, int NS>
 struct WFrag {
     s16x8 hi[NT][NS], lo[NT][NS];
+    template <int S0 = 0, int S1 = NS>  // k-steps S0 .. S1 - 1 (a caller short of registers requests the last steps later)
     __device__ __forceinline__ void load(const u16* const (&fhi)[NT], const u16* const (&flo)[NT]) {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int st = 0; st < NS; ++st) {  // every wave-wide load is one contiguous 1 KB fragment block
+            for (int st = S0; st < S1; ++st) {  // every wave-wide load is one contiguous 1 KB fragment block
                 hi[t][st] = *reinterpret_cast<const s16x8*>(fhi[t] + st * 512);
                 lo[t][st] = *reinterpret_cast<const s16x8*>(flo[t] + st * 512);
             }
@@ -743,11 +744,12 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
 template <int NT, int NS_>
 struct WFragF {
     f32x4 w0[NT][NS_], w1[NT][NS_];
+    template <int S0 = 0, int S1 = NS_>
     __device__ __forceinline__ void load(const float* const (&f)[NT]) {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int st = 0; st < NS_; ++st) {
+            for (int st = S0; st < S1; ++st) {
                 w0[t][st] = *reinterpret_cast<const f32x4*>(f[t] + st * 512);
                 w1[t][st] = *reinterpret_cast<const f32x4*>(f[t] + st * 512 + 4);
             }
@@ -939,8 +941,111 @@ __device__ __forceinline__ void gates_to_cell(const LstmStepArgs& a, int g, int 
     cell_finish(a, m, u, pre, ci);
 }
 
-// PRE: every term has K = 256 (the student's decoder LSTMs: two terms, or the input term alone in the zero-state form of step 0) -> all weight
-// fragments are requested at kernel entry.
+// A thread's share of a [16 x 256] fp32 row tile (rows m0.., clamped to M - 1), in two halves: request() issues the four float4 loads and nothing else,
+// so that a caller can have several tiles and its weight fragments in flight before the first wait; the store halves then split into the two LDS planes
+// (split_store, element mapping and rounding of load_rowtile_split) or copy (store).  256 threads.
+struct RowTile256 {
+    f32x4 v[4];
+    __device__ __forceinline__ void request(const float* src, int ld, int m0, int M) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
+            v[j] = *reinterpret_cast<const f32x4*>(src + (size_t)min(m0 + r, M - 1) * ld + c);
+        }
+    }
+    __device__ __forceinline__ void split_store(u16* Ah, u16* Al, int ldk) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
+            u16 h[4], l[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) split1(v[j][e], h[e], l[e]);
+            *reinterpret_cast<uint2*>(Ah + r * ldk + c) = make_uint2(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16));
+            *reinterpret_cast<uint2*>(Al + r * ldk + c) = make_uint2(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16));
+        }
+    }
+    __device__ __forceinline__ void store(float* dst, int ld_l) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
+            *reinterpret_cast<f32x4*>(dst + r * ld_l + c) = v[j];
+        }
+    }
+};
+
+constexpr int kSmallStepsAtEntry = 4;  // of term 1's eight k-steps of weight fragments, in the register-resident small steps (below)
+
+// The K walk of the register-resident small steps, NT = 1 or 2 terms of K = 256 (a template, not a run-time count: where the two forms share code the
+// compiler's wait counts are those of the form with fewer loads in flight).  Request order = order of use: every wave's activation rows (term 0 to
+// columns 0 - 255 of the K = 512 tile, term 1 to columns 256 - 511), an s_barrier (no data wait; as in feat_prenet_split_kernel: no wave's fragments in
+// front of another wave's rows), the weight fragments.  The rows' 32 registers are free once they are split into LDS (that wait covers the rows alone:
+// loads return in order); term 1's last k-steps then take their place, queued right behind the other fragments and first used ~40 MFMAs after the
+// barrier -- with all 16 steps requested at entry the kernel needs 184 VGPRs, two waves per SIMD instead of three.
+template <int NT>
+__device__ __forceinline__ f32x4 small_x3_walk(const LstmStepArgs& a, u16* A_h, u16* A_lo, int ldk, int m0, int M, int g, int u0, int lane) {
+    const int r16 = lane & 15, kq = lane >> 4;
+    RowTile256 rows[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) rows[t].request(a.term[t].A, a.term[t].lda, m0, M);
+    asm volatile("s_barrier" ::: "memory");
+    const size_t fo = (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8;  // W rows g*U + u0.. form fragment tile (g*U + u0)/16 (U % 16 == 0); 8 steps per row tile
+    WFrag<1, 8> wf[NT];
+    const u16* const wh0[1] = {a.term[0].Whi + fo};
+    const u16* const wl0[1] = {a.term[0].Wlo + fo};
+    const u16* const wh1[1] = {a.term[NT - 1].Whi + fo};
+    const u16* const wl1[1] = {a.term[NT - 1].Wlo + fo};
+    wf[0].load(wh0, wl0);
+    if (NT > 1) wf[NT - 1].template load<0, kSmallStepsAtEntry>(wh1, wl1);
+    __builtin_amdgcn_sched_barrier(0);  // (hipcc otherwise starts the split -- and its wait for the first row -- above the fragment requests)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) rows[t].split_store(A_h + t * 256, A_lo + t * 256, ldk);
+    asm volatile("" ::: "memory");  // (the late requests stay below the rows' last use)
+    if (NT > 1) wf[NT - 1].template load<kSmallStepsAtEntry, 8>(wh1, wl1);
+    __syncthreads();
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {  // the partial sums are formed and added as the one-term-at-a-time kernel did: 0 + term 0 + term 1
+        f32x4 part[1];
+        wf[t].mma(A_h + t * 256, A_lo + t * 256, ldk, 256, r16, kq, part);
+        acc += part[0];
+    }
+    return acc;
+}
+
+// the same walk on fragment-major fp32 weights and an fp32 tile (lstm_small_ff_kernel)
+template <int NT>
+__device__ __forceinline__ f32x4 small_ff_walk(const LstmStepArgs& a, float* A_f, int ld, int m0, int M, int g, int u0, int lane) {
+    const int r16 = lane & 15, kq = lane >> 4;
+    RowTile256 rows[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) rows[t].request(a.term[t].A, a.term[t].lda, m0, M);
+    asm volatile("s_barrier" ::: "memory");
+    const size_t fo = (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8;
+    WFragF<1, 8> wf[NT];
+    const float* const w0[1] = {a.term[0].Wff + fo};
+    const float* const w1[1] = {a.term[NT - 1].Wff + fo};
+    wf[0].load(w0);
+    if (NT > 1) wf[NT - 1].template load<0, kSmallStepsAtEntry>(w1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) rows[t].store(A_f + t * 256, ld);
+    asm volatile("" ::: "memory");
+    if (NT > 1) wf[NT - 1].template load<kSmallStepsAtEntry, 8>(w1);
+    __syncthreads();
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        f32x4 part[1];
+        mma_tf<1, 8>(wf[t], A_f + t * 256, ld, r16, kq, part);
+        acc += part[0];
+    }
+    return acc;
+}
+
+// PRE: every term has K = 256 (the student's decoder LSTMs: two terms, or the input term alone in the zero-state form of step 0) -> the activation
+// rows of every term and the weight fragments are requested at kernel entry (small_x3_walk; row stride KC + 16: 2 (mod 4) sixteen-byte slots, as
+// 256 + 16 is), ONE barrier, then the two terms' k-walks back to back.  (Until round 8 term 1's rows were requested after term 0's MFMAs, into term 0's
+// columns: a global round trip and two barriers exposed in every small step.)  Bit-identical outputs.
 template <bool PRE>
 __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a) {
     // device-driven loops: loads and MFMAs run on the host's row bound, only the final store is limited to the device's live-row count (its scalar
@@ -960,28 +1065,7 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
     CellIn ci;
     if (evalid) ci = cell_prefetch(a, em, eu);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    WFrag<1, 8> wf[2];
-    if (PRE) {
-        const int nt = a.nterms;  // 2, or 1 (wave-uniform)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {  // W rows g*U + u0.. form fragment tile (g*U + u0)/16 (U % 16 == 0); 8 steps per row tile
-            if (t >= nt) break;
-            const size_t fo = (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8;
-            const u16* const wh[1] = {a.term[t].Whi + fo};
-            const u16* const wl[1] = {a.term[t].Wlo + fo};
-            wf[t].load(wh, wl);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            if (t >= nt) break;
-            if (t) __syncthreads();
-            load_rowtile_split(A_h, A_lo, 256 + 16, a.term[t].A, a.term[t].lda, 256, m0, M);
-            __syncthreads();
-            f32x4 part[1];
-            wf[t].mma(A_h, A_lo, 256 + 16, 256, r16, kq, part);
-            acc += part[0];
-        }
-    }
+    if (PRE) acc = a.nterms == 2 ? small_x3_walk<2>(a, A_h, A_lo, KC + 16, m0, M, g, u0, lane) : small_x3_walk<1>(a, A_h, A_lo, KC + 16, m0, M, g, u0, lane);
     for (int t = 0; t < (PRE ? 0 : a.nterms); ++t) {
         const GemmTerm T = a.term[t];
         for (int k0 = 0; k0 < T.K; k0 += KC) {
@@ -1007,35 +1091,17 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
 __global__ __launch_bounds__(256) void lstm_small_ff_kernel(const LstmStepArgs a) {
     const int M = a.M, Ms = live_rows_of(a.M, a.m_dev);
     if ((int)blockIdx.y * 16 >= Ms) return;
-    constexpr int LD = 256 + 8;
+    constexpr int LD = 512 + 8;  // both terms' rows side by side (33 KB; row stride = 2 (mod 4) sixteen-byte slots, as 256 + 8 was), requested at entry
     __shared__ __attribute__((aligned(16))) float A_f[16 * LD];
     const int m0 = blockIdx.y * 16, u0 = blockIdx.x * 16;
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int r16 = lane & 15, kq = lane >> 4;
     const int erow = threadIdx.x >> 4, euc = threadIdx.x & 15;
     const int em = m0 + erow, eu = u0 + euc;
     const bool evalid = em < M && eu < a.U;
     CellIn ci;
     if (evalid) ci = cell_prefetch(a, em, eu);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    WFragF<1, 8> wf[2];
-    const int nt = a.nterms;  // 2, or 1 (wave-uniform)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (t >= nt) break;
-        const float* const w[1] = {a.term[t].Wff + (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8};
-        wf[t].load(w);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (t >= nt) break;
-        if (t) __syncthreads();
-        load_rowtile(A_f, LD, a.term[t].A, a.term[t].lda, 256, m0, M);
-        __syncthreads();
-        f32x4 part[1];
-        mma_tf<1, 8>(wf[t], A_f, LD, r16, kq, part);
-        acc += part[0];
-    }
+    acc = a.nterms == 2 ? small_ff_walk<2>(a, A_f, LD, m0, M, g, u0, lane) : small_ff_walk<1>(a, A_f, LD, m0, M, g, u0, lane);
     gates_to_cell(a, g, lane, acc, true, em, eu, evalid, Ms, ci);
 }
 

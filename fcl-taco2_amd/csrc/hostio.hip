@@ -20,8 +20,10 @@ namespace fcl {
 
 // The input block of a capacity graph (ids, segment bounds, durations, lengths, pad mask, speaker vectors: ~70 KB) comes out of PINNED host memory
 // by a kernel that is the graph's first node, instead of a hipMemcpyAsync in front of every launch: the runtime's copy call costs the host ~80 us
-// per pass (measured: as much as enqueueing the 90-node graph), the kernel costs nothing beside the graph launch and ~5 us of one workgroup on
-// the GPU (the reads cross PCIe once; fine-grained host memory is uncached on the device, so every pass sees what the host packed).  When every
+// per pass (measured: as much as enqueueing the 90-node graph), the kernel costs nothing beside the graph launch and ~13 us of one workgroup on
+// the GPU, 18 - 22 us on average with four passes in flight (kernel traces of rounds 6 - 8; the loop below is a load / store pair per iteration, ~9 PCIe
+// round trips one behind the other.  Issuing a chunk's loads before its first store halves the kernel, 18.4 -> 9.5 us, but does not move the four-stream
+// line: HISTORY.md, round 8).  The reads cross PCIe once; fine-grained host memory is uncached on the device, so every pass sees what the host packed.  When every
 // read has returned the kernel publishes a sequence number in host memory: the host packs the next batch into the same block once it sees the
 // number of its last launch.
 __global__ __launch_bounds__(1024) void feed_copy_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src, int n16, unsigned int* seq_dev,
