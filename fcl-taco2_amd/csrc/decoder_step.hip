@@ -2,13 +2,21 @@
 //
 // The loop is a chain of small dependent contractions (SURVEY.md §7 "sequential dependence"): once the
 // live row count drops, a 64-row LDS-staged GEMM tile spends its time in per-chunk barriers, not MFMAs.
-// Both kernels here use 16-row tiles whose A operand (the rows' activations, full K) sits in LDS once,
-// while every wave streams its own W rows straight from L2 into MFMA B fragments (no sharing between
-// waves => no LDS round trip, guide §5 "GEMV / small-M: load straight to VGPRs"):
-//   * feat_prenet_kernel : feat_out(t-1) -> [H10 scatter] -> prenet layer 0 -> prenet layer 1 of step t,
-//                          three row-local GEMMs chained through LDS in ONE launch (was three).
-//   * lstm_small_kernel  : one wave per gate (16 rows x 16 units each), gates exchanged through LDS, the
-//                          LSTMCell + zoneout epilogue one (row, unit) per thread.
+// Every kernel here uses 16-row tiles whose activations (full K) sit in LDS once, while every wave takes
+// its own W rows straight from L2 into MFMA fragments (no sharing between waves => no LDS round trip).
+// Two launches per decoder step, each in several forms that launch_feat_prenet / launch_lstm_small pick:
+//   feat/prenet: feat_out(t-1) -> [H10 scatter] -> prenet layer 0 -> prenet layer 1 of step t, three
+//   row-local GEMMs chained through LDS in ONE launch
+//     * feat_prenet_kernel                          fp32 operands, W streamed (any shape)
+//     * feat_prenet_x3_kernel                       bf16x3 planes, W fragments streamed (any shape)
+//     * feat_prenet_split_kernel<Ops, DROP, RT>     the student's shape, every W fragment register-resident:
+//                                                   OpsX3 (RT = 1, 2 row tiles) and OpsF32 (exact, RT = 1)
+//   small LSTM step: one wave per gate (16 rows x 16 units each), gates exchanged through LDS, the LSTMCell +
+//   zoneout epilogue one (row, unit) per thread
+//     * lstm_small_kernel, lstm_small_pair_kernel   fp32 operands, W streamed; the pair: two steps in one launch
+//     * lstm_small_x3_kernel                        bf16x3 planes, W fragments streamed (any K)
+//     * lstm_small_resident_kernel<Ops>             K = 256 terms, every W fragment register-resident: OpsX3, OpsF32
+// OpsX3 / OpsF32 are the operand policies of the register-resident bodies (below): each body exists once.
 #include "fcl_common.h"
 #include "lstm_epilogue.h"
 
@@ -281,47 +289,6 @@ __device__ __forceinline__ void rowtile_mma_x3(const u16* Ah, const u16* Al, int
     for (int t = 0; t < NT; ++t) out[t] = acc[t];
 }
 
-// Register-resident W fragments: the weights do not depend on the activation chain, so a wave can request ALL the
-// fragments it will need (NS 32-k steps x NT column tiles x 2 planes) up front and pay the L2/Infinity-Cache latency
-// once per kernel instead of once per k-step; the MFMAs then issue back to back from registers.
-template <int NT, int NS>
-struct WFrag {
-    s16x8 hi[NT][NS], lo[NT][NS];
-    template <int S0 = 0, int S1 = NS>  // k-steps S0 .. S1 - 1 (a caller short of registers requests the last steps later)
-    __device__ __forceinline__ void load(const u16* const (&fhi)[NT], const u16* const (&flo)[NT]) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int st = S0; st < S1; ++st) {  // every wave-wide load is one contiguous 1 KB fragment block
-                hi[t][st] = *reinterpret_cast<const s16x8*>(fhi[t] + st * 512);
-                lo[t][st] = *reinterpret_cast<const s16x8*>(flo[t] + st * 512);
-            }
-    }
-    __device__ __forceinline__ void mma(const u16* Ah, const u16* Al, int ldk, int K, int r16, int kq, f32x4 (&out)[NT]) const {
-        f32x4 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const u16* ah = Ah + r16 * ldk + kq * 8;
-        const u16* al = Al + r16 * ldk + kq * 8;
-#pragma unroll
-        for (int st = 0; st < NS; ++st) {
-            s16x8 a_hi = {0, 0, 0, 0, 0, 0, 0, 0}, a_lo = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (st * 32 + kq * 8 < K) {
-                a_hi = *reinterpret_cast<const s16x8*>(ah + st * 32);
-                a_lo = *reinterpret_cast<const s16x8*>(al + st * 32);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_lo, hi[t][st], acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi, lo[t][st], acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi, hi[t][st], acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) out[t] = acc[t];
-    }
-};
-
 // cooperative load of a [16 x K] fp32 row tile, split into the two LDS planes (rows clamped to M-1)
 __device__ __forceinline__ void load_rowtile_split(u16* Ah, u16* Al, int ldk, const float* src, int ld, int K, int m0, int M) {
     const int per_row = K >> 2;
@@ -336,6 +303,38 @@ __device__ __forceinline__ void load_rowtile_split(u16* Ah, u16* Al, int ldk, co
         *reinterpret_cast<uint2*>(Al + r * ldk + c) = make_uint2(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16));
     }
 }
+
+// A thread's share of a [16 x 256] fp32 row tile (rows m0.., clamped to M - 1), in two halves: request() issues the four float4 loads and nothing else,
+// so that a caller can have several tiles and its weight fragments in flight before the first wait; the store halves then split into the two LDS planes
+// (split_store, element mapping and rounding of load_rowtile_split) or copy (store).  256 threads.
+struct RowTile256 {
+    f32x4 v[4];
+    __device__ __forceinline__ void request(const float* src, int ld, int m0, int M) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
+            v[j] = *reinterpret_cast<const f32x4*>(src + (size_t)min(m0 + r, M - 1) * ld + c);
+        }
+    }
+    __device__ __forceinline__ void split_store(u16* Ah, u16* Al, int ldk) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
+            u16 h[4], l[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) split1(v[j][e], h[e], l[e]);
+            *reinterpret_cast<uint2*>(Ah + r * ldk + c) = make_uint2(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16));
+            *reinterpret_cast<uint2*>(Al + r * ldk + c) = make_uint2(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16));
+        }
+    }
+    __device__ __forceinline__ void store(float* dst, int ld_l) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
+            *reinterpret_cast<f32x4*>(dst + r * ld_l + c) = v[j];
+        }
+    }
+};
 
 // The streaming bf16x3 form, for the shapes feat_prenet_split_kernel does not cover: any U / O / P (multiples of 8), every wave walking its column
 // tiles' weight fragments from L2 one 32-k step ahead of the MFMAs (rowtile_mma_x3).
@@ -380,7 +379,6 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
         f32x4 accv[1];
         load_rowtile_split(A1h, A1l, ldU, a.h1, a.U, a.U, m0, M_feat);
         __syncthreads();
-        if (a.dbg_phase == 1) return;
         for (int tile = wave; tile * 16 < a.O; tile += nwaves) {
             const u16* const wh[1] = {frag(a.wf_hi, tile, nsU)};
             const u16* const wl[1] = {frag(a.wf_lo, tile, nsU)};
@@ -416,7 +414,7 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
     } else {
         for (int i = threadIdx.x; i < 16 * ldO; i += blockDim.x) { A2h[i] = 0; A2l[i] = 0; }  // prev_out = 0 at t = 0
     }
-    if (!has_pre || a.dbg_phase == 2) return;
+    if (!has_pre) return;
     lds_barrier();  // NOT __syncthreads(): its vmcnt(0) would wait for the prefetched biases, which nothing needs before an epilogue
     if (a.teacher_in) {
         load_rowtile_split(A2h, A2l, ldO, a.teacher_in, a.teacher_ld, a.O, m0, M_pre);
@@ -444,7 +442,6 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
         }
     }
     lds_barrier();
-    if (a.dbg_phase == 3) return;
     for (int tile = wave; tile * 16 < a.P; tile += 2 * nwaves) {
         const int tile2 = tile + nwaves;
         const u16* const wh[2] = {frag(a.w1_hi, tile, nsP), frag(a.w1_hi, min(tile2, ptmax), nsP)};
@@ -481,63 +478,209 @@ __global__ __launch_bounds__(512) void feat_prenet_x3_kernel(const FeatPrenetArg
 // (96 KB at RT = 4).  The h1 rows, then feat_out's and layer 0's fragments are requested at entry, layer 1's once feat_out's registers are free; no
 // __syncthreads (its vmcnt(0) would wait for every fragment before the first phase).
 // RNG mode draws a different (equally distributed) stream than the other feat/prenet kernels: 16 bits of a counter hash per decision instead of 24.
+// The exact fp32 form (OpsF32; launched with one row tile, without teacher input or plane outputs) replaces feat_prenet_kernel where the shape is covered:
+// there the weights were re-streamed from L2 at every k-step, 19.2 us per launch at 2 400 rows, the largest item of the exact-mode pass.
 __device__ __forceinline__ void p32_store4(unsigned short* __restrict__ p, int ld, long long m, int n, uint2 hi, uint2 lo) {
     unsigned short* line = p + ((size_t)m * ld + (n >> 5)) * 64 + (n & 31);
     *reinterpret_cast<uint2*>(line) = hi;
     *reinterpret_cast<uint2*>(line + 32) = lo;
 }
 
-template <int NT, int NS_>
-__device__ __forceinline__ void mma_t(const WFrag<NT, NS_>& w, const u16* Ah, const u16* Al, int ldk, int r16, int kq, f32x4 (&out)[NT]) {
-    f32x4 acc[NT];
+// ---- operand policies of the register-resident kernels (feat_prenet_split_kernel and lstm_small_resident_kernel, below): everything that differs
+// between the bf16x3 form (OpsX3: hi / lo bf16 planes in LDS and in the fragment-major weights, fcl_pack_frag_bf16) and the exact fp32 form (OpsF32:
+// FCL_PRECISION=0, fp32 tiles and fragment-major fp32 weights, fcl_pack_frag_f32, v_mfma_f32_16x16x4_f32).  The kernel bodies exist once.
+//   W     the fragment-major weights of one layer / term; at(): a (uniform, per-lane) element offset into each plane
+//   Tile  an LDS row tile (rows PAD elements apart beyond K: 2 (mod 4) sixteen-byte slots, conflict-free fragment reads); carve(): the next n elements of the
+//         dynamic LDS; fixed<N>(): static LDS
+//   Frag  register-resident W fragments.  The weights do not depend on the activation chain, so a wave can request ALL the fragments it will need
+//         (NS 32-k steps x NT column tiles) up front and pay the L2 / Infinity-Cache latency once per kernel instead of once per k-step; the MFMAs then
+//         issue back to back from registers.  load<S0, S1>: k-steps S0 .. S1 - 1 (a caller short of registers requests the last steps later); every
+//         wave-wide load is one contiguous 1 KB block (a lane's two float4 of an fp32 fragment are exactly the bytes of its hi + lo pair).
+//         mma_t: the weight fragment as the MFMA's A operand -- transposed accumulators, four consecutive columns of one row per lane.
+//   kPlanes        the plane outputs (before_p, pre_out_p) and the teacher input exist for this form: compiled out of the other
+//   kUnitsInLane   the small step's accumulator layout (gates_to_cell): the bf16x3 step keeps the activations as the A operand (Frag::mma_small)
+struct OpsX3 {
+    static constexpr bool kPlanes = true, kUnitsInLane = false;
+    static constexpr int PAD = 16, LDS_BYTES = 2 * sizeof(u16);  // (per tile element)
+    struct W {
+        const u16 *hi, *lo;
+        __device__ __forceinline__ W at(size_t o, size_t o2 = 0) const { return {hi + o + o2, lo + o + o2}; }
+    };
+    struct Tile {
+        u16 *h, *l;
+        __device__ __forceinline__ Tile at(int o) const { return {h + o, l + o}; }
+        static __device__ __forceinline__ Tile carve(u16*& p, int n) {
+            u16* b = p;
+            p += 2 * n;
+            return {b, b + n};
+        }
+        template <int N>
+        static __device__ __forceinline__ Tile fixed() {  // a tile of the workgroup's static LDS: two arrays (one array of both planes compiles to other code)
+            __shared__ __attribute__((aligned(16))) u16 A_h[N];
+            __shared__ __attribute__((aligned(16))) u16 A_lo[N];
+            return {A_h, A_lo};
+        }
+    };
+    template <int NT, int NS>
+    struct Frag {
+        s16x8 hi[NT][NS], lo[NT][NS];
+        template <int S0 = 0, int S1 = NS>
+        __device__ __forceinline__ void load(const W (&w)[NT]) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const u16* ah = Ah + r16 * ldk + kq * 8;
-    const u16* al = Al + r16 * ldk + kq * 8;
+            for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int st = 0; st < NS_; ++st) {
-        const s16x8 a_hi = *reinterpret_cast<const s16x8*>(ah + st * 32);
-        const s16x8 a_lo = *reinterpret_cast<const s16x8*>(al + st * 32);
+                for (int st = S0; st < S1; ++st) {
+                    hi[t][st] = *reinterpret_cast<const s16x8*>(w[t].hi + st * 512);
+                    lo[t][st] = *reinterpret_cast<const s16x8*>(w[t].lo + st * 512);
+                }
+        }
+        // out = A . W^T, hi / lo products in the order lo.hi, hi.lo, hi.hi.  W_IS_A: the weight fragment is the MFMA's A operand (D^T: a lane holds four
+        // consecutive columns of one row); otherwise the activations are (four rows of one column).  Same products, same order, either way.
+        template <bool W_IS_A>
+        __device__ __forceinline__ void chain(Tile A, int ldk, int r16, int kq, f32x4 (&out)[NT]) const {
+            auto mfma = [](s16x8 w, s16x8 a, f32x4 c) {
+                return W_IS_A ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, w, c, 0, 0, 0);
+            };
+            f32x4 acc[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi[t][st], a_lo, acc[t], 0, 0, 0);
+            for (int t = 0; t < NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            const u16* ah = A.h + r16 * ldk + kq * 8;
+            const u16* al = A.l + r16 * ldk + kq * 8;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.lo[t][st], a_hi, acc[t], 0, 0, 0);
+            for (int st = 0; st < NS; ++st) {
+                const s16x8 a_hi = *reinterpret_cast<const s16x8*>(ah + st * 32);
+                const s16x8 a_lo = *reinterpret_cast<const s16x8*>(al + st * 32);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi[t][st], a_hi, acc[t], 0, 0, 0);
+                for (int t = 0; t < NT; ++t) acc[t] = mfma(hi[t][st], a_lo, acc[t]);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) acc[t] = mfma(lo[t][st], a_hi, acc[t]);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) acc[t] = mfma(hi[t][st], a_hi, acc[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) out[t] = acc[t];
+        }
+        __device__ __forceinline__ void mma_t(Tile A, int ldk, int r16, int kq, f32x4 (&out)[NT]) const { chain<true>(A, ldk, r16, kq, out); }
+        __device__ __forceinline__ void mma_small(Tile A, int ldk, int r16, int kq, f32x4 (&out)[NT]) const { chain<false>(A, ldk, r16, kq, out); }
+    };
+    static __device__ __forceinline__ u16* dynamic_lds() {
+        extern __shared__ __attribute__((aligned(16))) u16 x3_lds[];
+        return x3_lds;
     }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) out[t] = acc[t];
-}
+    static __device__ __forceinline__ W wf(const FeatPrenetArgs& a) { return {a.wf_hi, a.wf_lo}; }
+    static __device__ __forceinline__ W w0(const FeatPrenetArgs& a) { return {a.w0_hi, a.w0_lo}; }
+    static __device__ __forceinline__ W w1(const FeatPrenetArgs& a) { return {a.w1_hi, a.w1_lo}; }
+    static __device__ __forceinline__ W w(const GemmTerm& t) { return {t.Whi, t.Wlo}; }
+    static __device__ __forceinline__ void store4(Tile t, int row, int ld, int col, const f32x4 v) {  // columns col .. col + 3 of a row
+        uint2 h, l;
+        split4(v, h, l);
+        *reinterpret_cast<uint2*>(t.h + row * ld + col) = h;
+        *reinterpret_cast<uint2*>(t.l + row * ld + col) = l;
+    }
+    static __device__ __forceinline__ void store_rows(const RowTile256& r, Tile t, int ld) { r.split_store(t.h, t.l, ld); }
+    static __device__ __forceinline__ void zero(Tile t, int n) {  // n elements, 512 threads
+        for (int i = threadIdx.x; i < n / 8; i += 512) {
+            reinterpret_cast<uint4*>(t.h)[i] = make_uint4(0, 0, 0, 0);
+            reinterpret_cast<uint4*>(t.l)[i] = make_uint4(0, 0, 0, 0);
+        }
+    }
+};
 
-template <int DROP, int RT>
+struct OpsF32 {
+    static constexpr bool kPlanes = false, kUnitsInLane = true;
+    static constexpr int PAD = 8, LDS_BYTES = sizeof(float);
+    struct W {
+        const float* f;
+        __device__ __forceinline__ W at(size_t o, size_t o2 = 0) const { return {f + o + o2}; }
+    };
+    struct Tile {
+        float* p;
+        __device__ __forceinline__ Tile at(int o) const { return {p + o}; }
+        static __device__ __forceinline__ Tile carve(float*& p, int n) {
+            float* b = p;
+            p += n;
+            return {b};
+        }
+        template <int N>
+        static __device__ __forceinline__ Tile fixed() {
+            __shared__ __attribute__((aligned(16))) float A_f[N];
+            return {A_f};
+        }
+    };
+    template <int NT, int NS>
+    struct Frag {
+        f32x4 w0[NT][NS], w1[NT][NS];
+        template <int S0 = 0, int S1 = NS>
+        __device__ __forceinline__ void load(const W (&w)[NT]) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int st = S0; st < S1; ++st) {
+                    w0[t][st] = *reinterpret_cast<const f32x4*>(w[t].f + st * 512);
+                    w1[t][st] = *reinterpret_cast<const f32x4*>(w[t].f + st * 512 + 4);
+                }
+        }
+        __device__ __forceinline__ void mma_t(Tile A, int ldk, int r16, int kq, f32x4 (&out)[NT]) const {
+            f32x4 acc[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            const float* a = A.p + r16 * ldk + kq * 4;
+#pragma unroll
+            for (int st = 0; st < NS; ++st) {
+                const f32x4 a0 = *reinterpret_cast<const f32x4*>(a + st * 32), a1 = *reinterpret_cast<const f32x4*>(a + st * 32 + 16);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[t][st][e], a0[e], acc[t], 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[t][st][e], a1[e], acc[t], 0, 0, 0);
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) out[t] = acc[t];
+        }
+        __device__ __forceinline__ void mma_small(Tile A, int ldk, int r16, int kq, f32x4 (&out)[NT]) const { mma_t(A, ldk, r16, kq, out); }
+    };
+    static __device__ __forceinline__ float* dynamic_lds() {
+        extern __shared__ __attribute__((aligned(16))) float f32_lds[];
+        return f32_lds;
+    }
+    static __device__ __forceinline__ W wf(const FeatPrenetArgs& a) { return {a.wf_ff}; }
+    static __device__ __forceinline__ W w0(const FeatPrenetArgs& a) { return {a.w0_ff}; }
+    static __device__ __forceinline__ W w1(const FeatPrenetArgs& a) { return {a.w1_ff}; }
+    static __device__ __forceinline__ W w(const GemmTerm& t) { return {t.Wff}; }
+    static __device__ __forceinline__ void store4(Tile t, int row, int ld, int col, const f32x4 v) { *reinterpret_cast<f32x4*>(t.p + row * ld + col) = v; }
+    static __device__ __forceinline__ void store_rows(const RowTile256& r, Tile t, int ld) { r.store(t.p, ld); }
+    static __device__ __forceinline__ void zero(Tile t, int n) {
+        for (int i = threadIdx.x; i < n / 4; i += 512) reinterpret_cast<f32x4*>(t.p)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+};
+
+template <class Ops, int DROP, int RT>
 __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenetArgs a) {
+    typedef typename Ops::Tile Tile;
     constexpr int SU = 8, SO = 3, SP = 8, U = 256, OP = 96, P = 256;
     const int M_feat = a.M_feat, M_pre = a.M_pre;
-    const int Ms_feat = (a.live && a.t_prev >= 0) ? min(a.M_feat, a.live[a.t_prev]) : a.M_feat, Ms_pre = a.live ? min(a.M_pre, a.live[a.t_cur]) : a.M_pre;
-    const int split = blockIdx.y;  // 0: the grid is one workgroup deep (the tests on it are what is left of a column split of layer 1 over gridDim.y)
-    if (a.live && a.w0 && blockIdx.x == 0 && split == 0 && threadIdx.x == 0 && a.live[a.t_cur] > a.M_pre) atomicOr(a.status, (unsigned int)FCL_STATUS_ROWS_CAP);
-    if ((int)blockIdx.x * (16 * RT) >= (a.h1 ? Ms_feat : Ms_pre)) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier)
-    constexpr int ldU = U + 16, ldO = OP + 16, ldP = P + 16, ROWS = 16 * RT;
+    int Ms_feat, Ms_pre;
+    if (!feat_prenet_rows(a, 16 * RT, Ms_feat, Ms_pre)) return;
+    constexpr int ldU = U + Ops::PAD, ldO = OP + Ops::PAD, ldP = P + Ops::PAD, ROWS = 16 * RT;
     static_assert(ldU == ldP, "the layer-1 operand tile re-uses the h1 tile's LDS");
-    extern __shared__ __attribute__((aligned(16))) u16 fp_lds[];
-    u16* A1h = fp_lds;
-    u16* A1l = A1h + ROWS * ldU;
-    u16* A2h = A1l + ROWS * ldU;
-    u16* A2l = A2h + ROWS * ldO;
-    u16* A3h = A1h;  // written in phase 2, when every wave is past its last read of the h1 tile (the barrier that ends phase 1)
-    u16* A3l = A1l;
+    auto* lds = Ops::dynamic_lds();
+    const Tile A1 = Tile::carve(lds, ROWS * ldU);  // h1 tile
+    const Tile A2 = Tile::carve(lds, ROWS * ldO);  // feat_out / prenet input
+    const Tile A3 = A1;  // layer 0's output: written in phase 2, when every wave is past its last read of the h1 tile (the barrier that ends phase 1)
     const int O = a.O;
     const int m0 = blockIdx.x * ROWS;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r16 = lane & 15, kq = lane >> 4;   // operand fragments: row / column r16, k-group kq
     const int arow = lane & 15, cq = lane >> 4;  // transposed accumulators: activation row arow, columns cq * 4 .. cq * 4 + 3 of the column tile
     const bool has_feat = a.h1 != nullptr, has_pre = a.w0 != nullptr && m0 < M_pre;
-    if (!has_pre && split != 0) return;
     const bool feat_wave = has_feat && wave * 16 < O;
     const size_t lane8 = (size_t)lane * 8;
-    auto frag = [&](const u16* base, int tile, int ns) { return base + (size_t)tile * ns * 512 + lane8; };
+    auto frag = [&](const typename Ops::W w, int tile, int ns) { return w.at((size_t)tile * ns * 512, lane8); };  // (the uniform offset first: a scalar add)
     const int t0 = wave, t1 = wave + 8;  // this wave's layer-0 column tiles
-    const int c1 = split * 16 + wave * 2;  // first of this wave's two layer-1 column tiles
+    const int c1 = wave * 2;  // first of this wave's two layer-1 column tiles
 
     // ---- phase 0 operands first (loads return in order: the first wait then covers the h1 rows alone) ---------------------------------------
     constexpr int HV = RT * 2;  // float4 loads of h1 per thread: ROWS x 64 float4 over 512 threads
@@ -555,16 +698,15 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
     // every wave's h1 rows, then feat_out's fragments, then layer 0's, then layer 1's.
     asm volatile("s_barrier" ::: "memory");
     // ---- weight fragments and epilogue operands of phases 1 and 2, requested now ------------------------------------------------------------------
-    WFrag<1, SU> ff;
-    WFrag<2, SO> f0;
-    WFrag<2, SP> f1;
+    typename Ops::template Frag<1, SU> ff;
+    typename Ops::template Frag<2, SO> f0;
+    typename Ops::template Frag<2, SP> f1;
     const int fnc = wave * 16 + cq * 4;  // feat_out columns fnc .. fnc + 3 of this lane (whole groups of four: O % 4 == 0)
     f32x4 f0v[RT];
     int fo[RT];
     if (feat_wave) {
-        const u16* const wh[1] = {frag(a.wf_hi, wave, SU)};
-        const u16* const wl[1] = {frag(a.wf_lo, wave, SU)};
-        ff.load(wh, wl);
+        const typename Ops::W w[1] = {frag(Ops::wf(a), wave, SU)};
+        ff.load(w);
     }
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
@@ -573,7 +715,7 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         if (feat_wave && fnc < O) {
             const int mc = min(m0 + q * 16 + arow, M_feat - 1);
             f0v[q] = *reinterpret_cast<const f32x4*>(a.F0 + (size_t)mc * O + fnc);
-            if (split == 0) fo[q] = a.frame_off[mc];
+            fo[q] = a.frame_off[mc];
         }
     }
     unsigned int seed0 = 0, seed1 = 0;
@@ -589,9 +731,8 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
     for (int tt = 0; tt < 2; ++tt) pb0[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (has_feat) asm volatile("s_barrier" ::: "memory");  // (feat_out's fragments are queued before anybody's layer-0 fragments)
     if (has_pre) {
-        const u16* const wh0[2] = {frag(a.w0_hi, t0, SO), frag(a.w0_hi, t1, SO)};
-        const u16* const wl0[2] = {frag(a.w0_lo, t0, SO), frag(a.w0_lo, t1, SO)};
-        f0.load(wh0, wl0);
+        const typename Ops::W w[2] = {frag(Ops::w0(a), t0, SO), frag(Ops::w0(a), t1, SO)};
+        f0.load(w);
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             const int nc = (tt ? t1 : t0) * 16 + cq * 4;
@@ -603,18 +744,12 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         }
     }
     // ---- phase 0: h1 tiles -> LDS planes; prenet-input tiles zeroed (prev_out = 0 at t = 0; zero padding past O otherwise) ------------------
-    for (int i = threadIdx.x; i < ROWS * ldO / 8; i += 512) {
-        reinterpret_cast<uint4*>(A2h)[i] = make_uint4(0, 0, 0, 0);
-        reinterpret_cast<uint4*>(A2l)[i] = make_uint4(0, 0, 0, 0);
-    }
+    Ops::zero(A2, ROWS * ldO);
     if (has_feat) {
 #pragma unroll
         for (int j = 0; j < HV; ++j) {
             const int i = threadIdx.x + j * 512, r = i >> 6, c = (i & 63) * 4;
-            uint2 h, l;
-            split4(hreg[j], h, l);
-            *reinterpret_cast<uint2*>(A1h + r * ldU + c) = h;
-            *reinterpret_cast<uint2*>(A1l + r * ldU + c) = l;
+            Ops::store4(A1, r, ldU, c, hreg[j]);
         }
     }
     // layer-1 fragments (all 16 column tiles: 128 VGPRs) and epilogue operands: requested after phase 1, once feat_out's fragments are dead
@@ -622,14 +757,10 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
     for (int tt = 0; tt < 2; ++tt) pb1[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto request_l1 = [&]() {
         if (has_pre) {
-            const u16* wh1[2];
-            const u16* wl1[2];
+            typename Ops::W w[2];
 #pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-                wh1[tt] = frag(a.w1_hi, c1 + tt, SP);
-                wl1[tt] = frag(a.w1_lo, c1 + tt, SP);
-            }
-            f1.load(wh1, wl1);
+            for (int tt = 0; tt < 2; ++tt) w[tt] = frag(Ops::w1(a), c1 + tt, SP);
+            f1.load(w);
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
                 const int nc = (c1 + tt) * 16 + cq * 4;
@@ -642,23 +773,22 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         }
     };
     lds_barrier();
-    if (a.dbg_phase == 1) return;
     // ---- phase 1: H8 feat_out of the previous step (+ H10 scatter) ---------------------------------------------------------------------------
     if (feat_wave) {
 #pragma unroll
         for (int q = 0; q < RT; ++q) {
             f32x4 accv[1];
-            mma_t<1, SU>(ff, A1h + q * 16 * ldU, A1l + q * 16 * ldU, ldU, r16, kq, accv);
+            ff.mma_t(A1.at(q * 16 * ldU), ldU, r16, kq, accv);
             const int row = q * 16 + arow, m = m0 + row;
             if (fnc < O) {
                 f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-                uint2 h, l;
                 if (m < Ms_feat) {
                     v = accv[0] + f0v[q];
-                    if (split == 0) {
-                        const long long fr = (long long)fo[q] + a.t_prev;
-                        *reinterpret_cast<f32x4*>(a.before + (size_t)fr * O + fnc) = v;
+                    const long long fr = (long long)fo[q] + a.t_prev;
+                    *reinterpret_cast<f32x4*>(a.before + (size_t)fr * O + fnc) = v;
+                    if constexpr (Ops::kPlanes) {
                         if (a.before_p) {
+                            uint2 h, l;
                             split4(v, h, l);
                             p32_store4(a.before_p, (O + 31) >> 5, fr, fnc, h, l);
                         }
@@ -668,32 +798,32 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
                         for (int r = 0; r < 4; ++r) v[r] = act_apply(v[r], a.out_act);
                     }
                 }
-                split4(v, h, l);
-                *reinterpret_cast<uint2*>(A2h + row * ldO + fnc) = h;
-                *reinterpret_cast<uint2*>(A2l + row * ldO + fnc) = l;
+                Ops::store4(A2, row, ldO, fnc, v);
             }
         }
     }
-    if (has_feat && split == 0 && a.before_p && (O & 31)) {  // zero padding of the last 32-column line of this tile's frames
+    if (Ops::kPlanes && has_feat && a.before_p && (O & 31)) {  // zero padding of the last 32-column line of this tile's frames
         const int padc = 32 - (O & 31);
         for (int i = threadIdx.x; i < ROWS * padc; i += 512) {
             const int m = m0 + i / padc;
             if (m < Ms_feat) store_p32(a.before_p, (O + 31) >> 5, a.frame_off[m] + a.t_prev, O + i % padc, 0.f);
         }
     }
-    if (!has_pre || a.dbg_phase == 2) return;
+    if (!has_pre) return;
     request_l1();
     lds_barrier();
-    if (a.teacher_in) {  // teacher forcing: prenet input is y_{t-1}, not the decoder's own output
+    if constexpr (Ops::kPlanes) {
+        if (a.teacher_in) {  // teacher forcing: prenet input is y_{t-1}, not the decoder's own output
 #pragma unroll
-        for (int q = 0; q < RT; ++q) load_rowtile_split(A2h + q * 16 * ldO, A2l + q * 16 * ldO, ldO, a.teacher_in, a.teacher_ld, O, m0 + q * 16, M_pre);
-        lds_barrier();
+            for (int q = 0; q < RT; ++q) load_rowtile_split(A2.h + q * 16 * ldO, A2.l + q * 16 * ldO, ldO, a.teacher_in, a.teacher_ld, O, m0 + q * 16, M_pre);
+            lds_barrier();
+        }
     }
     // ---- phase 2: H6 prenet layer 0 -> LDS (over the h1 tile) ----------------------------------------------------------------------------------
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
         f32x4 accv[2];
-        mma_t<2, SO>(f0, A2h + q * 16 * ldO, A2l + q * 16 * ldO, ldO, r16, kq, accv);
+        f0.mma_t(A2.at(q * 16 * ldO), ldO, r16, kq, accv);
         const int row = q * 16 + arow, m = m0 + row;
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -702,19 +832,15 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             v = drop4<DROP>(v, DROP == 1 ? k0[q][tt] : 0u, (unsigned int)m * (unsigned int)P + (unsigned int)nc, seed0, thr16, a.keep_scale);
-            uint2 h, l;
-            split4(v, h, l);
-            *reinterpret_cast<uint2*>(A3h + row * ldP + nc) = h;
-            *reinterpret_cast<uint2*>(A3l + row * ldP + nc) = l;
+            Ops::store4(A3, row, ldP, nc, v);
         }
     }
     lds_barrier();
-    if (a.dbg_phase == 3) return;
     // ---- phase 3: H6 prenet layer 1 -> global (+ KD tap, + P32 planes) --------------------------------------------------------------------------
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
         f32x4 accv[2];
-        mma_t<2, SP>(f1, A3h + q * 16 * ldP, A3l + q * 16 * ldP, ldP, r16, kq, accv);
+        f1.mma_t(A3.at(q * 16 * ldP), ldP, r16, kq, accv);
         const int m = m0 + q * 16 + arow;
         if (m >= Ms_pre) continue;
 #pragma unroll
@@ -725,201 +851,18 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             v = drop4<DROP>(v, DROP == 1 ? k1[q][tt] : 0u, (unsigned int)m * (unsigned int)P + (unsigned int)nc, seed1, thr16, a.keep_scale);
             if (a.pre_out) *reinterpret_cast<f32x4*>(a.pre_out + (size_t)m * P + nc) = v;
-            if (a.pre_out_p) {
-                uint2 h, l;
-                split4(v, h, l);
-                p32_store4(a.pre_out_p, SP, m, nc, h, l);
-            }
-            if (a.tap_prenet) *reinterpret_cast<f32x4*>(a.tap_prenet + (size_t)(a.frame_off[m] + a.t_cur) * P + nc) = v;
-        }
-    }
-}
-
-
-// The same launch in EXACT fp32 (FCL_PRECISION=0; round 4): v_mfma_f32_16x16x4_f32 on fragment-major fp32 weights (fcl_pack_frag_f32), one row tile per
-// workgroup.  Same structure as feat_prenet_split_kernel -- every weight fragment register-resident (a lane's two float4 per tile and
-// 32-k step are exactly the bytes of its hi + lo pair), transposed accumulators (the weight fragment is the MFMA's A operand), vector epilogues,
-// three phases chained through LDS -- with fp32 tiles in LDS instead of split planes.  Replaces feat_prenet_kernel (weights re-streamed from L2 at
-// every k-step: 19.2 us per launch at 2 400 rows, the largest item of the exact-mode pass) where the shape is covered.
-template <int NT, int NS_>
-struct WFragF {
-    f32x4 w0[NT][NS_], w1[NT][NS_];
-    template <int S0 = 0, int S1 = NS_>
-    __device__ __forceinline__ void load(const float* const (&f)[NT]) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int st = S0; st < S1; ++st) {
-                w0[t][st] = *reinterpret_cast<const f32x4*>(f[t] + st * 512);
-                w1[t][st] = *reinterpret_cast<const f32x4*>(f[t] + st * 512 + 4);
-            }
-    }
-};
-
-template <int NT, int NS_>
-__device__ __forceinline__ void mma_tf(const WFragF<NT, NS_>& w, const float* A, int ldk, int r16, int kq, f32x4 (&out)[NT]) {
-    f32x4 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float* a = A + r16 * ldk + kq * 4;
-#pragma unroll
-    for (int st = 0; st < NS_; ++st) {
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(a + st * 32), a1 = *reinterpret_cast<const f32x4*>(a + st * 32 + 16);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w0[t][st][e], a0[e], acc[t], 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w1[t][st][e], a1[e], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) out[t] = acc[t];
-}
-
-template <int DROP>
-__global__ __launch_bounds__(512) void feat_prenet_split_f32_kernel(const FeatPrenetArgs a) {
-    constexpr int SU = 8, SO = 3, SP = 8, U = 256, OP = 96, P = 256;
-    const int M_feat = a.M_feat, M_pre = a.M_pre;
-    int Ms_feat, Ms_pre;
-    if (!feat_prenet_rows(a, 16, Ms_feat, Ms_pre)) return;
-    constexpr int ldU = U + 8, ldO = OP + 8, ldP = P + 8;  // floats: rows 32 bytes apart modulo the 256-byte bank period, as the plane tiles are
-    static_assert(ldU == ldP, "the layer-1 operand tile re-uses the h1 tile's LDS");
-    extern __shared__ __attribute__((aligned(16))) float fpf_lds[];
-    float* A1 = fpf_lds;            // [16][ldU]  h1 tile, then (phase 2 on) layer 0's output
-    float* A2 = A1 + 16 * ldU;      // [16][ldO]  feat_out / prenet input
-    const int O = a.O;
-    const int m0 = blockIdx.x * 16;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int arow = lane & 15, cq = lane >> 4;
-    const bool has_feat = a.h1 != nullptr, has_pre = a.w0 != nullptr && m0 < M_pre;
-    const bool feat_wave = has_feat && wave * 16 < O;
-    const size_t lane8 = (size_t)lane * 8;
-    auto frag = [&](const float* base, int tile, int ns) { return base + (size_t)tile * ns * 512 + lane8; };
-    const int t0 = wave, t1 = wave + 8;  // this wave's column tiles of both prenet layers
-    // ---- phase 0 operands first
-    f32x4 hreg[2];
-    if (has_feat) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int i = threadIdx.x + j * 512, r = i >> 6, c = (i & 63) * 4;
-            hreg[j] = *reinterpret_cast<const f32x4*>(a.h1 + (size_t)min(m0 + r, M_feat - 1) * U + c);
-        }
-    }
-    asm volatile("s_barrier" ::: "memory");  // (queue order = order of use: see feat_prenet_split_kernel)
-    WFragF<1, SU> ff;
-    WFragF<2, SO> f0;
-    WFragF<2, SP> f1;
-    const int fnc = wave * 16 + cq * 4;
-    f32x4 f0v = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int fo = 0;
-    if (feat_wave) {
-        const float* const wf[1] = {frag(a.wf_ff, wave, SU)};
-        ff.load(wf);
-        if (fnc < O) {
-            const int mc = min(m0 + arow, M_feat - 1);
-            f0v = *reinterpret_cast<const f32x4*>(a.F0 + (size_t)mc * O + fnc);
-            fo = a.frame_off[mc];
-        }
-    }
-    unsigned int seed0 = 0, seed1 = 0;
-    const unsigned int thr16 = (unsigned int)(a.drop_p * 65536.0f);
-    if (DROP == 2) {
-        const unsigned int sbump = a.seed_dev ? *a.seed_dev * 0x9E3779B9u : 0u;
-        seed0 = hash_u32(a.seed0 + sbump);
-        seed1 = hash_u32(a.seed1 + sbump);
-    }
-    f32x4 pb0[2], pb1[2];
-    unsigned int k0[2] = {0u, 0u}, k1[2] = {0u, 0u};
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) pb0[tt] = pb1[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (has_feat) asm volatile("s_barrier" ::: "memory");
-    if (has_pre) {
-        const float* const w0p[2] = {frag(a.w0_ff, t0, SO), frag(a.w0_ff, t1, SO)};
-        f0.load(w0p);
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int nc = (tt ? t1 : t0) * 16 + cq * 4;
-            pb0[tt] = *reinterpret_cast<const f32x4*>(a.b0 + nc);
-            if (DROP == 1) k0[tt] = *reinterpret_cast<const unsigned int*>(a.keep0 + (size_t)min(m0 + arow, M_pre - 1) * P + nc);
-        }
-    }
-    // ---- phase 0: h1 tile -> LDS; the prenet-input tile zeroed (prev_out = 0 at t = 0; zero padding past O otherwise)
-    for (int i = threadIdx.x; i < 16 * ldO / 4; i += 512) reinterpret_cast<f32x4*>(A2)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (has_feat) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int i = threadIdx.x + j * 512, r = i >> 6, c = (i & 63) * 4;
-            *reinterpret_cast<f32x4*>(A1 + r * ldU + c) = hreg[j];
-        }
-    }
-    lds_barrier();
-    // ---- phase 1: feat_out of the previous step (+ frame scatter)
-    if (feat_wave) {
-        f32x4 accv[1];
-        mma_tf<1, SU>(ff, A1, ldU, r16, kq, accv);
-        const int m = m0 + arow;
-        if (fnc < O) {
-            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (m < Ms_feat) {
-                v = accv[0] + f0v;
-                *reinterpret_cast<f32x4*>(a.before + (size_t)((long long)fo + a.t_prev) * O + fnc) = v;
-                if (a.out_act) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = act_apply(v[r], a.out_act);
+            if constexpr (Ops::kPlanes) {
+                if (a.pre_out_p) {
+                    uint2 h, l;
+                    split4(v, h, l);
+                    p32_store4(a.pre_out_p, SP, m, nc, h, l);
                 }
             }
-            *reinterpret_cast<f32x4*>(A2 + arow * ldO + fnc) = v;
-        }
-    }
-    if (!has_pre) return;
-    {   // layer 1's fragments: requested once feat_out's are dead (128 VGPRs)
-        const float* const w1p[2] = {frag(a.w1_ff, t0, SP), frag(a.w1_ff, t1, SP)};
-        f1.load(w1p);
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int nc = (tt ? t1 : t0) * 16 + cq * 4;
-            pb1[tt] = *reinterpret_cast<const f32x4*>(a.b1 + nc);
-            if (DROP == 1) k1[tt] = *reinterpret_cast<const unsigned int*>(a.keep1 + (size_t)min(m0 + arow, M_pre - 1) * P + nc);
-        }
-    }
-    lds_barrier();
-    // ---- phase 2: prenet layer 0 -> LDS (over the h1 tile: every wave is past its last read of it)
-    {
-        f32x4 accv[2];
-        mma_tf<2, SO>(f0, A2, ldO, r16, kq, accv);
-        const int m = m0 + arow;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int nc = (tt ? t1 : t0) * 16 + cq * 4;
-            f32x4 v = accv[tt] + pb0[tt];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            v = drop4<DROP>(v, k0[tt], (unsigned int)m * (unsigned int)P + (unsigned int)nc, seed0, thr16, a.keep_scale);
-            *reinterpret_cast<f32x4*>(A1 + arow * ldP + nc) = v;
-        }
-    }
-    lds_barrier();
-    // ---- phase 3: prenet layer 1 -> global (+ KD tap)
-    {
-        f32x4 accv[2];
-        mma_tf<2, SP>(f1, A1, ldP, r16, kq, accv);
-        const int m = m0 + arow;
-        if (m >= Ms_pre) return;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int nc = (tt ? t1 : t0) * 16 + cq * 4;
-            f32x4 v = accv[tt] + pb1[tt];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            v = drop4<DROP>(v, k1[tt], (unsigned int)m * (unsigned int)P + (unsigned int)nc, seed1, thr16, a.keep_scale);
-            if (a.pre_out) *reinterpret_cast<f32x4*>(a.pre_out + (size_t)m * P + nc) = v;
             if (a.tap_prenet) *reinterpret_cast<f32x4*>(a.tap_prenet + (size_t)(a.frame_off[m] + a.t_cur) * P + nc) = v;
         }
     }
 }
+
 
 // Tail of the small LSTM steps with prefetched cell operands: wave g's accumulators (gate g of the tile's 16 rows x 16 units) go to LDS, then thread
 // (row, unit) of the workgroup collects its four gate pre-activations and runs the cell.  units_in_lane: the accumulator layout -- false: four rows
@@ -941,38 +884,6 @@ __device__ __forceinline__ void gates_to_cell(const LstmStepArgs& a, int g, int 
     cell_finish(a, m, u, pre, ci);
 }
 
-// A thread's share of a [16 x 256] fp32 row tile (rows m0.., clamped to M - 1), in two halves: request() issues the four float4 loads and nothing else,
-// so that a caller can have several tiles and its weight fragments in flight before the first wait; the store halves then split into the two LDS planes
-// (split_store, element mapping and rounding of load_rowtile_split) or copy (store).  256 threads.
-struct RowTile256 {
-    f32x4 v[4];
-    __device__ __forceinline__ void request(const float* src, int ld, int m0, int M) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
-            v[j] = *reinterpret_cast<const f32x4*>(src + (size_t)min(m0 + r, M - 1) * ld + c);
-        }
-    }
-    __device__ __forceinline__ void split_store(u16* Ah, u16* Al, int ldk) const {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
-            u16 h[4], l[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) split1(v[j][e], h[e], l[e]);
-            *reinterpret_cast<uint2*>(Ah + r * ldk + c) = make_uint2(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16));
-            *reinterpret_cast<uint2*>(Al + r * ldk + c) = make_uint2(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16));
-        }
-    }
-    __device__ __forceinline__ void store(float* dst, int ld_l) const {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = threadIdx.x + j * 256, r = i >> 6, c = (i & 63) * 4;
-            *reinterpret_cast<f32x4*>(dst + r * ld_l + c) = v[j];
-        }
-    }
-};
-
 constexpr int kSmallStepsAtEntry = 4;  // of term 1's eight k-steps of weight fragments, in the register-resident small steps (below)
 
 // The K walk of the register-resident small steps, NT = 1 or 2 terms of K = 256 (a template, not a run-time count: where the two forms share code the
@@ -981,77 +892,63 @@ constexpr int kSmallStepsAtEntry = 4;  // of term 1's eight k-steps of weight fr
 // front of another wave's rows), the weight fragments.  The rows' 32 registers are free once they are split into LDS (that wait covers the rows alone:
 // loads return in order); term 1's last k-steps then take their place, queued right behind the other fragments and first used ~40 MFMAs after the
 // barrier -- with all 16 steps requested at entry the kernel needs 184 VGPRs, two waves per SIMD instead of three.
-template <int NT>
-__device__ __forceinline__ f32x4 small_x3_walk(const LstmStepArgs& a, u16* A_h, u16* A_lo, int ldk, int m0, int M, int g, int u0, int lane) {
+template <class Ops, int NT>
+__device__ __forceinline__ f32x4 small_walk(const LstmStepArgs& a, typename Ops::Tile A, int ldk, int m0, int M, int g, int u0, int lane) {
     const int r16 = lane & 15, kq = lane >> 4;
     RowTile256 rows[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) rows[t].request(a.term[t].A, a.term[t].lda, m0, M);
     asm volatile("s_barrier" ::: "memory");
     const size_t fo = (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8;  // W rows g*U + u0.. form fragment tile (g*U + u0)/16 (U % 16 == 0); 8 steps per row tile
-    WFrag<1, 8> wf[NT];
-    const u16* const wh0[1] = {a.term[0].Whi + fo};
-    const u16* const wl0[1] = {a.term[0].Wlo + fo};
-    const u16* const wh1[1] = {a.term[NT - 1].Whi + fo};
-    const u16* const wl1[1] = {a.term[NT - 1].Wlo + fo};
-    wf[0].load(wh0, wl0);
-    if (NT > 1) wf[NT - 1].template load<0, kSmallStepsAtEntry>(wh1, wl1);
-    __builtin_amdgcn_sched_barrier(0);  // (hipcc otherwise starts the split -- and its wait for the first row -- above the fragment requests)
+    typename Ops::template Frag<1, 8> wf[NT];
+    const typename Ops::W w0[1] = {Ops::w(a.term[0]).at(fo)}, w1[1] = {Ops::w(a.term[NT - 1]).at(fo)};  // (both formed before the first request)
+    wf[0].load(w0);
+    if (NT > 1) wf[NT - 1].template load<0, kSmallStepsAtEntry>(w1);
+    __builtin_amdgcn_sched_barrier(0);  // (hipcc otherwise starts the stores -- and their wait for the first row -- above the fragment requests)
 #pragma unroll
-    for (int t = 0; t < NT; ++t) rows[t].split_store(A_h + t * 256, A_lo + t * 256, ldk);
+    for (int t = 0; t < NT; ++t) Ops::store_rows(rows[t], A.at(t * 256), ldk);
     asm volatile("" ::: "memory");  // (the late requests stay below the rows' last use)
-    if (NT > 1) wf[NT - 1].template load<kSmallStepsAtEntry, 8>(wh1, wl1);
+    if (NT > 1) wf[NT - 1].template load<kSmallStepsAtEntry, 8>(w1);
     __syncthreads();
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < NT; ++t) {  // the partial sums are formed and added as the one-term-at-a-time kernel did: 0 + term 0 + term 1
         f32x4 part[1];
-        wf[t].mma(A_h + t * 256, A_lo + t * 256, ldk, 256, r16, kq, part);
+        wf[t].mma_small(A.at(t * 256), ldk, r16, kq, part);
         acc += part[0];
     }
     return acc;
 }
 
-// the same walk on fragment-major fp32 weights and an fp32 tile (lstm_small_ff_kernel)
-template <int NT>
-__device__ __forceinline__ f32x4 small_ff_walk(const LstmStepArgs& a, float* A_f, int ld, int m0, int M, int g, int u0, int lane) {
-    const int r16 = lane & 15, kq = lane >> 4;
-    RowTile256 rows[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) rows[t].request(a.term[t].A, a.term[t].lda, m0, M);
-    asm volatile("s_barrier" ::: "memory");
-    const size_t fo = (size_t)((g * a.U + u0) >> 4) * 8 * 512 + (size_t)lane * 8;
-    WFragF<1, 8> wf[NT];
-    const float* const w0[1] = {a.term[0].Wff + fo};
-    const float* const w1[1] = {a.term[NT - 1].Wff + fo};
-    wf[0].load(w0);
-    if (NT > 1) wf[NT - 1].template load<0, kSmallStepsAtEntry>(w1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) rows[t].store(A_f + t * 256, ld);
-    asm volatile("" ::: "memory");
-    if (NT > 1) wf[NT - 1].template load<kSmallStepsAtEntry, 8>(w1);
-    __syncthreads();
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        f32x4 part[1];
-        mma_tf<1, 8>(wf[t], A_f + t * 256, ld, r16, kq, part);
-        acc += part[0];
-    }
-    return acc;
-}
-
-// PRE: every term has K = 256 (the student's decoder LSTMs: two terms, or the input term alone in the zero-state form of step 0) -> the activation
-// rows of every term and the weight fragments are requested at kernel entry (small_x3_walk; row stride KC + 16: 2 (mod 4) sixteen-byte slots, as
-// 256 + 16 is), ONE barrier, then the two terms' k-walks back to back.  (Until round 8 term 1's rows were requested after term 0's MFMAs, into term 0's
-// columns: a global round trip and two barriers exposed in every small step.)  Bit-identical outputs.
-template <bool PRE>
-__global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a) {
+// The register-resident small step, in either operand form.  Every term has K = 256 (the student's decoder LSTMs: two terms, or the input term alone in
+// the zero-state form of step 0) -> the activation rows of every term and the weight fragments are requested at kernel entry (small_walk; both terms'
+// rows side by side in one K = 512 tile), ONE barrier, then the two terms' k-walks back to back.  (Until round 8 term 1's rows were requested after term
+// 0's MFMAs, into term 0's columns: a global round trip and two barriers exposed in every small step.)
+template <class Ops>
+__global__ __launch_bounds__(256) void lstm_small_resident_kernel(const LstmStepArgs a) {
     // device-driven loops: loads and MFMAs run on the host's row bound, only the final store is limited to the device's live-row count (its scalar
     // load is then off the critical path: first use after the K walk)
     const int M = a.M, Ms = live_rows_of(a.M, a.m_dev);
     if ((int)blockIdx.y * 16 >= Ms) return;  // tile beyond the device's live rows (uniform per workgroup, before any barrier): a step of a loose bound costs a launch, not a pass
+    constexpr int LD = 512 + Ops::PAD;
+    const typename Ops::Tile A = Ops::Tile::template fixed<16 * LD>();
+    const int m0 = blockIdx.y * 16, u0 = blockIdx.x * 16;
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    // epilogue operands first (latency hides under the K walk)
+    const int erow = threadIdx.x >> 4, euc = threadIdx.x & 15;
+    const int em = m0 + erow, eu = u0 + euc;
+    const bool evalid = em < M && eu < a.U;
+    CellIn ci;
+    if (evalid) ci = cell_prefetch(a, em, eu);
+    const f32x4 acc = a.nterms == 2 ? small_walk<Ops, 2>(a, A, LD, m0, M, g, u0, lane) : small_walk<Ops, 1>(a, A, LD, m0, M, g, u0, lane);
+    gates_to_cell(a, g, lane, acc, Ops::kUnitsInLane, em, eu, evalid, Ms, ci);
+}
+
+// The streaming bf16x3 small step, for every other K: the row tile enters LDS one 512-k chunk at a time, the weight fragments stream from L2 one 32-k
+// step ahead of the MFMAs (rowtile_mma_x3).
+__global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a) {
+    const int M = a.M, Ms = live_rows_of(a.M, a.m_dev);
+    if ((int)blockIdx.y * 16 >= Ms) return;  // (as above)
     constexpr int KC = 512;
     __shared__ __attribute__((aligned(16))) u16 A_h[16 * (KC + 16)];  // row stride = 2 (mod 4) sixteen-byte slots: conflict-free fragment reads
     __shared__ __attribute__((aligned(16))) u16 A_lo[16 * (KC + 16)];
@@ -1065,8 +962,7 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
     CellIn ci;
     if (evalid) ci = cell_prefetch(a, em, eu);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (PRE) acc = a.nterms == 2 ? small_x3_walk<2>(a, A_h, A_lo, KC + 16, m0, M, g, u0, lane) : small_x3_walk<1>(a, A_h, A_lo, KC + 16, m0, M, g, u0, lane);
-    for (int t = 0; t < (PRE ? 0 : a.nterms); ++t) {
+    for (int t = 0; t < a.nterms; ++t) {
         const GemmTerm T = a.term[t];
         for (int k0 = 0; k0 < T.K; k0 += KC) {
             const int kc = min(KC, T.K - k0);
@@ -1084,26 +980,6 @@ __global__ __launch_bounds__(256) void lstm_small_x3_kernel(const LstmStepArgs a
     gates_to_cell(a, g, lane, acc, false, em, eu, evalid, Ms, ci);
 }
 
-
-// The small step in EXACT fp32 with register-resident weights (FCL_PRECISION=0; round 4): the structure of lstm_small_x3_kernel<true> on fragment-major
-// fp32 weights (fcl_gemm_term_t.Wff) and v_mfma_f32_16x16x4_f32, the weight fragment as the A operand (a lane's accumulators: four consecutive units
-// of one row).  Every term K = 256: two, or the input term alone in the zero-state form.
-__global__ __launch_bounds__(256) void lstm_small_ff_kernel(const LstmStepArgs a) {
-    const int M = a.M, Ms = live_rows_of(a.M, a.m_dev);
-    if ((int)blockIdx.y * 16 >= Ms) return;
-    constexpr int LD = 512 + 8;  // both terms' rows side by side (33 KB; row stride = 2 (mod 4) sixteen-byte slots, as 256 + 8 was), requested at entry
-    __shared__ __attribute__((aligned(16))) float A_f[16 * LD];
-    const int m0 = blockIdx.y * 16, u0 = blockIdx.x * 16;
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int erow = threadIdx.x >> 4, euc = threadIdx.x & 15;
-    const int em = m0 + erow, eu = u0 + euc;
-    const bool evalid = em < M && eu < a.U;
-    CellIn ci;
-    if (evalid) ci = cell_prefetch(a, em, eu);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = a.nterms == 2 ? small_ff_walk<2>(a, A_f, LD, m0, M, g, u0, lane) : small_ff_walk<1>(a, A_f, LD, m0, M, g, u0, lane);
-    gates_to_cell(a, g, lane, acc, true, em, eu, evalid, Ms, ci);
-}
 
 // ---- small-M LSTM step: wave g owns gate g of 16 units x 16 rows ------------------------------------
 constexpr int SMALL_KC = 512;  // K chunk resident in LDS
@@ -1171,11 +1047,11 @@ int launch_lstm_small(const LstmStepArgs& a, hipStream_t s) {
     }
     if (planes) {
         ProfScope ps("lstm_small_kernel/bf16x3", fl, a.M, s);
-        if (pre256) hipLaunchKernelGGL(lstm_small_x3_kernel<true>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(lstm_small_x3_kernel<false>, grid, dim3(256), 0, s, a);
+        if (pre256) hipLaunchKernelGGL(lstm_small_resident_kernel<OpsX3>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(lstm_small_x3_kernel, grid, dim3(256), 0, s, a);
     } else if (pre256 && ff && (a.U & 15) == 0) {
         ProfScope ps("lstm_small_ff_kernel/f32", fl, a.M, s);
-        hipLaunchKernelGGL(lstm_small_ff_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(lstm_small_resident_kernel<OpsF32>, grid, dim3(256), 0, s, a);
     } else {
         ProfScope ps("lstm_small_kernel", fl, a.M, s);
         hipLaunchKernelGGL(lstm_small_kernel, grid, dim3(256), 0, s, a);
@@ -1217,11 +1093,11 @@ static int launch_fp_drop(const void* const (&fn)[3], int drop_mode, dim3 grid, 
 // 14.1 us; this one at RT = 1 9.5, at RT = 2 11.9.  The 4-stream bench line does not move with either (44.5 - 45.7 M frames/s, same box): with four
 // passes in flight the pass is bound by the sum of workgroup-time, which RT = 1 doubles while it halves the latency.  Launched with one row tile per
 // workgroup (lowest single-pass latency: 339 -> 269 us of a 1.38 ms eager pass) below 4 096 rows, two above.
-template <int RT>
+template <class Ops, int RT>
 static int launch_feat_prenet_split(const FeatPrenetArgs& a, int rows, hipStream_t s) {
-    constexpr size_t lds_s = 2 * sizeof(unsigned short) * 16 * RT * ((256 + 16) + (96 + 16));
-    static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_split_kernel<0, RT>), reinterpret_cast<const void*>(feat_prenet_split_kernel<1, RT>),
-                                      reinterpret_cast<const void*>(feat_prenet_split_kernel<2, RT>)};
+    constexpr size_t lds_s = (size_t)Ops::LDS_BYTES * 16 * RT * ((256 + Ops::PAD) + (96 + Ops::PAD));
+    static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_split_kernel<Ops, 0, RT>), reinterpret_cast<const void*>(feat_prenet_split_kernel<Ops, 1, RT>),
+                                      reinterpret_cast<const void*>(feat_prenet_split_kernel<Ops, 2, RT>)};
     return launch_fp_drop(fn, a.drop_mode, dim3((rows + 16 * RT - 1) / (16 * RT), 1), lds_s, a, s);
 }
 
@@ -1231,43 +1107,34 @@ int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
     FCL_REQUIRE(!(a.U & 3) && !(a.O & 3) && !(a.P & 3), FCL_ERR_SHAPE, "feat_prenet: U/O/P must be multiples of 4");
     const size_t lds = sizeof(float) * 16 * ((size_t)(a.U + 4) + (a.O + 4) + (a.P + 4));
     FCL_REQUIRE(lds <= 160 * 1024, FCL_ERR_SHAPE, "feat_prenet: tile does not fit LDS (%zu B)", lds);
-    {
-        const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(feat_prenet_kernel), 160 * 1024);
-        if (rc) return rc;
-    }
     double fl = 0;
     if (a.h1) fl += 2.0 * a.M_feat * a.O * a.U;
     if (a.w0) fl += 2.0 * a.M_pre * ((double)a.P * a.O + (double)a.P * a.P);
-    static const int dbg = tunable("FP_DBG", 0);
-    const_cast<FeatPrenetArgs&>(a).dbg_phase = dbg;
     const bool planes = a.wf_hi && a.wf_lo && a.w0_hi && a.w0_lo && a.w1_hi && a.w1_lo && !(a.U & 7) && !(a.O & 7) && !(a.P & 7);
     FCL_REQUIRE(planes || (!a.pre_out_p && !a.before_p), FCL_ERR_INVALID, "feat_prenet: P32 outputs need the bf16x3 weight planes");
     FCL_REQUIRE(!a.w0 || a.pre_out || a.pre_out_p, FCL_ERR_INVALID, "feat_prenet: no prenet output buffer");
     FCL_REQUIRE(!a.pre_out_p || !(a.P & 31), FCL_ERR_SHAPE, "feat_prenet: P32 prenet output needs P %% 32 == 0");
     if (planes) {
-        const size_t lds3 = 2 * sizeof(unsigned short) * 16 * ((size_t)(a.U + 8) + (a.O + 8) + (a.P + 8));
-        {
-            const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(feat_prenet_x3_kernel), 160 * 1024);
-            if (rc) return rc;
-        }
         ProfScope ps("feat_prenet_kernel/bf16x3", fl, rows, s);
         if (a.U == 256 && a.O > 64 && a.O <= 96 && a.P == 256) {
-            const int rc = rows >= 4096 ? launch_feat_prenet_split<2>(a, rows, s) : launch_feat_prenet_split<1>(a, rows, s);
+            const int rc = rows >= 4096 ? launch_feat_prenet_split<OpsX3, 2>(a, rows, s) : launch_feat_prenet_split<OpsX3, 1>(a, rows, s);
             if (rc) return rc;
         } else {
+            const size_t lds3 = 2 * sizeof(unsigned short) * 16 * ((size_t)(a.U + 8) + (a.O + 8) + (a.P + 8));
+            const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(feat_prenet_x3_kernel), 160 * 1024);
+            if (rc) return rc;
             hipLaunchKernelGGL(feat_prenet_x3_kernel, dim3((rows + 15) / 16), dim3(512), lds3, s, a);
         }
     } else if (a.wf_ff && a.w0_ff && a.w1_ff && a.U == 256 && a.P == 256 && a.O > 64 && a.O <= 96 && !a.teacher_in && !a.pre_out_p && !a.before_p &&
                (!a.w0 || a.pre_out)) {
         // exact-fp32 mode with fragment-major fp32 weights: the register-resident form (19.2 -> ~9 us per launch at 2 400 rows)
         ProfScope ps("feat_prenet_split_kernel/f32", fl, rows, s);
-        constexpr size_t lds_f = sizeof(float) * 16 * ((256 + 8) + (96 + 8));
-        static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<0>), reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<1>),
-                                          reinterpret_cast<const void*>(feat_prenet_split_f32_kernel<2>)};
-        const int rc = launch_fp_drop(fn, a.drop_mode, dim3((rows + 15) / 16), lds_f, a, s);
+        const int rc = launch_feat_prenet_split<OpsF32, 1>(a, rows, s);
         if (rc) return rc;
     } else {
         ProfScope ps("feat_prenet_kernel", fl, rows, s);
+        const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(feat_prenet_kernel), 160 * 1024);
+        if (rc) return rc;
         hipLaunchKernelGGL(feat_prenet_kernel, dim3((rows + 15) / 16), dim3(512), lds, s, a);
     }
     return check_hip(hipGetLastError(), "feat_prenet launch");

@@ -154,7 +154,6 @@ struct FeatPrenetArgs {
     float* tap_prenet;  // optional [F, P]; row = frame_off[m] + t_cur
     unsigned short* pre_out_p;  // optional P32 planes of pre_out (ceil(P/32) lines per row): the next LSTM step's pre-split operand
     unsigned short* before_p;   // optional P32 planes of `before` (ceil(O/32) lines per row, zero past O): the postnet's pre-split operand
-    int dbg_phase;              // developer timing aid (FCL_FP_DBG): 1..3 = return after the loads / feat / prenet-0 phase (results are then garbage)
     const int* live;            // optional DEVICE live-row counts [*]: M_feat := min(M_feat, live[t_prev]), M_pre := min(M_pre, live[t_cur])
     unsigned int* status;       // with `live`: FCL_STATUS_ROWS_CAP when live[t_cur] exceeds the host's bound M_pre
     int out_act;                // FCL_ACT_*: output_activation_fn on the fed-back frame (decoder_sa.py:614-617); `before` stays raw

@@ -321,3 +321,36 @@ def seg_bounds(lens):
     lens = np.asarray(lens, dtype=np.int64)
     off = np.concatenate([[0], np.cumsum(lens)])
     return np.repeat(off[:-1], lens).astype(np.int32), np.repeat(off[1:], lens).astype(np.int32)
+
+
+def decoder_case(ops, hp, n_rows, seed, forced, masked, dur=None, dev="cuda:0"):
+    """One fcl_decoder_loop_fwd pass (closed-form weights, want_taps) and O.decoder_loop on the same inputs: ((before, taps), (ref_before, ref_taps)),
+    frame-major on the CPU.  dur: per-row durations, sorted descending (default: seeded Poisson draws); forced: teacher forcing on random frames;
+    masked: DROP_MASK with the closed-form keep masks (else DROP_NONE)."""
+    from fcl_taco2_amd.plan import SynthesisPlan
+    from oracle import fcl_oracle as O
+
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev).contiguous()  # noqa: E731
+    rng = np.random.RandomState(seed)
+    sd = torch_state_dict(hp)
+    plan = SynthesisPlan(np_state_dict(hp), hp, dev)
+    if dur is None:
+        dur = np.sort(np.clip(rng.poisson(6, n_rows), 1, 30))[::-1].astype(np.int32).copy()
+    lmax = int(dur[0])
+    att = rng.standard_normal((n_rows, hp.eunits)).astype(np.float32)
+    foff = np.concatenate([[0], np.cumsum(dur)[:-1]]).astype(np.int32)
+    F_ = int(dur.sum())
+    live = np.ascontiguousarray((dur[None, :] > np.arange(lmax)[:, None]).sum(1).astype(np.int32))
+    ys = rng.standard_normal((n_rows, lmax, hp.odim)).astype(np.float32) if forced else None
+    keep = SYN.closed_form_keep_mask((lmax, 2, n_rows, hp.prenet_units), seed) if masked else None
+    before, taps = ops.decoder_loop(plan.decoder, d(att), d(dur), live, d(foff), F_,
+                                    teacher_ys=d(ys) if ys is not None else None,
+                                    dropout_mode=ops.DROP_MASK if masked else ops.DROP_NONE,
+                                    prenet_keep=d(keep) if masked else None, want_taps=True)
+    pos = O.position_table(torch.from_numpy(dur))
+    with torch.no_grad():
+        outs, pres, l0, l1 = O.decoder_loop(sd, hp, torch.from_numpy(att), pos, lmax,
+                                            torch.from_numpy(ys) if ys is not None else None,
+                                            torch.from_numpy(keep) if masked else None)
+    mask = torch.from_numpy(dur[:, None] > np.arange(lmax)[None, :])
+    return (before.cpu(), [t.cpu() for t in taps]), (outs.transpose(1, 2)[mask], [pres[mask], l0[mask], l1[mask]])

@@ -1,6 +1,6 @@
 """Seeded inputs of the small-step row-tile tests (tests/test_small_step_rows_cpu.py without a GPU, tests/test_gpu_small_step_rows.py on one).
 
-The register-resident small LSTM step (csrc/decoder_step.hip: lstm_small_x3_kernel<true> / lstm_small_ff_kernel) keeps the activation rows of both
+The register-resident small LSTM step (csrc/decoder_step.hip: lstm_small_resident_kernel<OpsX3> / <OpsF32>) keeps the activation rows of both
 K = 256 terms side by side in ONE LDS tile: term 0 in columns 0 - 255, term 1 in columns 256 - 511.  A tile read from the wrong half is a wrong
 result only if the two terms' rows differ by more than the test's bound, so the two are drawn from different distributions: term 0's rows are
 N(0.25, 1), term 1's (the recurrent term: h_in) 0.5 N(0, 1), independent.  Everything else is lstm_step_ref.step_inputs's."""

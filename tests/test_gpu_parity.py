@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import TINY_S, TINY_T, max_abs, np_state_dict, torch_state_dict
+from helpers import TINY_S, TINY_T, decoder_case, max_abs, np_state_dict, torch_state_dict
 
 pytestmark = pytest.mark.gpu
 
@@ -193,39 +193,12 @@ def test_bilstm_both_algorithms(ops, hp):
         assert max_abs(out.cpu().reshape(B, T, 2 * H), ref) < 2e-5, algo
 
 
-def _decoder_case(ops, hp, n_rows, seed, forced, masked):
-    from fcl_taco2_amd.plan import SynthesisPlan
-
-    rng = np.random.RandomState(seed)
-    sd = torch_state_dict(hp)
-    plan = SynthesisPlan(np_state_dict(hp), hp, DEV)
-    dur = np.sort(np.clip(rng.poisson(6, n_rows), 1, 30))[::-1].astype(np.int32).copy()
-    lmax = int(dur[0])
-    att = rnd(rng, n_rows, hp.eunits)
-    foff = np.concatenate([[0], np.cumsum(dur)[:-1]]).astype(np.int32)
-    F_ = int(dur.sum())
-    live = np.ascontiguousarray((dur[None, :] > np.arange(lmax)[:, None]).sum(1).astype(np.int32))
-    ys = rnd(rng, n_rows, lmax, hp.odim) if forced else None
-    keep = SYN.closed_form_keep_mask((lmax, 2, n_rows, hp.prenet_units), seed) if masked else None
-    before, taps = ops.decoder_loop(plan.decoder, dev(att), dev(dur), live, dev(foff), F_,
-                                    teacher_ys=dev(ys) if ys is not None else None,
-                                    dropout_mode=ops.DROP_MASK if masked else ops.DROP_NONE,
-                                    prenet_keep=dev(keep) if masked else None, want_taps=True)
-    pos = O.position_table(torch.from_numpy(dur))
-    with torch.no_grad():
-        outs, pres, l0, l1 = O.decoder_loop(sd, hp, torch.from_numpy(att), pos, lmax,
-                                            torch.from_numpy(ys) if ys is not None else None,
-                                            torch.from_numpy(keep) if masked else None)
-    mask = torch.from_numpy(dur[:, None] > np.arange(lmax)[None, :])
-    return (before.cpu(), [t.cpu() for t in taps]), (outs.transpose(1, 2)[mask], [pres[mask], l0[mask], l1[mask]])
-
-
 @pytest.mark.parametrize("hp,n_rows", [(TINY_S, 37), (TINY_T, 5), (HP.student_hparams(dropout_rate=0.0), 300),
                                        (HP.student_hparams(), 97), (HP.teacher_hparams(), 70)], ids=["tinyS", "tinyT", "S_nodrop", "S_mask", "T_mask"])
 @pytest.mark.parametrize("forced", [False, True])
 def test_decoder_loop_vs_oracle(ops, hp, n_rows, forced):
     masked = hp.dropout_rate > 0
-    (before, taps), (ref_before, ref_taps) = _decoder_case(ops, hp, n_rows, 5, forced, masked)
+    (before, taps), (ref_before, ref_taps) = decoder_case(ops, hp, n_rows, 5, forced, masked)
     assert max_abs(before, ref_before) < 1e-4  # frame-major scatter (H10) + H6-H8 maths
     for a, b in zip(taps, ref_taps):
         assert max_abs(a, b) < 1e-4

@@ -1,4 +1,4 @@
-"""-m gpu: the register-resident small LSTM step (U = 256, K = 256 terms: lstm_small_x3_kernel<true>, and lstm_small_ff_kernel on fragment-major fp32
+"""-m gpu: the register-resident small LSTM step (U = 256, K = 256 terms: lstm_small_resident_kernel<OpsX3>, and <OpsF32> on fragment-major fp32
 weights) with BOTH terms' activation rows in one LDS tile, against the float64 cell of tests/lstm_step_ref.py at its per-element bound.
 
 M = 1, 16, 17, 33 (one row; exactly one tile; one tile plus a row; two tiles plus a row) x option sets l0, l1 (two terms) and l0z, l1z (one term,
@@ -6,7 +6,7 @@ h_in == NULL), and M = 17 once more with the device's row count at 11.  The two 
 (tests/small_step_rows_inputs.py; tests/test_small_step_rows_cpu.py shows that a tile read from the wrong half exceeds the bound on these arrays).
 As tests/test_gpu_lstm_step_f64.py, every case asserts the launched kernel (from the library's launch record), h and c within the bound, guard lines
 of a NaN pattern around every written buffer, and the sentinel in rows from min(M, *m_dev) on.  Under FCL_PRECISION=0 (read once per process) a
-child pytest re-runs the M = 17 cases: there the fp32-fragment operands select lstm_small_ff_kernel as well."""
+child pytest re-runs the M = 17 cases: there the fp32-fragment operands select the fp32 form as well."""
 import ctypes as C
 import os
 import subprocess
