@@ -137,6 +137,12 @@ class Evaluate(C.Structure):  # fcl_ev_t
         (n, _P) for n in ("path", "path_len", "cost", "pitch_a", "pitch_b", "counts", "sums")]
 
 
+class Align(C.Structure):  # fcl_al_t
+    _fields_ = [(n, C.c_int64) for n in ("frames", "rows", "cells")] + [(n, C.c_int32) for n in ("n_utt", "n_states", "max_t", "max_s", "max_skip", "reserved")] + [
+        (n, _P) for n in ("ll", "frame_off", "row_off", "cell_off", "row_state", "row_skip", "workspace")] + [("workspace_bytes", _Z)] + [
+        (n, _P) for n in ("frame_row", "row_begin", "row_frames", "score", "ok")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -306,6 +312,10 @@ SIGNATURES = {
     "fcl_ev_cepstra_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
     "fcl_ev_dtw_fwd": (_I, [C.POINTER(Evaluate), _P]),
     "fcl_ev_path_pitch_fwd": (_I, [C.POINTER(Evaluate), _P]),
+    "fcl_al_workspace_bytes": (_Z, [C.c_int64, _I]),
+    "fcl_al_loglik_fwd": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _P]),
+    "fcl_al_viterbi_fwd": (_I, [C.POINTER(Align), _P]),
+    "fcl_al_stats_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _I, _I, _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

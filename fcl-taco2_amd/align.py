@@ -1,0 +1,213 @@
+"""Forced-alignment driver on MI355X: wavs and phoneme transcripts -> TextGrids that `preprocess` reads, on fcl_taco2_amd/alignment.py.
+
+    python -m fcl_taco2_amd.align --wav-dir wavs --transcripts phones.txt --textgrid-out TextGrid --optional sp --model-out align.npz
+    python -m fcl_taco2_amd.align --wav-dir more_wavs --transcripts more.txt --textgrid-out TextGrid2 --optional sp --model align.npz
+
+`--transcripts` holds one utterance per line, `utt ph ph ...`: the phonemes, not words (there is no dictionary and no G2P here).  Every utterance of
+the transcripts needs `<utt>.wav` (16-bit PCM mono) in `--wav-dir`.  Without `--model` the inventory is the set of labels and the models are
+trained on these very utterances from a flat start (`--iterations`, default 15: not tuned, the synthetic corpora of the tests converge within 6);
+with `--model` the driver only aligns.  `--optional` names the labels that may be skipped as a whole (pauses between words); such a label must stand
+between two mandatory ones.  A label outside the inventory, an utterance longer than 4096 frames or 1024 rows (phonemes x states) and a misplaced
+optional label are refused by name before the first device call.
+
+Per utterance `<utt>.TextGrid` (long text format, one tier `phones`) goes to `--textgrid-out`: a boundary at frame k is written as
+(k hop + 0.5) / fs, the last interval ends at the wav's end, so that textgrid.alignment() gives back the aligner's durations with the last one less
+by 1, which preprocess's last-duration rule restores.  `--durations-out` also keeps the durations as `<utt>.npy` (int64, summing to the frame
+count).  `--report` holds the mean score per frame of every iteration and the utterances that could not be aligned (they get no TextGrid)."""
+import argparse
+import json
+import logging
+import os
+
+import numpy as np
+import torch
+
+from . import alignment, extract_features as X, features, griffinlim, resample, textgrid
+
+
+def read_transcripts(path):
+    """`utt ph ph ...` lines -> {utt: [labels]} in file order; a duplicate id or a line without labels is refused"""
+    out = {}
+    with open(path, encoding="utf-8") as f:
+        for no, ln in enumerate(f, 1):
+            parts = ln.split()
+            if not parts:
+                continue
+            if len(parts) < 2:
+                raise ValueError("%s:%d: utterance %s has no labels" % (path, no, parts[0]))
+            if parts[0] in out:
+                raise ValueError("%s:%d: utterance %s appears twice" % (path, no, parts[0]))
+            out[parts[0]] = parts[1:]
+    if not out:
+        raise ValueError("no transcripts in %s" % path)
+    return out
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="fcl_taco2_amd.align", description="flat-start forced alignment of phoneme transcripts on MI355X")
+    ap.add_argument("--wav-dir", required=True, metavar="DIR", help="<utt>.wav, 16-bit PCM mono")
+    ap.add_argument("--transcripts", required=True, metavar="FILE", help="lines `utt ph ph ...`")
+    ap.add_argument("--textgrid-out", required=True, metavar="DIR", help="<utt>.TextGrid with the tier `phones`")
+    ap.add_argument("--durations-out", default=None, metavar="DIR", help="<utt>.npy: durations in frames")
+    ap.add_argument("--optional", nargs="*", default=[], metavar="LABEL", help="labels that may be skipped (pauses)")
+    ap.add_argument("--states", type=int, default=alignment.STATES_DEFAULT, help="states per phoneme, 1 .. %d" % alignment.STATES_MAX)
+    ap.add_argument("--iterations", type=int, default=alignment.ITERATIONS_DEFAULT, help="alignment / re-estimation rounds after the flat start (not tuned)")
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--model-out", default=None, metavar="FILE.npz", help="keep the trained models")
+    g.add_argument("--model", default=None, metavar="FILE.npz", help="align with these models, without training")
+    ap.add_argument("--resample", action="store_true", help="resample wavs whose rate is not --fs on the GPU instead of refusing them")
+    ap.add_argument("--report", default=None, metavar="FILE.json", help="per-iteration mean score per frame, the utterances without an alignment")
+    ap.add_argument("--batch-cells", type=int, default=alignment.BATCH_CELLS, help="cells S x T per GPU batch")
+    ap.add_argument("--batch-frames", type=int, default=51200, help="frames per feature-extraction batch")
+    ap.add_argument("--n-mels", type=int, default=griffinlim.DEFAULTS["n_mels"])
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--verbose", type=int, default=1)
+    g = ap.add_argument_group("analysis (the defaults are the reference's preprocessing)")
+    g.add_argument("--mel-basis", default=None, metavar="FILE.npy", help="[n_mels, n_fft / 2 + 1] mel filterbank replacing the built Slaney one")
+    griffinlim.add_analysis_arguments(g)
+    return ap
+
+
+def parse_args(argv=None):
+    """Parses and checks what can be checked before the first device call; flag errors end in ap.error (SystemExit 2)."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if not os.path.isdir(args.wav_dir):
+        ap.error("--wav-dir %s is not a directory" % args.wav_dir)
+    for flag, p in (("--transcripts", args.transcripts), ("--model", args.model), ("--mel-basis", args.mel_basis)):
+        if p is not None and not os.path.isfile(p):
+            ap.error("%s %s is not a file" % (flag, p))
+    if not 1 <= args.states <= alignment.STATES_MAX:
+        ap.error("--states must lie in 1 .. %d" % alignment.STATES_MAX)
+    if args.iterations < 0 or args.batch_cells < 1 or args.batch_frames < 1:
+        ap.error("--iterations must not be negative, --batch-cells and --batch-frames must be positive")
+    if args.n_mels - 1 < alignment.ORDER:
+        ap.error("--n-mels must exceed the %d cepstra the features take" % alignment.ORDER)
+    try:
+        griffinlim.check_config(args.n_fft, args.hop, args.n_fft if args.win_length is None else args.win_length, args.n_mels, args.fs, args.fmin, args.fmax)
+    except (NotImplementedError, ValueError) as e:
+        ap.error(str(e))
+    return args
+
+
+def plan_utterances(args, transcripts):
+    """[(utt, path, rate, samples at the analysis rate)] from the headers alone; a missing wav, another rate without --resample and more than 4096
+    frames are refused by name"""
+    out = []
+    for u in transcripts:
+        path = os.path.join(args.wav_dir, u + ".wav")
+        if not os.path.isfile(path):
+            raise ValueError("utterance %s of %s has no wav: %s is missing" % (u, args.transcripts, path))
+        rate, n = X.wav_rate_and_samples(path)
+        if rate != args.fs:
+            if not args.resample:
+                raise ValueError("%s: sampling rate %d, --fs is %d (--resample resamples on the device)" % (path, rate, args.fs))
+            L, M, _ = resample.check_rates(rate, args.fs)
+            n = resample.out_samples(n, L, M)
+        T = features.frames_of(n, args.hop)
+        if T > alignment.FRAMES_MAX:
+            raise ValueError("utterance %s has %d frames; the alignment covers 1 .. %d" % (u, T, alignment.FRAMES_MAX))
+        out.append((u, path, rate, n))
+    return out
+
+
+def extract(args, utts, af):
+    """the aligner's features of every utterance, on the device, in feature batches of --batch-frames"""
+    dev, fs = af.extractor.plan.device, args.fs
+    cache = resample.ResamplerCache(args.device, fs) if args.resample else None
+    feats, batch, frames = [], [], 0
+
+    def flush():
+        if not batch:
+            return
+        xs = [torch.from_numpy(X.read_wav(path, rate)).to(dev) for _, path, rate, _ in batch]
+        lens = [int(x.numel()) for x in xs]
+        groups = {}
+        for i, (_, _, rate, _) in enumerate(batch):
+            if rate != fs:
+                groups.setdefault(rate, []).append(i)
+        for rate, g in groups.items():
+            y, out_lens = cache(rate).resample_packed(torch.cat([xs[i] for i in g]), [lens[i] for i in g])
+            o = np.concatenate([[0], np.cumsum(out_lens)])
+            for k, i in enumerate(g):
+                xs[i], lens[i] = y[int(o[k]) : int(o[k + 1])], int(out_lens[k])
+        if lens != [n for _, _, _, n in batch]:
+            raise RuntimeError("align: the sample counts read do not match the headers' (%s .. %s)" % (batch[0][0], batch[-1][0]))
+        ids = [u for u, _, _, _ in batch]
+        mel, energy, frame_lens = af.extractor.extract_packed(torch.cat(xs), lens, ids=ids)
+        feats.extend(af.from_mel(mel, energy, frame_lens))
+        del batch[:]
+
+    for item in utts:
+        T = features.frames_of(item[3], args.hop)
+        if batch and frames + T > args.batch_frames:
+            flush()
+            frames = 0
+        batch.append(item)
+        frames += T
+    flush()
+    return feats
+
+
+def align(args):
+    """-> the --report document"""
+    transcripts = read_transcripts(args.transcripts)
+    ids = list(transcripts)
+    model = alignment.AlignModel.load(args.model) if args.model else None
+    phones = model.phones if model else sorted(set(p for tr in transcripts.values() for p in tr))
+    states = model.K if model else args.states
+    for p in args.optional:
+        if p not in phones:
+            logging.warning("--optional %s: no such label in the %s", p, "model" if model else "transcripts")
+    al = alignment.Aligner(args.device, phones, states, optional=[p for p in args.optional if p in phones], model=model, batch_cells=args.batch_cells)
+    for u in ids:  # every refusal of a transcript, before the first device call
+        alignment.build_graph(transcripts[u], al.index, al.optional, al.K, u)
+    utts = plan_utterances(args, transcripts)
+    af = alignment.AlignFeatures(features.from_args(args, args.device))
+    if model is not None and model.settings != af.settings:
+        diff = sorted(k for k in set(model.settings) | set(af.settings) if model.settings.get(k) != af.settings.get(k))
+        raise ValueError("%s was trained on other features: %s differ" % (args.model, ", ".join(diff)))
+    al.settings = af.settings
+    feats = extract(args, utts, af)
+    trs = [transcripts[u] for u in ids]
+    history = dict(score=[], failed=[])
+    if model is None:
+        history = al.fit(feats, trs, args.iterations, ids=ids)
+        for it, s in enumerate(history["score"]):
+            logging.info("iteration %d: mean score per frame %.4f, %d utterances without an alignment", it + 1, s, len(history["failed"][it]))
+        if args.model_out:
+            al.model.save(args.model_out)
+    res = al.align(feats, trs, ids=ids)
+    os.makedirs(args.textgrid_out, exist_ok=True)
+    if args.durations_out:
+        os.makedirs(args.durations_out, exist_ok=True)
+    failed, frames, total = [], 0, 0.0
+    for (u, _, _, n), r in zip(utts, res):
+        if not r["ok"]:
+            failed.append(u)
+            continue
+        frames, total = frames + sum(r["durations"]), total + r["score"]
+        rows = textgrid.frame_intervals(r["phones"], r["durations"], args.fs, args.hop, n)
+        textgrid.write_textgrid(os.path.join(args.textgrid_out, u + ".TextGrid"), {"phones": rows}, rows[-1][1])
+        if args.durations_out:
+            np.save(os.path.join(args.durations_out, u + ".npy"), np.asarray(r["durations"], dtype=np.int64))
+    return dict(n_utt=len(ids), n_aligned=len(ids) - len(failed), not_aligned=failed, score_per_frame=total / max(frames, 1),
+                iterations=[dict(score_per_frame=s, not_aligned=f) for s, f in zip(history["score"], history["failed"])],
+                settings=dict(states=al.K, optional=sorted(al.optional), phones=al.phones, trained=model is None, model=args.model, features=af.settings,
+                              resample=bool(args.resample)))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
+    doc = align(args)
+    torch.cuda.synchronize()
+    if args.report:
+        with open(args.report, "w") as f:
+            json.dump(doc, f, indent=1)
+    print("align: %d of %d utterances aligned, mean score per frame %.4f" % (doc["n_aligned"], doc["n_utt"], doc["score_per_frame"]))
+    return doc
+
+
+if __name__ == "__main__":
+    main()

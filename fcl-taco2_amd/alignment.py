@@ -1,0 +1,426 @@
+"""Forced alignment on the HIP path: flat-start Viterbi training of single-Gaussian monophone models, and the alignment they give (csrc/align.hip;
+DESIGN.md §6i).
+
+What Kaldi's monophone pass and HTK's flat start do: start from an equal segmentation of every utterance over its transcript, then alternate a
+Viterbi alignment with a re-estimation of the Gaussians, and keep the last alignment.  Every phoneme of the inventory has K left-to-right states
+without transition probabilities; a phoneme named optional (a pause between words) may be skipped as a whole.  The E-step runs on the device
+(log-likelihoods, Viterbi with its backtrack, statistics in float64), the M-step on the host in float64.  The contract is stated in
+include/fcl_hip.h "Forced alignment" and restated in float64 numpy in tests/align_ref.py.  Agreement with the Montreal Forced Aligner on real
+recordings stays unpinned: neither that tool nor real speech is available here.
+
+    al = Aligner("cuda:0", phones, states=3, optional=("sp",))
+    history = al.fit(features, transcripts, iterations=15)      # features: per utterance [T, D] on the device
+    results = al.align(features, transcripts)                   # per utterance: phones, durations in frames (summing to T), score
+
+No CPU fallback."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, metrics, ops
+
+STATES_DEFAULT, STATES_MAX, MODEL_STATES_MAX, DIM_MAX, FRAMES_MAX, ROWS_MAX, UTT_MAX = 3, 3, 1024, 40, 4096, 1024, 65535
+BATCH_CELLS = 16 << 20
+BATCH_LL = 1 << 28  # frames x M of one batch's log-likelihood matrix (the entries need it below 2^31)
+VAR_FLOOR = 0.01
+ORDER, DELTA_WINDOW, ENERGY_FLOOR = 13, 2, 1e-10
+ITERATIONS_DEFAULT = 15  # not tuned: the synthetic corpora of the tests converge within 6
+
+
+# ---- model ------------------------------------------------------------------------------------------------------------------------------------------
+def gconst(var):
+    """gconst[m] = -0.5 (D ln 2pi + sum_d ln var[m][d]), float64"""
+    var = np.asarray(var, dtype=np.float64)
+    return -0.5 * (var.shape[1] * math.log(2.0 * math.pi) + np.log(var).sum(axis=1))
+
+
+class AlignModel(object):
+    """phones (the inventory, in index order), K states per phoneme, mean / var [M = len(phones) K][D] in float64, and the settings of the
+    features they were trained on (a dict of plain values; a model is only good for features made the same way)."""
+
+    def __init__(self, phones, states, mean, var, settings=None):
+        self.phones, self.K = [str(p) for p in phones], int(states)
+        check_inventory(self.phones, self.K)
+        self.mean, self.var = np.array(mean, dtype=np.float64), np.array(var, dtype=np.float64)
+        self.settings = dict(settings or {})
+        M = len(self.phones) * self.K
+        if self.mean.ndim != 2 or self.mean.shape != self.var.shape or self.mean.shape[0] != M or not 1 <= self.mean.shape[1] <= DIM_MAX:
+            raise ValueError("fcl-taco2_amd: alignment: mean / var must be [%d states][1 .. %d], got %r and %r" % (M, DIM_MAX, self.mean.shape, self.var.shape))
+        if not (np.isfinite(self.mean).all() and np.isfinite(self.var).all() and (self.var > 0).all()):
+            raise ValueError("fcl-taco2_amd: alignment: the model needs finite means and positive finite variances")
+
+    @property
+    def n_states(self):
+        return self.mean.shape[0]
+
+    @property
+    def dim(self):
+        return self.mean.shape[1]
+
+    def params32(self):
+        """(mean, ivar, gconst) as uploaded: formed in float64, rounded to float32"""
+        return self.mean.astype(np.float32), (1.0 / self.var).astype(np.float32), gconst(self.var).astype(np.float32)
+
+    def upload(self, dev):
+        return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.params32())
+
+    def save(self, path):
+        import json
+
+        with open(path, "wb") as f:
+            np.savez(f, phones=np.asarray(self.phones), states=np.int64(self.K), mean=self.mean, var=self.var,
+                     settings=np.asarray(json.dumps(self.settings, sort_keys=True)))
+
+    @classmethod
+    def load(cls, path):
+        import json
+
+        with np.load(path, allow_pickle=False) as z:
+            missing = [k for k in ("phones", "states", "mean", "var", "settings") if k not in z.files]
+            if missing:
+                raise ValueError("%s: not an alignment model (no %s)" % (path, ", ".join(missing)))
+            return cls([str(p) for p in z["phones"]], int(z["states"]), z["mean"], z["var"], json.loads(str(z["settings"])))
+
+
+def check_inventory(phones, states):
+    if not 1 <= int(states) <= STATES_MAX:
+        raise ValueError("fcl-taco2_amd: alignment: --states %r must lie in 1 .. %d" % (states, STATES_MAX))
+    if len(set(phones)) != len(phones) or not phones:
+        raise ValueError("fcl-taco2_amd: alignment: the phoneme inventory must be non-empty and without duplicates")
+    if len(phones) * int(states) > MODEL_STATES_MAX:
+        raise ValueError("fcl-taco2_amd: alignment: %d phonemes x %d states exceed %d model states" % (len(phones), int(states), MODEL_STATES_MAX))
+
+
+# ---- utterance graph --------------------------------------------------------------------------------------------------------------------------------
+def build_graph(labels, index, optional, K, utt="#?"):
+    """A transcript -> (row_state, row_skip, row_phone) int32: K rows per phoneme, row_skip[a + K] = K + 1 behind an optional phoneme on the rows
+    [a, a + K).  Refused naming the utterance: a label that is not in the inventory, an optional phoneme that is first, last or next to another
+    optional one, no labels, more than 1024 rows."""
+    labels = list(labels)
+    if not labels:
+        raise ValueError("fcl-taco2_amd: alignment: utterance %s has an empty transcript" % utt)
+    for p in labels:
+        if p not in index:
+            raise ValueError("fcl-taco2_amd: alignment: utterance %s: label %r is not in the inventory" % (utt, p))
+    n = len(labels)
+    if n * K > ROWS_MAX:
+        raise ValueError("fcl-taco2_amd: alignment: utterance %s has %d phonemes x %d states = %d rows; the alignment covers at most %d"
+                         % (utt, n, K, n * K, ROWS_MAX))
+    opt = [p in optional for p in labels]
+    row_skip = np.zeros(n * K, dtype=np.int32)
+    for i in np.flatnonzero(opt):
+        if i == 0 or i == n - 1:
+            raise ValueError("fcl-taco2_amd: alignment: utterance %s: the optional phoneme %r is the %s label; an optional phoneme needs a mandatory "
+                             "one on either side" % (utt, labels[i], "first" if i == 0 else "last"))
+        if opt[i - 1] or opt[i + 1]:
+            raise ValueError("fcl-taco2_amd: alignment: utterance %s: the optional phonemes %r and %r are next to each other (labels %d and %d)"
+                             % (utt, labels[i - 1 if opt[i - 1] else i], labels[i if opt[i - 1] else i + 1], i - 1 if opt[i - 1] else i,
+                                i if opt[i - 1] else i + 1))
+        row_skip[(i + 1) * K] = K + 1
+    row_state = np.asarray([index[p] * K + k for p in labels for k in range(K)], dtype=np.int32)
+    return row_state, row_skip, np.repeat(np.arange(n, dtype=np.int32), K)
+
+
+def optional_rows(row_skip):
+    """the rows a skip jumps over"""
+    opt = np.zeros(len(row_skip), dtype=bool)
+    for r in np.flatnonzero(np.asarray(row_skip) >= 2):
+        opt[r - int(row_skip[r]) + 1 : r] = True
+    return opt
+
+
+def uniform_alignment(T, row_skip):
+    """row_frames [S] int64 of the equal split of T frames: over all rows when T >= S, over the mandatory rows otherwise; None when the mandatory
+    rows alone do not fit.  Row i of the n rows taken gets floor((i + 1) T / n) - floor(i T / n) frames."""
+    S = len(row_skip)
+    rows = np.arange(S) if T >= S else np.flatnonzero(~optional_rows(row_skip))
+    n = len(rows)
+    if n == 0 or T < n:
+        return None
+    out = np.zeros(S, dtype=np.int64)
+    out[rows] = np.diff((np.arange(n + 1, dtype=np.int64) * int(T)) // n)
+    return out
+
+
+def mstep(n, s, q, mean, var, var_floor=VAR_FLOOR):
+    """float64 on the host: mean = s / n, var = max(q / n - mean^2, var_floor x global variance); a state with n < 2 keeps its parameters"""
+    n, s, q = np.asarray(n, dtype=np.float64), np.asarray(s, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    N = n.sum()
+    if N < 2:
+        raise _lib.FclError("fcl-taco2_amd: alignment: no aligned frames to estimate the model from")
+    gmean = s.sum(axis=0) / N
+    floor = float(var_floor) * (q.sum(axis=0) / N - gmean * gmean)
+    mean, var = np.array(mean, dtype=np.float64), np.array(var, dtype=np.float64)
+    for m in np.flatnonzero(n >= 2):
+        mean[m] = s[m] / n[m]
+        var[m] = np.maximum(q[m] / n[m] - mean[m] * mean[m], floor)
+    return mean, var
+
+
+def global_model(n, s, q, n_states):
+    """every state at the global mean and variance of the frames counted: the parameters a state keeps that the flat start gives fewer than 2 frames"""
+    N = float(np.sum(n))
+    gmean = np.sum(s, axis=0) / N
+    return np.tile(gmean, (n_states, 1)), np.tile(np.sum(q, axis=0) / N - gmean * gmean, (n_states, 1))
+
+
+# ---- packed batches -----------------------------------------------------------------------------------------------------------------------------------
+class AlignMaps(object):
+    """The tables of a packed batch on the device: frame_off / row_off [n + 1] int32, cell_off [n + 1] int64 (cumulative S T), row_state /
+    row_skip [rows] int32, and the batch's rows grouped by model state (state_off [M + 1], state_rows [rows]: ascending row index inside a group),
+    with their totals on the host"""
+
+    def __init__(self, frame_lens, graphs, n_states, dev):
+        self.frame_lens = [int(t) for t in frame_lens]
+        self.row_lens = [len(g[0]) for g in graphs]
+        assert len(self.frame_lens) == len(self.row_lens)
+        self.n_utt, self.n_states = len(self.frame_lens), int(n_states)
+        cum = lambda v: np.concatenate([[0], np.cumsum(np.asarray(v, dtype=np.int64))]).astype(np.int64)
+        self.frame_offs, self.row_offs = cum(self.frame_lens), cum(self.row_lens)
+        self.cell_offs = cum([t * s for t, s in zip(self.frame_lens, self.row_lens)])
+        self.frames, self.rows, self.cells = int(self.frame_offs[-1]), int(self.row_offs[-1]), int(self.cell_offs[-1])
+        self.max_t, self.max_s = max(self.frame_lens + [0]), max(self.row_lens + [0])
+        self.row_states = np.concatenate([np.asarray(g[0], dtype=np.int32) for g in graphs]) if graphs else np.zeros(0, np.int32)
+        self.row_skips = np.concatenate([np.asarray(g[1], dtype=np.int32) for g in graphs]) if graphs else np.zeros(0, np.int32)
+        self.max_skip = int(self.row_skips.max()) if self.rows else 0
+        self.state_rows_h = np.argsort(self.row_states, kind="stable").astype(np.int32)
+        self.state_offs = cum(np.bincount(self.row_states, minlength=self.n_states))
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        self.frame_off, self.row_off, self.cell_off = t(self.frame_offs, np.int32), t(self.row_offs, np.int32), t(self.cell_offs, np.int64)
+        self.row_state, self.row_skip = t(self.row_states, np.int32), t(self.row_skips, np.int32)
+        self.state_off, self.state_rows = t(self.state_offs, np.int32), t(self.state_rows_h, np.int32)
+
+    def workspace_bytes(self):
+        return int(_lib.load().fcl_al_workspace_bytes(self.cells, self.n_utt))
+
+
+# one launch each, on caller-owned buffers (the tests surround them with guard zones)
+def launch_loglik(params, x, ll, frames):
+    """params: (mean [M][D], ivar [M][D], gconst [M]) float32 on the device; x [frames][D] -> ll [frames][M]"""
+    mean, ivar, gc = params
+    _lib.check(_lib.load().fcl_al_loglik_fwd(x.data_ptr(), mean.data_ptr(), ivar.data_ptr(), gc.data_ptr(), ll.data_ptr(), int(frames), int(mean.shape[1]),
+                                             int(mean.shape[0]), ops._stream()))
+
+
+def launch_viterbi(mp, ll, workspace, frame_row, row_begin, row_frames, score, ok):
+    """ll [frames][M] float32 -> frame_row [frames], row_begin / row_frames [rows], ok [n_utt] int32, score [n_utt] float32; workspace: uint8,
+    AlignMaps.workspace_bytes() of it"""
+    a = _lib.Align()
+    a.frames, a.rows, a.cells = mp.frames, mp.rows, mp.cells
+    a.n_utt, a.n_states, a.max_t, a.max_s, a.max_skip = mp.n_utt, mp.n_states, mp.max_t, mp.max_s, mp.max_skip
+    a.frame_off, a.row_off, a.cell_off = mp.frame_off.data_ptr(), mp.row_off.data_ptr(), mp.cell_off.data_ptr()
+    a.row_state, a.row_skip = mp.row_state.data_ptr(), mp.row_skip.data_ptr()
+    a.ll, a.workspace, a.workspace_bytes = ll.data_ptr(), workspace.data_ptr(), int(workspace.numel() * workspace.element_size())
+    a.frame_row, a.row_begin, a.row_frames, a.score, a.ok = (v.data_ptr() for v in (frame_row, row_begin, row_frames, score, ok))
+    _lib.check(_lib.load().fcl_al_viterbi_fwd(C.byref(a), ops._stream()))
+
+
+def launch_stats(mp, x, row_begin, row_frames, acc_n, acc_s, acc_q):
+    """x [frames][D] float32 over the rows' runs: ADDS to acc_n [M] int64, acc_s / acc_q [M][D] float64"""
+    _lib.check(_lib.load().fcl_al_stats_fwd(x.data_ptr(), row_begin.data_ptr(), row_frames.data_ptr(), mp.state_off.data_ptr(), mp.state_rows.data_ptr(),
+                                            acc_n.data_ptr(), acc_s.data_ptr(), acc_q.data_ptr(), mp.frames, mp.rows, int(acc_s.shape[1]), mp.n_states,
+                                            ops._stream()))
+
+
+def utt_batches(frame_lens, row_lens, batch_cells, n_states=1):
+    """consecutive runs of utterances whose cells S T sum to at most batch_cells (a larger single utterance goes alone) and whose frames x M stay
+    below BATCH_LL, at most 65535 utterances each"""
+    out, cur, cells, frames = [], [], 0, 0
+    for i, (t, s) in enumerate(zip(frame_lens, row_lens)):
+        c = int(t) * int(s)
+        if cur and (cells + c > batch_cells or (frames + int(t)) * n_states > BATCH_LL or len(cur) >= UTT_MAX):
+            out.append(cur)
+            cur, cells, frames = [], 0, 0
+        cur.append(i)
+        cells, frames = cells + c, frames + int(t)
+    return out + ([cur] if cur else [])
+
+
+# ---- features -----------------------------------------------------------------------------------------------------------------------------------------
+def deltas(x, window=DELTA_WINDOW):
+    """[T, C] -> the regression deltas over +-window frames with replicated edges: sum_n n (x[t + n] - x[t - n]) / (2 sum_n n^2)"""
+    T = x.shape[0]
+    idx = torch.arange(T, device=x.device)
+    out = torch.zeros_like(x)
+    for n in range(1, window + 1):
+        out = out + float(n) * (x[torch.clamp(idx + n, max=T - 1)] - x[torch.clamp(idx - n, min=0)])
+    return out / (2.0 * sum(n * n for n in range(1, window + 1)))
+
+
+def feature_settings(plan, order=ORDER):
+    """the settings an AlignModel carries: the analysis of the FeaturePlan and the make of the features"""
+    return dict(fs=plan.fs, n_fft=plan.n_fft, hop=plan.hop, win_length=plan.win_length, n_mels=plan.A, fmin=plan.fmin, fmax=plan.fmax, order=int(order),
+                delta_window=DELTA_WINDOW, dim=2 * (int(order) + 1))
+
+
+class AlignFeatures(object):
+    """FeatureExtractor output -> the aligner's features, torch expressions on the device: `order` cepstra of the raw log-mel (metrics.CepstraPlan)
+    with the utterance mean subtracted, the log frame energy minus its utterance maximum, and the deltas of both over +-2 frames with replicated
+    edges: D = 2 (order + 1) = 28."""
+
+    def __init__(self, extractor, order=ORDER):
+        if extractor.plan.mel_stats is not None:
+            raise ValueError("fcl-taco2_amd: alignment: the feature extractor must give raw log10 mels (no mel_stats)")
+        self.extractor, self.order = extractor, int(order)
+        self.cepstra = metrics.CepstraPlan(extractor.plan.device, extractor.plan.A, self.order)
+        self.dim = 2 * (self.order + 1)
+        self.settings = feature_settings(extractor.plan, self.order)
+
+    def from_mel(self, mel, energy, frame_lens):
+        """mel [sum T, n_mels] raw log10, energy [sum T] -> list of [T, D] float32 device tensors"""
+        dev = self.extractor.plan.device
+        with torch.cuda.device(dev):
+            c = torch.empty(mel.shape[0], self.order, device=dev, dtype=torch.float32)
+            metrics.launch_cepstra(self.cepstra, mel.contiguous(), c, mel.shape[0])
+            le = torch.log(torch.clamp(energy.to(torch.float32), min=ENERGY_FLOOR))
+            out, o = [], 0
+            for T in frame_lens:
+                cu, eu = c[o : o + T], le[o : o + T]
+                base = torch.cat([cu - cu.mean(dim=0, keepdim=True), (eu - eu.max()).unsqueeze(1)], dim=1)
+                out.append(torch.cat([base, deltas(base)], dim=1).contiguous())
+                o += T
+        return out
+
+    def from_waves(self, waves, ids=None):
+        """list of 1-D float waveforms at the analysis rate -> list of [T, D] device tensors: one mel launch, one cepstra launch"""
+        xs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in waves]
+        mel, energy, frame_lens = self.extractor.extract_packed(np.concatenate(xs), [len(x) for x in xs], ids=ids)
+        return self.from_mel(mel, energy, frame_lens)
+
+
+def check_features(features, ids=None):
+    """per-utterance [T, D] tensors -> (frame counts, D); another shape, more than one D, D > 40 and T outside 1 .. 4096 are refused by id"""
+    D = None
+    for i, x in enumerate(features):
+        name = ids[i] if ids is not None else "#%d" % i
+        if x.dim() != 2 or not 1 <= x.shape[1] <= DIM_MAX or (D is not None and x.shape[1] != D):
+            raise ValueError("fcl-taco2_amd: alignment: utterance %s: features %r; [T, D] with one 1 <= D <= %d expected" % (name, tuple(x.shape), DIM_MAX))
+        D = int(x.shape[1])
+        if not 1 <= x.shape[0] <= FRAMES_MAX:
+            raise ValueError("fcl-taco2_amd: alignment: utterance %s has %d frames; the alignment covers 1 .. %d" % (name, x.shape[0], FRAMES_MAX))
+    return [int(x.shape[0]) for x in features], D
+
+
+# ---- the aligner --------------------------------------------------------------------------------------------------------------------------------------
+class Aligner(object):
+    """Flat-start training and alignment.  phones: the inventory; optional: the labels that may be skipped (pauses); model: an AlignModel to align
+    with (fit replaces it); settings: what the model is to carry about its features."""
+
+    def __init__(self, device, phones=None, states=STATES_DEFAULT, optional=(), model=None, var_floor=VAR_FLOOR, batch_cells=BATCH_CELLS, settings=None):
+        if not str(device).startswith("cuda"):
+            raise _lib.FclError("fcl-taco2_amd: Aligner needs a GPU device (no CPU fallback)")
+        if model is not None:
+            phones, states = model.phones, model.K
+        check_inventory(list(phones or []), states)
+        if batch_cells < 1:
+            raise ValueError("fcl-taco2_amd: alignment: --batch-cells must be positive (got %r)" % (batch_cells,))
+        self.device, self.phones, self.K = torch.device(device), [str(p) for p in phones], int(states)
+        self.index = {p: i for i, p in enumerate(self.phones)}
+        self.optional = set(str(p) for p in optional)
+        for p in sorted(self.optional):
+            if p not in self.index:
+                raise ValueError("fcl-taco2_amd: alignment: the optional label %r is not in the inventory" % p)
+        self.n_states = len(self.phones) * self.K
+        self.model, self.var_floor, self.batch_cells, self.settings = model, float(var_floor), int(batch_cells), dict(settings or {})
+
+    # -- preparation: everything that can be refused is refused before the first launch
+    def _prepare(self, features, transcripts, ids):
+        if len(features) != len(transcripts):
+            raise _lib.FclError("fcl-taco2_amd: alignment: %d feature matrices for %d transcripts" % (len(features), len(transcripts)))
+        features[:] = [torch.as_tensor(x) for x in features]
+        graphs = [build_graph(tr, self.index, self.optional, self.K, ids[i] if ids is not None else "#%d" % i) for i, tr in enumerate(transcripts)]
+        return (graphs,) + check_features(features, ids)
+
+    def _batches(self, features, graphs, frame_lens):
+        """[(indices, AlignMaps, x [frames][D])] of the consecutive batches"""
+        dev = self.device
+        for idx in utt_batches(frame_lens, [len(g[0]) for g in graphs], self.batch_cells, self.n_states):
+            mp = AlignMaps([frame_lens[i] for i in idx], [graphs[i] for i in idx], self.n_states, dev)
+            x = torch.cat([torch.as_tensor(features[i]).to(device=dev, dtype=torch.float32) for i in idx]).contiguous()
+            yield idx, mp, x
+
+    def _viterbi(self, mp, x, params):
+        """one batch: log-likelihoods and Viterbi -> (row_begin, row_frames, score, ok) device tensors"""
+        dev = self.device
+        ll = torch.empty(mp.frames, mp.n_states, device=dev, dtype=torch.float32)
+        launch_loglik(params, x, ll, mp.frames)
+        ws = torch.empty(mp.workspace_bytes(), device=dev, dtype=torch.uint8)
+        frame_row = torch.empty(mp.frames, device=dev, dtype=torch.int32)
+        row_begin, row_frames = torch.empty(mp.rows, device=dev, dtype=torch.int32), torch.empty(mp.rows, device=dev, dtype=torch.int32)
+        score, ok = torch.empty(mp.n_utt, device=dev, dtype=torch.float32), torch.empty(mp.n_utt, device=dev, dtype=torch.int32)
+        launch_viterbi(mp, ll, ws, frame_row, row_begin, row_frames, score, ok)
+        return row_begin, row_frames, score, ok
+
+    def _acc(self, D):
+        dev = self.device
+        return (torch.zeros(self.n_states, device=dev, dtype=torch.int64), torch.zeros(self.n_states, D, device=dev, dtype=torch.float64),
+                torch.zeros(self.n_states, D, device=dev, dtype=torch.float64))
+
+    def fit(self, features, transcripts, iterations=ITERATIONS_DEFAULT, ids=None, callback=None):
+        """features: per utterance a [T, D] tensor; transcripts: per utterance its labels.  The flat start, then `iterations` times align and
+        re-estimate.  -> dict(score: the mean score per aligned frame of each iteration, failed: per iteration the utterances without an alignment
+        (ids, or positions)); self.model is the trained AlignModel.  callback(iteration, model) runs after every re-estimation."""
+        features = list(features)
+        graphs, frame_lens, D = self._prepare(features, transcripts, ids)
+        name = lambda i: ids[i] if ids is not None else i
+        with torch.cuda.device(self.device):
+            batches = list(self._batches(features, graphs, frame_lens))
+            acc = self._acc(D)
+            for idx, mp, x in batches:  # the flat start: the statistics of the equal split
+                flat = [uniform_alignment(frame_lens[i], graphs[i][1]) for i in idx]
+                counts = np.concatenate([np.zeros(len(graphs[i][0]), np.int64) if c is None else c for i, c in zip(idx, flat)])
+                begin = np.concatenate([mp.frame_offs[k] + np.concatenate([[0], np.cumsum(c)[:-1]]) if c is not None else np.zeros(len(graphs[i][0]), np.int64)
+                                        for k, (i, c) in enumerate(zip(idx, flat))])
+                t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+                launch_stats(mp, x, t(begin), t(counts), *acc)
+            n, s, q = (v.cpu().numpy() for v in acc)
+            mean, var = mstep(n, s, q, *global_model(n, s, q, self.n_states), var_floor=self.var_floor)
+            self.model = AlignModel(self.phones, self.K, mean, var, self.settings)
+            history = dict(score=[], failed=[])
+            for it in range(int(iterations)):
+                params, acc = self.model.upload(self.device), self._acc(D)
+                total, frames, failed = 0.0, 0, []
+                for idx, mp, x in batches:
+                    row_begin, row_frames, score, ok = self._viterbi(mp, x, params)
+                    launch_stats(mp, x, row_begin, row_frames, *acc)
+                    okh, sh = ok.cpu().numpy(), score.cpu().numpy().astype(np.float64)
+                    for k, i in enumerate(idx):
+                        if okh[k]:
+                            total, frames = total + sh[k], frames + frame_lens[i]
+                        else:
+                            failed.append(name(i))
+                n, s, q = (v.cpu().numpy() for v in acc)
+                mean, var = mstep(n, s, q, self.model.mean, self.model.var, var_floor=self.var_floor)
+                self.model = AlignModel(self.phones, self.K, mean, var, self.settings)
+                history["score"].append(total / max(frames, 1))
+                history["failed"].append(failed)
+                if callback is not None:
+                    callback(it, self.model)
+        return history
+
+    def align(self, features, transcripts, ids=None):
+        """-> per utterance dict(ok, score, phones, durations, row_frames): durations in frames on the features' grid, summing to T, the skipped
+        optional phonemes dropped from phones and durations; an utterance without an alignment has ok False and phones / durations None"""
+        if self.model is None:
+            raise _lib.FclError("fcl-taco2_amd: alignment: no model (fit first, or pass model=)")
+        features = list(features)
+        graphs, frame_lens, D = self._prepare(features, transcripts, ids)
+        if D is not None and D != self.model.dim:
+            raise ValueError("fcl-taco2_amd: alignment: the features have %d coefficients, the model %d" % (D, self.model.dim))
+        out = [None] * len(features)
+        with torch.cuda.device(self.device):
+            params = self.model.upload(self.device)
+            for idx, mp, x in self._batches(features, graphs, frame_lens):
+                _, row_frames, score, ok = self._viterbi(mp, x, params)
+                rf, okh, sh = row_frames.cpu().numpy().astype(np.int64), ok.cpu().numpy(), score.cpu().numpy()
+                for k, i in enumerate(idx):
+                    c = rf[mp.row_offs[k] : mp.row_offs[k + 1]]
+                    if not okh[k]:
+                        out[i] = dict(ok=False, score=float("-inf"), phones=None, durations=None, row_frames=c)
+                        continue
+                    per = c.reshape(-1, self.K).sum(axis=1)
+                    keep = [j for j, p in enumerate(transcripts[i]) if per[j] > 0 or p not in self.optional]
+                    out[i] = dict(ok=True, score=float(sh[k]), phones=[transcripts[i][j] for j in keep], durations=[int(per[j]) for j in keep], row_frames=c)
+        return out

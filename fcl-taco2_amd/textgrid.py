@@ -7,6 +7,7 @@ formats itself and restates the reference's integer rules exactly (DESIGN.md §6
     phn2idx = symbol_table(labels)                            # the reference's phn2idx.json
 """
 import json
+import math
 import re
 
 SIL_PHONES = ("sil", "sp", "spn")
@@ -110,6 +111,44 @@ def alignment(intervals, fs, hop, empty_label=None):
     phones = [empty_label if p == "" and empty_label is not None else p for _, _, p in parts]
     durations = [int(e / hop) - int(s / hop) for s, e, _ in parts]
     return phones, durations
+
+
+def frame_intervals(phones, durations, fs, hop, n_samples):
+    """Durations in frames -> [(xmin, xmax, text)] that alignment() reads back: a boundary at frame k stands at (k hop + 0.5) / fs seconds, so that
+    int(time fs) == k hop whatever the rounding of the division; the first interval begins at 0 and the last ends at the wav's end, n_samples / fs
+    (moved up by single ulps until int(time fs) == n_samples).  alignment() therefore returns these durations with the last one less by 1 when they
+    sum to n_samples // hop + 1, the frame count of features.py: what preprocess's own last-duration rule restores."""
+    if len(phones) != len(durations) or not phones:
+        raise ValueError("frame_intervals: %d phones and %d durations" % (len(phones), len(durations)))
+    edges = [0]
+    for d in durations:
+        if int(d) < 0:
+            raise ValueError("frame_intervals: a negative duration")
+        edges.append(edges[-1] + int(d))
+    if (edges[-1] - 1) * int(hop) > int(n_samples):
+        raise ValueError("frame_intervals: %d frames begin past the end of %d samples at hop %d" % (edges[-1], int(n_samples), int(hop)))
+    times = [0.0] + [(k * int(hop) + 0.5) / float(fs) for k in edges[1:-1]]
+    end = int(n_samples) / float(fs)
+    while int(end * fs) < int(n_samples):
+        end = math.nextafter(end, math.inf)
+    times.append(end)
+    return [(times[i], times[i + 1], str(p)) for i, p in enumerate(phones)]
+
+
+def write_textgrid(path, tiers, xmax):
+    """{tier name: [(xmin, xmax, text)]} (or a list of (name, intervals)) -> a Praat TextGrid in the long text format, interval tiers only.  Times
+    are written with repr, the shortest digits that read back to the same float64."""
+    items = list(tiers.items()) if isinstance(tiers, dict) else list(tiers)
+    q = lambda s: '"%s"' % str(s).replace('"', '""')
+    out = ['File type = "ooTextFile"', 'Object class = "TextGrid"', "", "xmin = 0", "xmax = %r" % float(xmax), "tiers? <exists>", "size = %d" % len(items),
+           "item []:"]
+    for i, (name, rows) in enumerate(items, 1):
+        out += ["    item [%d]:" % i, '        class = "IntervalTier"', "        name = %s" % q(name), "        xmin = 0", "        xmax = %r" % float(xmax),
+                "        intervals: size = %d" % len(rows)]
+        for j, (a, b, text) in enumerate(rows, 1):
+            out += ["        intervals [%d]:" % j, "            xmin = %r" % float(a), "            xmax = %r" % float(b), "            text = %s" % q(text)]
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\n".join(out) + "\n")
 
 
 def symbol_table(all_labels):

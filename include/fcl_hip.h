@@ -1113,6 +1113,63 @@ int fcl_ev_cepstra_fwd(const float* x, const float* table, const float* bias, fl
 int fcl_ev_dtw_fwd(const fcl_ev_t* a, fcl_stream_t stream);
 int fcl_ev_path_pitch_fwd(const fcl_ev_t* a, fcl_stream_t stream);
 
+/* ---- Forced alignment: flat-start Viterbi training of single-Gaussian monophone models (fcl_taco2_amd/alignment.py, align.py; restated
+ *      in float64 numpy in tests/align_ref.py).  Features x [frames][D] on the frame grid of the blocks above.
+ * Model: every phoneme of the inventory has K states, 1 <= K <= 3; model state m = phoneme * K + k; M states in all.  mean [M][D], ivar [M][D]
+ *      (inverse variances) and gconst [M], gconst[m] = -0.5 (D ln 2pi + sum_d ln var[m][d]), are built in float64 on the host and uploaded as
+ *      float32.  There are no transition probabilities: every allowed move costs 0.  1 <= M <= 1024, 1 <= D <= 40.
+ * Log-likelihood (fcl_al_loglik_fwd): ll [frames][M],  ll[t][m] = fma(-0.5, q, gconst[m]),  q = sum_d (x_d - mean_d)^2 ivar_d formed from the
+ *      differences as ONE float32 fma chain in ascending d from 0:  df = x_d - mean_d;  q = fma(df * df, ivar_d, q)  (df * df rounded once).  D is
+ *      padded to a multiple of 4 with zero x, mean and ivar, which adds exactly 0.  The model is staged in LDS in tiles of 64 states.
+ * Utterance graph: utterance u owns S_u rows; row_state [rows] is each row's model state; row_skip [rows] is 0, or j >= 2: "this row may also be
+ *      entered from row r - j".  An optional phoneme on the rows [a, a + K) is expressed by row_skip[a + K] = K + 1.  max_skip is 0 or the largest
+ *      row_skip of the batch (2 .. 4); a row_skip outside 2 .. max_skip, or one that points before row 0, counts as 0.
+ * Viterbi (fcl_al_viterbi_fwd) over an utterance of T frames and S rows, in float32:  V(0, 0) = ll(0, row_state[0]),  V(r, 0) = -inf for r > 0;
+ *      V(r, t) = ll(t, row_state[r]) + max(stay V(r, t - 1), advance V(r - 1, t - 1), skip V(r - row_skip[r], t - 1)), predecessors that do not
+ *      exist do not count.  Ties: stay wins; advance replaces it only when strictly greater; skip replaces the winner only when strictly greater.
+ *      The backtrack runs from (S - 1, T - 1) in the same launch.  Outputs: frame_row [frames], the row within the utterance, non-decreasing;
+ *      row_begin / row_frames [rows], each row's first GLOBAL frame and its count (a skipped row: 0 frames, beginning where the next row with frames
+ *      begins); score [n_utt] = V(S - 1, T - 1); ok [n_utt].  An utterance gets ok 0, score -inf, frame_row -1 and row_frames 0 (row_begin: its first
+ *      frame) when it has too few frames for its mandatory rows, when its backtrack does not arrive at row 0 in frame 0 (non-finite inputs, a
+ *      foreign workspace), or when its slices are too small for its lengths (or longer than max_t / max_s); the rest of the batch is unaffected.
+ * A batch is packed: utterance u owns the frames frame_off[u] .. frame_off[u + 1] of ll and frame_row, the rows row_off[u] .. row_off[u + 1] of
+ *      row_state / row_skip / row_begin / row_frames and the back-pointer cells cell_off[u] .. cell_off[u + 1] (cumulative S T, int64) of the
+ *      workspace.  frames, rows and cells are the totals the tables end at.  One workgroup per utterance, no atomics: a batch is bit for bit its
+ *      per-utterance runs.
+ * Statistics (fcl_al_stats_fwd): state_off [M + 1] / state_rows [rows] list the batch's rows grouped by model state, ascending row index inside a
+ *      group.  The kernel ADDS to acc_n [M] (int64: frames), acc_s [M][D] and acc_q [M][D] (float64: sum x, sum x^2), so that batches chain in
+ *      stream order.  The summation order is part of the contract: one float64 chain per (state, coefficient), rows in list order, frames
+ *      ascending, x and x * x (exact in double) widened before the add; the chain starts at 0 and its total is added to the accumulator.
+ * Workspace: fcl_al_workspace_bytes(total_cells, n_utt) bytes; its layout is the library's own (one back-pointer byte per cell).
+ * Supported: 1 <= T <= 4096 (max_t: the batch's largest), 1 <= S <= 1024 (max_s), n_utt <= 65535.  The kernels clamp every offset they read from a
+ *      device table, check every move of the backtrack against [0, S), and keep every store inside the utterance's slices whatever the inputs
+ *      hold.  Each entry validates before any HIP call: a null pointer FCL_ERR_INVALID; a count, a length, D, M or max_skip out of range
+ *      FCL_ERR_SHAPE; a workspace that is too small FCL_ERR_WORKSPACE; an empty batch: nothing is launched.  No entry allocates, synchronises or
+ *      copies. */
+typedef struct {
+    int64_t frames, rows, cells;
+    int32_t n_utt, n_states, max_t, max_s, max_skip, reserved;
+    const float* ll;
+    const int32_t* frame_off;
+    const int32_t* row_off;
+    const int64_t* cell_off;
+    const int32_t* row_state;
+    const int32_t* row_skip;
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* frame_row;
+    int32_t* row_begin;
+    int32_t* row_frames;
+    float* score;
+    int32_t* ok;
+} fcl_al_t;
+size_t fcl_al_workspace_bytes(int64_t total_cells, int n_utt);
+int fcl_al_loglik_fwd(const float* x, const float* mean, const float* ivar, const float* gconst, float* ll, int64_t frames, int d, int n_states,
+                      fcl_stream_t stream);
+int fcl_al_viterbi_fwd(const fcl_al_t* a, fcl_stream_t stream);
+int fcl_al_stats_fwd(const float* x, const int32_t* row_begin, const int32_t* row_frames, const int32_t* state_off, const int32_t* state_rows,
+                     int64_t* acc_n, double* acc_s, double* acc_q, int64_t frames, int64_t rows, int d, int n_states, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
