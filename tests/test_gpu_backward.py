@@ -111,6 +111,8 @@ def test_l1_mse_grad(ops):
 
 @pytest.mark.parametrize("c", [20, 384])
 def test_layernorm_bwd_with_scalar_head(ops, c):
+    """Against torch autograd at M = 97 (one row per wave), no dropout.  The keep mask, M = 1029 (a wave's second row) and C = 65 / 257 / 513 (the
+    first channel count of each wider arm) are in tests/test_gpu_train_pointwise_f64.py, against the float64 statement."""
     rng = np.random.RandomState(c)
     m = 97
     x0, g0, b0, lw0, lb0 = 2 * rnd(rng, m, c) + 0.5, 1 + 0.1 * rnd(rng, c), rnd(rng, c), (rnd(rng, c) / np.sqrt(c)).astype(np.float32), rnd(rng, 1)
