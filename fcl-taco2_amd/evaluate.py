@@ -13,6 +13,12 @@ Per utterance: mel-cepstral distortion in dB over the DTW path of the order-`--o
 the F0 RMSE in cents over the cells voiced on both sides, the share of cells voiced on one side only and the count of the former.  `--out` holds
 these records, the corpus figures (MCD and V/UV error: the mean of the per-utterance values; F0 RMSE: the mean over the utterances with n_vv > 0),
 n_utt and the settings; one summary line goes to stdout.  The MCD is this package's own: comparability with SPTK / WORLD mel-cepstra is unpinned.
+
+`--aligned` (wavs on both sides) adds the figure for time-aligned pairs -- copy-synthesis: a vocoder run on a recording's own mel -- where a DTW
+path is the wrong tool: the multi-resolution STFT distance of stft_loss.py, spectral convergence and log-magnitude distance over the
+`--stft-*` resolutions (Parallel WaveGAN's by default).  Each pair is cut to its shorter side; a pair whose lengths differ by more than
+`--aligned-max-diff` samples (default: two hops of the analysis) is refused by id before the first device call.  Every record gains `stft_sc`,
+`stft_log_mag` (the means over the resolutions), `stft` (per resolution) and `aligned_samples`; the document gains the corpus means of the first two.
 """
 import argparse
 import json
@@ -24,7 +30,7 @@ import struct
 import numpy as np
 import torch
 
-from . import extract_features as X, features, griffinlim, kaldi_io, metrics, pitch, resample
+from . import extract_features as X, features, griffinlim, kaldi_io, metrics, pitch, resample, stft_loss
 
 SIDES = ("ref", "syn")
 
@@ -115,6 +121,50 @@ def frame_counts(src, ids, fs, hop, n_mels, resampling):
     return frames, rates
 
 
+def sample_counts(src, ids, fs, resampling):
+    """samples per utterance of a wav source at the analysis rate, from the headers alone (after resampling, in integers)"""
+    out = []
+    for u in ids:
+        rate, n = X.wav_rate_and_samples(src.items[u])
+        if rate != fs and resampling:
+            L, M, _ = resample.check_rates(rate, fs)
+            n = resample.out_samples(n, L, M)
+        out.append(int(n))
+    return out
+
+
+def check_aligned(ids, ref_samples, syn_samples, max_diff, n_fft):
+    """-> the pairs' common lengths (the shorter side).  A pair whose lengths differ by more than max_diff samples is no time-aligned pair, and one
+    shorter than n_fft / 2 + 1 (n_fft: the largest resolution) has no single reflection: the first such pair is refused by id."""
+    out = []
+    for u, a, b in zip(ids, ref_samples, syn_samples):
+        if abs(int(a) - int(b)) > max_diff:
+            raise ValueError("fcl-taco2_amd: evaluate: utterance %s has %d reference and %d synthesised samples; --aligned compares time-aligned pairs "
+                             "and allows a difference of %d samples (--aligned-max-diff)" % (u, int(a), int(b), max_diff))
+        out.append(min(int(a), int(b)))
+    features.check_lens(out, n_fft, ids)
+    return out
+
+
+def sample_batches(lens, batch_samples):
+    """consecutive runs of pairs whose samples sum to at most batch_samples (a longer single pair goes alone)"""
+    out, cur, tot = [], [], 0
+    for i, n in enumerate(lens):
+        if cur and tot + n > batch_samples:
+            out.append(cur)
+            cur, tot = [], 0
+        cur.append(i)
+        tot += n
+    return out + ([cur] if cur else [])
+
+
+def add_aligned(records, sc, mag, lens, configs):
+    """the per-utterance records gain the multi-resolution STFT figures (sc, mag [n_utt, R])"""
+    for r, s, m, n in zip(records, sc, mag, lens):
+        r.update(stft_sc=float(np.mean(s)), stft_log_mag=float(np.mean(m)), aligned_samples=int(n),
+                 stft=[dict(n_fft=c[0], hop=c[1], win_length=c[2], sc=float(a), log_mag=float(b)) for c, a, b in zip(configs, s, m)])
+
+
 def summarise(records, settings):
     """The --out document from the per-utterance records (dicts with id, ref_frames, syn_frames, path_len, mcd_db and, with F0, f0_rmse_cents (None
     for n_vv = 0), vuv_error, n_vv): corpus MCD and V/UV error are the means of the per-utterance values, the F0 RMSE the mean over the utterances
@@ -125,6 +175,8 @@ def summarise(records, settings):
         doc["vuv_error"] = mean([r["vuv_error"] for r in records])
         voiced = [r["f0_rmse_cents"] for r in records if r["n_vv"] > 0]
         doc["f0_rmse_cents"], doc["n_utt_voiced"] = mean(voiced), len(voiced)
+    if records and "stft_sc" in records[0]:
+        doc["stft_sc"], doc["stft_log_mag"] = mean([r["stft_sc"] for r in records]), mean([r["stft_log_mag"] for r in records])
     doc["settings"], doc["utterances"] = settings, records
     return doc
 
@@ -145,6 +197,8 @@ def summary_line(doc):
     if "vuv_error" in doc:
         s += ", F0 RMSE %s cents over %d utterances, V/UV error %.2f %%" % ("%.1f" % doc["f0_rmse_cents"] if doc["f0_rmse_cents"] is not None else "n/a",
                                                                              doc["n_utt_voiced"], 100.0 * doc["vuv_error"])
+    if "stft_sc" in doc:
+        s += ", STFT spectral convergence %.4f, log-magnitude %.4f" % (doc["stft_sc"], doc["stft_log_mag"])
     return s
 
 
@@ -168,6 +222,11 @@ def build_parser():
     g.add_argument("--mel-basis", default=None, metavar="FILE.npy", help="[n_mels, n_fft / 2 + 1] mel filterbank replacing the built Slaney one")
     griffinlim.add_analysis_arguments(g)
     pitch.add_pitch_arguments(ap.add_argument_group("F0 tracking (both sides wavs)"))
+    g = ap.add_argument_group("time-aligned pairs (both sides wavs): the multi-resolution STFT distance")
+    g.add_argument("--aligned", action="store_true", help="the pairs are time-aligned (copy-synthesis): add spectral convergence and log-magnitude distance")
+    g.add_argument("--aligned-max-diff", type=int, default=None, metavar="SAMPLES", help="largest length difference of a pair (default: 2 x --hop)")
+    g.add_argument("--aligned-batch-samples", type=int, default=1 << 22, metavar="SAMPLES", help="samples per GPU batch of the STFT distance")
+    stft_loss.add_arguments(g)
     return ap
 
 
@@ -201,6 +260,16 @@ def parse_args(argv=None):
         ap.error(str(e))
     if args.ref_wav_dir is not None and args.syn_wav_dir is not None:
         pitch.check_arguments(ap, args)
+    if args.aligned and (args.ref_wav_dir is None or args.syn_wav_dir is None):
+        ap.error("--aligned compares waveforms: it needs --ref-wav-dir and --syn-wav-dir")
+    try:
+        stft_loss.check_resolutions(args.stft_fft_sizes, args.stft_hops, args.stft_win_lengths)
+    except (NotImplementedError, ValueError) as e:
+        ap.error("--stft-fft-sizes / --stft-hops / --stft-win-lengths: %s" % e)
+    if args.aligned_max_diff is None:
+        args.aligned_max_diff = 2 * args.hop
+    if args.aligned_max_diff < 0 or args.aligned_batch_samples < 1:
+        ap.error("--aligned-max-diff must not be negative and --aligned-batch-samples must be positive")
     return args
 
 
@@ -212,6 +281,11 @@ def evaluate(args):
     fa, ra = frame_counts(ref, ids, args.fs, args.hop, args.n_mels, args.resample)
     fb, rb = frame_counts(syn, ids, args.fs, args.hop, args.n_mels, args.resample)
     metrics.check_pairs(fa, fb, ids)  # refused by id before the first device call
+    aligned_lens = None
+    if args.aligned:
+        configs = stft_loss.check_resolutions(args.stft_fft_sizes, args.stft_hops, args.stft_win_lengths)
+        aligned_lens = check_aligned(ids, sample_counts(ref, ids, args.fs, args.resample), sample_counts(syn, ids, args.fs, args.resample),
+                                     args.aligned_max_diff, max(c[0] for c in configs))
     stats = None if args.mel_stats is None else np.load(args.mel_stats)
     any_wav, both_wav = "wav" in (ref.kind, syn.kind), ref.kind == syn.kind == "wav"
     fx = features.from_args(args, args.device) if any_wav else None
@@ -239,6 +313,18 @@ def evaluate(args):
     settings = dict(order=args.order, n_mels=args.n_mels, ref=dict(kind=ref.kind, source=ref.where, normalised=bool(args.ref_normalised)),
                     syn=dict(kind=syn.kind, source=syn.where, normalised=bool(args.syn_normalised)), mel_stats=args.mel_stats, batch_cells=args.batch_cells,
                     analysis=dict(fs=args.fs, n_fft=args.n_fft, hop=args.hop, win_length=args.win_length, fmin=args.fmin, fmax=args.fmax, resample=bool(args.resample)))
+    if args.aligned:
+        loss = stft_loss.MultiResolutionSTFTLoss(args.device, args.stft_fft_sizes, args.stft_hops, args.stft_win_lengths)
+        for idx in sample_batches(aligned_lens, args.aligned_batch_samples):
+            bid, n = [ids[i] for i in idx], [aligned_lens[i] for i in idx]
+            xa, la = ev.at_analysis_rate([X.read_wav(ref.items[u], ra[i]) for u, i in zip(bid, idx)], [ra[i] for i in idx], bid)
+            xb, lb = ev.at_analysis_rate([X.read_wav(syn.items[u], rb[i]) for u, i in zip(bid, idx)], [rb[i] for i in idx], bid)
+            if [min(a, b) for a, b in zip(la, lb)] != n:
+                raise RuntimeError("evaluate: the sample counts read do not match the headers' (%r)" % (bid,))
+            sc, mag = loss.distances(torch.cat([v[:k] for v, k in zip(xb, n)]), n, torch.cat([v[:k] for v, k in zip(xa, n)]), ids=bid)
+            add_aligned([records[i] for i in idx], sc, mag, n, configs)
+        settings["aligned"] = dict(max_diff=args.aligned_max_diff, fft_sizes=[c[0] for c in configs], hops=[c[1] for c in configs],
+                                   win_lengths=[c[2] for c in configs])
     if both_wav:
         settings["f0"] = dict(floor=args.f0_floor, ceil=args.f0_ceil, threshold=args.f0_threshold, min_voiced=args.f0_min_voiced, frame_length=args.f0_frame_length)
     return summarise(records, settings)

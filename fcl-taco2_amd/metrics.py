@@ -260,9 +260,9 @@ class Evaluator(object):
             out.update(ref_cepstra=ca, syn_cepstra=cb, ref_cents=pa, syn_cents=pb)
         return out
 
-    def analyse(self, waves, rates=None, ids=None):
-        """list of 1-D float waveforms (rates: their sampling rates where they are not the analysis rate; needs resampler_for) -> (mel rows
-        [sum T, n_mels] raw log10, frame counts, F0 [sum T] Hz or None without a tracker): the mel launch and the tracker's two on shared Maps"""
+    def at_analysis_rate(self, waves, rates=None, ids=None):
+        """list of 1-D float waveforms -> (the same as float32 device tensors at the analysis rate, their sample counts): those whose rate (rates)
+        is another one go through resampler_for, one packed launch per rate"""
         fx, dev = self.extractor, self.device
         if fx is None:
             raise _lib.FclError("fcl-taco2_amd: metrics: compare_waves needs a feature extractor")
@@ -281,6 +281,13 @@ class Evaluator(object):
                 o = np.concatenate([[0], np.cumsum(out_lens)])
                 for k, i in enumerate(g):
                     xs[i], lens[i] = y[int(o[k]) : int(o[k + 1])], int(out_lens[k])
+        return xs, lens
+
+    def analyse(self, waves, rates=None, ids=None):
+        """list of 1-D float waveforms (rates: their sampling rates where they are not the analysis rate; needs resampler_for) -> (mel rows
+        [sum T, n_mels] raw log10, frame counts, F0 [sum T] Hz or None without a tracker): the mel launch and the tracker's two on shared Maps"""
+        fx, dev = self.extractor, self.device
+        xs, lens = self.at_analysis_rate(waves, rates, ids)
         fx.check_lens(lens, ids)
         if self.tracker is not None:
             self.tracker.check_lens(lens, ids)

@@ -1170,6 +1170,44 @@ int fcl_al_viterbi_fwd(const fcl_al_t* a, fcl_stream_t stream);
 int fcl_al_stats_fwd(const float* x, const int32_t* row_begin, const int32_t* row_frames, const int32_t* state_off, const int32_t* state_rows,
                      int64_t* acc_n, double* acc_s, double* acc_q, int64_t frames, int64_t rows, int d, int n_states, fcl_stream_t stream);
 
+/* ---- Multi-resolution STFT loss: spectral convergence and log-magnitude distance of a generated waveform x against a target y, and the gradient
+ *      with respect to x (fcl_taco2_amd/stft_loss.py; restated in float64 numpy in tests/stft_loss_ref.py).  One resolution (n_fft, hop,
+ *      window) per call, on the LDS-resident FFT and the frame grid of the feature extraction above.
+ * Inputs: x and y, the utterances' float samples back to back; utterance u owns the samples smp_off[u] .. smp_off[u + 1] of both (L_u >= n_fft / 2 + 1)
+ *      and the T_u = L_u / hop + 1 frames utt_off[u] .. utt_off[u + 1]; frame_utt / utt_off / window / twiddle as fcl_fx_*.
+ * Frame t: samples q = t * hop + n - n_fft / 2, n < n_fft, reflected once at either end; times the window; X[k] = rfft, k <= n_fft / 2, for x and y alike.
+ *      p = re^2 + im^2, m = sqrt(max(p, 1e-7)).
+ * fcl_stl_sums_fwd: frame_sums [frames, 3] float = per frame (sum_k (m_y - m_x)^2, sum_k m_y^2, sum_k |log m_y - log m_x|) over a fixed partition of the
+ *      bins; utt_sums [n_utt, 3] double = each utterance's frames added in ascending order in float64 (64 contiguous chunks, then the chunk totals).
+ *      The caller forms sc = sqrt(A / B) and mag = C / (frames x bins) over one utterance or the batch.
+ * fcl_stl_grad_bwd: coef [n_utt, 2] float = per utterance (-g_sc / sqrt(A B), g_mag / n), the reduction folded in by the caller.
+ *      dm = coef0 (m_y - m_x) - coef1 sign(log m_y - log m_x) / m_x;  G[k] = (dm / m_x) X[k] where p_x > 1e-7, else 0 (the clamp passes no gradient);
+ *      fr [frames, n_fft] = w N irfft(Yh), Yh[0] = Re G[0], Yh[N / 2] = Re G[N / 2], Yh[k] = G[k] / 2 between (each one-sided bin counts once);
+ *      gx[j] = the sum of fr over the frames that cover the padded position j + N / 2, then its left mirror N / 2 - j (1 <= j <= N / 2), then its right
+ *      mirror N / 2 + 2 (L - 1) - j (L - 1 - N / 2 <= j <= L - 2), each in ascending frame order; accumulate != 0 adds that to gx instead of storing it.
+ *      Both transforms are recomputed: nothing of size frames x bins is kept between the two entries or reaches memory.
+ * No atomics: a batch is bit for bit its per-utterance runs.  Supported: n_fft 512 / 1024 / 2048, 1 <= hop <= n_fft / 2; window, twiddle, fr and utt_sums
+ *      8-byte aligned; frames x n_fft and samples below 2^31.  Shorter utterances are refused by the package, by id, before any device call; the kernels
+ *      clamp every index read from a device table.  No entry allocates, synchronises or copies. */
+typedef struct {
+    int64_t frames, samples;
+    int32_t n_fft, hop, n_utt, accumulate;
+    const float* x;
+    const float* y;
+    const int32_t* smp_off;
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    const float* window;
+    const float* twiddle;
+    float* frame_sums;
+    double* utt_sums;
+    const float* coef;
+    float* fr;
+    float* gx;
+} fcl_stl_t;
+int fcl_stl_sums_fwd(const fcl_stl_t* a, fcl_stream_t stream);
+int fcl_stl_grad_bwd(const fcl_stl_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
