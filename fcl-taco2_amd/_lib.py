@@ -234,6 +234,7 @@ SIGNATURES = {
     "fcl_conv1d_planes_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fcl_conv1d_planes_rows_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "fcl_embedding_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "fcl_embed_conv_table_fwd": (_I, [_P] * 8 + [_I, _I, _I, _I, _I, _P, _P]),
     "fcl_linear_fwd": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fcl_conv1d_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fcl_layernorm_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),

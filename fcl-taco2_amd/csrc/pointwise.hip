@@ -2,6 +2,7 @@
 // Every kernel is coalesced along the channel dimension (channels-last rows), float4 where widths allow.
 #include <algorithm>
 #include "fcl_common.h"
+#include "lstm_epilogue.h"
 #include "row_maps.h"
 
 namespace fcl {
@@ -93,6 +94,54 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, const IdxT* __
             if (dst && j < c) dst[(size_t)wave * c + j] = v;
             if (dst_p) store_p32(dst_p, ldp, wave, j, v);
         }
+    }
+}
+
+// ---- H1 + the first encoder Conv1d as a table lookup (fcl_embed_conv_table_fwd) -----------------------------------------------------
+// The convolution's input rows are rows of the embedding table and its weights are constants, so W_tap . E[id] is one of k * V rows of a
+// plan-time table tab[tap][id][cout]: an output row is bias + the k table rows its segment admits, summed in tap order.  One thread works on
+// four channels of one row; ids outside [0, V) contribute nothing (the zero row fcl_embedding_fwd gives them).
+// No branch sits between the loads: every tap's id is read at a row clamped into the block and its table row at a clamped id, then the rows the
+// segment admits are added in tap order (a tap that is not admitted leaves the sum as it is) -- with KT = k known at compile time the k id loads
+// and then the k table loads are in flight together: two dependent round trips instead of 2 k.  KT = 0: any k.
+template <int KT>
+__global__ __launch_bounds__(256) void embed_conv_table_kernel(const int64_t* __restrict__ ids, const float* __restrict__ tab, const float* __restrict__ bias,
+                                                               const int* __restrict__ seg_lo, const int* __restrict__ seg_hi,
+                                                               const float* __restrict__ res_tab, float* __restrict__ y, unsigned short* __restrict__ yp,
+                                                               int m, int v, int cout, int k, int act, const int* __restrict__ m_dev) {
+    const int q = cout >> 2;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row_l = g / q;
+    if (row_l >= live_rows_of(m, m_dev)) return;
+    const int row = (int)row_l, c = (int)(g - row_l * q) * 4;
+    const int kk = KT > 0 ? KT : k, pad = (kk - 1) / 2;
+    const int lo = max(seg_lo[row], 0), hi = min(seg_hi[row], m);
+    const long long id0 = ids[row];
+    const bool res_on = res_tab && id0 >= 0 && id0 < v;
+    f32x4 acc = *reinterpret_cast<const f32x4*>(bias + c);
+    f32x4 res = {0.f, 0.f, 0.f, 0.f};
+    if (res_tab) res = *reinterpret_cast<const f32x4*>(res_tab + (size_t)(res_on ? id0 : 0) * cout + c);
+#pragma unroll KT > 0 ? KT : 1
+    for (int tap = 0; tap < kk; ++tap) {
+        const int r = row + tap - pad;
+        const long long id = ids[min(max(r, 0), m - 1)];
+        const bool in = r >= lo && r < hi && id >= 0 && id < v;
+        const f32x4 t = *reinterpret_cast<const f32x4*>(tab + ((size_t)tap * v + (size_t)(in ? id : 0)) * cout + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = in ? acc[e] + t[e] : acc[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        acc[e] = act_apply(acc[e], act);
+        if (res_on) acc[e] += res[e];
+    }
+    if (y) *reinterpret_cast<f32x4*>(y + (size_t)row * cout + c) = acc;
+    if (yp) {
+        uint2 h, l;
+        split4(acc, h, l);
+        unsigned short* line = yp + ((size_t)row * (cout >> 5) + (c >> 5)) * 64 + (c & 31);
+        *reinterpret_cast<uint2*>(line) = h;
+        *reinterpret_cast<uint2*>(line + 32) = l;
     }
 }
 
@@ -575,8 +624,32 @@ int fcl_embedding_fwd(const int64_t* ids, const float* table, float* out, uint16
     if (m == 0) return 0;
     FCL_REQUIRE((e & 3) != 0 || (aligned16(table) && aligned16(out)), FCL_ERR_ALIGN, "embedding_fwd: 16-byte alignment required");
     FCL_REQUIRE((reinterpret_cast<uintptr_t>(out_p) & 127u) == 0, FCL_ERR_ALIGN, "embedding_fwd: planes must be 128-byte aligned");
+    ProfScope ps("gather_rows_kernel<long>", 0.0, (double)m, (hipStream_t)stream);
     hipLaunchKernelGGL((gather_rows_kernel<int64_t>), dim3((m + 3) / 4), dim3(256), 0, (hipStream_t)stream, table, ids, out, m, e, (long long)v, out_p);
     return check_hip(hipGetLastError(), "embedding_fwd");
+}
+
+int fcl_embed_conv_table_fwd(const int64_t* ids, const float* tables, const float* bias, const int32_t* seg_lo, const int32_t* seg_hi,
+                             const float* residual_table, float* y, uint16_t* y_p, int m, int v, int cout, int k, int act, const int32_t* m_dev,
+                             fcl_stream_t stream) {
+    FCL_REQUIRE(ids && tables && bias && seg_lo && seg_hi && (y || y_p) && m >= 0 && v > 0 && cout > 0 && k > 0 && (k & 1), FCL_ERR_INVALID,
+                "embed_conv_table_fwd: bad arguments (null pointer, no output, bad size or even k)");
+    FCL_REQUIRE(act >= FCL_ACT_NONE && act <= FCL_ACT_SIGMOID, FCL_ERR_INVALID, "embed_conv_table_fwd: unknown activation %d", act);
+    FCL_REQUIRE((cout & 3) == 0 && (!y_p || (cout & 31) == 0), FCL_ERR_SHAPE, "embed_conv_table_fwd: Cout=%d must be a multiple of 4 (of 32 with planes)", cout);
+    FCL_REQUIRE(aligned16(tables) && aligned16(bias) && aligned16(residual_table) && aligned16(y), FCL_ERR_ALIGN,
+                "embed_conv_table_fwd: 16-byte alignment required");
+    FCL_REQUIRE((reinterpret_cast<uintptr_t>(y_p) & 127u) == 0, FCL_ERR_ALIGN, "embed_conv_table_fwd: planes must be 128-byte aligned");
+    if (m == 0) return 0;
+    ProfScope ps("embed_conv_table_kernel", 0.0, (double)m, (hipStream_t)stream);
+    const long long threads = (long long)m * (cout >> 2);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (k == 5)  // the shipped recipes' encoder kernel size: unrolled, all loads of a thread in flight together
+        hipLaunchKernelGGL((embed_conv_table_kernel<5>), grid, dim3(256), 0, (hipStream_t)stream, ids, tables, bias, seg_lo, seg_hi, residual_table, y, y_p, m,
+                           v, cout, k, act, m_dev);
+    else
+        hipLaunchKernelGGL((embed_conv_table_kernel<0>), grid, dim3(256), 0, (hipStream_t)stream, ids, tables, bias, seg_lo, seg_hi, residual_table, y, y_p, m,
+                           v, cout, k, act, m_dev);
+    return check_hip(hipGetLastError(), "embed_conv_table_fwd");
 }
 
 int fcl_gather_rows_fwd(const float* src, const int32_t* idx, float* dst, uint16_t* dst_p, int n, int c, fcl_stream_t stream) {

@@ -296,14 +296,21 @@ def encode(plan, prep, bilstm_algo=0, planes=False, row_maps=None):
     row_maps (ops.RowMapsRequest): maps of FORCED durations, which depend on nothing the encoder computes: built inside the BiLSTM's launch."""
     bl = plan.blstm
     res = plan.hp.use_residual  # convs[i](xs) + xs (encoder_sa_kd.py:213-214): the residual rides in the conv's epilogue (after ReLU), fp32 kept for it
+    convs, tabs = plan.enc_convs, getattr(plan, "embed_conv_tables", None)
+    if tabs is not None:  # embedding + first convolution: k rows of a plan-time table summed per output row (plan.py; FCL_EMBED_CONV_TABLE=0: off)
+        x, xp = ops.embed_conv_table(prep.ids, tabs, convs[0].bias, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual_table=plan.embed if res else None,
+                                     want_f32=res or not planes, want_planes=planes)
+        convs = convs[1:]
     if planes:  # every GEMM operand travels pre-split: embedding -> planes, conv -> planes, ..., BiLSTM -> fp32 + planes
-        x, xp = ops.embedding(prep.ids, plan.embed, want_f32=res, want_planes=True)
-        for cv in plan.enc_convs:
+        if tabs is None:
+            x, xp = ops.embedding(prep.ids, plan.embed, want_f32=res, want_planes=True)
+        for cv in convs:
             x, xp = ops.conv1d_planes(xp, cv, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual=x if res else None, want_f32=res)
         return ops.bilstm(None, prep.lens_dev, bl["w_ih_f"], bl["w_hh_f"], bl["b_f"], bl["w_ih_r"], bl["w_hh_r"], bl["b_r"], prep.B, prep.T, bilstm_algo,
                           x_p=xp, w_ih_p=(bl["w_ih_p_f"], bl["w_ih_p_r"]), want_planes=True, row_maps=row_maps)
-    x = ops.embedding(prep.ids, plan.embed)
-    for cv in plan.enc_convs:
+    if tabs is None:
+        x = ops.embedding(prep.ids, plan.embed)
+    for cv in convs:
         x = ops.conv1d(x, cv.wp, cv.bias, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual=x if res else None)
     for i, bl in enumerate(plan.blstm_layers):  # (`elayers` > 1: the stacked layers run one after the other; use_planes() is off for them)
         x = ops.bilstm(x, prep.lens_dev, bl["w_ih_f"], bl["w_hh_f"], bl["b_f"], bl["w_ih_r"], bl["w_hh_r"], bl["b_r"], prep.B, prep.T, bilstm_algo,

@@ -157,6 +157,18 @@ def embedding(ids, table, want_f32=True, want_planes=False):
     return (out, outp) if want_planes else out
 
 
+def embed_conv_table(ids, tables, bias, seg_lo, seg_hi, act=ACT_NONE, residual_table=None, want_f32=True, want_planes=False, m_dev=None):
+    """Embedding + the first encoder Conv1d as k table rows summed per output row (include/fcl_hip.h fcl_embed_conv_table_fwd).
+    tables: float32 [k, V, Cout] (plan.embed_conv_tables).  Returns (y fp32 or None, y planes or None)."""
+    m = ids.numel()
+    k, v, cout = tables.shape
+    y = torch.empty(m, cout, device=tables.device, dtype=torch.float32) if want_f32 else None
+    yp = planes_empty(m, cout, tables.device) if want_planes else None
+    check(_lib.load().fcl_embed_conv_table_fwd(_p(ids, torch.int64), _p(tables), _p(bias), _p(seg_lo, torch.int32), _p(seg_hi, torch.int32),
+                                               _p(residual_table), _p(y), _p(yp, torch.int16), m, v, cout, k, act, _p(m_dev, torch.int32), _stream()))
+    return y, yp
+
+
 def linear(x, w, bias=None, act=ACT_NONE, out=None):
     m, k = x.shape
     n = w.shape[0]

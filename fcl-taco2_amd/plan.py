@@ -29,6 +29,11 @@ def _conv_planes(c):
     return c
 
 
+def embed_conv_tables_f64(wp, embed):
+    """wp: tap-major folded weights [k, Cout, Cin]; embed [V, Cin] -> float64 [k, V, Cout]: tables[tap, v, co] = sum_ci wp[tap, co, ci] * embed[v, ci]."""
+    return np.matmul(np.asarray(embed, dtype=np.float64)[None], np.asarray(wp, dtype=np.float64).transpose(0, 2, 1))
+
+
 class PredictorPack(object):
     __slots__ = ("convs", "ln", "lin_w", "lin_b")
 
@@ -97,6 +102,7 @@ class SynthesisPlan(object):
         with torch.cuda.device(self.device):
             self.embed = g("enc.embed.weight")
             self.enc_convs = [self._conv_bn(g, "enc.convs.%d" % i) for i in range(hp.econv_layers)]
+            self.embed_conv_tables = self._embed_conv_tables()
             self.blstm_layers = []  # `elayers` stacked bidirectional layers (encoder_sa.py:96-100); layer l > 0 reads [forward | reverse] of layer l - 1
             for l in range(hp.elayers):
                 bl = {}
@@ -133,6 +139,20 @@ class SynthesisPlan(object):
         c.wp = ops.pack_conv1d_weight(w, scale)
         c.bias = shift
         return _conv_planes(c)
+
+    def _embed_conv_tables(self):
+        """The first encoder convolution contracts rows of the embedding table with constant (BatchNorm-folded) weights: its products take only
+        k * idim distinct values per output channel.  tables[tap][v][co] = sum_ci Wfold[co, ci, tap] * E[v, ci], accumulated in float64 and rounded
+        once to fp32 (ops.embed_conv_table sums k of these rows per output row).  None: FCL_EMBED_CONV_TABLE=0, no convolution, or a width the
+        kernel does not take -- engine.encode then launches the embedding gather and the convolution."""
+        import os
+
+        if os.environ.get("FCL_EMBED_CONV_TABLE", "1") in ("", "0") or not self.enc_convs:
+            return None
+        cv = self.enc_convs[0]
+        if cv.cout % 4 != 0 or cv.cin != self.embed.shape[1] or (self.hp.use_residual and cv.cout != cv.cin):
+            return None
+        return torch.from_numpy(embed_conv_tables_f64(cv.wp.cpu().numpy(), self.embed.cpu().numpy()).astype(np.float32)).to(self.device).contiguous()
 
     def _predictor(self, g, prefix, layers):
         p = PredictorPack()

@@ -111,6 +111,17 @@ int fcl_add_vec(const float* a, const float* b, float* out, int n, fcl_stream_t 
  * row) for the convolution that consumes them; out may then be NULL. */
 int fcl_embedding_fwd(const int64_t* ids, const float* table, float* out, uint16_t* out_p, int m, int v, int e, fcl_stream_t stream);
 
+/* H1 + the first encoder Conv1d (+ folded BatchNorm) in one launch, for CONSTANT weights (synthesis): the convolution's input rows are rows of the
+ * embedding table, so with tables[tap][id][co] = sum_ci W[co, ci, tap] * E[id, ci] (built once, in float64, rounded once; [k, V, Cout] fp32)
+ *   y[r, :] = act(bias + sum over tap = 0 .. k-1, in that order, of tables[tap][ids[r + tap - k/2]] where seg_lo[r] <= r + tap - k/2 < seg_hi[r])
+ *             (+ residual_table[ids[r]] when residual_table != NULL: the embedding table itself, `use_residual`, V x Cout).
+ * k fp32 additions of correctly rounded entries replace the k * Cin products of fcl_embedding_fwd + fcl_conv1d_planes_fwd.  An id outside [0, V)
+ * contributes nothing, as the zero row fcl_embedding_fwd gives it.  y (fp32) and / or y_p (P32 planes, Cout % 32 == 0); Cout % 4 == 0.  m_dev
+ * (optional DEVICE row count): rows at or beyond min(m, *m_dev) are not written. */
+int fcl_embed_conv_table_fwd(const int64_t* ids, const float* tables, const float* bias, const int32_t* seg_lo, const int32_t* seg_hi,
+                             const float* residual_table, float* y, uint16_t* y_p, int m, int v, int cout, int k, int act, const int32_t* m_dev,
+                             fcl_stream_t stream);
+
 /* ---- H6/H8 + every nn.Linear: y = act(x . w^T + bias) --------------------------------------------- */
 /* x [M, K] (lda), w [N, K] (torch layout, ldw), y [M, N] (ldy).  K, lda, ldw multiples of 4. */
 int fcl_linear_fwd(const float* x, int lda, const float* w, int ldw, const float* bias, float* y, int ldy,
