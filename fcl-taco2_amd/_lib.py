@@ -148,6 +148,12 @@ class StftLoss(C.Structure):  # fcl_stl_t
         (n, _P) for n in ("x", "y", "smp_off", "frame_utt", "utt_off", "window", "twiddle", "frame_sums", "utt_sums", "coef", "fr", "gx")]
 
 
+class MelLoss(C.Structure):  # fcl_msl_t
+    _fields_ = [("frames", C.c_int64), ("samples", C.c_int64)] + [(n, C.c_int32) for n in ("n_fft", "hop", "n_utt", "accumulate", "n_mels", "nnz")] + [
+        (n, _P) for n in ("x", "y", "smp_off", "frame_utt", "utt_off", "window", "twiddle", "fb_lo", "fb_off", "fb_w", "bt_off", "bt_ch", "bt_w",
+                          "frame_sums", "utt_sums", "coef", "fr", "gx")]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -324,6 +330,8 @@ SIGNATURES = {
     "fcl_al_stats_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _I, _I, _P]),
     "fcl_stl_sums_fwd": (_I, [C.POINTER(StftLoss), _P]),
     "fcl_stl_grad_bwd": (_I, [C.POINTER(StftLoss), _P]),
+    "fcl_msl_sums_fwd": (_I, [C.POINTER(MelLoss), _P]),
+    "fcl_msl_grad_bwd": (_I, [C.POINTER(MelLoss), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

@@ -18,7 +18,9 @@ n_utt and the settings; one summary line goes to stdout.  The MCD is this packag
 path is the wrong tool: the multi-resolution STFT distance of stft_loss.py, spectral convergence and log-magnitude distance over the
 `--stft-*` resolutions (Parallel WaveGAN's by default).  Each pair is cut to its shorter side; a pair whose lengths differ by more than
 `--aligned-max-diff` samples (default: two hops of the analysis) is refused by id before the first device call.  Every record gains `stft_sc`,
-`stft_log_mag` (the means over the resolutions), `stft` (per resolution) and `aligned_samples`; the document gains the corpus means of the first two.
+`stft_log_mag` (the means over the resolutions), `stft` (per resolution) and `aligned_samples`; the document gains the corpus means of the first two.  `--aligned-mel` (with `--aligned`) adds `mel_l1`, the
+mel-spectrogram L1 distance of mel_loss.py on the log10 mels of the analysis flags -- the distance in the acoustic model's own output
+space -- to the records, its corpus mean to the document and one clause to the summary line.
 """
 import argparse
 import json
@@ -30,7 +32,7 @@ import struct
 import numpy as np
 import torch
 
-from . import extract_features as X, features, griffinlim, kaldi_io, metrics, pitch, resample, stft_loss
+from . import extract_features as X, features, griffinlim, kaldi_io, mel_loss, metrics, pitch, resample, stft_loss
 
 SIDES = ("ref", "syn")
 
@@ -165,6 +167,12 @@ def add_aligned(records, sc, mag, lens, configs):
                  stft=[dict(n_fft=c[0], hop=c[1], win_length=c[2], sc=float(a), log_mag=float(b)) for c, a, b in zip(configs, s, m)])
 
 
+def add_aligned_mel(records, d):
+    """the per-utterance records gain the mel-spectrogram L1 distance (d [n_utt, 1]: the analysis flags' single resolution)"""
+    for r, v in zip(records, d):
+        r["mel_l1"] = float(np.mean(v))
+
+
 def summarise(records, settings):
     """The --out document from the per-utterance records (dicts with id, ref_frames, syn_frames, path_len, mcd_db and, with F0, f0_rmse_cents (None
     for n_vv = 0), vuv_error, n_vv): corpus MCD and V/UV error are the means of the per-utterance values, the F0 RMSE the mean over the utterances
@@ -177,6 +185,8 @@ def summarise(records, settings):
         doc["f0_rmse_cents"], doc["n_utt_voiced"] = mean(voiced), len(voiced)
     if records and "stft_sc" in records[0]:
         doc["stft_sc"], doc["stft_log_mag"] = mean([r["stft_sc"] for r in records]), mean([r["stft_log_mag"] for r in records])
+    if records and "mel_l1" in records[0]:
+        doc["mel_l1"] = mean([r["mel_l1"] for r in records])
     doc["settings"], doc["utterances"] = settings, records
     return doc
 
@@ -199,6 +209,8 @@ def summary_line(doc):
                                                                              doc["n_utt_voiced"], 100.0 * doc["vuv_error"])
     if "stft_sc" in doc:
         s += ", STFT spectral convergence %.4f, log-magnitude %.4f" % (doc["stft_sc"], doc["stft_log_mag"])
+    if "mel_l1" in doc:
+        s += ", mel L1 %.4f" % doc["mel_l1"]
     return s
 
 
@@ -227,6 +239,7 @@ def build_parser():
     g.add_argument("--aligned-max-diff", type=int, default=None, metavar="SAMPLES", help="largest length difference of a pair (default: 2 x --hop)")
     g.add_argument("--aligned-batch-samples", type=int, default=1 << 22, metavar="SAMPLES", help="samples per GPU batch of the STFT distance")
     stft_loss.add_arguments(g)
+    g.add_argument("--aligned-mel", action="store_true", help="with --aligned: add the mel-spectrogram L1 distance (log10 mels of the analysis flags above)")
     return ap
 
 
@@ -262,6 +275,8 @@ def parse_args(argv=None):
         pitch.check_arguments(ap, args)
     if args.aligned and (args.ref_wav_dir is None or args.syn_wav_dir is None):
         ap.error("--aligned compares waveforms: it needs --ref-wav-dir and --syn-wav-dir")
+    if args.aligned_mel and not args.aligned:
+        ap.error("--aligned-mel is a figure of time-aligned pairs: it needs --aligned")
     try:
         stft_loss.check_resolutions(args.stft_fft_sizes, args.stft_hops, args.stft_win_lengths)
     except (NotImplementedError, ValueError) as e:
@@ -315,6 +330,7 @@ def evaluate(args):
                     analysis=dict(fs=args.fs, n_fft=args.n_fft, hop=args.hop, win_length=args.win_length, fmin=args.fmin, fmax=args.fmax, resample=bool(args.resample)))
     if args.aligned:
         loss = stft_loss.MultiResolutionSTFTLoss(args.device, args.stft_fft_sizes, args.stft_hops, args.stft_win_lengths)
+        mel = mel_loss.from_args(args, args.device) if args.aligned_mel else None
         for idx in sample_batches(aligned_lens, args.aligned_batch_samples):
             bid, n = [ids[i] for i in idx], [aligned_lens[i] for i in idx]
             xa, la = ev.at_analysis_rate([X.read_wav(ref.items[u], ra[i]) for u, i in zip(bid, idx)], [ra[i] for i in idx], bid)
@@ -323,8 +339,13 @@ def evaluate(args):
                 raise RuntimeError("evaluate: the sample counts read do not match the headers' (%r)" % (bid,))
             sc, mag = loss.distances(torch.cat([v[:k] for v, k in zip(xb, n)]), n, torch.cat([v[:k] for v, k in zip(xa, n)]), ids=bid)
             add_aligned([records[i] for i in idx], sc, mag, n, configs)
+            if mel is not None:
+                add_aligned_mel([records[i] for i in idx], mel.distances(torch.cat([v[:k] for v, k in zip(xb, n)]), n, torch.cat([v[:k] for v, k in zip(xa, n)]),
+                                                                         ids=bid))
         settings["aligned"] = dict(max_diff=args.aligned_max_diff, fft_sizes=[c[0] for c in configs], hops=[c[1] for c in configs],
                                    win_lengths=[c[2] for c in configs])
+        if args.aligned_mel:
+            settings["aligned"]["mel"] = dict(n_mels=args.n_mels, mel_basis=args.mel_basis)
     if both_wav:
         settings["f0"] = dict(floor=args.f0_floor, ceil=args.f0_ceil, threshold=args.f0_threshold, min_voiced=args.f0_min_voiced, frame_length=args.f0_frame_length)
     return summarise(records, settings)

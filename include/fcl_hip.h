@@ -1219,6 +1219,50 @@ typedef struct {
 int fcl_stl_sums_fwd(const fcl_stl_t* a, fcl_stream_t stream);
 int fcl_stl_grad_bwd(const fcl_stl_t* a, fcl_stream_t stream);
 
+/* ---- Mel-spectrogram loss: the L1 distance of the log10 mel spectrograms of a generated waveform x and a target y, and the gradient with respect
+ *      to x (fcl_taco2_amd/mel_loss.py; restated in float64 numpy in tests/mel_loss_ref.py).  HiFi-GAN's reconstruction term.  One
+ *      resolution per call: n_fft N, hop, window, and a mel matrix B [n_mels, N / 2 + 1] of contiguous bands (fb_lo / fb_off / fb_w as fcl_fx_*).
+ * Inputs, utterances, frames, the reflection, the window and X = rfft(frame w) exactly as in the STFT loss above (L_u >= n_fft / 2 + 1).
+ *      p = re^2 + im^2;  m = sqrt(max(p, 1e-10)) for x and for y (this floor is the mel loss's own: neither the STFT loss's 1e-7 nor
+ *      fcl_fx_logmel_fwd's unclamped magnitude);  M_c = max(sum_k m_k B[c, k], 1e-10), summed in ascending k;  l_c = log10 M_c.
+ * fcl_msl_sums_fwd: frame_sums [frames] float = per frame sum_c |l_x,c - l_y,c| (a fixed-order tree); utt_sums [n_utt] double = each utterance's
+ *      frames added in ascending order in float64 (64 contiguous chunks that depend on the utterance's own frame count only, then the chunk totals).
+ *      The caller forms D / (frames x n_mels) over one utterance or the batch.
+ * fcl_msl_grad_bwd: coef [n_utt] float = per utterance kappa = g / (ln 10 n), the reduction folded in by the caller.
+ *      dl_c = kappa sign(l_x,c - l_y,c) / M_x,c where sum_k m_x,k B[c, k] > 1e-10, else 0;  dm_k = sum_c B[c, k] dl_c over the channels that cover
+ *      bin k in ascending c: the bin-major transpose of B, bt_off [bins + 1], bt_ch [nnz], bt_w [nnz], a list because the channels covering a bin
+ *      need not be contiguous;  G[k] = (dm_k / m_x,k) X[k] where p_x > 1e-10, else 0 (neither floor passes a gradient);  from G on as
+ *      fcl_stl_grad_bwd: fr [frames, n_fft] = w N irfft(Yh) with each one-sided bin counted once, then the gather over a sample's own position
+ *      and its two mirrors; accumulate != 0 adds to gx.  Both transforms and the mels are recomputed: nothing of size frames x bins or
+ *      frames x n_mels is kept between the two entries or reaches memory.
+ * No atomics: a batch is bit for bit its per-utterance runs.  Supported: n_fft 512 / 1024 / 2048, 1 <= hop <= n_fft / 2, 1 <= n_mels <= 256,
+ *      nnz >= 1; window, twiddle, fr and utt_sums 8-byte aligned; frames x n_fft and samples below 2^31.  The kernels clamp every index read from a
+ *      device table.  No entry allocates, synchronises or copies. */
+typedef struct {
+    int64_t frames, samples;
+    int32_t n_fft, hop, n_utt, accumulate, n_mels, nnz;
+    const float* x;
+    const float* y;
+    const int32_t* smp_off;
+    const int32_t* frame_utt;
+    const int32_t* utt_off;
+    const float* window;
+    const float* twiddle;
+    const int32_t* fb_lo;
+    const int32_t* fb_off;
+    const float* fb_w;
+    const int32_t* bt_off;
+    const int32_t* bt_ch;
+    const float* bt_w;
+    float* frame_sums;
+    double* utt_sums;
+    const float* coef;
+    float* fr;
+    float* gx;
+} fcl_msl_t;
+int fcl_msl_sums_fwd(const fcl_msl_t* a, fcl_stream_t stream);
+int fcl_msl_grad_bwd(const fcl_msl_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
