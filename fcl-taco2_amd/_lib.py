@@ -251,6 +251,7 @@ SIGNATURES = {
     "fcl_variance_embed_add_fwd": (_I, [_P] * 12 + [_I, _I, _I, _P]),
     "fcl_duration_round_ctl_fwd": (_I, [_P, _P, _I, _I, _F, _P, _P, _I, _I, _P]),
     "fcl_variance_embed_add_ctl_fwd": (_I, [_P] * 10 + [_I, _I] + [_P] * 5 + [_I, _I, _I, _P]),
+    "fcl_variance_embed_rows_fwd": (_I, [_P] * 11 + [_I, _I] + [_P] * 3 + [_I, _I, _I, _I, _P]),
     "fcl_position_table_fwd": (_I, [_P, _P, _I, _I, _P]),
     "fcl_concat_spk_fwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "fcl_kaldi_ark_append": (C.c_longlong, [_I, C.c_longlong, _I, _P, _P, _P, _I, _P]),

@@ -341,6 +341,129 @@ __global__ void variance_ctl_rows_kernel(const float* __restrict__ p, const floa
     if (e_out) e_out[row] = ev;
 }
 
+// ---- H5 + H9 in one launch (fcl_variance_embed_rows_fwd): the variance embedding written as the decoder's sorted rows, as P32 planes ----------------
+// out_p row i = split((hs[r] + p_emb(r)) + e_emb(r)) with r = src_rows[i]; r outside [0, m): a zero row (gather_rows_kernel's answer to idx < 0).  The fp32
+// [m, c] sum that variance_embed_add_kernel writes and gather_rows_kernel reads back never reaches memory, and only the gathered rows are computed.
+// A wave owns 256 channels (a lane four consecutive ones) of VER_ROWS destination rows.  The tap weights come TAP-MAJOR ([k][c], built once by the plan):
+// a lane's taps are one coalesced float4 per tap -- with KT = k known at compile time they are loaded once and stay in registers for all of the wave's rows
+// (the [c][k] layout made every wave-wide tap load touch 64 lines, per row: the kernel was bound by L1 line requests, round 9).  Row index and segment bounds
+// are the same for all lanes of a wave: scalar loads (uniform_word).  The 2 k window values of a row are ONE vector load (lane L: tap L of p, lane k + L: tap L
+// of e, at a row CLAMPED into [0, m)) and reach the taps by readlane.  No branch sits between the loads, and all rows' loads are requested before the first
+// row is computed; a tap the segment does not admit leaves the sum as it is.  Taps are taken in order j = 0 .. k - 1 with fmaf, as variance_embed_add_kernel
+// takes them: bit-identical rows.  CTL: every tap applies the control of the row it reads (variance_embed_add_ctl_kernel), on the lane that loaded it;
+// identity controls skip the affine.  Workgroups at and beyond main_blocks write the controlled scalars p_out / e_out of all m padded rows
+// (variance_ctl_rows_kernel's body).  KT = 0: any odd k <= 31, taps read per row (they stay L1-resident).
+// (4 rows per wave: a wave is alone on its SIMD and issues ~330 VALU instructions per row; with 8 rows the launch was bound by 320 waves' instruction streams,
+// 7.8 us against 5.9 us per launch with four passes in flight -- profiles/r10_variance_rows_registers.txt)
+enum { VER_ROWS = 4 };
+
+template <int KT, bool CTL>
+__global__ __launch_bounds__(64) void variance_embed_rows_kernel(const float* __restrict__ hs, const float* __restrict__ p, const float* __restrict__ e,
+                                                                 const float* __restrict__ wp_t, const float* __restrict__ bp, const float* __restrict__ we_t,
+                                                                 const float* __restrict__ be, const int* __restrict__ seg_lo, const int* __restrict__ seg_hi,
+                                                                 const int* __restrict__ src_rows, const float* __restrict__ ctl, int ctl_ld, int ctl_row_div,
+                                                                 unsigned short* __restrict__ out_p, float* __restrict__ p_out, float* __restrict__ e_out,
+                                                                 int m, int n, int c, int k, int main_blocks, int groups) {
+    if ((int)blockIdx.x >= main_blocks) {  // the controlled scalars of the padded rows (only launched when p_out / e_out are asked for)
+        const int row = ((int)blockIdx.x - main_blocks) * 64 + (int)threadIdx.x;
+        if (row >= m) return;
+        float pv = p[row], ev = e[row];
+        if (CTL) {
+            const float* cr = ctl_row(ctl, ctl_ld, ctl_row_div, row);
+            pv = ctl_affine(pv, cr[1], cr[2]);
+            ev = ctl_affine(ev, cr[3], cr[4]);
+        }
+        if (p_out) p_out[row] = pv;
+        if (e_out) e_out[row] = ev;
+        return;
+    }
+    const int blk = (int)blockIdx.x / groups, grp = (int)blockIdx.x - blk * groups;  // (row block, group of 256 channels): uniform
+    const int lane = (int)threadIdx.x, ch = grp * 256 + lane * 4;
+    const bool active = ch < c;       // (c % 32 == 0: a lane owns four channels or none); every lane stays: the first 2 k of them load the windows
+    const int chl = active ? ch : 0;  // loads of a lane without channels go to channel 0 and are dropped: no branch around a load
+    constexpr int KA = KT > 0 ? KT : 1;
+    const int kk = KT > 0 ? KT : k, pad = (kk - 1) / 2, ldp = c >> 5;
+    const f32x4 bp4 = *reinterpret_cast<const f32x4*>(bp + chl), be4 = *reinterpret_cast<const f32x4*>(be + chl);
+    f32x4 wpr[KA], wer[KA];
+    if (KT > 0) {
+#pragma unroll
+        for (int j = 0; j < KA; ++j) {
+            wpr[j] = *reinterpret_cast<const f32x4*>(wp_t + (size_t)j * c + chl);
+            wer[j] = *reinterpret_cast<const f32x4*>(we_t + (size_t)j * c + chl);
+        }
+    }
+    // Phase 1, all rows of the wave before anything is used: the row index and its segment (scalar), the row of hs, and the row's WINDOW -- lane L < k holds
+    // tap L of the (controlled) pitch, lane k + L tap L of the energy, each read at a row clamped into [0, m) (2 k <= 64).
+    const bool is_e = lane >= kk;
+    const int tapl = min(is_e ? lane - kk : lane, kk - 1);
+    const float* const src = is_e ? e : p;
+    int lo[VER_ROWS], hi[VER_ROWS], rsv[VER_ROWS];
+    bool okv[VER_ROWS];
+    float win[VER_ROWS];
+    f32x4 h[VER_ROWS];
+#pragma unroll
+    for (int rr = 0; rr < VER_ROWS; ++rr) {
+        const int i = min(blk * VER_ROWS + rr, n - 1);  // (rows past n repeat the last one and are not stored)
+        const int r = uniform_word(src_rows, i);
+        okv[rr] = r >= 0 && r < m;
+        rsv[rr] = okv[rr] ? r : 0;
+        lo[rr] = uniform_word(seg_lo, rsv[rr]);
+        hi[rr] = uniform_word(seg_hi, rsv[rr]);
+        const int qc = min(max(rsv[rr] + tapl - pad, 0), m - 1);
+        float wv = src[qc];
+        if (CTL) {
+            const float* cr = ctl_row(ctl, ctl_ld, ctl_row_div, qc) + (is_e ? 3 : 1);
+            wv = ctl_affine(wv, cr[0], cr[1]);
+        }
+        win[rr] = wv;
+        h[rr] = *reinterpret_cast<const f32x4*>(hs + (size_t)rsv[rr] * c + chl);
+    }
+    // Phase 2: per row, the taps in order (a tap outside the segment leaves the sums as they are), the sum in the reference order, split, two 8-byte stores
+#pragma unroll
+    for (int rr = 0; rr < VER_ROWS; ++rr) {
+        const int i = blk * VER_ROWS + rr;
+        f32x4 ap = bp4, ae = be4;
+        const int wbits = __builtin_bit_cast(int, win[rr]);
+        if (KT > 0) {
+#pragma unroll
+            for (int j = 0; j < KA; ++j) {
+                const int q = rsv[rr] + j - pad;
+                const bool in = q >= lo[rr] && q < hi[rr];
+                const float pv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(wbits, j));
+                const float ev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(wbits, KA + j));
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    ap[x] = in ? fmaf(wpr[j][x], pv, ap[x]) : ap[x];
+                    ae[x] = in ? fmaf(wer[j][x], ev, ae[x]) : ae[x];
+                }
+            }
+        } else {
+            for (int j = 0; j < kk; ++j) {
+                const int q = rsv[rr] + j - pad;
+                const bool in = q >= lo[rr] && q < hi[rr];
+                const float pv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(wbits, j));
+                const float ev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(wbits, kk + j));
+                const f32x4 w1 = *reinterpret_cast<const f32x4*>(wp_t + (size_t)j * c + chl), w2 = *reinterpret_cast<const f32x4*>(we_t + (size_t)j * c + chl);
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    ap[x] = in ? fmaf(w1[x], pv, ap[x]) : ap[x];
+                    ae[x] = in ? fmaf(w2[x], ev, ae[x]) : ae[x];
+                }
+            }
+        }
+        f32x4 v;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) v[x] = okv[rr] ? (h[rr][x] + ap[x]) + ae[x] : 0.f;  // reference order: (h + p_embs) + e_embs
+        uint2 vh, vl;
+        split4(v, vh, vl);
+        if (active && i < n) {
+            unsigned short* line = out_p + ((size_t)i * ldp + (ch >> 5)) * 64 + (ch & 31);
+            *reinterpret_cast<uint2*>(line) = vh;
+            *reinterpret_cast<uint2*>(line + 32) = vl;
+        }
+    }
+}
+
 // ---- speaker embedding: hs <- cat[hs, F.normalize(spemb)] (..._sa.py:555-557, 636-638) -------------------------------------------------
 // out[row, 0:C] = hs[row, 0:C]; out[row, C:C+S] = spk[b] / max(||spk[b]||_2, 1e-12) with b = row / T (the padded [B, T] row layout).  One wave per
 // row: the norm of its utterance's vector by a wave reduction (S <= a few hundred floats, L2-resident), then C + S contiguous outputs; outp
@@ -753,6 +876,40 @@ int fcl_variance_embed_add_ctl_fwd(const float* hs, const float* p, const float*
         hipLaunchKernelGGL(variance_ctl_rows_kernel, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, e, ctl, ctl_ld, ctl_row_div, p_out,
                            e_out, m);
     return check_hip(hipGetLastError(), "variance_embed_add_ctl_fwd");
+}
+
+int fcl_variance_embed_rows_fwd(const float* hs, const float* p, const float* e, const float* wp_t, const float* bp, const float* we_t, const float* be,
+                                const int32_t* seg_lo, const int32_t* seg_hi, const int32_t* src_rows, const float* ctl, int ctl_ld, int ctl_row_div,
+                                uint16_t* out_p, float* p_out, float* e_out, int m, int n, int c, int k, fcl_stream_t stream) {
+    FCL_REQUIRE(hs && p && e && wp_t && bp && we_t && be && seg_lo && seg_hi && m >= 0 && n >= 0 && c > 0 && k > 0 && (k & 1), FCL_ERR_INVALID,
+                "variance_embed_rows_fwd: bad arguments (null pointer, negative size or even k)");
+    FCL_REQUIRE(n == 0 || (src_rows && out_p), FCL_ERR_INVALID, "variance_embed_rows_fwd: destination rows need src_rows and out_p");
+    FCL_REQUIRE(!ctl || (ctl_ld >= 5 && ctl_row_div >= 1), FCL_ERR_INVALID, "variance_embed_rows_fwd: ctl_ld < 5 or ctl_row_div < 1");
+    FCL_REQUIRE((!p_out || p_out != p) && (!e_out || e_out != e), FCL_ERR_INVALID, "variance_embed_rows_fwd: p_out / e_out alias p / e");
+    FCL_REQUIRE((c & 31) == 0 && k <= 31, FCL_ERR_SHAPE, "variance_embed_rows_fwd: C=%d must be a multiple of 32 (whole lines of the planes) and k=%d <= 31", c, k);
+    FCL_REQUIRE(aligned16(hs) && aligned16(wp_t) && aligned16(bp) && aligned16(we_t) && aligned16(be), FCL_ERR_ALIGN,
+                "variance_embed_rows_fwd: 16-byte alignment required");
+    FCL_REQUIRE((reinterpret_cast<uintptr_t>(out_p) & 127u) == 0, FCL_ERR_ALIGN, "variance_embed_rows_fwd: planes must be 128-byte aligned");
+    FCL_REQUIRE(m > 0 || n == 0, FCL_ERR_INVALID, "variance_embed_rows_fwd: destination rows without source rows");
+    if (m == 0) return 0;
+    const int groups = (c + 255) / 256;  // a wave covers 256 channels of its rows
+    const long long main_blocks = (long long)((n + VER_ROWS - 1) / VER_ROWS) * groups;
+    const long long blocks = main_blocks + ((p_out || e_out) ? (m + 63) / 64 : 0);
+    if (blocks == 0) return 0;
+    FCL_REQUIRE(blocks <= 0x7fffffffLL, FCL_ERR_SHAPE, "variance_embed_rows_fwd: too many rows for one launch");
+    ProfScope ps("variance_embed_rows_kernel", 0.0, (double)n, (hipStream_t)stream);
+#define FCL_VER(KT_, CTL_)                                                                                                                                   \
+    hipLaunchKernelGGL((variance_embed_rows_kernel<KT_, CTL_>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, hs, p, e, wp_t, bp, we_t, be, seg_lo, \
+                       seg_hi, src_rows, ctl, ctl_ld, ctl_row_div, out_p, p_out, e_out, m, n, c, k, (int)main_blocks, groups)
+    if (k == 9) {  // the shipped recipes' embedding kernel size: taps resident in registers
+        if (ctl) FCL_VER(9, true);
+        else FCL_VER(9, false);
+    } else {
+        if (ctl) FCL_VER(0, true);
+        else FCL_VER(0, false);
+    }
+#undef FCL_VER
+    return check_hip(hipGetLastError(), "variance_embed_rows_fwd");
 }
 
 int fcl_masked_l1_mse_fwd(const float* a, int lda, const float* b, int ldb, const uint8_t* row_valid, int m, int c, int b_log,

@@ -197,6 +197,8 @@ _RING = None
 import os as _os
 
 _GROUP_PREDICTORS = _os.environ.get("FCL_PRED_GROUP", "1") not in ("", "0")  # 0: one launch per predictor and layer (rounds 1-2)
+# 0: the variance embedding as its own launch over all padded rows, then the gather of the decoder's rows (rounds 1-9)
+_VAR_EMBED_ROWS = _os.environ.get("FCL_VAR_EMBED_ROWS", "1") not in ("", "0")
 
 
 def _ring():
@@ -395,14 +397,23 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
         elif p is None:
             p = predictor(plan.pitch, prep.pad)
             e = predictor(plan.energy, prep.pad)
-        if ctl is not None:  # the same launch with the pitch / energy controls folded in; p, e become the controlled values
+        att_c = att_c_p = None
+        if planes and _VAR_EMBED_ROWS and not return_intermediates and hs.shape[1] % 32 == 0 and plan.pitch_embed_wt.shape[0] <= 31:
+            # the embedding computed for the decoder's sorted rows only and written as their planes: one launch instead of embed + gather, no fp32 [m, C] sum
+            p_emb = e_emb = None
+            att_c_p, p_c, e_c = ops.variance_embed_rows(hs, p, e, plan.pitch_embed_wt, plan.pitch_embed_b, plan.energy_embed_wt, plan.energy_embed_b,
+                                                        prep.seg_lo, prep.seg_hi, rm.src_rows, ctl, 1, want_scalars=ctl is not None)
+            if ctl is not None:
+                p, e = p_c, e_c
+        elif ctl is not None:  # the same launch with the pitch / energy controls folded in; p, e become the controlled values
             att, p_emb, e_emb, p, e = ops.variance_embed_add_ctl(hs, p, e, plan.pitch_embed_w, plan.pitch_embed_b, plan.energy_embed_w,
                                                                  plan.energy_embed_b, prep.seg_lo, prep.seg_hi, ctl, 1, want_embs=return_intermediates)
         else:
             att, p_emb, e_emb = ops.variance_embed_add(hs, p, e, plan.pitch_embed_w, plan.pitch_embed_b, plan.energy_embed_w,
                                                        plan.energy_embed_b, prep.seg_lo, prep.seg_hi, want_embs=return_intermediates)
         maps = rm.maps
-        att_c, att_c_p = (ops.gather_rows(att, rm.src_rows, want_f32=False, want_planes=True) if planes else (ops.gather_rows(att, rm.src_rows), None))
+        if att_c_p is None:
+            att_c, att_c_p = (ops.gather_rows(att, rm.src_rows, want_f32=False, want_planes=True) if planes else (ops.gather_rows(att, rm.src_rows), None))
         keep_dev = None
         if hp.dropout_rate <= 0.0:
             dropout_mode = ops.DROP_NONE

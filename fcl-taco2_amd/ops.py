@@ -286,6 +286,21 @@ def variance_embed_add_ctl(hs, p, e, wp, bp, we, be, seg_lo, seg_hi, ctl=None, c
     return out, pe, ee, p_out, e_out
 
 
+def variance_embed_rows(hs, p, e, wp_t, bp, we_t, be, seg_lo, seg_hi, src_rows, ctl=None, ctl_row_div=1, want_scalars=False):
+    """fcl_variance_embed_rows_fwd: variance_embed_add[_ctl] followed by gather_rows(src_rows, planes only) as ONE launch, bit for bit.  wp_t / we_t: the
+    tap-major [k, C] weights (plan.tap_major).  Returns (P32 planes of the n = src_rows.numel() gathered rows, p_out, e_out); the controlled scalars
+    [m] are written when want_scalars (else None)."""
+    m, c = hs.shape
+    k, n = wp_t.shape[0], src_rows.numel()
+    out_p = planes_empty(n, c, hs.device)
+    p_out = torch.empty_like(p) if want_scalars else None
+    e_out = torch.empty_like(e) if want_scalars else None
+    cp, ld, div = _ctl_args(ctl, ctl_row_div)
+    check(_lib.load().fcl_variance_embed_rows_fwd(_p(hs), _p(p), _p(e), _p(wp_t), _p(bp), _p(we_t), _p(be), _p(seg_lo, torch.int32), _p(seg_hi, torch.int32),
+                                                  _p(src_rows, torch.int32), cp, ld, div, _p(out_p, torch.int16), _p(p_out), _p(e_out), m, n, c, k, _stream()))
+    return out_p, p_out, e_out
+
+
 def position_table(dur_i32, lmax):
     n = dur_i32.numel()
     pos = torch.empty(n, lmax, device=dur_i32.device, dtype=torch.float32)

@@ -29,6 +29,14 @@ def _conv_planes(c):
     return c
 
 
+def tap_major(w):
+    """[C, k] stencil weights (Conv1d(1, C, k).weight without its unit dimension) as a contiguous tap-major [k, C] table (torch tensor or numpy array):
+    the layout fcl_variance_embed_rows_fwd reads, one coalesced row of channels per tap.  A pure transposition: every value is kept exactly."""
+    if isinstance(w, np.ndarray):
+        return np.ascontiguousarray(w.reshape(w.shape[0], -1).T)
+    return w.reshape(w.shape[0], -1).t().contiguous()
+
+
 def embed_conv_tables_f64(wp, embed):
     """wp: tap-major folded weights [k, Cout, Cin]; embed [V, Cin] -> float64 [k, V, Cout]: tables[tap, v, co] = sum_ci wp[tap, co, ci] * embed[v, ci]."""
     return np.matmul(np.asarray(embed, dtype=np.float64)[None], np.asarray(wp, dtype=np.float64).transpose(0, 2, 1))
@@ -123,6 +131,9 @@ class SynthesisPlan(object):
             self.pitch_embed_b = g("pitch_embed.0.bias")
             self.energy_embed_w = g("energy_embed.0.weight").reshape(hp.adim, -1).contiguous()
             self.energy_embed_b = g("energy_embed.0.bias")
+            # tap-major copies for ops.variance_embed_rows: a lane that owns four consecutive channels reads one float4 per tap
+            self.pitch_embed_wt = tap_major(self.pitch_embed_w)
+            self.energy_embed_wt = tap_major(self.energy_embed_w)
             self.postnet = [self._conv_bn(g, "dec.postnet.postnet.%d" % i) for i in range(hp.postnet_layers)]
             self.decoder = self._decoder(g)
             torch.cuda.synchronize(self.device)

@@ -213,6 +213,15 @@ int fcl_duration_round_ctl_fwd(const float* x, int64_t* out, int n, int linear_d
 int fcl_variance_embed_add_ctl_fwd(const float* hs, const float* p, const float* e, const float* wp, const float* bp, const float* we,
                                    const float* be, const int32_t* seg_lo, const int32_t* seg_hi, const float* ctl, int ctl_ld, int ctl_row_div,
                                    float* out, float* p_emb, float* e_emb, float* p_out, float* e_out, int m, int c, int k, fcl_stream_t stream);
+/* The entry above followed by fcl_gather_rows_fwd(out, src_rows, NULL, out_p, n, c) in ONE launch, bit for bit: out_p row i (P32 planes, c % 32 == 0,
+ * c / 32 lines per row) is row r = src_rows[i] of (hs + p_emb) + e_emb; r outside [0, m) gives a zero row.  The fp32 [m, c] sum is never written and only
+ * the n gathered rows are computed.  wp_t / we_t are the embedding weights TAP-MAJOR ([k][c]: the transpose of wp / we [c][k]), a constant of the plan;
+ * k odd, <= 31.
+ * ctl == NULL: no controls.  p_out / e_out (optional, [m], must not alias p / e): the controlled scalars of all m padded rows, from the same launch.
+ * n == 0 writes only p_out / e_out (src_rows and out_p may then be NULL). */
+int fcl_variance_embed_rows_fwd(const float* hs, const float* p, const float* e, const float* wp_t, const float* bp, const float* we_t, const float* be,
+                                const int32_t* seg_lo, const int32_t* seg_hi, const int32_t* src_rows, const float* ctl, int ctl_ld, int ctl_row_div,
+                                uint16_t* out_p, float* p_out, float* e_out, int m, int n, int c, int k, fcl_stream_t stream);
 
 /* ---- speaker embedding (..._sa.py:555-557 forward, :636-638 inference; `--spk-embed-dim`): out [M, C + S] = cat[hs, F.normalize(spemb)] over the
  *      padded [B, T] row layout (row m belongs to utterance m / t; spk [B, S]; F.normalize: x / max(||x||_2, 1e-12)).  out_p (optional, (C + S) % 32
