@@ -154,6 +154,11 @@ class MelLoss(C.Structure):  # fcl_msl_t
                           "frame_sums", "utt_sums", "coef", "fr", "gx")]
 
 
+class PwdLayer(C.Structure):  # fcl_pwd_t
+    _fields_ = [("samples", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "ksize", "dilation")] + [("slope", _F), ("reserved", C.c_int32)] + [
+        (n, _P) for n in ("x", "w", "bias", "h", "g", "seg_lo", "seg_hi", "y", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -333,6 +338,10 @@ SIGNATURES = {
     "fcl_stl_grad_bwd": (_I, [C.POINTER(StftLoss), _P]),
     "fcl_msl_sums_fwd": (_I, [C.POINTER(MelLoss), _P]),
     "fcl_msl_grad_bwd": (_I, [C.POINTER(MelLoss), _P]),
+    "fcl_pwd_dw_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I]),
+    "fcl_pwd_layer_fwd": (_I, [C.POINTER(PwdLayer), _P]),
+    "fcl_pwd_layer_dx": (_I, [C.POINTER(PwdLayer), _P]),
+    "fcl_pwd_layer_dw": (_I, [C.POINTER(PwdLayer), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

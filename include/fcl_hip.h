@@ -1272,6 +1272,49 @@ typedef struct {
 int fcl_msl_sums_fwd(const fcl_msl_t* a, fcl_stream_t stream);
 int fcl_msl_grad_bwd(const fcl_msl_t* a, fcl_stream_t stream);
 
+/* ---- Parallel WaveGAN discriminator: a stack of dilated Conv1d + LeakyReLU on the waveform, one layer per call, forward and backward
+ *      (fcl_taco2_amd/pwg_discriminator.py; restated in float64 numpy in tests/pwgd_ref.py).
+ * Layout: activations and gradients float32, channel-last [samples, C]; the batch packed, one row per sample, the utterances back to back.  Row t's
+ *      utterance is [seg_lo[t], seg_hi[t]) (as fcl_conv1d_fwd; the kernels clamp both to [0, samples]): a tap that falls outside it reads zero.
+ * A layer is 1 -> C (the first), C -> C or C -> 1 (the last), C a multiple of 16 from 16 to 128, ksize k 3 or 5, tap j at offset (j - (k - 1) / 2) d,
+ *      d = dilation >= 1 (no upper limit).  Weights are tap-major: wf [k][cin][cout], wf[j][ci][co] = W[co][ci][j] of torch's Conv1d.
+ * fcl_pwd_layer_fwd: y[t, co] = act(bias[co] + sum_j sum_ci x[t + (j - (k - 1) / 2) d, ci] wf[j][ci][co]); act is LeakyReLU(slope) except for the last
+ *      layer (cout 1), which has none.  w = wf; bias optional; x [samples, cin], y [samples, cout].
+ * fcl_pwd_layer_dx: y[t, ci] = m(h[t, ci]) sum_j sum_co g[t + (j - (k - 1) / 2) d, co] wb[j][co][ci], the gradient of the PRE-activation of the layer
+ *      below: g [samples, cout] is the gradient of this layer's pre-activation, w = wb [k][cout][cin] with wb[j][co][ci] = W[co][ci][k - 1 - j] (taps
+ *      reversed, transposed), h [samples, cin] the stored post-activation of this layer's input, m = 1 where h > 0, else slope (h == 0 takes the slope,
+ *      as torch does).  The first layer (cin 1) has no mask: h must be null, y [samples] is the waveform gradient.
+ * fcl_pwd_layer_dw: dw [k][cin][cout] (the layout of wf) = sum_t x[t + (j - (k - 1) / 2) d, ci] g[t, co]; db [cout] = sum_t g[t, co] (optional).  x is the
+ *      layer's input.  Each chunk of 1024 samples leaves a partial in the workspace (fcl_pwd_dw_workspace_bytes); a second launch adds them in
+ *      ascending order.  No atomics anywhere: two runs give the same bits, and a batch's activations and input gradients are bit for bit those of its
+ *      per-utterance runs.
+ * One arithmetic mode, exact fp32: the C -> C contractions run on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain), the rest on fmaf.  Every entry
+ *      validates before any HIP call: a null pointer or a slope outside [0, 1) FCL_ERR_INVALID; channels, ksize, dilation or samples (1 .. 2^31 - 1)
+ *      out of range FCL_ERR_SHAPE; x, g, w, h, y not 16-byte aligned FCL_ERR_ALIGN; a workspace that is too small FCL_ERR_WORKSPACE.  No entry
+ *      allocates, synchronises or copies. */
+typedef struct {
+    int64_t samples;
+    int32_t cin, cout, ksize, dilation;
+    float slope;
+    int32_t reserved;
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* h;
+    const float* g;
+    const int32_t* seg_lo;
+    const int32_t* seg_hi;
+    float* y;
+    float* dw;
+    float* db;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_pwd_t;
+size_t fcl_pwd_dw_workspace_bytes(int64_t samples, int cin, int cout, int ksize);
+int fcl_pwd_layer_fwd(const fcl_pwd_t* a, fcl_stream_t stream);
+int fcl_pwd_layer_dx(const fcl_pwd_t* a, fcl_stream_t stream);
+int fcl_pwd_layer_dw(const fcl_pwd_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
