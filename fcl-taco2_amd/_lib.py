@@ -266,6 +266,8 @@ SIGNATURES = {
     "fcl_gather_rows_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "fcl_bilstm_workspace_bytes": (_Z, [_I, _I, _I]),
     "fcl_bilstm_fwd": (_I, [_P] * 13 + [_I, _I, _I, _I, _I, _P, _Z, _P, _P, _P]),
+    "fcl_bilstm_rows_workspace_bytes": (_Z, [_I, _I]),
+    "fcl_bilstm_rows_fwd": (_I, [_P] * 14 + [_I, _I, _I, _I, _P, _Z, _P, _P]),
     "fcl_decoder_loop_workspace_bytes": (_Z, [C.POINTER(DecoderWeights), _I]),
     "fcl_decoder_stream_bytes": (_Z, [C.POINTER(DecoderWeights)]),
     "fcl_decoder_stream_pack": (_I, [C.POINTER(DecoderWeights), _P, _Z, _P]),

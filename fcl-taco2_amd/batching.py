@@ -21,8 +21,11 @@ def _grown_caps(engine, maps, n_rows, scale=1.3):
     bounds[: maps.lmax] = live
     bounds[maps.lmax :] = live[-1]
     bounds = np.maximum.accumulate(bounds[::-1])[::-1].astype(np.int32)  # non-increasing, as the loop requires
-    # the steps past this batch's own longest duration (+ 2) are slack: the rows that do reach them continue in one launch of the row-tile kernel
-    return engine.Caps(lmax, (int(maps.n_frames * scale) + 255) // 256 * 256, bounds, tail_from=maps.lmax + 2)
+    # the steps past this batch's own longest duration (+ 2) are slack: the rows that do reach them continue in one launch of the row-tile kernel;
+    # the phoneme rows (live_rows[0]: every row has a duration above 0) get the live rows' slack and cap: at n_rows the runner keeps the padded layout
+    caps = engine.Caps(lmax, (int(maps.n_frames * scale) + 255) // 256 * 256, bounds, tail_from=maps.lmax + 2)
+    caps.rows = int(live[0])
+    return caps
 
 
 class _ScaledMaps(object):

@@ -181,12 +181,17 @@ __device__ __forceinline__ KsCell ks_cell(float z, int g, float c) {
     return o;
 }
 
-template <bool SAVE = false, bool MAPS = false>
+// ROWS (fcl_bilstm_rows_fwd): the compact row layout.  Utterance b owns rows [utt_row0[b], utt_row0[b] + lens[b]) of an [n_rows, .] input and output; T is
+// n_rows.  The workgroup reads its row base once in place of b * T, and the rows [utt_row0[B], n_rows) -- the capacity's slack, which takes the place of the
+// padded tails -- are zeroed by all the workgroups of a direction together.  A length that would run past n_rows is cut there: nothing is written beyond it.
+template <bool SAVE = false, bool MAPS = false, bool ROWS = false>
 __global__ __launch_bounds__(512) void bilstm_ksplit_kernel(const float* __restrict__ gx_f, const float* __restrict__ gx_r,
                                                             const float* __restrict__ whh_f, const float* __restrict__ whh_r,
                                                             const int* __restrict__ lens, float* __restrict__ out, int T, BilstmSave sv = BilstmSave(),
-                                                            unsigned short* __restrict__ out_p = nullptr, fcl_row_maps_t mp = fcl_row_maps_t()) {
+                                                            unsigned short* __restrict__ out_p = nullptr, fcl_row_maps_t mp = fcl_row_maps_t(),
+                                                            const int* __restrict__ utt_row0 = nullptr) {
     constexpr int H = 128;
+    static_assert(!(ROWS && SAVE), "the training forward keeps the padded layout");
     if constexpr (MAPS) {
         if (blockIdx.x == gridDim.x - 1) {
             if (blockIdx.y == 0) {
@@ -201,9 +206,11 @@ __global__ __launch_bounds__(512) void bilstm_ksplit_kernel(const float* __restr
     const int b = blockIdx.x, dir = blockIdx.y, j = threadIdx.x;
     const int q = j & 7, R = j >> 3;       // k-slice, row group (2 units x 4 gates)
     const int g = q & 3, U = 2 * R + (q >> 2);  // the gate / unit this lane ends up with after the reduce-scatter
-    const float* gx = (dir ? gx_r : gx_f) + (size_t)b * T * (4 * H);
+    const int nutt = (int)gridDim.x - (MAPS ? 1 : 0);
+    const int row0 = ROWS ? min(max(utt_row0[b], 0), T) : b * T;  // first row of this utterance
+    const float* gx = (dir ? gx_r : gx_f) + (size_t)row0 * (4 * H);
     const float* whh = dir ? whh_r : whh_f;
-    const int len = lens[b];
+    const int len = ROWS ? max(min(lens[b], T - row0), 0) : lens[b];
 
     f32x2 w[4][16];  // pair p = rows i = 2p, 2p + 1 of the block; row i = gate (i & 3) of unit 2R + (i >> 2)
 #pragma unroll
@@ -218,10 +225,11 @@ __global__ __launch_bounds__(512) void bilstm_ksplit_kernel(const float* __restr
         }
     }
     if (j < 2 * H) (&h_s[0][0])[j] = 0.f;
-    // zero the padded tail of this direction's half of the output rows
-    for (int t = len + (j / H); t < T; t += 4) {
-        out[((size_t)b * T + t) * (2 * H) + dir * H + (j % H)] = 0.f;
-        if (out_p) store_p32(out_p, (2 * H + 31) >> 5, b * T + t, dir * H + (j % H), 0.f);
+    // zero the padded tail of this direction's half of the output rows (ROWS: this workgroup's share of the rows behind the last utterance)
+    const int z0 = ROWS ? min(max(utt_row0[nutt], 0), T) + 4 * b : row0 + len, z1 = ROWS ? T : row0 + T, zs = ROWS ? 4 * nutt : 4;
+    for (int r = z0 + (j / H); r < z1; r += zs) {
+        out[(size_t)r * (2 * H) + dir * H + (j % H)] = 0.f;
+        if (out_p) store_p32(out_p, (2 * H + 31) >> 5, r, dir * H + (j % H), 0.f);
     }
     __syncthreads();
 
@@ -255,8 +263,8 @@ __global__ __launch_bounds__(512) void bilstm_ksplit_kernel(const float* __restr
             }
             if (g == 0) {
                 h_s[(d & 1) ^ 1][U] = h;
-                out[((size_t)b * T + t) * (2 * H) + dir * H + U] = h;
-                if (out_p) store_p32(out_p, (2 * H + 31) >> 5, b * T + t, dir * H + U, h);
+                out[((size_t)row0 + t) * (2 * H) + dir * H + U] = h;
+                if (out_p) store_p32(out_p, (2 * H + 31) >> 5, row0 + t, dir * H + U, h);
             }
             c = c_new;
             h_prev = h;
@@ -1060,6 +1068,69 @@ int fcl_bilstm_fwd(const float* x, const int32_t* lens, const float* w_ih_f, con
         }
     }
     return after.finish(out_p ? fcl_pack_planes(out, 2 * h, b * t, 2 * h, out_p, stream) : 0);  // the per-step path writes fp32 only: split once at the end
+}
+
+// workspace: Gx_f [n_rows, 4H] | Gx_r [n_rows, 4H]
+size_t fcl_bilstm_rows_workspace_bytes(int n_rows, int h) {
+    if (n_rows <= 0 || h <= 0) return 0;
+    return sizeof(float) * ((size_t)2 * n_rows * 4 * h) + 256;
+}
+
+// The synthesis BiLSTM over COMPACT rows: two input projections with M = n_rows, then the lane-split recurrence reading its row base from utt_row0.
+// H = 128 only (the form synthesis selects); anything else is refused, never run some other way.
+int fcl_bilstm_rows_fwd(const float* x, const int32_t* lens, const int32_t* utt_row0, const float* w_ih_f, const float* w_hh_f, const float* b_f,
+                        const float* w_ih_r, const float* w_hh_r, const float* b_r, float* out, uint16_t* out_p, const uint16_t* x_p,
+                        const uint16_t* w_ih_f_p, const uint16_t* w_ih_r_p, int b, int n_rows, int c, int h, void* workspace, size_t workspace_bytes,
+                        const fcl_row_maps_t* row_maps, fcl_stream_t stream) {
+    FCL_REQUIRE((x || x_p) && lens && utt_row0 && w_ih_f && w_hh_f && b_f && w_ih_r && w_hh_r && b_r && out, FCL_ERR_INVALID, "bilstm_rows_fwd: null argument");
+    FCL_REQUIRE((x_p == nullptr) == (w_ih_f_p == nullptr) && (x_p == nullptr) == (w_ih_r_p == nullptr), FCL_ERR_INVALID,
+                "bilstm_rows_fwd: x_p / w_ih_f_p / w_ih_r_p come together");
+    FCL_REQUIRE(b > 0 && n_rows > 0 && c > 0 && (c & 3) == 0, FCL_ERR_SHAPE, "bilstm_rows_fwd: bad sizes B=%d rows=%d C=%d", b, n_rows, c);
+    FCL_REQUIRE(h == 128, FCL_ERR_SHAPE, "bilstm_rows_fwd: H=%d: the compact row layout covers H = 128 (fcl_bilstm_fwd takes the padded layout)", h);
+    FCL_REQUIRE(workspace && workspace_bytes >= fcl_bilstm_rows_workspace_bytes(n_rows, h), FCL_ERR_WORKSPACE, "bilstm_rows_fwd: workspace too small");
+    FCL_REQUIRE(aligned16(workspace) && aligned16(out), FCL_ERR_ALIGN, "bilstm_rows_fwd: 16-byte alignment required");
+    bool maps_fusable = false;
+    if (row_maps) {
+        const int rc = row_maps_check(row_maps, &maps_fusable);
+        if (rc) return rc;
+        FCL_REQUIRE(row_maps->n == n_rows && row_maps->b == b && row_maps->utt_row0 && !row_maps->row_src, FCL_ERR_INVALID,
+                    "bilstm_rows_fwd: the row maps take the same compact universe (n = rows, utt_row0, no row_src)");
+    }
+    const bool fuse = row_maps && maps_fusable;
+    FCL_REQUIRE(fuse ? ks_claims_simd(bilstm_ksplit_kernel<false, true, true>, "bilstm_ksplit_kernel<false, true, true>")
+                     : ks_claims_simd(bilstm_ksplit_kernel<false, false, true>, "bilstm_ksplit_kernel<false, false, true>"),
+                FCL_ERR_INVALID, "bilstm_rows_fwd: the lane-split kernel is off in this build");
+    hipStream_t s = (hipStream_t)stream;
+    float* gx_f = reinterpret_cast<float*>(workspace);
+    float* gx_r = gx_f + (size_t)n_rows * 4 * h;
+    for (int d = 0; d < 2; ++d) {
+        GemmArgs g = {};
+        g.term[0] = GemmTerm{x, d ? w_ih_r : w_ih_f, c, c, c, 0};
+        if (x_p) {
+            g.term[0].Ap = x_p;
+            g.term[0].Wp = d ? w_ih_r_p : w_ih_f_p;
+            g.term[0].lda_p = g.term[0].ldw_p = (c + 31) / 32;
+        }
+        g.nterms = 1;
+        g.M = n_rows;
+        g.N = 4 * h;
+        g.bias = d ? b_r : b_f;
+        g.Y = d ? gx_r : gx_f;
+        g.ldy = 4 * h;
+        int rc = launch_gemm(g, s);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(fuse ? "bilstm_ksplit_kernel+maps/rows" : "bilstm_ksplit_kernel/rows", 2.0 * 2 * (double)n_rows * 4 * h * h, (double)n_rows, s);
+        if (fuse)
+            hipLaunchKernelGGL((bilstm_ksplit_kernel<false, true, true>), dim3(b + 1, 2), dim3(512), 0, s, gx_f, gx_r, w_hh_f, w_hh_r, lens, out, n_rows,
+                               BilstmSave(), out_p, *row_maps, utt_row0);
+        else
+            hipLaunchKernelGGL((bilstm_ksplit_kernel<false, false, true>), dim3(b, 2), dim3(512), 0, s, gx_f, gx_r, w_hh_f, w_hh_r, lens, out, n_rows,
+                               BilstmSave(), out_p, fcl_row_maps_t(), utt_row0);
+    }
+    const int rc = check_hip(hipGetLastError(), "bilstm k-split (rows) launch");
+    return (fuse || rc || !row_maps) ? rc : fcl_row_maps_build(row_maps, stream);
 }
 
 }  // extern "C"

@@ -264,6 +264,11 @@ def decode(model, utts, out_prefix, batch_size=32, seed=137, depth=4, stats=None
                 for it in take(pending, lambda p: p[1] == j):  # stream j's previous batch (of any bucket) must have left the runner's static buffers
                     frames += harvest(it)
                 r = pool.runner(j)
+                if r.R is not None and n_ph > r.R:  # more phonemes than the bucket's compact rows hold: handled like a capacity the device reports
+                    n_redo += 1
+                    got, pool.grow = eager(chunk)
+                    frames += got
+                    continue
                 slot = pool.slots[j][(pool.next // len(streams)) % 2]
                 slot.free.wait()  # the writer thread is done with what this landing buffer held
                 slot.free.clear()

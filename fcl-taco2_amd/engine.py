@@ -128,24 +128,30 @@ def use_planes(plan):
 
 class PreparedBatch(object):
     """Everything `run` needs, resident in HBM: padded ids, segment bounds, and (forced durations) row maps -- built on the host (`maps`), or
-    left to the device (`dur_pad`: the forced durations in the padded [B, T] layout; run() then needs `caps`)."""
+    left to the device (`dur_pad`: the forced durations in the padded [B, T] layout; run() then needs `caps`).
+    Compact rows (BatchRunner with caps.rows): `n_rows` is set, every per-row array has n_rows entries with the utterances back to back,
+    `utt_row0` [B + 1] holds their row ranges and `rows_total` [1] the batch's row count, both in HBM."""
     __slots__ = ("B", "T", "lens", "ids", "seg_lo", "seg_hi", "pad", "lens_dev", "f0e", "maps", "src_rows", "dur", "frame_off",
-                 "frame_lo", "frame_hi", "dur_pad", "spk", "ctl")
+                 "frame_lo", "frame_hi", "dur_pad", "spk", "ctl", "n_rows", "utt_row0", "rows_total")
 
 
 class Caps(object):
     """Capacities of a pass whose row maps are built on the DEVICE (ops.row_maps_build): everything the host would otherwise have to know about the
     durations.  lmax: decoder steps to launch; frames: rows of the frame-major buffers; bounds: int32 [lmax] upper bounds of the live rows per
     step (grid sizes and kernel selection only).  None of them is trusted: a batch that exceeds one raises FCL_STATUS_* in the device status word
-    (read it with DeviceFrames.resolve() / ops.check_status) and decodes nothing."""
-    __slots__ = ("lmax", "frames", "bounds", "tail_from")
+    (read it with DeviceFrames.resolve() / ops.check_status) and decodes nothing.
+    rows: phoneme rows of the pass's COMPACT row universe (BatchRunner: utterances back to back, `rows` rows in all), or None: the padded
+    [batch, t_cap] universe.  A batch with more phonemes than `rows` is refused by BatchRunner.load() on the host, before anything runs."""
+    __slots__ = ("lmax", "frames", "bounds", "tail_from", "rows")
 
-    def __init__(self, lmax, frames, bounds, tail_from=0):
+    def __init__(self, lmax, frames, bounds, tail_from=0, rows=None):
         """tail_from (0 = off): from that decoder step on, the rows still live continue in ONE launch of the persistent row-tile kernel
         (fcl_decoder_io_t.tail_from): set it to where the slack of `lmax` begins -- steps nobody reaches then cost one launch instead of three each."""
         self.lmax, self.frames = int(lmax), int(frames)
         self.bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.int32))
         self.tail_from = int(tail_from) if 0 < int(tail_from) < self.lmax else 0
+        self.rows = int(rows) if rows is not None else None
+        assert self.rows is None or self.rows > 0
         assert self.bounds.shape == (self.lmax,) and self.lmax > 0 and self.frames > 0
 
     @staticmethod
@@ -156,13 +162,14 @@ class Caps(object):
     @staticmethod
     def for_batches(host_maps, slack_steps=0, frame_round=256):
         """Exact capacities of a KNOWN set of batches (their host-built maps): steps = the longest duration (+ slack_steps), frames = the largest
-        total rounded up to `frame_round`, per-step row bounds = the maximum over the batches.  This is the best case -- what bench.py's headline
+        total rounded up to `frame_round`, per-step row bounds and phoneme rows = the maximum over the batches.  This is the best case -- what bench.py's headline
         line uses for the four batches it feeds; a driver that cannot know its batches in advance calibrates with slack (batching._grown_caps)."""
         lmax = max(m.lmax for m in host_maps) + int(slack_steps)
         bounds = np.ones(lmax, dtype=np.int32)
         for m in host_maps:
             bounds[: m.lmax] = np.maximum(bounds[: m.lmax], m.live_rows)
-        return Caps(lmax, (max(m.n_frames for m in host_maps) + frame_round - 1) // frame_round * frame_round, bounds)
+        return Caps(lmax, (max(m.n_frames for m in host_maps) + frame_round - 1) // frame_round * frame_round, bounds,
+                    rows=max(int(m.src_rows.shape[0]) for m in host_maps))
 
     @staticmethod
     def generous(n_rows, lmax, frames):
@@ -199,6 +206,11 @@ import os as _os
 _GROUP_PREDICTORS = _os.environ.get("FCL_PRED_GROUP", "1") not in ("", "0")  # 0: one launch per predictor and layer (rounds 1-2)
 # 0: the variance embedding as its own launch over all padded rows, then the gather of the decoder's rows (rounds 1-9)
 _VAR_EMBED_ROWS = _os.environ.get("FCL_VAR_EMBED_ROWS", "1") not in ("", "0")
+
+
+def compact_rows_enabled():
+    """FCL_COMPACT_ROWS (default on; read when a BatchRunner is built): 0 = every capacity pass on the padded [batch, t_cap] rows, whatever caps.rows says."""
+    return _os.environ.get("FCL_COMPACT_ROWS", "1") not in ("", "0")
 
 
 def _ring():
@@ -299,21 +311,29 @@ def encode(plan, prep, bilstm_algo=0, planes=False, row_maps=None):
     bl = plan.blstm
     res = plan.hp.use_residual  # convs[i](xs) + xs (encoder_sa_kd.py:213-214): the residual rides in the conv's epilogue (after ReLU), fp32 kept for it
     convs, tabs = plan.enc_convs, getattr(plan, "embed_conv_tables", None)
+    n_rows = getattr(prep, "n_rows", None)  # compact rows: the launches are sized by it, the tiles behind the batch's own total are skipped
+    m_dev = prep.rows_total if n_rows is not None else None
     if tabs is not None:  # embedding + first convolution: k rows of a plan-time table summed per output row (plan.py; FCL_EMBED_CONV_TABLE=0: off)
         x, xp = ops.embed_conv_table(prep.ids, tabs, convs[0].bias, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual_table=plan.embed if res else None,
-                                     want_f32=res or not planes, want_planes=planes)
+                                     want_f32=res or not planes, want_planes=planes, m_dev=m_dev)
         convs = convs[1:]
     if planes:  # every GEMM operand travels pre-split: embedding -> planes, conv -> planes, ..., BiLSTM -> fp32 + planes
         if tabs is None:
             x, xp = ops.embedding(prep.ids, plan.embed, want_f32=res, want_planes=True)
         for cv in convs:
-            x, xp = ops.conv1d_planes(xp, cv, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual=x if res else None, want_f32=res)
+            x, xp = ops.conv1d_planes(xp, cv, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual=x if res else None, want_f32=res, m_dev=m_dev)
+        if n_rows is not None:
+            return ops.bilstm_rows(None, prep.lens_dev, prep.utt_row0, bl["w_ih_f"], bl["w_hh_f"], bl["b_f"], bl["w_ih_r"], bl["w_hh_r"], bl["b_r"], prep.B,
+                                   n_rows, x_p=xp, w_ih_p=(bl["w_ih_p_f"], bl["w_ih_p_r"]), want_planes=True, row_maps=row_maps)
         return ops.bilstm(None, prep.lens_dev, bl["w_ih_f"], bl["w_hh_f"], bl["b_f"], bl["w_ih_r"], bl["w_hh_r"], bl["b_r"], prep.B, prep.T, bilstm_algo,
                           x_p=xp, w_ih_p=(bl["w_ih_p_f"], bl["w_ih_p_r"]), want_planes=True, row_maps=row_maps)
     if tabs is None:
         x = ops.embedding(prep.ids, plan.embed)
     for cv in convs:
         x = ops.conv1d(x, cv.wp, cv.bias, prep.seg_lo, prep.seg_hi, ops.ACT_RELU, residual=x if res else None)
+    if n_rows is not None:  # (BatchRunner takes the compact layout for one-layer encoders only)
+        return ops.bilstm_rows(x, prep.lens_dev, prep.utt_row0, bl["w_ih_f"], bl["w_hh_f"], bl["b_f"], bl["w_ih_r"], bl["w_hh_r"], bl["b_r"], prep.B, n_rows,
+                               row_maps=row_maps)
     for i, bl in enumerate(plan.blstm_layers):  # (`elayers` > 1: the stacked layers run one after the other; use_planes() is off for them)
         x = ops.bilstm(x, prep.lens_dev, bl["w_ih_f"], bl["w_hh_f"], bl["b_f"], bl["w_ih_r"], bl["w_hh_r"], bl["b_r"], prep.B, prep.T, bilstm_algo,
                        row_maps=row_maps if i == 0 else None)
@@ -343,8 +363,14 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
         planes = use_planes(plan)
         hs_p = None
         maps_req = None
+        # the row universe of the front end and of the device-built maps: the padded [B, T] layout, or a BatchRunner's compact rows (utterance b at
+        # utt_row0[b]; the rows behind the batch's total are padding rows with an empty segment, which sort last like the padded tails do)
+        n_univ = getattr(prep, "n_rows", None)
+        utt_row0 = prep.utt_row0 if n_univ is not None else None
+        if n_univ is None:
+            n_univ = prep.B * prep.T
         if prep.maps is None and prep.dur_pad is not None and caps is not None:  # forced durations, device-built maps: nothing to wait for
-            maps_req = ops.row_maps_request(prep.B * prep.T, prep.B, caps.lmax, caps.frames, dur_i32=prep.dur_pad, t_max=prep.T, pad=prep.pad,
+            maps_req = ops.row_maps_request(n_univ, prep.B, caps.lmax, caps.frames, dur_i32=prep.dur_pad, utt_row0=utt_row0, t_max=prep.T, pad=prep.pad,
                                             status=status)
         if planes:
             hs, hs_p = encode(plan, prep, bilstm_algo, planes=True, row_maps=maps_req)
@@ -356,13 +382,14 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
         if hp.spk_embed_dim is not None:  # hs <- cat[hs, F.normalize(spemb)]: predictors, embeddings and decoder see eunits + spk_embed_dim channels
             if getattr(prep, "spk", None) is None:
                 raise ValueError("fcl-taco2_amd: this pass needs speaker embeddings (prepare(..., spembs=...))")
+            assert utt_row0 is None, "concat_spk finds the utterance as row // T: speaker models keep the padded layout"
             hs, hs_p = ops.concat_spk(hs, prep.spk, prep.T, want_f32=True, want_planes=planes)
         rm = prep  # holder of the row maps
         frames_info = None
         ctl = getattr(prep, "ctl", None)  # prosody controls [B * T, 5] (None: the uncontrolled kernels, exactly)
         # the predictors share one geometry in the shipped recipes: one launch per layer for all of them (plan.PredictorGroup) instead of one each
         grouped = planes and prep.f0e is None and _GROUP_PREDICTORS
-        m_rows = prep.B * prep.T
+        m_rows = n_univ
         p = e = None
         if prep.maps is None:  # maps depend on durations that live in HBM: predicted by this pass, or forced and uploaded
             d_int = None
@@ -377,9 +404,9 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
                     d_int = ops.duration_round(d_log, False, 1.0, prep.pad)
                 if inter is not None:
                     inter["d_log"], inter["d_int"] = d_log, d_int
-            if caps is not None:  # device-built maps over the padded [B, T] row universe: no host round trip
-                dm = maps_req.maps if maps_req is not None else ops.row_maps_build(prep.B * prep.T, prep.B, caps.lmax, caps.frames, dur_i64=d_int,
-                                                                                   t_max=prep.T, pad=prep.pad, status=status)
+            if caps is not None:  # device-built maps over the padded [B, T] (or the compact) row universe: no host round trip
+                dm = maps_req.maps if maps_req is not None else ops.row_maps_build(n_univ, prep.B, caps.lmax, caps.frames, dur_i64=d_int,
+                                                                                   utt_row0=utt_row0, t_max=prep.T, pad=prep.pad, status=status)
                 rm = PreparedBatch()
                 rm.maps = _DevMaps(dm, caps)
                 rm.src_rows, rm.dur, rm.frame_off, rm.frame_lo, rm.frame_hi = dm["src_rows"], dm["dur"], dm["frame_off"], dm["frame_lo"], dm["frame_hi"]
@@ -387,6 +414,7 @@ def run(plan, prep, dropout_mode=ops.DROP_RNG, prenet_keep=None, seed=0, bilstm_
             else:
                 if d_int is None:
                     raise ValueError("prepare(device_maps=True) leaves the row maps to the device: run() needs caps")
+                assert utt_row0 is None, "compact rows come with capacities (BatchRunner)"
                 d_host = d_int.cpu().numpy().reshape(prep.B, prep.T)  # the one host sync of the predicted-duration path
                 rm = PreparedBatch()
                 _upload_maps(rm, build_row_maps(prep.lens, [d_host[b, : prep.lens[b]] for b in range(prep.B)], prep.T, hp.reduction_factor), dev)
@@ -611,7 +639,9 @@ class BatchRunner(object):
     decoder_sa_kd.py:736-791) -- and this build's own numpy row maps run on the device inside the graph (ops.row_maps_build over the padded
     [batch, t_cap] row universe), with predicted OR forced durations.  Nothing about the durations is known to the host until it reads the mels
     back (`frames()`): capacities are verified on the device (FCL_STATUS_*), a batch that does not fit is reported, never silently truncated.
-    forced=True: the graph takes uploaded durations (load(xs, durs)); forced=False: it contains the duration predictor + rounding."""
+    forced=True: the graph takes uploaded durations (load(xs, durs)); forced=False: it contains the duration predictor + rounding.
+    caps.rows (below batch * t_cap; FCL_COMPACT_ROWS=0: ignored): the row universe is `rows` compact phoneme rows, the utterances back to back, instead
+    of the padded one (self.R; one-layer H = 128 encoders without speaker embeddings) -- same results, every front-end launch smaller."""
 
     def __init__(self, plan, batch, t_cap, caps, forced=True, stream=None, dropout_mode=ops.DROP_RNG, seed=0, depth=3, pack_outputs=False, mempool=None,
                  controls=False, tail=None):
@@ -630,27 +660,17 @@ class BatchRunner(object):
         self.plan, self.B, self.T, self.caps, self.forced = plan, int(batch), int(t_cap), caps, bool(forced)
         self.S = int(plan.hp.spk_embed_dim or 0)  # speaker-embedding width: one vector per utterance rides in the same block
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        n = self.B * self.T
-        # one byte block: ids int64 [n] | seg_lo, seg_hi int32 [n] each | dur int32 [n] | lens int32 [B, padded to 4] | pad uint8 [n]
-        self._off = {}
-        off = 0
-        for name, nbytes in (("ids", 8 * n), ("seg_lo", 4 * n), ("seg_hi", 4 * n), ("dur", 4 * n), ("lens", 4 * ((self.B + 3) // 4 * 4)), ("pad", n),
-                             ("spk", 4 * self.B * self.S), ("ctl", 4 * n * _prosody.NCTL if self.controls else 0)):
-            self._off[name] = (off, nbytes)
-            off += (nbytes + 15) // 16 * 16
-        self._nbytes = off
-        # the feed: by default the graph's FIRST NODE pulls the packed block out of pinned host memory (ops.feed_copy: no copy call per pass, the
-        # host waits for the sequence number of its last launch before it repacks the block); FCL_FEED_INGRAPH=0 = one hipMemcpyAsync per pass
-        # out of `depth` rotating staging buffers in front of the launch (the form of the first half of round 3)
-        self._ingraph = os.environ.get("FCL_FEED_INGRAPH", "1") not in ("", "0")
-        self._host = [torch.zeros(off, dtype=torch.uint8).pin_memory() for _ in range(1 if self._ingraph else depth)]
-        self._host_ev = [None] * len(self._host)
-        self._slot = 0
-        self._launched = 0
-        self._seq_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        self._seq_np = self._seq_host.numpy()
-        rows = np.arange(n, dtype=np.int32)
-        self._rows = (rows // self.T, rows - (rows // self.T) * self.T, ((rows // self.T) * self.T).astype(np.int32))
+        # compact rows (caps.rows; FCL_COMPACT_ROWS=0: off): the utterances lie back to back in a universe of caps.rows rows instead of batch * t_cap,
+        # and every front-end launch, the row maps and the decoder are sized by it.  The BiLSTM's rows form covers the shipped one-layer H = 128
+        # encoder; concat_spk finds the utterance as row // t_cap, so speaker models keep the padded layout.
+        rows = None
+        if (compact_rows_enabled() and caps.rows is not None and self.B <= caps.rows < self.B * self.T and not self.S and plan.hp.elayers == 1
+                and not getattr(plan, "generic_decoder", False) and int(plan.blstm["w_hh_f"].shape[1]) == 128):
+            rows = int(caps.rows)
+        self._host_init(rows, depth)
+        if self.R is not None:  # the decoder has R rows: no step's bound may ask for more
+            caps = self.caps = Caps(caps.lmax, caps.frames, np.minimum(caps.bounds, self.R), caps.tail_from, self.R)
+        n, off = self.R if self.R is not None else self.B * self.T, self._nbytes
         with torch.cuda.device(dev):
             self._dev = torch.zeros(off, dtype=torch.uint8, device=dev)
             view = lambda name, dt: self._dev[self._off[name][0] : self._off[name][0] + self._off[name][1]].view(dt)
@@ -662,6 +682,9 @@ class BatchRunner(object):
             p.f0e, p.maps = None, None
             p.spk = view("spk", torch.float32).view(self.B, self.S) if self.S else None
             p.ctl = view("ctl", torch.float32).view(n, _prosody.NCTL) if self.controls else None
+            if self.R is not None:
+                p.n_rows = self.R
+                p.utt_row0, p.rows_total = view("row0", torch.int32)[: self.B + 1], view("row0", torch.int32)[self.B + 1 : self.B + 2]
             self.prep = p
             self.seed_word = torch.zeros(1, dtype=torch.int32, device=dev)
             self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # this runner's own status word (violations are attributed to ITS batches)
@@ -676,7 +699,7 @@ class BatchRunner(object):
             # the kernel forms THIS geometry selects: once per (plan, geometry) -- the other runners of a bucket (the decode driver keeps one per
             # stream) capture straight away (round 5: 16 warm-ups of a first decode() call -> 4)
             warm_key = (self.B, self.T, caps.lmax, caps.frames, caps.bounds.tobytes(), caps.tail_from, self.forced, int(dropout_mode), self.S,
-                        self.controls)
+                        self.controls, self.R)
             warmed = plan.__dict__.setdefault("_runner_warm", set())
             if warm_key not in warmed:
                 with torch.cuda.stream(self.stream):
@@ -706,6 +729,36 @@ class BatchRunner(object):
                     self.out[:n].view_as(self.mel).copy_(self.mel)
                     self.out[n : n + b1].view(torch.int32).copy_(self._frames.utt_frame0[:b1])
                     self.out[n + b1 : n + b1 + 1].view(torch.int32).copy_(self.status)
+        self.n_loaded = 0
+
+    def _host_init(self, rows, depth, pin=True):
+        """The host side of the feed: the block's layout (self.R = `rows`: compact rows, None: the padded layout), the staging buffers load() packs
+        and the launch counters.  Needs B, T, S, controls; no device call with pin=False (the packing is then testable without one)."""
+        self.R = rows
+        n = self.R if self.R is not None else self.B * self.T
+        # one byte block: ids int64 [n] | seg_lo, seg_hi int32 [n] each | dur int32 [n] | lens int32 [B, padded to 4] | pad uint8 [n]
+        # (compact rows: + utt_row0 int32 [B + 1] and the batch's row total, one word behind it)
+        self._off = {}
+        off = 0
+        for name, nbytes in (("ids", 8 * n), ("seg_lo", 4 * n), ("seg_hi", 4 * n), ("dur", 4 * n), ("lens", 4 * ((self.B + 3) // 4 * 4)), ("pad", n),
+                             ("spk", 4 * self.B * self.S), ("ctl", 4 * n * _prosody.NCTL if self.controls else 0),
+                             ("row0", 4 * (self.B + 2) if self.R is not None else 0)):
+            self._off[name] = (off, nbytes)
+            off += (nbytes + 15) // 16 * 16
+        self._nbytes = off
+        # the feed: by default the graph's FIRST NODE pulls the packed block out of pinned host memory (ops.feed_copy: no copy call per pass, the
+        # host waits for the sequence number of its last launch before it repacks the block); FCL_FEED_INGRAPH=0 = one hipMemcpyAsync per pass
+        # out of `depth` rotating staging buffers in front of the launch (the form of the first half of round 3)
+        self._ingraph = os.environ.get("FCL_FEED_INGRAPH", "1") not in ("", "0")
+        pinned = (lambda t: t.pin_memory()) if pin else (lambda t: t)
+        self._host = [pinned(torch.zeros(off, dtype=torch.uint8)) for _ in range(1 if self._ingraph else depth)]
+        self._host_ev = [None] * len(self._host)
+        self._slot = 0
+        self._launched = 0
+        self._seq_host = pinned(torch.zeros(4, dtype=torch.int32))
+        self._seq_np = self._seq_host.numpy()
+        rows = np.arange(self.B * self.T, dtype=np.int32)  # (the padded layout's row -> utterance, position, base tables; the compact pack needs none)
+        self._rows = (rows // self.T, rows - (rows // self.T) * self.T, ((rows // self.T) * self.T).astype(np.int32))
         self.n_loaded = 0
 
     def _feed(self, bump):
@@ -748,6 +801,9 @@ class BatchRunner(object):
         ln = np.fromiter((x.shape[0] for x in xs), np.int32, nb)
         if int(ln.max()) > T or int(ln.min()) < 1:
             raise ValueError("BatchRunner: utterances of %d..%d phonemes, capacity %d" % (int(ln.min()), int(ln.max()), T))
+        total = int(ln.sum())
+        if self.R is not None and total > self.R:
+            raise ValueError("BatchRunner: %d phonemes in the batch, row capacity %d (caps.rows)" % (total, self.R))
         dcat = None
         if durs is not None:
             if len(durs) != nb or any(np.asarray(d).size != k for d, k in zip(durs, ln)):
@@ -770,6 +826,22 @@ class BatchRunner(object):
         ids, dur, lens = seg("ids", np.int64), seg("dur", np.int32), seg("lens", np.int32)
         lens[:nb] = ln
         lens[nb:] = 0
+        if self.R is not None:
+            self._pack_compact(seg, xs, ln, total, dcat, ctl_rows)
+        else:
+            self._pack_padded(seg, xs, nb, dcat, spk_rows, ctl_rows)
+        if not self._ingraph:
+            with torch.cuda.stream(self.stream):
+                self._dev.copy_(self._host[j], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+            self._host_ev[j] = ev
+        self.n_loaded = nb
+
+    def _pack_padded(self, seg, xs, nb, dcat, spk_rows, ctl_rows):
+        """The padded [B, T] block: utterance b at rows [b * T, b * T + len_b)."""
+        B, T, n = self.B, self.T, self.B * self.T
+        ids, dur, lens = seg("ids", np.int64), seg("dur", np.int32), seg("lens", np.int32)
         b_of, t_of, base = self._rows
         lfull = lens[:B][b_of]
         valid = t_of < lfull  # the non-padded rows, row-major: exactly the order of the concatenated utterances
@@ -791,13 +863,33 @@ class BatchRunner(object):
         seg("seg_lo", np.int32)[:] = base
         np.add(base, lfull, out=seg("seg_hi", np.int32))
         np.logical_not(valid, out=seg("pad", np.uint8).view(np.bool_))
-        if not self._ingraph:
-            with torch.cuda.stream(self.stream):
-                self._dev.copy_(self._host[j], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-            self._host_ev[j] = ev
-        self.n_loaded = nb
+
+    def _pack_compact(self, seg, xs, ln, total, dcat, ctl_rows):
+        """The compact block: utterance b at rows [row0[b], row0[b] + len_b), back to back; the rows from the batch's total up to the capacity are
+        PAD ids with an empty segment, duration 0 and pad = 1 (they sort behind every real row, like the padded layout's tails)."""
+        B, T, R, nb = self.B, self.T, self.R, ln.shape[0]
+        row0 = seg("row0", np.int32)
+        row0[0] = 0
+        np.cumsum(ln, out=row0[1 : nb + 1])
+        row0[nb + 1 :] = total  # utterances beyond the batch are empty; the last word is the row total the launches skip tiles by
+        ids, dur = seg("ids", np.int64), seg("dur", np.int32)
+        ids[:total] = np.concatenate(xs)
+        ids[total:] = 0
+        if dcat is not None:
+            dur[:total] = dcat
+            dur[total:] = 0
+        lo, hi, pad = seg("seg_lo", np.int32), seg("seg_hi", np.int32), seg("pad", np.uint8)
+        lo[:total] = np.repeat(row0[:nb], ln)
+        hi[:total] = np.repeat(row0[1 : nb + 1], ln)
+        lo[total:] = 0
+        hi[total:] = 0
+        pad[:total] = 0
+        pad[total:] = 1
+        if self.controls:
+            ctl = seg("ctl", np.float32).reshape(R, _prosody.NCTL)
+            ctl[:] = _prosody.IDENTITY
+            if ctl_rows is not None:  # prosody.pack gives the padded [nb * T, 5] rows: keep the real ones, in order
+                ctl[:total] = ctl_rows[(np.arange(T, dtype=np.int32)[None, :] < ln[:, None]).reshape(-1)]
 
     def replay(self):
         """Enqueue one pass over the loaded batch; returns the static mel buffer [caps.frames, odim] (rows past the batch's total are not valid)."""

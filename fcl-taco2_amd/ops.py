@@ -385,6 +385,29 @@ def bilstm(x, lens_i32, w_ih_f, w_hh_f, b_f, w_ih_r, w_hh_r, b_r, b, t, algo=0, 
     return (out, outp) if want_planes else out
 
 
+def bilstm_rows(x, lens_i32, utt_row0_i32, w_ih_f, w_hh_f, b_f, w_ih_r, w_hh_r, b_r, b, n_rows, x_p=None, w_ih_p=None, want_planes=False, row_maps=None,
+                out=None, out_p=None):
+    """fcl_bilstm_rows_fwd: the synthesis BiLSTM (H = 128) over compact rows -- utterance i owns rows [utt_row0[i], utt_row0[i] + lens[i]) of the
+    [n_rows, .] input and output, rows from utt_row0[b] on come back zero.  Other arguments as bilstm(); row_maps: a RowMapsRequest over the same
+    compact universe (n = n_rows, utt_row0).  out / out_p: the caller's buffers of at least n_rows rows (default: fresh ones)."""
+    c, dev = w_ih_f.shape[1], w_ih_f.device
+    h = w_hh_f.shape[1]
+    lib = _lib.load()
+    assert utt_row0_i32.numel() >= b + 1 and lens_i32.numel() >= b
+    nbytes = lib.fcl_bilstm_rows_workspace_bytes(n_rows, h)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty(n_rows, 2 * h, device=dev, dtype=torch.float32)
+    outp = out_p if out_p is not None else (planes_empty(n_rows, 2 * h, dev) if want_planes else None)
+    assert out.shape[0] >= n_rows and out.shape[1] == 2 * h and (outp is None or outp.shape[0] >= n_rows)
+    wf_p, wr_p = w_ih_p if (x_p is not None and w_ih_p is not None) else (None, None)
+    check(lib.fcl_bilstm_rows_fwd(_p(x), _p(lens_i32, torch.int32), _p(utt_row0_i32, torch.int32), _p(w_ih_f), _p(w_hh_f), _p(b_f), _p(w_ih_r), _p(w_hh_r),
+                                  _p(b_r), _p(out), _p(outp, torch.int16), _p(x_p if wf_p is not None else None, torch.int16), _p(wf_p, torch.int16),
+                                  _p(wr_p, torch.int16), b, n_rows, c, h, ws.data_ptr(), nbytes,
+                                  C.byref(row_maps.struct) if row_maps is not None else None, _stream()))
+    return (out, outp) if (want_planes or out_p is not None) else out
+
+
 def masked_l1_mse(a, b, row_valid, out_f64, b_log_offset=None):
     """Accumulate sum|a-b'|, sum(a-b')^2, count into out_f64[0:3] (device float64, caller-zeroed)."""
     m, c = a.shape

@@ -182,6 +182,12 @@ def synthesize(model, gen, utts, outdir, rate, batch_size=32, seed=137, prosody=
                     for sl in b.slots:
                         sl["free"].set()
                 r = b.runner
+                if r.R is not None and n_ph > r.R:  # more phonemes than the bucket's compact rows hold: handled like a capacity the device reports
+                    counts["redone_batches"] += 1
+                    logging.info("batch %d: %d phonemes, row capacity %d -- redone through the two-step route", k, n_ph, r.R)
+                    got, b.grow = two_step(chunk, k)
+                    samples += got
+                    continue
                 slot = b.slots[b.next % 2]
                 b.next += 1
                 for it in take(pending, lambda p: p[2] is slot):  # this landing area's previous batch

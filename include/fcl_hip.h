@@ -255,6 +255,17 @@ int fcl_bilstm_fwd(const float* x, const int32_t* lens, const float* w_ih_f, con
                    const float* w_ih_r, const float* w_hh_r, const float* b_r, float* out, uint16_t* out_p, const uint16_t* x_p,
                    const uint16_t* w_ih_f_p, const uint16_t* w_ih_r_p, int b, int t, int c, int h,
                    int algo, void* workspace, size_t workspace_bytes, uint32_t* status, const struct fcl_row_maps* row_maps, fcl_stream_t stream);
+/* The same layer over COMPACT rows (capacity passes of synthesis: engine.Caps.rows): utterance b owns rows [utt_row0[b], utt_row0[b] + lens[b]) of
+ * x [n_rows, C] and out [n_rows, 2H]; utt_row0 [B + 1] int32 (device), utt_row0[B] = the batch's row total <= n_rows.  The input projections run with
+ * M = n_rows; every recurrence workgroup reads its row base once in place of b * T; rows [utt_row0[B], n_rows) of out / out_p are zeroed (they take
+ * the place of the padded tails).  A row range that would pass n_rows is cut there.  H = 128 only, fp32 or pre-split operands as above; other H,
+ * stacked layers and training keep the padded entry.  row_maps: the same compact universe (n = n_rows, utt_row0, row_src == NULL); built by one more
+ * workgroup of the recurrence's launch when the counting-sort form applies, by fcl_row_maps_build's launches otherwise. */
+size_t fcl_bilstm_rows_workspace_bytes(int n_rows, int h);
+int fcl_bilstm_rows_fwd(const float* x, const int32_t* lens, const int32_t* utt_row0, const float* w_ih_f, const float* w_hh_f, const float* b_f,
+                        const float* w_ih_r, const float* w_hh_r, const float* b_r, float* out, uint16_t* out_p, const uint16_t* x_p,
+                        const uint16_t* w_ih_f_p, const uint16_t* w_ih_r_p, int b, int n_rows, int c, int h, void* workspace, size_t workspace_bytes,
+                        const struct fcl_row_maps* row_maps, fcl_stream_t stream);
 
 /* ---- H7 as a single step: one LSTMCell (+ zoneout) update of M rows — the building block of the decoder loop, of the per-step
  *      BiLSTM, and of the TRAINING forward, which also saves what the backward pass needs (decoder_sa.py:63-96, 500-504) ------ */
