@@ -159,6 +159,12 @@ class PwdLayer(C.Structure):  # fcl_pwd_t
         (n, _P) for n in ("x", "w", "bias", "h", "g", "seg_lo", "seg_hi", "y", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
 
 
+class PwtBlock(C.Structure):  # fcl_pwt_t
+    _fields_ = [("samples", C.c_int64)] + [(n, C.c_int32) for n in ("residual", "aux", "ksize", "dilation", "first", "last")] + [
+        (n, _P) for n in ("seg_lo", "seg_hi", "x", "c", "w_gate", "b_gate", "w_out", "b_out", "ab", "x_out", "skips", "z_out", "dxo", "ds", "w_dz", "w_dx",
+                          "w_dc", "dz", "dx", "dc", "dw_gate", "db_gate", "dw_out", "db_out", "workspace")] + [("workspace_bytes", _Z)]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -344,6 +350,10 @@ SIGNATURES = {
     "fcl_pwd_layer_fwd": (_I, [C.POINTER(PwdLayer), _P]),
     "fcl_pwd_layer_dx": (_I, [C.POINTER(PwdLayer), _P]),
     "fcl_pwd_layer_dw": (_I, [C.POINTER(PwdLayer), _P]),
+    "fcl_pwt_dw_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I]),
+    "fcl_pwt_block_fwd": (_I, [C.POINTER(PwtBlock), _P]),
+    "fcl_pwt_block_dx": (_I, [C.POINTER(PwtBlock), _P]),
+    "fcl_pwt_block_dw": (_I, [C.POINTER(PwtBlock), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

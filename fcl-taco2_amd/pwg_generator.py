@@ -1,0 +1,384 @@
+"""The Parallel WaveGAN generator in its training form: the residual stack forward (activations kept) and backward on the HIP path (the pwt_* kernels of
+csrc/pwg_train.hip), under an nn.Module with the parallel_wavegan package's constructor arguments and parameter names.
+
+    gen = TrainableParallelWaveGANGenerator().to("cuda:0")
+    fake = gen(z, c)                     # z [B, 1, T] noise, c [B, aux, T / hop + 2 ctx] features (replicate-padded) -> [B, 1, T]
+    loss(fake).backward()                # the 30 residual blocks run backward in HIP kernels; the small layers around them are torch's
+    vocoder.PWGPlan(gen.state_dict(), "cuda:0")   # the inference generator takes the trained weights as they are
+
+The block's contract is stated in include/fcl_hip.h "Parallel WaveGAN generator, training form" and restated in float64 numpy in tests/pwgt_ref.py; the
+forward pass is oracle/pwg_oracle.generator_forward.  Activations are float32, channel-last [samples, C], the batch packed with the utterances back to
+back; per block the input x_l [samples, R] and the gate activations ab_l = (tanh | sigmoid) [samples, 2 R] are kept.  One arithmetic mode (exact fp32).
+The upsampling network, first_conv, the sqrt(1 / layers) scale and the two last ReLU + 1x1 layers are torch operations under autograd.  No CPU fallback."""
+import ctypes as C
+import math
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib, ops
+from .pwg_discriminator import Maps  # the packed batch's seg_lo / seg_hi
+
+KERNEL_SIZES = (3, 5)
+BLOCK_PARAMS = ("conv.weight", "conv.bias", "conv1x1_aux.weight", "conv1x1_out.weight", "conv1x1_out.bias", "conv1x1_skip.weight", "conv1x1_skip.bias")
+FWD_KERNELS = ("pwt_gate_kernel", "pwt_out_kernel")
+DZ_KERNEL, DX_KERNEL, DC_KERNEL = "pwt_dz_kernel", "pwt_dx_kernel", "pwt_dc_kernel"
+DW_KERNELS = ("pwt_dw_kernel<gate>", "pwt_dw_kernel<out>", "pwt_dw_reduce_kernel")
+DEFAULT_UPSAMPLE = {"upsample_scales": [4, 4, 4, 4]}
+
+
+def check_configuration(in_channels=1, out_channels=1, kernel_size=3, layers=30, stacks=3, residual_channels=64, gate_channels=128, skip_channels=64,
+                        aux_channels=80, aux_context_window=2, dropout=0.0, bias=True, use_weight_norm=True, use_causal_conv=False,
+                        upsample_conditional_features=True, upsample_net="ConvInUpsampleNetwork", upsample_params=None):
+    """-> the dilation of every block; anything the kernels do not cover is refused by the argument's name"""
+    bad = lambda name, got, want: ValueError("fcl-taco2_amd: PWG generator: %s=%r is not supported on the HIP path (%s)" % (name, got, want))
+    if in_channels != 1:
+        raise bad("in_channels", in_channels, "1")
+    if out_channels != 1:
+        raise bad("out_channels", out_channels, "1")
+    if kernel_size not in KERNEL_SIZES:
+        raise bad("kernel_size", kernel_size, "3 or 5")
+    if not (isinstance(layers, int) and 1 <= layers <= 60):
+        raise bad("layers", layers, "1 to 60")
+    if not (isinstance(stacks, int) and stacks >= 1 and layers % stacks == 0):
+        raise bad("stacks", stacks, "a divisor of layers")
+    if not (isinstance(residual_channels, int) and 16 <= residual_channels <= 64 and residual_channels % 16 == 0):
+        raise bad("residual_channels", residual_channels, "a multiple of 16 from 16 to 64")
+    if gate_channels != 2 * residual_channels:
+        raise bad("gate_channels", gate_channels, "2 x residual_channels")
+    if skip_channels != residual_channels:
+        raise bad("skip_channels", skip_channels, "residual_channels")
+    if not (isinstance(aux_channels, int) and 16 <= aux_channels <= 128 and aux_channels % 16 == 0):
+        raise bad("aux_channels", aux_channels, "a multiple of 16 from 16 to 128")
+    if not (isinstance(aux_context_window, int) and aux_context_window >= 0):
+        raise bad("aux_context_window", aux_context_window, "an integer >= 0")
+    if float(dropout) != 0.0:
+        raise bad("dropout", dropout, "0")
+    if bias is not True:
+        raise bad("bias", bias, "True")
+    if use_weight_norm not in (True, False):
+        raise bad("use_weight_norm", use_weight_norm, "True or False")
+    if use_causal_conv:
+        raise bad("use_causal_conv", use_causal_conv, "False")
+    if not upsample_conditional_features:
+        raise bad("upsample_conditional_features", upsample_conditional_features, "True")
+    if upsample_net != "ConvInUpsampleNetwork":
+        raise bad("upsample_net", upsample_net, "ConvInUpsampleNetwork")
+    params = dict(DEFAULT_UPSAMPLE if upsample_params is None else upsample_params)
+    scales = params.pop("upsample_scales", None)
+    if params or not scales or any(not (isinstance(s, int) and s >= 1) for s in scales):
+        raise bad("upsample_params", upsample_params, "upsample_scales: a list of positive integers, nothing else")
+    per = layers // stacks
+    if per > 31:
+        raise bad("stacks", stacks, "layers / stacks at most 31: a dilation below 2^31")
+    return [2 ** (l % per) for l in range(layers)]
+
+
+class GeneratorPlan(object):
+    """Per-block geometry (the dilations) and the sizes of what a pass over n samples needs"""
+
+    def __init__(self, device="cuda:0", **config):
+        self.dilations = check_configuration(**config)
+        cfg = dict(kernel_size=3, layers=30, stacks=3, residual_channels=64, aux_channels=80)
+        cfg.update({k: v for k, v in config.items() if k in cfg})
+        self.kernel_size, self.layers, self.stacks, self.R, self.A = (cfg[k] for k in ("kernel_size", "layers", "stacks", "residual_channels", "aux_channels"))
+        if not str(device).startswith("cuda"):
+            raise _lib.FclError("fcl-taco2_amd: GeneratorPlan needs a GPU device (no CPU fallback)")
+        self.device = torch.device(device)
+        self.receptive_field = 1 + (self.kernel_size - 1) * sum(self.dilations)
+
+    def kept_shapes(self, n):
+        """what the forward pass keeps: x_0 .. x_layers [n, R] (x_layers, the last block's output, is read by nobody) and ab_0 .. ab_{layers - 1} [n, 2 R]"""
+        return [(n, self.R)] * (self.layers + 1), [(n, 2 * self.R)] * self.layers
+
+    def kept_bytes(self, n):
+        return 4 * n * 3 * self.R * self.layers
+
+    def workspace_floats(self, n):
+        """the partials of a block's larger weight gradient"""
+        return _lib.load().fcl_pwt_dw_workspace_bytes(n, self.R, self.A, self.kernel_size) // 4
+
+    def dweight_shapes(self):
+        """per block (dw_gate [k R + A, 2 R], db_gate [2 R], dw_out [R, 2 R], db_out [2 R]) in the kernels' layout"""
+        R = self.R
+        return ((self.kernel_size * R + self.A, 2 * R), (2 * R,), (R, 2 * R), (2 * R,))
+
+
+def pack_weights(blocks):
+    """per block the seven torch parameters in BLOCK_PARAMS order -> dict of the kernels' forms (include/fcl_hip.h), contiguous float32.  The backward
+    forms are permutations of the forward ones; nothing here is differentiated."""
+    out = []
+    for conv_w, conv_b, aux_w, out_w, out_b, skip_w, skip_b in blocks:
+        f = lambda v: v.detach().to(torch.float32)
+        conv_w, aux_w, out_w, skip_w = f(conv_w), f(aux_w)[:, :, 0], f(out_w)[:, :, 0], f(skip_w)[:, :, 0]
+        G, R, k = conv_w.shape
+        out.append(dict(
+            w_gate=torch.cat([conv_w.permute(2, 1, 0).reshape(k * R, G), aux_w.t()]).contiguous(), b_gate=f(conv_b).contiguous(),
+            w_out=torch.cat([out_w.t(), skip_w.t()], dim=1).contiguous(), b_out=torch.cat([f(out_b), f(skip_b)]).contiguous(),
+            w_dz=torch.cat([out_w, skip_w]).contiguous(), w_dx=conv_w.flip(2).permute(2, 0, 1).contiguous(), w_dc=aux_w.contiguous()))
+    return out
+
+
+def unpack_dweights(plan, dw_gate, db_gate, dw_out, db_out):
+    """the kernels' gradient forms of one block -> torch's, in BLOCK_PARAMS order"""
+    R, k = plan.R, plan.kernel_size
+    return (dw_gate[: k * R].reshape(k, R, 2 * R).permute(2, 1, 0).contiguous(), db_gate, dw_gate[k * R :].t().unsqueeze(2).contiguous(),
+            dw_out[:, :R].t().unsqueeze(2).contiguous(), db_out[:R].contiguous(), dw_out[:, R:].t().unsqueeze(2).contiguous(), db_out[R:].contiguous())
+
+
+def _args(plan, maps, block, first=False, last=False, **ptr):
+    a = _lib.PwtBlock()
+    a.samples, a.residual, a.aux, a.ksize, a.dilation = maps.samples, plan.R, plan.A, plan.kernel_size, plan.dilations[block]
+    a.first, a.last = int(first), int(last)
+    a.seg_lo, a.seg_hi = maps.seg_lo.data_ptr(), maps.seg_hi.data_ptr()
+    for k, v in ptr.items():
+        if v is not None:
+            setattr(a, k, v.data_ptr())
+    return a
+
+
+# on caller-owned buffers (the tests surround them with guard zones)
+def launch_forward(plan, maps, c, weights, xs, abs_, skips, z_outs=None):
+    """xs[0] [samples, R] the stack's input, c [samples, A], weights from pack_weights -> xs[1 ..], abs_[l] (plan.kept_shapes) and skips [samples, R],
+    the un-scaled skip sum (written by block 0, added to by the others).  z_outs (tests): per block a [samples, 2 R] buffer for the pre-activations."""
+    lib, st = _lib.load(), ops._stream()
+    for l, w in enumerate(weights):
+        a = _args(plan, maps, l, first=l == 0, x=xs[l], c=c, w_gate=w["w_gate"], b_gate=w["b_gate"], w_out=w["w_out"], b_out=w["b_out"], ab=abs_[l],
+                  x_out=xs[l + 1], skips=skips, z_out=None if z_outs is None else z_outs[l])
+        _lib.check(lib.fcl_pwt_block_fwd(C.byref(a), st))
+
+
+def launch_backward(plan, maps, ds, c, weights, xs, abs_, dx0, dc, dweights, grads, dz, workspace=None):
+    """ds [samples, R], the gradient of the un-scaled skip sum -> dx0 [samples, R] (None: block 0's conv-backward is not launched), dc [samples, A]
+    (None: no aux-backward is launched; written by the last block, added to by the others) and dweights = per block (dw_gate, db_gate, dw_out, db_out)
+    (plan.dweight_shapes; None: no weight-gradient kernel is launched).  grads: two [samples, R] buffers, dz: one [samples, 2 R] buffer, workspace:
+    plan.workspace_floats(samples) floats (needed with dweights)."""
+    lib, st = _lib.load(), ops._stream()
+    g = None
+    for l in range(plan.layers - 1, -1, -1):
+        w, last = weights[l], l == plan.layers - 1
+        out = grads[l & 1] if l > 0 else dx0
+        a = _args(plan, maps, l, last=last, x=xs[l], c=c, ab=abs_[l], dxo=g, ds=ds, w_dz=w["w_dz"], w_dx=w["w_dx"], w_dc=w["w_dc"], dz=dz, dx=out, dc=dc)
+        _lib.check(lib.fcl_pwt_block_dx(C.byref(a), st))
+        if dweights is not None:
+            a.dw_gate, a.db_gate, a.dw_out, a.db_out = (b.data_ptr() for b in dweights[l])
+            a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
+            _lib.check(lib.fcl_pwt_block_dw(C.byref(a), st))
+        g = out
+
+
+class _Function(torch.autograd.Function):
+    """the un-scaled skip sum [samples, R] of the residual stack on x_0 [samples, R], c [samples, A] and the blocks' plain weights (BLOCK_PARAMS order,
+    block by block); backward gives the gradients of all of them that are asked for"""
+
+    @staticmethod
+    def forward(ctx, plan, maps, x0, c, *params):
+        dev, n = plan.device, maps.samples
+        blocks = [params[7 * l : 7 * l + 7] for l in range(plan.layers)]
+        with torch.cuda.device(dev):
+            new = lambda s: torch.empty(s, device=dev, dtype=torch.float32)
+            packed = pack_weights(blocks)
+            sx, sab = plan.kept_shapes(n)
+            xs, abs_ = [x0.detach().to(torch.float32).contiguous()] + [new(s) for s in sx[1:]], [new(s) for s in sab]
+            c = c.detach().to(torch.float32).contiguous()
+            skips = new((n, plan.R))
+            launch_forward(plan, maps, c, packed, xs, abs_, skips)
+        ctx.plan, ctx.maps, ctx.packed, ctx.xs, ctx.abs, ctx.c = plan, maps, packed, xs[:-1], abs_, c
+        return skips
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ds):
+        plan, maps, dev, n = ctx.plan, ctx.maps, ctx.plan.device, ctx.maps.samples
+        need_x, need_c, need_w = ctx.needs_input_grad[2], ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
+        with torch.cuda.device(dev):
+            new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+            dx0, dc = new(n, plan.R) if need_x else None, new(n, plan.A) if need_c else None
+            dweights = [tuple(new(s) for s in plan.dweight_shapes()) for _ in range(plan.layers)] if need_w else None
+            launch_backward(plan, maps, ds.detach().to(torch.float32).contiguous(), ctx.c, ctx.packed, ctx.xs, ctx.abs, dx0, dc, dweights,
+                            grads=[new(n, plan.R), new(n, plan.R)], dz=new(n, 2 * plan.R), workspace=new(plan.workspace_floats(n)) if need_w else None)
+        out = [None, None, dx0, dc]
+        if need_w:
+            for dw in dweights:
+                out += unpack_dweights(plan, *dw)
+        else:
+            out += [None] * (len(ctx.needs_input_grad) - 4)
+        return tuple(out)
+
+
+def residual_stack(plan, maps, x0, c, blocks):
+    """blocks: per block the seven plain parameters in BLOCK_PARAMS order -> the un-scaled skip sum [samples, R]"""
+    return _Function.apply(plan, maps, x0, c, *[p for b in blocks for p in b])
+
+
+def _norm(v):
+    return torch.linalg.vector_norm(v, dim=tuple(range(1, v.dim())), keepdim=True)
+
+
+class _Conv(torch.nn.Module):
+    """the parameters of one convolution under the reference's names: weight (and bias), or weight_g / weight_v under weight norm"""
+
+    def __init__(self, shape, bias, weight_norm, init=None):
+        super().__init__()
+        w = torch.empty(*shape)
+        if init is None:
+            torch.nn.init.kaiming_normal_(w, nonlinearity="relu")
+        else:
+            w.fill_(init)
+        if weight_norm:
+            self.weight_g = torch.nn.Parameter(_norm(w))
+            self.weight_v = torch.nn.Parameter(w)
+        else:
+            self.weight = torch.nn.Parameter(w)
+        self.register_parameter("bias", torch.nn.Parameter(torch.zeros(shape[0])) if bias else None)
+
+    def folded(self):
+        """w = v g / ||v|| over every dim but 0 (torch.nn.utils.weight_norm with dim 0), in torch operations so that autograd carries it"""
+        if "weight" in self._parameters:
+            return self.weight
+        return self.weight_v * (self.weight_g / _norm(self.weight_v))
+
+
+class _Holder(torch.nn.Module):  # an index of the reference's Sequential / ModuleList that holds no parameter (Stretch2d, ReLU), or a plain container
+    pass
+
+
+class _Block(torch.nn.Module):
+    def __init__(self, R, A, k, weight_norm):
+        super().__init__()
+        self.conv = _Conv((2 * R, R, k), True, weight_norm)
+        self.conv1x1_aux = _Conv((2 * R, A, 1), False, weight_norm)
+        self.conv1x1_out = _Conv((R, R, 1), True, weight_norm)
+        self.conv1x1_skip = _Conv((R, R, 1), True, weight_norm)
+
+    def plain(self):
+        """BLOCK_PARAMS order"""
+        return (self.conv.folded(), self.conv.bias, self.conv1x1_aux.folded(), self.conv1x1_out.folded(), self.conv1x1_out.bias,
+                self.conv1x1_skip.folded(), self.conv1x1_skip.bias)
+
+
+class TrainableParallelWaveGANGenerator(torch.nn.Module):
+    """forward(z, c, lens=None) -> waveform [B, 1, T].  Parameter names and shapes are vocoder.param_spec's (weight_g / weight_v under use_weight_norm);
+    Kaiming-normal weights, zero biases, smoothing filters 1 / (2 s + 1), as the reference initialises them."""
+
+    def __init__(self, in_channels=1, out_channels=1, kernel_size=3, layers=30, stacks=3, residual_channels=64, gate_channels=128, skip_channels=64,
+                 aux_channels=80, aux_context_window=2, dropout=0.0, bias=True, use_weight_norm=True, use_causal_conv=False,
+                 upsample_conditional_features=True, upsample_net="ConvInUpsampleNetwork", upsample_params=None):
+        super().__init__()
+        self.config = dict(in_channels=in_channels, out_channels=out_channels, kernel_size=kernel_size, layers=layers, stacks=stacks,
+                           residual_channels=residual_channels, gate_channels=gate_channels, skip_channels=skip_channels, aux_channels=aux_channels,
+                           aux_context_window=aux_context_window, dropout=dropout, bias=bias, use_weight_norm=use_weight_norm,
+                           use_causal_conv=use_causal_conv, upsample_conditional_features=upsample_conditional_features, upsample_net=upsample_net,
+                           upsample_params=dict(DEFAULT_UPSAMPLE if upsample_params is None else upsample_params))
+        check_configuration(**self.config)
+        R, A, wn = residual_channels, aux_channels, bool(use_weight_norm)
+        self.scales = tuple(int(s) for s in self.config["upsample_params"]["upsample_scales"])
+        self.hop, self.ctx = int(math.prod(self.scales)), int(aux_context_window)
+        self.first_conv = _Conv((R, 1, 1), True, wn)
+        self.upsample_net = _Holder()
+        self.upsample_net.conv_in = _Conv((A, A, 2 * self.ctx + 1), False, wn)
+        self.upsample_net.upsample = _Holder()
+        ups = []
+        for s in self.scales:
+            ups += [_Holder(), _Conv((1, 1, 1, 2 * s + 1), False, wn, init=1.0 / (2 * s + 1))]
+        self.upsample_net.upsample.up_layers = torch.nn.ModuleList(ups)
+        self.conv_layers = torch.nn.ModuleList([_Block(R, A, kernel_size, wn) for _ in range(layers)])
+        self.last_conv_layers = torch.nn.ModuleList([_Holder(), _Conv((R, R, 1), True, wn), _Holder(), _Conv((1, R, 1), True, wn)])
+        self.use_weight_norm = wn
+        self._plan, self._maps_key, self._maps = None, None, None
+
+    def cfg(self):
+        """the configuration in the form vocoder.PWGPlan takes"""
+        c = self.config
+        return dict(layers=c["layers"], stacks=c["stacks"], residual_channels=c["residual_channels"], gate_channels=c["gate_channels"],
+                    skip_channels=c["skip_channels"], aux_channels=c["aux_channels"], aux_context_window=c["aux_context_window"],
+                    kernel_size=c["kernel_size"], upsample_scales=self.scales)
+
+    def convs(self):
+        """[(state-dict prefix, _Conv)]"""
+        return [(name + ".", m) for name, m in self.named_modules() if isinstance(m, _Conv)]
+
+    def remove_weight_norm(self):
+        """fold weight_g / weight_v into weight"""
+        for _, m in self.convs():
+            if "weight" not in m._parameters:
+                w = m.folded().detach()
+                del m.weight_g, m.weight_v
+                m.weight = torch.nn.Parameter(w)
+        self.use_weight_norm = False
+
+    def load_state_dict(self, state_dict, strict=True):
+        """either form of the names (a weight-norm dict into a plain module is folded, a plain one into a weight-norm module gets g = ||w||), or a
+        whole parallel_wavegan checkpoint ({"model": {"generator": ...}})"""
+        sd = state_dict
+        if "model" in sd and isinstance(sd["model"], dict) and "generator" in sd["model"]:
+            sd = sd["model"]["generator"]
+        sd = {k: torch.as_tensor(v) for k, v in sd.items()}
+        for p, m in self.convs():
+            plain = "weight" in m._parameters
+            if plain and p + "weight_v" in sd:
+                v, g = sd.pop(p + "weight_v"), sd.pop(p + "weight_g")
+                sd[p + "weight"] = v * (g / _norm(v))
+            elif not plain and p + "weight" in sd:
+                w = sd.pop(p + "weight")
+                sd[p + "weight_v"], sd[p + "weight_g"] = w, _norm(w)
+        return super().load_state_dict(sd, strict=strict)
+
+    def plan(self):
+        dev = next(self.parameters()).device
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda:%d" % torch.cuda.current_device())
+        if self._plan is None or self._plan.device != dev:
+            self._plan = GeneratorPlan(dev, **self.config)
+            self._maps_key = None
+        return self._plan
+
+    def maps(self, lens):
+        """kept for the next batch of the same lengths"""
+        key = tuple(lens)
+        if key != self._maps_key:
+            self._maps_key, self._maps = key, Maps(lens, self.plan().device)
+        return self._maps
+
+    def upsample(self, c):
+        """ConvInUpsampleNetwork: c [B, A, T' + 2 ctx] -> [B, A, T' hop] (torch operations)"""
+        c = F.conv1d(c, self.upsample_net.conv_in.folded()).unsqueeze(1)
+        for i, s in enumerate(self.scales):
+            c = F.interpolate(c, scale_factor=(1, s), mode="nearest")
+            c = F.conv2d(c, self.upsample_net.upsample.up_layers[2 * i + 1].folded(), padding=(0, s))
+        return c.squeeze(1)
+
+    def forward(self, z, c, lens=None):
+        """z [B, 1, T], c [B, A, T / hop + 2 ctx]; lens (frames per utterance): the rows past lens[b] * hop are padding, come out as zero and get exactly
+        zero gradient, and every utterance is computed as if it were alone"""
+        dev = self.plan().device
+        z, c = torch.as_tensor(z).to(device=dev, dtype=torch.float32), torch.as_tensor(c).to(device=dev, dtype=torch.float32)
+        if z.dim() != 3 or z.shape[1] != 1 or c.dim() != 3 or c.shape[1] != self.config["aux_channels"] or c.shape[0] != z.shape[0]:
+            raise ValueError("fcl-taco2_amd: PWG generator: z [B, 1, T] and c [B, %d, T / hop + 2 ctx] expected, got %r and %r"
+                             % (self.config["aux_channels"], tuple(z.shape), tuple(c.shape)))
+        B, T = int(z.shape[0]), int(z.shape[2])
+        if (int(c.shape[2]) - 2 * self.ctx) * self.hop != T:
+            raise ValueError("fcl-taco2_amd: PWG generator: %d frames (+ 2 x %d of context) at hop %d do not make %d samples"
+                             % (int(c.shape[2]) - 2 * self.ctx, self.ctx, self.hop, T))
+        x = F.conv1d(z, self.first_conv.folded(), self.first_conv.bias).transpose(1, 2)  # [B, T, R]
+        if lens is None:
+            n_of = [T] * B
+            x0, cu = x.reshape(B * T, -1), self.upsample(c).transpose(1, 2).reshape(B * T, -1)
+        else:
+            lens = [int(n) for n in lens]
+            if len(lens) != B or min(lens) < 1 or max(lens) * self.hop > T:
+                raise ValueError("fcl-taco2_amd: PWG generator: lens %r (frames) do not fit %d samples at hop %d" % (lens, T, self.hop))
+            n_of = [n * self.hop for n in lens]
+            x0 = torch.cat([x[b, :n] for b, n in enumerate(n_of)])
+            cu = torch.cat([self.upsample(c[b : b + 1, :, : lens[b] + 2 * self.ctx])[0].t() for b in range(B)])
+        skips = residual_stack(self.plan(), self.maps(n_of), x0.contiguous(), cu.contiguous(), [blk.plain() for blk in self.conv_layers])
+        l1, l3 = self.last_conv_layers[1], self.last_conv_layers[3]
+        y = F.linear(torch.relu(skips * math.sqrt(1.0 / self.config["layers"])), l1.folded()[:, :, 0], l1.bias)
+        y = F.linear(torch.relu(y), l3.folded()[:, :, 0], l3.bias)[:, 0]
+        if lens is None:
+            return y.reshape(B, 1, T)
+        rows, off = [], 0
+        for n in n_of:
+            rows.append(F.pad(y[off : off + n], (0, T - n)))
+            off += n
+        return torch.stack(rows).unsqueeze(1)

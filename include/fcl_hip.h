@@ -1326,6 +1326,66 @@ int fcl_pwd_layer_fwd(const fcl_pwd_t* a, fcl_stream_t stream);
 int fcl_pwd_layer_dx(const fcl_pwd_t* a, fcl_stream_t stream);
 int fcl_pwd_layer_dw(const fcl_pwd_t* a, fcl_stream_t stream);
 
+/* ---- Parallel WaveGAN generator, training form: one residual block per call, forward (activations kept) and backward
+ *      (fcl_taco2_amd/pwg_generator.py; restated in float64 numpy in tests/pwgt_ref.py).
+ * Layout: as the discriminator above -- float32, channel-last, packed [samples, C], row t's utterance [seg_lo[t], seg_hi[t]), a tap outside it reads zero, no
+ *      dilation limit.  R = residual = skip channels (a multiple of 16 from 16 to 64), the gate has 2 R channels, A = aux channels (a multiple of 16 from 16 to
+ *      128), ksize k 3 or 5, tap j at offset (j - (k - 1) / 2) d, d = dilation >= 1.
+ * Weights: w_gate [k R + A][2 R], rows j R + ci = Wconv[:, ci, j] and rows k R + ai = Waux[:, ai, 0] of torch's Conv1d; b_gate [2 R] (conv.bias; the aux
+ *      convolution has none); w_out [R][2 R], columns [0, R) = Wout^T, [R, 2 R) = Wskip^T; b_out [2 R] = (b_out | b_skip).  The backward forms are
+ *      permutations of them: w_dz [2 R][R] = (Wout ; Wskip) (rows: output channel, columns: gate channel), w_dx [k][2 R][R] with w_dx[j][co][ci] =
+ *      Wconv[co][ci][k - 1 - j] (taps reversed), w_dc [2 R][A] = Waux.
+ * fcl_pwt_block_fwd (launches pwt_gate_kernel, pwt_out_kernel):
+ *      z = b_gate + sum_j x[t + (j - (k - 1) / 2) d] Wconv_j + c[t] Waux;  ab = (tanh(z[:, :R]) | sigmoid(z[:, R:])) [samples, 2 R], KEPT for the backward pass
+ *      (tanhf, and 1 / (1 + expf(-z)) with a true division: the backward pass takes 1 - a^2 and b (1 - b), differences near saturation);  g = a * b;
+ *      x_out = (g Wout + b_out + x) sqrt(.5);  skips = g Wskip + b_skip (first != 0) or skips + that (first == 0).  z_out (optional, for tests): z.
+ * fcl_pwt_block_dx (pwt_dz_kernel, then pwt_dx_kernel when dx is given, pwt_dc_kernel when dc is given): dxo [samples, R] is the gradient of x_out and must
+ *      be null exactly when last != 0 (the last block's x_out is read by nobody); ds [samples, R] the gradient of the skip sum.
+ *      dg = sqrt(.5) dxo Wout^T + ds Wskip^T;  dz = (dg b (1 - a^2) | dg a b (1 - b)) [samples, 2 R], written for fcl_pwt_block_dw;
+ *      dx = sum_j dz[t - (j - (k - 1) / 2) d] Wconv_j^T + sqrt(.5) dxo;  dc = dz Waux^T (last != 0) or dc + that (last == 0).
+ * fcl_pwt_block_dw (pwt_dw_kernel<gate>, pwt_dw_kernel<out>, each followed by pwt_dw_reduce_kernel), after fcl_pwt_block_dx of the same block:
+ *      dw_gate [k R + A][2 R] = (sum_t x[t + shift_j]^T dz[t] ; sum_t c^T dz), db_gate [2 R] = sum_t dz;  dw_out [R][2 R] = sum_t g^T (sqrt(.5) dxo | ds),
+ *      db_out [2 R] = sum_t (sqrt(.5) dxo | ds); with last != 0 the Wout halves are exactly zero.  Each chunk of 1024 samples leaves a partial in the
+ *      workspace (fcl_pwt_dw_workspace_bytes); a second launch adds them in ascending order.  No atomics anywhere.
+ * One arithmetic mode, exact fp32: every contraction runs on v_mfma_f32_16x16x4_f32.  Every entry validates before any HIP call: a null pointer (or a dxo
+ *      that contradicts last) FCL_ERR_INVALID; channels, ksize, dilation or samples (1 .. 2^31 - 1) out of range FCL_ERR_SHAPE; an activation, gradient or
+ *      weight pointer not 16-byte aligned FCL_ERR_ALIGN; a workspace that is too small FCL_ERR_WORKSPACE.  No entry allocates, synchronises or copies. */
+typedef struct {
+    int64_t samples;
+    int32_t residual, aux, ksize, dilation;
+    int32_t first, last;
+    const int32_t* seg_lo;
+    const int32_t* seg_hi;
+    const float* x;        /* [samples, R] the block's input */
+    const float* c;        /* [samples, A] the conditioning */
+    const float* w_gate;
+    const float* b_gate;
+    const float* w_out;
+    const float* b_out;
+    float* ab;             /* [samples, 2 R] written by fwd, read by dx and dw */
+    float* x_out;          /* [samples, R] */
+    float* skips;          /* [samples, R] */
+    float* z_out;          /* [samples, 2 R] or null */
+    const float* dxo;      /* [samples, R] or null (last) */
+    const float* ds;       /* [samples, R] */
+    const float* w_dz;
+    const float* w_dx;
+    const float* w_dc;
+    float* dz;             /* [samples, 2 R] written by dx, read by dw */
+    float* dx;             /* [samples, R] or null: not computed */
+    float* dc;             /* [samples, A] or null: not computed */
+    float* dw_gate;
+    float* db_gate;
+    float* dw_out;
+    float* db_out;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_pwt_t;
+size_t fcl_pwt_dw_workspace_bytes(int64_t samples, int residual, int aux, int ksize);
+int fcl_pwt_block_fwd(const fcl_pwt_t* a, fcl_stream_t stream);
+int fcl_pwt_block_dx(const fcl_pwt_t* a, fcl_stream_t stream);
+int fcl_pwt_block_dw(const fcl_pwt_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,
