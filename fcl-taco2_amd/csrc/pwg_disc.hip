@@ -10,13 +10,12 @@
 // One launch per layer and one arithmetic mode: exact fp32, the C -> C contractions on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain).  The
 // shifted row blocks come straight from global memory / L2 (no halo in LDS), so there is no dilation limit.  No atomics: the weight gradients are
 // per-chunk partials added in ascending chunk order by a second launch; a batch is bit for bit its per-utterance runs.
-#include "fcl_common.h"
+// The keep mask, the bounds lookup, the C -> C weight-gradient kernel and the reduce are pwg_rows.h's, shared with pwg_train.hip.  pwd_conv_kernel keeps
+// its own two-operand form of the header's pipelined loop: through the general one it ran 6 - 9 % slower.
+#include "pwg_rows.h"
 
 namespace fcl {
 
-constexpr int PWD_ROWS = 128;       // rows per workgroup of pwd_conv_kernel: 4 waves x 2 tiles of 16 rows
-constexpr int PWD_DW_CHUNK = 1024;  // samples per partial of the weight gradients
-constexpr int PWD_DW_GROUP = 4;     // MFMA steps (of 4 samples) per register set of pwd_dw_kernel
 constexpr int PWD_SMALL_GROUPS = 8; // row groups of pwd_dw_small_kernel (1024 threads)
 constexpr int PWD_SMALL_UNROLL = 4; // samples per register set of pwd_dw_small_kernel
 
@@ -24,21 +23,6 @@ enum { PWD_FWD = 0, PWD_DX = 1 };
 
 // d LeakyReLU / d pre-activation from the stored post-activation (the activation keeps the sign); h == 0 takes the slope, as torch does
 __device__ __forceinline__ float pwd_mask(float h, float slope) { return h > 0.f ? 1.f : slope; }
-
-// v where keep, else +0.0, as a bitwise AND: the loaded value is USED whatever keep says, so the compiler cannot move the load under the condition
-// (where it would wait for each load on the spot), and whatever an unused lane loaded -- a NaN included -- leaves no trace
-__device__ __forceinline__ float pwd_keep(float v, bool keep) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & (keep ? 0xFFFFFFFFu : 0u));
-}
-
-__device__ __forceinline__ void pwd_bounds(const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi, long long t, long long n, long long& lo,
-                                           long long& hi) {
-    lo = hi = 0;
-    if (t < n) {
-        lo = max(0, seg_lo[t]);
-        hi = min(n, (long long)seg_hi[t]);
-    }
-}
 
 // ---- C -> C: y[t, co] = epi(sum_j sum_ci x[t + (j - (k - 1) / 2) d, ci] w[j][ci][co]).  A workgroup owns 128 rows x 16 NT columns (blockIdx.y: the column
 // block; pwd_tiles: NT = 1 .. 5 or 7, the whole width or half of it), a wave 32 rows: 2 x NT accumulator tiles of v_mfma_f32_16x16x4_f32.  A lane loads
@@ -52,13 +36,13 @@ __global__ __launch_bounds__(256) void pwd_conv_kernel(const float* __restrict__
                                                        float* __restrict__ y, long long n, int cin, int cout, int ksize, int dil, float slope) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, q = lane >> 4;
-    const long long t0 = (long long)blockIdx.x * PWD_ROWS + wave * 32;
+    const long long t0 = (long long)blockIdx.x * PWR_ROWS + wave * 32;
     const int n0 = blockIdx.y * (NT * 16);
     long long trow[2], lo[2], hi[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         trow[mt] = t0 + mt * 16 + r;
-        pwd_bounds(seg_lo, seg_hi, trow[mt], n, lo[mt], hi[mt]);
+        pwr_bounds(seg_lo, seg_hi, trow[mt], n, lo[mt], hi[mt]);
     }
     f32x4 acc[2][NT];
 #pragma unroll
@@ -93,7 +77,7 @@ __global__ __launch_bounds__(256) void pwd_conv_kernel(const float* __restrict__
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) a0[mt][s] = pwd_keep(a0[mt][s], ok0[mt]);
+        for (int s = 0; s < 4; ++s) a0[mt][s] = pwr_keep(a0[mt][s], ok0[mt]);
     for (int step = 0; step < steps; ++step) {
         f32x4 a1[2];
         bool ok1[2];
@@ -108,7 +92,7 @@ __global__ __launch_bounds__(256) void pwd_conv_kernel(const float* __restrict__
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) a0[mt][s] = pwd_keep(a1[mt][s], ok1[mt]);
+            for (int s = 0; s < 4; ++s) a0[mt][s] = pwr_keep(a1[mt][s], ok1[mt]);
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(256) void pwd_expand_kernel(const float* __restrict
     const long long t = i / cq;
     const int ch = (int)(i - t * cq) * 4;
     long long lo, hi;
-    pwd_bounds(seg_lo, seg_hi, t, n, lo, hi);
+    pwr_bounds(seg_lo, seg_hi, t, n, lo, hi);
     const int half = (ksize - 1) >> 1;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < ksize; ++j) {
@@ -184,7 +168,7 @@ __global__ __launch_bounds__(256) void pwd_reduce_kernel(const float* __restrict
     const int sub = threadIdx.x & 15;
     const long long t = blockIdx.x * 16LL + (threadIdx.x >> 4);
     long long lo, hi;
-    pwd_bounds(seg_lo, seg_hi, t, n, lo, hi);
+    pwr_bounds(seg_lo, seg_hi, t, n, lo, hi);
     const int half = (ksize - 1) >> 1;
     float acc = 0.f;
     for (int j = 0; j < ksize; ++j) {
@@ -201,85 +185,6 @@ __global__ __launch_bounds__(256) void pwd_reduce_kernel(const float* __restrict
     if (sub == 0 && t < n) y[t] = acc + (bias ? bias[0] : 0.f);
 }
 
-// ---- weight gradient of a C -> C layer: partial[chunk][j * cin + ci][co] = sum over the chunk's samples t of hs[t + (j - (k - 1) / 2) d, ci] g[t, co], and row
-// k cin of the partial is the bias gradient sum_t g[t, co] (an A operand of ones in row 0).  The contraction runs over the samples, 4 per MFMA; a wave owns
-// one (tap, 16 input channels) x all output channels; blockIdx.x is the chunk of PWD_DW_CHUNK samples.  No barrier in the kernel: an idle wave returns.
-template <int NT>
-__global__ __launch_bounds__(256) void pwd_dw_kernel(const float* __restrict__ hs, const float* __restrict__ g, const int32_t* __restrict__ seg_lo,
-                                                     const int32_t* __restrict__ seg_hi, float* __restrict__ partial, long long n, int cin, int cout, int ksize,
-                                                     int dil) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const int mtiles = cin >> 4;
-    const int combo = blockIdx.y * 4 + wave;
-    if (combo > ksize * mtiles) return;
-    const bool ones = combo == ksize * mtiles;
-    const int j = ones ? 0 : combo / mtiles, mt = ones ? 0 : combo % mtiles;
-    const long long shift = ones ? 0 : (long long)(j - ((ksize - 1) >> 1)) * dil;
-    const long long t_begin = (long long)blockIdx.x * PWD_DW_CHUNK, t_end = min(n, t_begin + PWD_DW_CHUNK);
-    f32x4 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // Groups of PWD_DW_GROUP steps, two register sets: the loads of group i + 1 are all issued before the MFMAs of group i, and scheduling barriers keep
-    // the compiler from moving each load down to its use (where it would wait out one latency per load).  Every load is unconditional, from a clamped
-    // row; what a dead lane loaded is masked to zero (pwd_keep).  The trip count is fixed: the steps past the chunk's end are dead lanes.
-    const long long last = t_end - 1;
-    struct Group {
-        int lo[PWD_DW_GROUP], hi[PWD_DW_GROUP];
-        float av[PWD_DW_GROUP], bv[PWD_DW_GROUP][NT];
-    };
-    auto issue = [&](int grp, Group& G) {
-#pragma unroll
-        for (int u = 0; u < PWD_DW_GROUP; ++u) {
-            const long long tq = t_begin + 4 * (grp * PWD_DW_GROUP + u) + q, tc = min(tq, last);
-            G.lo[u] = seg_lo[tc];
-            G.hi[u] = seg_hi[tc];
-            G.av[u] = hs[min(max(tq + shift, 0LL), n - 1) * cin + mt * 16 + r];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) G.bv[u][nt] = g[tc * cout + nt * 16 + r];
-        }
-    };
-    auto compute = [&](int grp, const Group& G) {
-#pragma unroll
-        for (int u = 0; u < PWD_DW_GROUP; ++u) {
-            const long long tq = t_begin + 4 * (grp * PWD_DW_GROUP + u) + q, rr = tq + shift;
-            const bool live = tq <= last;
-            const long long lo = max(0, G.lo[u]), hi = min(n, (long long)G.hi[u]);
-            // (branch-free: the row of ones OR the masked activation, never a select between a loaded value and a constant)
-            const float a = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pwd_keep(G.av[u], !ones && live && rr >= lo && rr < hi)) |
-                                                          ((ones && live && r == 0) ? 0x3F800000u : 0u));
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pwd_keep(G.bv[u][nt], live), acc[nt], 0, 0, 0);
-        }
-    };
-    constexpr int groups = PWD_DW_CHUNK / 4 / PWD_DW_GROUP;  // even
-    Group G0, G1;
-    issue(0, G0);
-    for (int grp = 0; grp < groups; grp += 2) {
-        issue(grp + 1, G1);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(grp, G0);
-        __builtin_amdgcn_sched_barrier(0);
-        issue(grp + 2, G0);  // (past the last group: clamped rows, never used)
-        __builtin_amdgcn_sched_barrier(0);
-        compute(grp + 1, G1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    float* out = partial + (size_t)blockIdx.x * ((size_t)ksize * cin + 1) * cout;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int m = 4 * q + reg;
-            if (ones) {
-                if (m == 0) out[(size_t)ksize * cin * cout + nt * 16 + r] = acc[nt][reg];
-            } else {
-                out[((size_t)j * cin + mt * 16 + m) * cout + nt * 16 + r] = acc[nt][reg];
-            }
-        }
-    }
-}
-
 // ---- weight gradient of the 1 -> C and C -> 1 layers, one chunk's partial per workgroup in the same layout.  vec [samples, c], sc [samples].
 // VEC_SHIFTED = 0 (first layer, cin 1): partial[j][ch] = sum_t sc[t + shift_j] vec[t, ch], row k = sum_t vec[t, ch].
 // VEC_SHIFTED = 1 (last layer, cout 1): partial[j c + ch] = sum_t vec[t + shift_j, ch] sc[t], element k c = sum_t sc[t].
@@ -290,14 +195,14 @@ __global__ __launch_bounds__(1024) void pwd_dw_small_kernel(const float* __restr
     __shared__ float red[PWD_SMALL_GROUPS - 1][(KSIZE + 1) * 128];
     const int ch = threadIdx.x & 127, grp = threadIdx.x >> 7;
     const int chc = min(ch, c - 1);  // (the threads past the width load a valid channel and store nothing)
-    const long long t_begin = (long long)blockIdx.x * PWD_DW_CHUNK, t_end = min(n, t_begin + PWD_DW_CHUNK);
+    const long long t_begin = (long long)blockIdx.x * PWR_DW_CHUNK, t_end = min(n, t_begin + PWR_DW_CHUNK);
     const long long last = t_end - 1;
     constexpr int half = (KSIZE - 1) >> 1;
     float acc[KSIZE + 1];
 #pragma unroll
     for (int j = 0; j <= KSIZE; ++j) acc[j] = 0.f;
-    // loads first (unconditional, clamped rows), a scheduling barrier, then the arithmetic: as pwd_dw_kernel, one register set
-    for (int it0 = 0; it0 < PWD_DW_CHUNK / PWD_SMALL_GROUPS; it0 += PWD_SMALL_UNROLL) {
+    // loads first (unconditional, clamped rows), a scheduling barrier, then the arithmetic: as pwr_dw_kernel, one register set
+    for (int it0 = 0; it0 < PWR_DW_CHUNK / PWD_SMALL_GROUPS; it0 += PWD_SMALL_UNROLL) {
         int lo[PWD_SMALL_UNROLL], hi[PWD_SMALL_UNROLL];
         float ov[PWD_SMALL_UNROLL], xv[PWD_SMALL_UNROLL][KSIZE];
 #pragma unroll
@@ -318,11 +223,11 @@ __global__ __launch_bounds__(1024) void pwd_dw_small_kernel(const float* __restr
             const long long t = t_begin + (long long)(it0 + u) * PWD_SMALL_GROUPS + grp;
             const bool live = t <= last;
             const long long l = max(0, lo[u]), h = min(n, (long long)hi[u]);
-            const float own = pwd_keep(ov[u], live);
+            const float own = pwr_keep(ov[u], live);
 #pragma unroll
             for (int j = 0; j < KSIZE; ++j) {
                 const long long rr = t + (long long)(j - half) * dil;
-                acc[j] = fmaf(pwd_keep(xv[u][j], live && rr >= l && rr < h), own, acc[j]);
+                acc[j] = fmaf(pwr_keep(xv[u][j], live && rr >= l && rr < h), own, acc[j]);
             }
             acc[KSIZE] += own;
         }
@@ -345,20 +250,6 @@ __global__ __launch_bounds__(1024) void pwd_dw_small_kernel(const float* __restr
     }
 }
 
-// the partials added in ascending chunk order: elements [0, nw) are dw, [nw, nw + nb) db (db may be null)
-__global__ __launch_bounds__(256) void pwd_dw_reduce_kernel(const float* __restrict__ partial, int chunks, int nw, int nb, float* __restrict__ dw,
-                                                            float* __restrict__ db) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nw + nb) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < chunks; ++k) s += partial[(size_t)k * (nw + nb) + e];
-    if (e < nw)
-        dw[e] = s;
-    else if (db)
-        db[e - nw] = s;
-}
-
 static bool pwd_width_ok(int c) { return c >= 16 && c <= 128 && c % 16 == 0; }
 
 // column tiles per workgroup of pwd_conv_kernel for c / 16 tiles in all: the whole width up to 5 tiles and at 7, half of it at 6 and 8
@@ -371,7 +262,7 @@ template <int EPI>
 static void pwd_launch_conv(const float* x, const float* w, const float* bias, const float* h, const int32_t* seg_lo, const int32_t* seg_hi, float* y, long long n,
                             int cin, int cout, int ksize, int dil, float slope, hipStream_t s) {
     const int nt = pwd_tiles(cout);
-    const dim3 grid((unsigned)((n + PWD_ROWS - 1) / PWD_ROWS), (unsigned)(cout / 16 / nt));
+    const dim3 grid((unsigned)((n + PWR_ROWS - 1) / PWR_ROWS), (unsigned)(cout / 16 / nt));
 #define PWD_CONV(NN)                                                                                                                                  \
     case NN:                                                                                                                                          \
         hipLaunchKernelGGL((pwd_conv_kernel<EPI, NN>), grid, dim3(256), 0, s, x, w, bias, h, seg_lo, seg_hi, y, n, cin, cout, ksize, dil, slope);    \
@@ -381,8 +272,6 @@ static void pwd_launch_conv(const float* x, const float* w, const float* bias, c
     }
 #undef PWD_CONV
 }
-
-static long long pwd_chunks(long long samples) { return (samples + PWD_DW_CHUNK - 1) / PWD_DW_CHUNK; }
 
 // what every entry checks: the struct, the layer class (1 -> C, C -> C, C -> 1), the kernel size, the dilation, the slope, the tables
 static int pwd_check(const fcl_pwd_t* a, const char* who) {
@@ -406,7 +295,7 @@ extern "C" {
 
 size_t fcl_pwd_dw_workspace_bytes(int64_t samples, int cin, int cout, int ksize) {
     if (samples < 1 || cin < 1 || cout < 1 || ksize < 1) return 0;
-    return (size_t)pwd_chunks(samples) * ((size_t)ksize * cin + 1) * cout * sizeof(float);
+    return (size_t)pwr_chunks(samples) * ((size_t)ksize * cin + 1) * cout * sizeof(float);
 }
 
 int fcl_pwd_layer_fwd(const fcl_pwd_t* a, fcl_stream_t stream) {
@@ -464,7 +353,7 @@ int fcl_pwd_layer_dw(const fcl_pwd_t* a, fcl_stream_t stream) {
                 fcl_pwd_dw_workspace_bytes(a->samples, a->cin, a->cout, a->ksize));
     hipStream_t s = (hipStream_t)stream;
     const long long n = a->samples;
-    const unsigned chunks = (unsigned)pwd_chunks(n);
+    const unsigned chunks = (unsigned)pwr_chunks(n);
     if (a->cin == 1) {
         ProfScope ps("pwd_dw_small_kernel<first>", 2.0 * (a->ksize + 1) * a->cout * (double)n, (double)n, s);
         if (a->ksize == 3)
@@ -479,11 +368,12 @@ int fcl_pwd_layer_dw(const fcl_pwd_t* a, fcl_stream_t stream) {
             hipLaunchKernelGGL((pwd_dw_small_kernel<1, 5>), dim3(chunks), dim3(1024), 0, s, a->x, a->g, a->seg_lo, a->seg_hi, a->workspace, n, a->cin, a->dilation);
     } else {
         const int combos = a->ksize * (a->cin / 16) + 1;
+        const PwrA in = {a->x, a->cin, a->cin, a->ksize, a->dilation, 1.f, nullptr, 0, 0};  // B = g alone: no b1 tile
         ProfScope ps("pwd_dw_kernel", 2.0 * a->ksize * a->cin * a->cout * (double)n, (double)n, s);
         const dim3 grid(chunks, (unsigned)((combos + 3) / 4));
 #define PWD_DW(NN)                                                                                                                                         \
     case NN:                                                                                                                                               \
-        hipLaunchKernelGGL(pwd_dw_kernel<NN>, grid, dim3(256), 0, s, a->x, a->g, a->seg_lo, a->seg_hi, a->workspace, n, a->cin, a->cout, a->ksize, a->dilation); \
+        hipLaunchKernelGGL((pwr_dw_kernel<PWR_PLAIN, NN, 0>), grid, dim3(256), 0, s, in, a->g, a->g, a->cout, 1.f, 1, a->seg_lo, a->seg_hi, a->workspace, n); \
         break;
         switch (a->cout / 16) {
             PWD_DW(1) PWD_DW(2) PWD_DW(3) PWD_DW(4) PWD_DW(5) PWD_DW(6) PWD_DW(7) PWD_DW(8)
@@ -493,7 +383,7 @@ int fcl_pwd_layer_dw(const fcl_pwd_t* a, fcl_stream_t stream) {
     {
         const int nw = a->ksize * a->cin * a->cout, nb = a->cout;
         ProfScope ps("pwd_dw_reduce_kernel", 0.0, (double)chunks, s);
-        hipLaunchKernelGGL(pwd_dw_reduce_kernel, dim3((unsigned)((nw + nb + 255) / 256)), dim3(256), 0, s, a->workspace, (int)chunks, nw, nb, a->dw, a->db);
+        hipLaunchKernelGGL(pwr_dw_reduce_kernel, dim3((unsigned)((nw + nb + 255) / 256)), dim3(256), 0, s, a->workspace, (int)chunks, nw, nb, a->dw, a->db);
     }
     return check_hip(hipGetLastError(), "pwd_layer_dw");
 }

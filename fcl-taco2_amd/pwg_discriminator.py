@@ -16,9 +16,9 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
+from .pwg_common import MAX_SAMPLES, Maps, _Conv, _Module  # noqa: F401 (Maps: the packed batch's seg_lo / seg_hi, used through this module too)
 
 KERNEL_SIZES = (3, 5)
-MAX_SAMPLES = 2 ** 31 - 1
 
 
 def check_configuration(in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1, nonlinear_activation="LeakyReLU",
@@ -53,22 +53,6 @@ def check_configuration(in_channels=1, out_channels=1, kernel_size=3, layers=10,
         geo.append((1 if i == 0 else conv_channels, conv_channels, d))
     geo.append((conv_channels, 1, 1))
     return geo
-
-
-class Maps(object):
-    """the packed batch's rows: seg_lo / seg_hi [samples] int32 on the device, row t's utterance is [seg_lo[t], seg_hi[t])"""
-
-    def __init__(self, lens, device):
-        self.lens = [int(n) for n in lens]
-        if not self.lens or min(self.lens) < 1:
-            raise ValueError("fcl-taco2_amd: PWG discriminator: every utterance needs at least one sample (lens %r)" % (self.lens,))
-        self.samples, self.n_utt = sum(self.lens), len(self.lens)
-        if self.samples > MAX_SAMPLES:
-            raise _lib.FclError("fcl-taco2_amd: more than 2^31 samples in one discriminator batch")
-        ln = torch.tensor(self.lens, dtype=torch.int64)
-        hi = torch.cumsum(ln, 0)
-        self.seg_lo = torch.repeat_interleave(hi - ln, ln).to(torch.int32).to(device)
-        self.seg_hi = torch.repeat_interleave(hi, ln).to(torch.int32).to(device)
 
 
 class DiscriminatorPlan(object):
@@ -194,35 +178,15 @@ class _Function(torch.autograd.Function):
         return tuple(out)
 
 
-class _Conv(torch.nn.Module):
-    """the parameters of one Conv1d under the reference's names: weight and bias, or weight_g / weight_v under weight norm"""
-
-    def __init__(self, cin, cout, k, bias, weight_norm):
-        super().__init__()
-        w = torch.empty(cout, cin, k)
-        torch.nn.init.kaiming_normal_(w)
-        if weight_norm:
-            self.weight_g = torch.nn.Parameter(w.flatten(1).norm(dim=1).reshape(cout, 1, 1))
-            self.weight_v = torch.nn.Parameter(w)
-        else:
-            self.weight = torch.nn.Parameter(w)
-        self.register_parameter("bias", torch.nn.Parameter(torch.zeros(cout)) if bias else None)
-
-    def folded(self):
-        """w = v g / ||v|| over dims 1, 2 (torch.nn.utils.weight_norm with dim 0), in torch operations so that autograd carries it"""
-        if "weight" in self._parameters:
-            return self.weight
-        v = self.weight_v
-        return v * (self.weight_g / torch.linalg.vector_norm(v, dim=(1, 2), keepdim=True))
-
-
 class _Activation(torch.nn.Module):  # holds the odd indices of conv_layers, as the reference's Sequential of conv, activation, conv, ...
     pass
 
 
-class ParallelWaveGANDiscriminator(torch.nn.Module):
+class ParallelWaveGANDiscriminator(_Module):
     """forward(x, lens=None) -> scores.  Parameters: conv_layers.{2 i}.weight / .bias (weight_g / weight_v under use_weight_norm), the last convolution at
     index 2 (layers - 1); Kaiming-normal weights, zero biases."""
+
+    CHECKPOINT_KEY, PLAN = "discriminator", DiscriminatorPlan
 
     def __init__(self, in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1, nonlinear_activation="LeakyReLU",
                  nonlinear_activation_params=None, bias=True, use_weight_norm=True, negative_slope=None):
@@ -239,58 +203,15 @@ class ParallelWaveGANDiscriminator(torch.nn.Module):
         geo = check_configuration(**self.config)
         mods = []
         for i, (ci, co, _) in enumerate(geo):
-            mods.append(_Conv(ci, co, kernel_size, bias, use_weight_norm))
+            mods.append(_Conv((co, ci, kernel_size), bias, use_weight_norm))
             if i < layers - 1:
                 mods.append(_Activation())
         self.conv_layers = torch.nn.ModuleList(mods)
         self.use_weight_norm = bool(use_weight_norm)
-        self._plan, self._maps_key, self._maps = None, None, None
+        self._reset_cache()
 
     def convs(self):
         return [m for m in self.conv_layers if isinstance(m, _Conv)]
-
-    def remove_weight_norm(self):
-        """fold weight_g / weight_v into weight"""
-        for m in self.convs():
-            if "weight" not in m._parameters:
-                w = m.folded().detach()
-                del m.weight_g, m.weight_v
-                m.weight = torch.nn.Parameter(w)
-        self.use_weight_norm = False
-
-    def load_state_dict(self, state_dict, strict=True):
-        """either form of the names (a weight-norm dict into a plain module is folded, a plain one into a weight-norm module gets g = ||w||), or a
-        whole parallel_wavegan checkpoint ({"model": {"discriminator": ...}})"""
-        sd = state_dict
-        if "model" in sd and isinstance(sd["model"], dict) and "discriminator" in sd["model"]:
-            sd = sd["model"]["discriminator"]
-        sd = dict(sd)
-        for i, m in enumerate(self.convs()):
-            p = "conv_layers.%d." % (2 * i)
-            plain = "weight" in m._parameters
-            if plain and p + "weight_v" in sd:
-                v, g = sd.pop(p + "weight_v"), sd.pop(p + "weight_g")
-                sd[p + "weight"] = v * (g / torch.linalg.vector_norm(v, dim=(1, 2), keepdim=True))
-            elif not plain and p + "weight" in sd:
-                w = sd.pop(p + "weight")
-                sd[p + "weight_v"], sd[p + "weight_g"] = w, torch.linalg.vector_norm(w, dim=(1, 2), keepdim=True)
-        return super().load_state_dict(sd, strict=strict)
-
-    def plan(self):
-        dev = next(self.parameters()).device
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda:%d" % torch.cuda.current_device())
-        if self._plan is None or self._plan.device != dev:
-            self._plan = DiscriminatorPlan(dev, **self.config)
-            self._maps_key = None
-        return self._plan
-
-    def maps(self, lens):
-        """kept for the next batch of the same lengths"""
-        key = tuple(lens)
-        if key != self._maps_key:
-            self._maps_key, self._maps = key, Maps(lens, self.plan().device)
-        return self._maps
 
     def pack(self, x, lens=None):
         """-> (packed x, lens, the shape to give back); torch operations, so the padding of a [B, T] input with lens gets zero gradient"""

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .pwg_discriminator import Maps  # the packed batch's seg_lo / seg_hi
+from .pwg_common import Maps, _Conv, _Module  # noqa: F401 (Maps: the packed batch's seg_lo / seg_hi, used through this module too)
 
 KERNEL_SIZES = (3, 5)
 BLOCK_PARAMS = ("conv.weight", "conv.bias", "conv1x1_aux.weight", "conv1x1_out.weight", "conv1x1_out.bias", "conv1x1_skip.weight", "conv1x1_skip.bias")
@@ -211,34 +211,6 @@ def residual_stack(plan, maps, x0, c, blocks):
     return _Function.apply(plan, maps, x0, c, *[p for b in blocks for p in b])
 
 
-def _norm(v):
-    return torch.linalg.vector_norm(v, dim=tuple(range(1, v.dim())), keepdim=True)
-
-
-class _Conv(torch.nn.Module):
-    """the parameters of one convolution under the reference's names: weight (and bias), or weight_g / weight_v under weight norm"""
-
-    def __init__(self, shape, bias, weight_norm, init=None):
-        super().__init__()
-        w = torch.empty(*shape)
-        if init is None:
-            torch.nn.init.kaiming_normal_(w, nonlinearity="relu")
-        else:
-            w.fill_(init)
-        if weight_norm:
-            self.weight_g = torch.nn.Parameter(_norm(w))
-            self.weight_v = torch.nn.Parameter(w)
-        else:
-            self.weight = torch.nn.Parameter(w)
-        self.register_parameter("bias", torch.nn.Parameter(torch.zeros(shape[0])) if bias else None)
-
-    def folded(self):
-        """w = v g / ||v|| over every dim but 0 (torch.nn.utils.weight_norm with dim 0), in torch operations so that autograd carries it"""
-        if "weight" in self._parameters:
-            return self.weight
-        return self.weight_v * (self.weight_g / _norm(self.weight_v))
-
-
 class _Holder(torch.nn.Module):  # an index of the reference's Sequential / ModuleList that holds no parameter (Stretch2d, ReLU), or a plain container
     pass
 
@@ -257,9 +229,11 @@ class _Block(torch.nn.Module):
                 self.conv1x1_skip.folded(), self.conv1x1_skip.bias)
 
 
-class TrainableParallelWaveGANGenerator(torch.nn.Module):
+class TrainableParallelWaveGANGenerator(_Module):
     """forward(z, c, lens=None) -> waveform [B, 1, T].  Parameter names and shapes are vocoder.param_spec's (weight_g / weight_v under use_weight_norm);
     Kaiming-normal weights, zero biases, smoothing filters 1 / (2 s + 1), as the reference initialises them."""
+
+    CHECKPOINT_KEY, PLAN = "generator", GeneratorPlan
 
     def __init__(self, in_channels=1, out_channels=1, kernel_size=3, layers=30, stacks=3, residual_channels=64, gate_channels=128, skip_channels=64,
                  aux_channels=80, aux_context_window=2, dropout=0.0, bias=True, use_weight_norm=True, use_causal_conv=False,
@@ -285,7 +259,7 @@ class TrainableParallelWaveGANGenerator(torch.nn.Module):
         self.conv_layers = torch.nn.ModuleList([_Block(R, A, kernel_size, wn) for _ in range(layers)])
         self.last_conv_layers = torch.nn.ModuleList([_Holder(), _Conv((R, R, 1), True, wn), _Holder(), _Conv((1, R, 1), True, wn)])
         self.use_weight_norm = wn
-        self._plan, self._maps_key, self._maps = None, None, None
+        self._reset_cache()
 
     def cfg(self):
         """the configuration in the form vocoder.PWGPlan takes"""
@@ -294,51 +268,7 @@ class TrainableParallelWaveGANGenerator(torch.nn.Module):
                     skip_channels=c["skip_channels"], aux_channels=c["aux_channels"], aux_context_window=c["aux_context_window"],
                     kernel_size=c["kernel_size"], upsample_scales=self.scales)
 
-    def convs(self):
-        """[(state-dict prefix, _Conv)]"""
-        return [(name + ".", m) for name, m in self.named_modules() if isinstance(m, _Conv)]
-
-    def remove_weight_norm(self):
-        """fold weight_g / weight_v into weight"""
-        for _, m in self.convs():
-            if "weight" not in m._parameters:
-                w = m.folded().detach()
-                del m.weight_g, m.weight_v
-                m.weight = torch.nn.Parameter(w)
-        self.use_weight_norm = False
-
-    def load_state_dict(self, state_dict, strict=True):
-        """either form of the names (a weight-norm dict into a plain module is folded, a plain one into a weight-norm module gets g = ||w||), or a
-        whole parallel_wavegan checkpoint ({"model": {"generator": ...}})"""
-        sd = state_dict
-        if "model" in sd and isinstance(sd["model"], dict) and "generator" in sd["model"]:
-            sd = sd["model"]["generator"]
-        sd = {k: torch.as_tensor(v) for k, v in sd.items()}
-        for p, m in self.convs():
-            plain = "weight" in m._parameters
-            if plain and p + "weight_v" in sd:
-                v, g = sd.pop(p + "weight_v"), sd.pop(p + "weight_g")
-                sd[p + "weight"] = v * (g / _norm(v))
-            elif not plain and p + "weight" in sd:
-                w = sd.pop(p + "weight")
-                sd[p + "weight_v"], sd[p + "weight_g"] = w, _norm(w)
-        return super().load_state_dict(sd, strict=strict)
-
-    def plan(self):
-        dev = next(self.parameters()).device
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda:%d" % torch.cuda.current_device())
-        if self._plan is None or self._plan.device != dev:
-            self._plan = GeneratorPlan(dev, **self.config)
-            self._maps_key = None
-        return self._plan
-
-    def maps(self, lens):
-        """kept for the next batch of the same lengths"""
-        key = tuple(lens)
-        if key != self._maps_key:
-            self._maps_key, self._maps = key, Maps(lens, self.plan().device)
-        return self._maps
+    convs = _Module._named_convs
 
     def upsample(self, c):
         """ConvInUpsampleNetwork: c [B, A, T' + 2 ctx] -> [B, A, T' hop] (torch operations)"""

@@ -23,6 +23,8 @@ CONFIGS = {
     "default": dict(conv_channels=64, kernel_size=3, layers=10, dilation_factor=1, bias=True, negative_slope=0.2),
     "c16k5f2": dict(conv_channels=16, kernel_size=5, layers=5, dilation_factor=2, bias=True, negative_slope=0.2),
     "c128relu": dict(conv_channels=128, kernel_size=3, layers=3, dilation_factor=1, bias=False, negative_slope=0.0),
+    "c96k5": dict(conv_channels=96, kernel_size=5, layers=3, dilation_factor=1, bias=True, negative_slope=0.2),  # the half-width split with 3 tiles, pwd_dw_kernel<6>
+    "c112": dict(conv_channels=112, kernel_size=3, layers=3, dilation_factor=1, bias=True, negative_slope=0.2),  # the 7-tile arm
 }
 CASES = [(name, LENS) for name in CONFIGS]
 MUTANTS = ("taps_not_reversed", "dilation_plus_one", "across_boundary", "slope_one_at_zero", "no_bias_gradient", "d_i_is_i_plus_1")

@@ -8,7 +8,10 @@ Three cases per leg: the forward pass alone (no_grad); forward + backward with f
 forward + backward with weight gradients and a detached input (the discriminator's update).  One process, alternating legs, event timers, a synchronise
 at each end, medians.  Prints one JSON line.
 
-    python tools/pwgd_ab.py [--batch 6] [--samples 25600] [--repeats 20] [--warmup 3] [--prof]
+    python tools/pwgd_ab.py [--batch 6] [--samples 25600] [--repeats 20] [--warmup 3] [--prof] [--dump PATH]
+
+--dump PATH saves leg B's scores, waveform gradient and weight gradients of this fixed-seed run as PATH (.npy, one float32 vector): two builds of the
+library computed the same bits where np.array_equal of their dumps holds.
 """
 import argparse
 import copy
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prof", action="store_true", help="also one profiled discriminator update of leg B: per-kernel ms and TFLOP/s from the library's launch record")
+    ap.add_argument("--dump", metavar="PATH", help="save leg B's scores and all gradients of the fixed-seed run as one .npy vector")
     args = ap.parse_args()
     import fcl_taco2_amd  # noqa: F401
     from fcl_taco2_amd import _lib, pwg_discriminator as P
@@ -104,6 +108,8 @@ def main():
     x64 = x.double().requires_grad_(True)
     P.generator_adversarial_loss(ref(x64)).backward()
     out["waveform_gradient"]["rel_2norm_vs_float64"] = {k: float((g.double() - x64.grad).norm() / x64.grad.norm()) for k, g in (("A_eager_f32", gb), ("B_hip", ga))}
+    if args.dump:
+        np.save(args.dump, torch.cat([v.detach().reshape(-1) for v in [forward(hip), ga] + update(hip)]).cpu().numpy())
     if args.prof:
         _lib.prof_enable(True)
         update(hip)

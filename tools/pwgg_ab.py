@@ -8,7 +8,11 @@ the same random weights on both legs, no weight norm on either.
 Three cases per leg: the forward pass alone (no_grad); forward + backward (every parameter's gradient); forward + backward + one Adam step.  One
 process, alternating legs, event timers, a synchronise at each end, medians.  Prints one JSON line.
 
-    python tools/pwgg_ab.py [--batch 6] [--frames 100] [--repeats 20] [--warmup 3] [--prof]
+    python tools/pwgg_ab.py [--batch 6] [--frames 100] [--repeats 20] [--warmup 3] [--prof] [--dump PATH]
+
+--dump PATH saves leg B's waveform and every parameter's gradient of this fixed-seed run (before any Adam step) as PATH (.npy, one float32 vector): two
+builds of the library computed the same bits where np.array_equal of their dumps holds -- apart from the gradients of first_conv and the upsampling
+network, torch's own convolution weight gradients, which differ in the last bits between two runs of one build.
 """
 import argparse
 import json
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prof", action="store_true", help="also one profiled forward + backward of leg B: per-kernel ms and TFLOP/s from the library's launch record")
+    ap.add_argument("--dump", metavar="PATH", help="save leg B's waveform and all gradients of the fixed-seed run as one .npy vector")
     args = ap.parse_args()
     import fcl_taco2_amd  # noqa: F401
     from fcl_taco2_amd import _lib, pwg_generator as G
@@ -83,6 +88,8 @@ def main():
     out["max_rel_B_minus_A"] = dict(waveform=rel(forward("B_hip"), forward("A_eager_f32")),
                                     gradients=max(rel(b, a) for i, (a, b) in enumerate(zip(ga, gb)) if i not in dead),
                                     last_block_out_gradient_zero=all(not gb[i].any() and (ga[i] is None or not ga[i].any()) for i in dead))
+    if args.dump:
+        np.save(args.dump, torch.cat([v.detach().reshape(-1) for v in [forward("B_hip")] + gb]).cpu().numpy())
     times = {k: [] for k in legs}
     for _ in range(args.warmup):
         for fn in legs.values():
