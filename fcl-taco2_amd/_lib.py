@@ -165,6 +165,14 @@ class PwtBlock(C.Structure):  # fcl_pwt_t
                           "w_dc", "dz", "dx", "dc", "dw_gate", "db_gate", "dw_out", "db_out", "workspace")] + [("workspace_bytes", _Z)]
 
 
+class PweEnds(C.Structure):  # fcl_pwe_t
+    _fields_ = [("samples", C.c_int64)] + [(n, C.c_int32) for n in ("frames", "n_utt", "residual", "aux", "ctx", "n_scales")] + [
+        ("scales", C.c_int32 * 6), ("sigma", _F), ("reserved", C.c_int32)] + [(n, _P) for n in ("seg_lo", "seg_hi", "frame_off", "c", "z", "w_in")] + [
+        ("h", _P * 6), ("w0", _P), ("b0", _P), ("u", _P * 6)] + [(n, _P) for n in ("cu", "x0", "dcu", "dx0")] + [("dh", _P * 6)] + [
+        (n, _P) for n in ("dw_in", "dw0", "db0", "dc", "dz", "skips", "w1", "w1t", "b1", "w3", "b3", "y1", "wav", "dwav", "dy1", "ds", "dw1", "db1", "dw3",
+                          "db3", "workspace")] + [("workspace_bytes", _Z)]
+
+
 class BernoulliSite(C.Structure):  # fcl_bernoulli_site_t
     _fields_ = [("out", _P), ("n", C.c_int64), ("p_one", _F), ("seed", C.c_uint32)]
 
@@ -354,6 +362,11 @@ SIGNATURES = {
     "fcl_pwt_block_fwd": (_I, [C.POINTER(PwtBlock), _P]),
     "fcl_pwt_block_dx": (_I, [C.POINTER(PwtBlock), _P]),
     "fcl_pwt_block_dw": (_I, [C.POINTER(PwtBlock), _P]),
+    "fcl_pwe_workspace_bytes": (_Z, [C.POINTER(PweEnds)]),
+    "fcl_pwe_in_fwd": (_I, [C.POINTER(PweEnds), _P]),
+    "fcl_pwe_in_bwd": (_I, [C.POINTER(PweEnds), _P]),
+    "fcl_pwe_out_fwd": (_I, [C.POINTER(PweEnds), _P]),
+    "fcl_pwe_out_bwd": (_I, [C.POINTER(PweEnds), _P]),
     "fcl_derive_blocks": (_I, [_I, _I, _I]),
     "fcl_derive_batch": (_I, [_P, _I, _I, _P]),
     "fcl_sumsq_accum": (_I, [_P, _Z, _P, _P]),

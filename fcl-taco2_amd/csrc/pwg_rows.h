@@ -17,7 +17,7 @@ constexpr int PWR_ROWS = 128;       // rows per workgroup of the row kernels: 4 
 constexpr int PWR_DW_CHUNK = 1024;  // samples per partial of the weight gradients
 constexpr int PWR_DW_GROUP = 4;     // MFMA steps (of 4 samples) per register set of pwr_dw_kernel
 
-enum { PWR_PLAIN = 0, PWR_GATED = 1 };  // the A operand as stored / g = a * b formed on load from ab [samples, 2 R]
+enum { PWR_PLAIN = 0, PWR_GATED = 1, PWR_RELU = 2 };  // the A operand as stored / g = a * b formed on load from ab [samples, 2 R] / max(s1 p1, 0)
 
 // v where keep, else +0.0, as a bitwise AND: the loaded value is USED whatever keep says, so the compiler cannot move the load under the condition
 // (where it would wait for each load on the spot), and whatever an unused lane loaded -- a NaN included -- leaves no trace
@@ -36,7 +36,8 @@ __device__ __forceinline__ void pwr_bounds(const int32_t* __restrict__ seg_lo, c
 
 // The A operand of a contraction: `taps` shifted views of p1 [samples, ld1] (c1 channels each, tap j at (j - (taps - 1) / 2) dil, times s1), followed by
 // p2 [samples, ld2] (c2 channels, unshifted).  Contraction row of the weight matrix: j c1 + channel, then taps c1 + channel of p2.  taps == 0 or c2 == 0
-// leaves a source out (its pointer is then never used).  PWR_GATED: p1 is ab [samples, 2 c1] and the value is ab[:, ch] * ab[:, c1 + ch].
+// leaves a source out (its pointer is then never used).  PWR_GATED: p1 is ab [samples, 2 c1] and the value is ab[:, ch] * ab[:, c1 + ch].  PWR_RELU: the
+// value is max(s1 p1, 0) (the generator's output end, pwg_ends.hip), in pwr_dw_kernel too, which otherwise takes p1 as stored.
 struct PwrA {
     const float* p1;
     int ld1, c1, taps, dil;
@@ -85,6 +86,9 @@ __device__ __forceinline__ void pwr_contract(const PwrA& A, const float* __restr
                 const f32x4 u = *reinterpret_cast<const f32x4*>(src + A.c1);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) a[mt][s] = v[s] * u[s];
+            } else if (MODE == PWR_RELU) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) a[mt][s] = fmaxf(v[s] * sc, 0.f);
             } else {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) a[mt][s] = v[s] * sc;
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256) void pwr_dw_kernel(PwrA A, const float* __rest
             G.lo[u] = seg_lo[tc];
             G.hi[u] = seg_hi[tc];
             const float* src = ap + min(max(tq + shift, 0LL), n - 1) * lda + mt * 16 + r;
-            G.av[u] = MODE == PWR_GATED ? src[0] * src[A.c1] : src[0];
+            G.av[u] = MODE == PWR_GATED ? src[0] * src[A.c1] : MODE == PWR_RELU ? fmaxf(src[0] * A.s1, 0.f) : src[0];
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) G.bv[u][nt] = nt < NB1 ? b1[tc * ldb + nt * 16 + r] * s1b : b2[tc * ldb + (nt - NB1) * 16 + r];
         }

@@ -3,13 +3,15 @@ csrc/pwg_train.hip), under an nn.Module with the parallel_wavega
 
     gen = TrainableParallelWaveGANGenerator().to("cuda:0")
     fake = gen(z, c)                     # z [B, 1, T] noise, c [B, aux, T / hop + 2 ctx] features (replicate-padded) -> [B, 1, T]
-    loss(fake).backward()                # the 30 residual blocks run backward in HIP kernels; the small layers around them are torch's
+    loss(fake).backward()                # the 30 residual blocks and the layers around them run backward in HIP kernels; torch folds weight norm
     vocoder.PWGPlan(gen.state_dict(), "cuda:0")   # the inference generator takes the trained weights as they are
 
 The block's contract is stated in include/fcl_hip.h "Parallel WaveGAN generator, training form" and restated in float64 numpy in tests/pwgt_ref.py; the
 forward pass is oracle/pwg_oracle.generator_forward.  Activations are float32, channel-last [samples, C], the batch packed with the utterances back to
 back; per block the input x_l [samples, R] and the gate activations ab_l = (tanh | sigmoid) [samples, 2 R] are kept.  One arithmetic mode (exact fp32).
-The upsampling network, first_conv, the sqrt(1 / layers) scale and the two last ReLU + 1x1 layers are torch operations under autograd.  No CPU fallback."""
+The generator's two ends -- the upsampling network and first_conv in front of the stack, the sqrt(1 / layers) scale and the two last ReLU + 1x1 layers
+behind it -- run on the HIP path too (the pwe_* kernels of csrc/pwg_ends.hip; restated in tests/pwge_ref.py); forward(..., ends="torch")
+keeps them as torch operations under autograd.  Weight norm is folded in torch in front of the functions.  No CPU fallback."""
 import ctypes as C
 import math
 
@@ -25,6 +27,12 @@ FWD_KERNELS = ("pwt_gate_kernel", "pwt_out_kernel")
 DZ_KERNEL, DX_KERNEL, DC_KERNEL = "pwt_dz_kernel", "pwt_dx_kernel", "pwt_dc_kernel"
 DW_KERNELS = ("pwt_dw_kernel<gate>", "pwt_dw_kernel<out>", "pwt_dw_reduce_kernel")
 DEFAULT_UPSAMPLE = {"upsample_scales": [4, 4, 4, 4]}
+IN_FWD_KERNELS = ("pwe_convin_kernel", "pwe_stage_kernel", "pwe_first_kernel")
+IN_DW_KERNELS = ("pwe_outer_kernel", "pwe_dh_kernel", "pwe_dwin_kernel", "pwe_reduce_kernel")
+IN_DU_KERNEL, IN_DC_KERNEL, IN_DZ_KERNEL = "pwe_stage_bwd_kernel", "pwe_dc_kernel", "pwe_first_dz_kernel"
+OUT_FWD_KERNEL, OUT_DX_KERNELS = "pwe_out_kernel", ("pwe_dy1_kernel", "pwe_ds_kernel")
+OUT_DW_KERNELS = ("pwe_dw_kernel<last>", "pwe_outer_kernel", "pwe_reduce_kernel")
+MAX_SCALES, MAX_SCALE, MAX_CONTEXT = 6, 16, 8
 
 
 def check_configuration(in_channels=1, out_channels=1, kernel_size=3, layers=30, stacks=3, residual_channels=64, gate_channels=128, skip_channels=64,
@@ -74,6 +82,40 @@ def check_configuration(in_channels=1, out_channels=1, kernel_size=3, layers=30,
     return [2 ** (l % per) for l in range(layers)]
 
 
+def check_ends(upsample_scales, aux_context_window):
+    """what the HIP ends cover beyond check_configuration: 1 to 6 scales of 2 to 16 each, a context window of 0 to 8"""
+    bad = lambda name, got, want: ValueError("fcl-taco2_amd: PWG generator: %s=%r is not supported on the HIP path (%s)" % (name, got, want))
+    scales = list(upsample_scales)
+    if not 1 <= len(scales) <= MAX_SCALES or any(not (isinstance(s, int) and 2 <= s <= MAX_SCALE) for s in scales):
+        raise bad("upsample_scales", upsample_scales, "1 to %d scales, each 2 to %d" % (MAX_SCALES, MAX_SCALE))
+    if not (isinstance(aux_context_window, int) and 0 <= aux_context_window <= MAX_CONTEXT):
+        raise bad("aux_context_window", aux_context_window, "0 to %d" % MAX_CONTEXT)
+
+
+class FrameMaps(Maps):
+    """Maps of a batch given in frames per utterance: the sample tables at `hop` samples per frame, and frame_off [n_utt + 1] int32 on the device"""
+
+    def __init__(self, frames, hop, device):
+        self.frames, self.hop = [int(f) for f in frames], int(hop)
+        super().__init__([f * self.hop for f in self.frames], device)
+        self.n_frames = sum(self.frames)
+        off = [0]
+        for f in self.frames:
+            off.append(off[-1] + f)
+        self.frame_off = torch.tensor(off, dtype=torch.int32).to(device)
+        self._rows = {}
+
+    def rows(self, T, ctx):
+        """(z_rows, c_rows) int64 on the device: where the pack's samples sit in a padded batch's [B T] samples, and the pack's conditioning rows in its
+        [B (T / hop + 2 ctx)] rows, in the pack's order (built once per padded length)"""
+        if (T, ctx) not in self._rows:
+            ln = torch.tensor(self.frames).unsqueeze(1)
+            zm = torch.arange(T).unsqueeze(0) < ln * self.hop
+            cm = torch.arange(T // self.hop + 2 * ctx).unsqueeze(0) < ln + 2 * ctx
+            self._rows[(T, ctx)] = tuple(torch.nonzero(m.reshape(-1))[:, 0].to(self.seg_lo.device) for m in (zm, cm))
+        return self._rows[(T, ctx)]
+
+
 class GeneratorPlan(object):
     """Per-block geometry (the dilations) and the sizes of what a pass over n samples needs"""
 
@@ -86,6 +128,21 @@ class GeneratorPlan(object):
             raise _lib.FclError("fcl-taco2_amd: GeneratorPlan needs a GPU device (no CPU fallback)")
         self.device = torch.device(device)
         self.receptive_field = 1 + (self.kernel_size - 1) * sum(self.dilations)
+        # the ends (§6o); check_ends refuses what they do not cover where they are used, so that a plan of such a geometry still serves the stack
+        self.scales = tuple((config.get("upsample_params") or DEFAULT_UPSAMPLE)["upsample_scales"])
+        self.ctx, self.hop, self.sigma = config.get("aux_context_window", 2), int(math.prod(self.scales)), math.sqrt(1.0 / self.layers)
+
+    def stage_rows(self, frames):
+        """rows of u_0 .. u_{n - 1}, the stage inputs the input side keeps"""
+        rows, out = frames, []
+        for s in self.scales:
+            out.append(rows)
+            rows *= s
+        return out
+
+    def ends_workspace_floats(self, maps):
+        check_ends(self.scales, self.ctx)
+        return _lib.load().fcl_pwe_workspace_bytes(C.byref(_ends_args(self, maps))) // 4
 
     def kept_shapes(self, n):
         """what the forward pass keeps: x_0 .. x_layers [n, R] (x_layers, the last block's output, is read by nobody) and ab_0 .. ab_{layers - 1} [n, 2 R]"""
@@ -211,6 +268,156 @@ def residual_stack(plan, maps, x0, c, blocks):
     return _Function.apply(plan, maps, x0, c, *[p for b in blocks for p in b])
 
 
+def pack_in_weights(win, hs, w0, b0):
+    """the input side's plain torch parameters (conv_in, the stage filters, first_conv) -> the kernels' forms (include/fcl_hip.h)"""
+    f = lambda v: v.detach().to(torch.float32)
+    return dict(w_in=f(win).permute(2, 1, 0).reshape(-1, win.shape[0]).contiguous(), h=[f(h).reshape(-1).contiguous() for h in hs],
+                w0=f(w0).reshape(-1).contiguous(), b0=f(b0).contiguous())
+
+
+def pack_out_weights(w1, b1, w3, b3):
+    """last_conv_layers 1 and 3 -> the kernels' forms: W1 in both orientations, the last layer as a vector and a one-element bias"""
+    f = lambda v: v.detach().to(torch.float32)
+    return dict(w1=f(w1)[:, :, 0].t().contiguous(), w1t=f(w1)[:, :, 0].contiguous(), b1=f(b1).contiguous(), w3=f(w3).reshape(-1).contiguous(),
+                b3=f(b3).reshape(1).contiguous())
+
+
+def _ends_args(plan, maps, **ptr):
+    a = _lib.PweEnds()
+    a.samples, a.frames, a.n_utt = maps.samples, maps.n_frames, maps.n_utt
+    a.residual, a.aux, a.ctx, a.n_scales, a.sigma = plan.R, plan.A, plan.ctx, len(plan.scales), plan.sigma
+    for i, s in enumerate(plan.scales):
+        a.scales[i] = s
+    a.seg_lo, a.seg_hi, a.frame_off = maps.seg_lo.data_ptr(), maps.seg_hi.data_ptr(), maps.frame_off.data_ptr()
+    for k, v in ptr.items():
+        if v is None:
+            continue
+        if isinstance(v, (list, tuple)):
+            for i, b in enumerate(v):
+                getattr(a, k)[i] = b.data_ptr()
+        elif k == "workspace":
+            a.workspace, a.workspace_bytes = v.data_ptr(), v.numel() * 4
+        else:
+            setattr(a, k, v.data_ptr())
+    return a
+
+
+# on caller-owned buffers, as launch_forward / launch_backward
+def launch_in_forward(plan, maps, z, c, w, us, cu, x0):
+    """z [samples], c [frames + 2 ctx n_utt, A], w from pack_in_weights -> us (plan.stage_rows: u_i [rows_i, A], kept), cu [samples, A], x0 [samples, R]"""
+    check_ends(plan.scales, plan.ctx)
+    a = _ends_args(plan, maps, z=z, c=c, w_in=w["w_in"], h=w["h"], w0=w["w0"], b0=w["b0"], u=us, cu=cu, x0=x0)
+    _lib.check(_lib.load().fcl_pwe_in_fwd(C.byref(a), ops._stream()))
+
+
+def launch_in_backward(plan, maps, dcu, dx0, z, c, w, us, dweights, dc, dz, workspace):
+    """dcu [samples, A], dx0 [samples, R] -> dweights = (dw_in [(2 ctx + 1) A, A], [dh_i], dw0 [R], db0 [R]) (None: no weight-gradient kernel is
+    launched), dc (None: not computed), dz [samples] (None: not computed); workspace: plan.ends_workspace_floats floats (needed with dweights or dc)"""
+    check_ends(plan.scales, plan.ctx)
+    a = _ends_args(plan, maps, dcu=dcu, dx0=dx0, z=z, c=c, w_in=w["w_in"], h=w["h"], w0=w["w0"], u=us, dc=dc, dz=dz, workspace=workspace)
+    if dweights is not None:
+        a.dw_in, a.dw0, a.db0 = dweights[0].data_ptr(), dweights[2].data_ptr(), dweights[3].data_ptr()
+        for i, b in enumerate(dweights[1]):
+            a.dh[i] = b.data_ptr()
+    _lib.check(_lib.load().fcl_pwe_in_bwd(C.byref(a), ops._stream()))
+
+
+def launch_out_forward(plan, maps, skips, w, y1, wav):
+    """skips [samples, R] -> y1 [samples, R] (kept), wav [samples]"""
+    a = _ends_args(plan, maps, skips=skips, w1=w["w1"], b1=w["b1"], w3=w["w3"], b3=w["b3"], y1=y1, wav=wav)
+    _lib.check(_lib.load().fcl_pwe_out_fwd(C.byref(a), ops._stream()))
+
+
+def launch_out_backward(plan, maps, dwav, skips, y1, w, dy1, ds, dweights, workspace):
+    """dwav [samples] -> ds [samples, R] (dy1 [samples, R] is scratch) and dweights = (dw1 [R, R] (row: input channel), db1 [R], dw3 [R], db3 [1])
+    (None: no weight-gradient kernel is launched; workspace is needed with them)"""
+    a = _ends_args(plan, maps, dwav=dwav, skips=skips, y1=y1, w1t=w["w1t"], w3=w["w3"], dy1=dy1, ds=ds, workspace=workspace)
+    if dweights is not None:
+        a.dw1, a.db1, a.dw3, a.db3 = (b.data_ptr() for b in dweights)
+    _lib.check(_lib.load().fcl_pwe_out_bwd(C.byref(a), ops._stream()))
+
+
+def _new(dev):
+    return lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+
+
+class _InputEnd(torch.autograd.Function):
+    """(cu [samples, A], x0 [samples, R]) from the packed noise z [samples], the packed conditioning c [frames + 2 ctx n_utt, A] and the plain weights
+    conv_in, the stage filters, first_conv weight and bias"""
+
+    @staticmethod
+    def forward(ctx, plan, maps, z, c, win, w0, b0, *hs):
+        dev, n = plan.device, maps.samples
+        with torch.cuda.device(dev):
+            new = _new(dev)
+            w = pack_in_weights(win, hs, w0, b0)
+            z, c = z.detach().to(torch.float32).contiguous(), c.detach().to(torch.float32).contiguous()
+            us, cu, x0 = [new(r, plan.A) for r in plan.stage_rows(maps.n_frames)], new(n, plan.A), new(n, plan.R)
+            launch_in_forward(plan, maps, z, c, w, us, cu, x0)
+        ctx.plan, ctx.maps, ctx.w, ctx.z, ctx.c, ctx.us = plan, maps, w, z, c, us
+        return cu, x0
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dcu, dx0):
+        plan, maps, dev, n = ctx.plan, ctx.maps, ctx.plan.device, ctx.maps.samples
+        need_z, need_c, need_w = ctx.needs_input_grad[2], ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
+        with torch.cuda.device(dev):
+            new = _new(dev)
+            K = (2 * plan.ctx + 1) * plan.A
+            dws = (new(K, plan.A), [new(2 * s + 1) for s in plan.scales], new(plan.R), new(plan.R)) if need_w else None
+            dc, dz = new(tuple(ctx.c.shape)) if need_c else None, new(n) if need_z else None
+            work = new(plan.ends_workspace_floats(maps)) if need_w or need_c else None
+            launch_in_backward(plan, maps, dcu.detach().to(torch.float32).contiguous(), dx0.detach().to(torch.float32).contiguous(), ctx.z, ctx.c, ctx.w,
+                               ctx.us, dws, dc, dz, work)
+        if not need_w:
+            return (None, None, dz, dc) + (None,) * (len(ctx.needs_input_grad) - 4)
+        A, R = plan.A, plan.R
+        return (None, None, dz, dc, dws[0].reshape(2 * plan.ctx + 1, A, A).permute(2, 1, 0).contiguous(), dws[2].reshape(R, 1, 1), dws[3]) + tuple(
+            h.reshape(1, 1, 1, -1) for h in dws[1])
+
+
+class _OutputEnd(torch.autograd.Function):
+    """the waveform [samples] from the stack's un-scaled skip sum [samples, R] and the plain weights of last_conv_layers 1 and 3"""
+
+    @staticmethod
+    def forward(ctx, plan, maps, skips, w1, b1, w3, b3):
+        dev, n = plan.device, maps.samples
+        with torch.cuda.device(dev):
+            new = _new(dev)
+            w = pack_out_weights(w1, b1, w3, b3)
+            skips = skips.detach().to(torch.float32).contiguous()
+            y1, wav = new(n, plan.R), new(n)
+            launch_out_forward(plan, maps, skips, w, y1, wav)
+        ctx.plan, ctx.maps, ctx.w, ctx.skips, ctx.y1 = plan, maps, w, skips, y1
+        return wav
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dwav):
+        plan, maps, dev, n, R = ctx.plan, ctx.maps, ctx.plan.device, ctx.maps.samples, ctx.plan.R
+        need_w = any(ctx.needs_input_grad[3:])
+        with torch.cuda.device(dev):
+            new = _new(dev)
+            dws = (new(R, R), new(R), new(R), new(1)) if need_w else None
+            ds = new(n, R)
+            launch_out_backward(plan, maps, dwav.detach().to(torch.float32).contiguous(), ctx.skips, ctx.y1, ctx.w, new(n, R), ds, dws,
+                                new(plan.ends_workspace_floats(maps)) if need_w else None)
+        if not need_w:
+            return None, None, ds, None, None, None, None
+        return None, None, ds, dws[0].t().unsqueeze(2).contiguous(), dws[1], dws[2].reshape(1, R, 1), dws[3]
+
+
+def input_end(plan, maps, z, c, win, hs, w0, b0):
+    """-> (cu [samples, A], x0 [samples, R]); maps: FrameMaps"""
+    return _InputEnd.apply(plan, maps, z, c, win, w0, b0, *hs)
+
+
+def output_end(plan, maps, skips, w1, b1, w3, b3):
+    """-> the waveform [samples]"""
+    return _OutputEnd.apply(plan, maps, skips, w1, b1, w3, b3)
+
+
 class _Holder(torch.nn.Module):  # an index of the reference's Sequential / ModuleList that holds no parameter (Stretch2d, ReLU), or a plain container
     pass
 
@@ -230,7 +437,7 @@ class _Block(torch.nn.Module):
 
 
 class TrainableParallelWaveGANGenerator(_Module):
-    """forward(z, c, lens=None) -> waveform [B, 1, T].  Parameter names and shapes are vocoder.param_spec's (weight_g / weight_v under use_weight_norm);
+    """forward(z, c, lens=None, ends="hip") -> waveform [B, 1, T].  Parameter names and shapes are vocoder.param_spec's (weight_g / weight_v under use_weight_norm);
     Kaiming-normal weights, zero biases, smoothing filters 1 / (2 s + 1), as the reference initialises them."""
 
     CHECKPOINT_KEY, PLAN = "generator", GeneratorPlan
@@ -278,9 +485,19 @@ class TrainableParallelWaveGANGenerator(_Module):
             c = F.conv2d(c, self.upsample_net.upsample.up_layers[2 * i + 1].folded(), padding=(0, s))
         return c.squeeze(1)
 
-    def forward(self, z, c, lens=None):
+    def maps(self, lens):
+        """lens in samples (multiples of the hop); kept for the next batch of the same lengths"""
+        key = tuple(lens)
+        if key != self._maps_key:
+            self._maps_key, self._maps = key, FrameMaps([n // self.hop for n in lens], self.hop, self.plan().device)
+        return self._maps
+
+    def forward(self, z, c, lens=None, ends="hip"):
         """z [B, 1, T], c [B, A, T / hop + 2 ctx]; lens (frames per utterance): the rows past lens[b] * hop are padding, come out as zero and get exactly
-        zero gradient, and every utterance is computed as if it were alone"""
+        zero gradient, and every utterance is computed as if it were alone.  ends: "hip", the ends in the pwe_* kernels, or "torch", as torch operations
+        (the reference of the tests and the other leg of the timing)"""
+        if ends not in ("hip", "torch"):
+            raise ValueError("fcl-taco2_amd: PWG generator: ends=%r is not \"hip\" or \"torch\"" % (ends,))
         dev = self.plan().device
         z, c = torch.as_tensor(z).to(device=dev, dtype=torch.float32), torch.as_tensor(c).to(device=dev, dtype=torch.float32)
         if z.dim() != 3 or z.shape[1] != 1 or c.dim() != 3 or c.shape[1] != self.config["aux_channels"] or c.shape[0] != z.shape[0]:
@@ -290,6 +507,8 @@ class TrainableParallelWaveGANGenerator(_Module):
         if (int(c.shape[2]) - 2 * self.ctx) * self.hop != T:
             raise ValueError("fcl-taco2_amd: PWG generator: %d frames (+ 2 x %d of context) at hop %d do not make %d samples"
                              % (int(c.shape[2]) - 2 * self.ctx, self.ctx, self.hop, T))
+        if ends == "hip":
+            return self._forward_hip(z, c, lens, B, T)
         x = F.conv1d(z, self.first_conv.folded(), self.first_conv.bias).transpose(1, 2)  # [B, T, R]
         if lens is None:
             n_of = [T] * B
@@ -312,3 +531,25 @@ class TrainableParallelWaveGANGenerator(_Module):
             rows.append(F.pad(y[off : off + n], (0, T - n)))
             off += n
         return torch.stack(rows).unsqueeze(1)
+
+    def _forward_hip(self, z, c, lens, B, T):
+        plan = self.plan()
+        check_ends(self.scales, self.ctx)
+        if lens is None:
+            maps = self.maps([T] * B)
+            zp, cp = z.reshape(B * T), c.transpose(1, 2).reshape(-1, c.shape[1])
+        else:
+            lens = [int(n) for n in lens]
+            if len(lens) != B or min(lens) < 1 or max(lens) * self.hop > T:
+                raise ValueError("fcl-taco2_amd: PWG generator: lens %r (frames) do not fit %d samples at hop %d" % (lens, T, self.hop))
+            maps = self.maps([n * self.hop for n in lens])
+            zr, cr = maps.rows(T, self.ctx)
+            zp, cp = z.reshape(B * T)[zr], c.transpose(1, 2).reshape(-1, c.shape[1])[cr]
+        up, l1, l3 = self.upsample_net.upsample.up_layers, self.last_conv_layers[1], self.last_conv_layers[3]
+        cu, x0 = input_end(plan, maps, zp, cp, self.upsample_net.conv_in.folded(), [up[2 * i + 1].folded() for i in range(len(self.scales))],
+                           self.first_conv.folded(), self.first_conv.bias)
+        skips = residual_stack(plan, maps, x0, cu, [blk.plain() for blk in self.conv_layers])
+        y = output_end(plan, maps, skips, l1.folded(), l1.bias, l3.folded(), l3.bias)
+        if lens is None:
+            return y.reshape(B, 1, T)
+        return torch.zeros(B * T, device=y.device, dtype=y.dtype).index_copy(0, zr, y).reshape(B, 1, T)

@@ -1,0 +1,488 @@
+"""Parallel WaveGAN training on one MI355X by the published parallel_wavegan.v1 recipe (restated from its paper and config, not diffed against a
+file): the generator step is HIP from (z, c) to the waveform and back (pwg_generator.py), the discriminator and the multi-resolution
+STFT loss are §6l and §6j; torch keeps weight norm, the optimisers and the schedulers.
+
+    python -m fcl_taco2_amd.train_vocoder --wav-dir wavs --feature-root feats --train-list train.txt --valid-list valid.txt --outdir exp/pwg
+
+reads `feats/mels/<utt>.npy` (the normalised [T, n_mels] mels that preprocess / extract_features write, T = samples // hop + 1) and 16-bit PCM mono wavs,
+and writes config.yml (parallel_wavegan's layout), checkpoint-<steps>steps.pkl (vocoder.PWGPlan, vocoder_decode and tts load them as they are) and
+train_log.jsonl into --outdir.  Which utterances and windows make step n's batch, and the noise of step n, are functions of (--seed, n) alone, so
+--resume needs nothing but the checkpoint: 2 + 2 steps give the bytes of 4.  One process, one GPU; data-parallel training is not built."""
+import argparse
+import concurrent.futures
+import json
+import logging
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import extract_features as XF
+
+# the published v1 recipe; every one is a flag
+DEFAULTS = dict(sampling_rate=22050, batch_size=6, batch_max_steps=25600, generator_lr=1e-4, discriminator_lr=5e-5, optimizer_eps=1e-6,
+                scheduler_step_size=200000, scheduler_gamma=0.5, generator_grad_norm=10.0, discriminator_grad_norm=1.0, lambda_adv=4.0,
+                discriminator_train_start_steps=100000, train_max_steps=400000, save_interval_steps=5000, eval_interval_steps=1000, log_interval_steps=100,
+                fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240))
+GENERATOR_DEFAULTS = dict(in_channels=1, out_channels=1, kernel_size=3, layers=30, stacks=3, residual_channels=64, gate_channels=128, skip_channels=64,
+                          aux_channels=80, aux_context_window=2, dropout=0.0, bias=True, use_weight_norm=True, use_causal_conv=False,
+                          upsample_conditional_features=True, upsample_net="ConvInUpsampleNetwork", upsample_params={"upsample_scales": [4, 4, 4, 4]})
+DISCRIMINATOR_DEFAULTS = dict(in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1, bias=True, use_weight_norm=True,
+                              nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2})
+# a checkpoint is resumed only under the values it was trained with: these keys of config.yml must agree with the flags
+PINNED = ("generator_params", "discriminator_params", "batch_size", "batch_max_steps", "generator_optimizer_params", "discriminator_optimizer_params",
+          "generator_scheduler_params", "discriminator_scheduler_params", "generator_grad_norm", "discriminator_grad_norm", "lambda_adv",
+          "discriminator_train_start_steps", "stft_loss_params", "sampling_rate", "hop_size", "seed")
+LOSS_TERMS = ("spectral_convergence_loss", "log_stft_magnitude_loss", "adversarial_loss", "real_loss", "fake_loss")
+
+
+def _ints(text):
+    return tuple(int(v) for v in str(text).replace(",", " ").split())
+
+
+def _params(text, what):
+    """constructor arguments as JSON or as a yaml file"""
+    if text is None:
+        return {}
+    if os.path.exists(text):
+        import yaml
+
+        with open(text) as f:
+            out = yaml.safe_load(f) or {}
+    else:
+        out = json.loads(text)
+    if not isinstance(out, dict):
+        raise ValueError("fcl-taco2_amd: train_vocoder: %s must be a mapping of constructor arguments, got %r" % (what, out))
+    return out
+
+
+def build_parser():
+    d = DEFAULTS
+    ap = argparse.ArgumentParser(prog="fcl_taco2_amd.train_vocoder", description="Parallel WaveGAN training on MI355X (parallel_wavegan.v1 recipe)")
+    ap.add_argument("--wav-dir", default=None, help="directory of <utt>.wav (16-bit PCM mono at --sampling-rate); this or --wav-scp")
+    ap.add_argument("--wav-scp", default=None, help="Kaldi-style `utt path` list")
+    ap.add_argument("--feature-root", default=None, help="reads mels/<utt>.npy: normalised [T, n_mels] mels as preprocess / extract_features write them")
+    ap.add_argument("--train-list", default=None, help="utterance ids, one per line")
+    ap.add_argument("--valid-list", default=None, help="utterance ids for the evaluation lines (optional)")
+    ap.add_argument("--outdir", required=True)
+    ap.add_argument("--config", default=None, help="parallel_wavegan-style config.yml for everything below; flags given beside it win")
+    ap.add_argument("--generator-params", default=None, help="TrainableParallelWaveGANGenerator arguments, JSON or a yaml file (v1 without)")
+    ap.add_argument("--discriminator-params", default=None, help="ParallelWaveGANDiscriminator arguments, JSON or a yaml file (v1 without)")
+    ap.add_argument("--sampling-rate", type=int, default=None, help="default %d" % d["sampling_rate"])
+    for k in ("batch_size", "batch_max_steps", "scheduler_step_size", "discriminator_train_start_steps", "train_max_steps", "save_interval_steps",
+              "eval_interval_steps", "log_interval_steps"):
+        ap.add_argument("--" + k.replace("_", "-"), type=int, default=None, help="default %d" % d[k])
+    for k in ("generator_lr", "discriminator_lr", "optimizer_eps", "scheduler_gamma", "generator_grad_norm", "discriminator_grad_norm", "lambda_adv"):
+        ap.add_argument("--" + k.replace("_", "-"), type=float, default=None, help="default %g" % d[k])
+    for k in ("fft_sizes", "hop_sizes", "win_lengths"):
+        ap.add_argument("--" + k.replace("_", "-"), type=_ints, default=None, help="STFT loss resolutions, default %s" % ",".join(map(str, d[k])))
+    ap.add_argument("--seed", type=int, default=None, help="default 0; of the batches, the windows and the noise (functions of the seed and the step alone)")
+    ap.add_argument("--resume", default=None, help="checkpoint-Nsteps.pkl: continue with models, optimisers, schedulers and the step count")
+    ap.add_argument("--pretrain", default=None, help="checkpoint.pkl: load the models only")
+    ap.add_argument("--ends", choices=("hip", "torch"), default="hip", help="the generator's ends (DESIGN §6o)")
+    ap.add_argument("--verbose", type=int, default=1)
+    return ap
+
+
+CONFIG_KEYS = {"sampling_rate", "hop_size", "generator_type", "generator_params", "discriminator_type", "discriminator_params", "stft_loss_params",
+               "lambda_adv", "batch_size", "batch_max_steps", "generator_optimizer_params", "discriminator_optimizer_params", "generator_scheduler_params",
+               "discriminator_scheduler_params", "generator_grad_norm", "discriminator_grad_norm", "discriminator_train_start_steps", "train_max_steps",
+               "save_interval_steps", "eval_interval_steps", "log_interval_steps", "generator_optimizer_type", "discriminator_optimizer_type",
+               "generator_scheduler_type", "discriminator_scheduler_type", "seed"}
+
+
+def _extras(d, allowed, where):
+    """the keys of d outside `allowed`, as `where.key`"""
+    return ["%s.%s" % (where, k) if where else str(k) for k in sorted(set(d) - set(allowed), key=str)]
+
+
+def _refuse(extras):
+    if extras:
+        raise ValueError("fcl-taco2_amd: train_vocoder: %s not supported: %s" % ("this key is" if len(extras) == 1 else "these keys are", ", ".join(extras)))
+
+
+def _only(d, allowed, where):
+    _refuse(_extras(d, allowed, where))
+    return d
+
+
+def read_config(path):
+    """a parallel_wavegan-style config.yml -> the flat values of DEFAULTS' names (plus generator_params / discriminator_params / seed); an unknown or
+    unsupported key is refused by name"""
+    import yaml
+
+    with open(path) as f:
+        y = yaml.safe_load(f) or {}
+    # every key that is refused, in one message: a real parallel_wavegan config carries a dozen the driver has no use for
+    bad = _extras(y, CONFIG_KEYS, "")
+    for sec, allowed in (("generator_params", GENERATOR_DEFAULTS), ("discriminator_params", DISCRIMINATOR_DEFAULTS),
+                         ("stft_loss_params", ("fft_sizes", "hop_sizes", "win_lengths")), ("generator_optimizer_params", ("lr", "eps")),
+                         ("discriminator_optimizer_params", ("lr", "eps")), ("generator_scheduler_params", ("step_size", "gamma")),
+                         ("discriminator_scheduler_params", ("step_size", "gamma"))):
+        if isinstance(y.get(sec), dict):
+            bad += _extras(y[sec], allowed, sec)
+    _refuse(bad)
+    for k, want in (("generator_type", "ParallelWaveGANGenerator"), ("discriminator_type", "ParallelWaveGANDiscriminator"), ("generator_optimizer_type", "RAdam"),
+                    ("discriminator_optimizer_type", "RAdam"), ("generator_scheduler_type", "StepLR"), ("discriminator_scheduler_type", "StepLR")):
+        if y.get(k, want) != want:
+            raise ValueError("fcl-taco2_amd: train_vocoder: config key %s=%r is not supported (%s)" % (k, y[k], want))
+    out = {k: y[k] for k in ("sampling_rate", "hop_size", "generator_params", "discriminator_params", "lambda_adv", "batch_size", "batch_max_steps",
+                             "generator_grad_norm", "discriminator_grad_norm", "discriminator_train_start_steps", "train_max_steps", "save_interval_steps",
+                             "eval_interval_steps", "log_interval_steps", "seed") if k in y}
+    for k in ("fft_sizes", "hop_sizes", "win_lengths"):
+        if k in _only(y.get("stft_loss_params", {}), ("fft_sizes", "hop_sizes", "win_lengths"), "stft_loss_params"):
+            out[k] = tuple(y["stft_loss_params"][k])
+    lr = {"generator": {}, "discriminator": {}}
+    for net in lr:
+        o = _only(y.get(net + "_optimizer_params", {}), ("lr", "eps"), net + "_optimizer_params")
+        s = _only(y.get(net + "_scheduler_params", {}), ("step_size", "gamma"), net + "_scheduler_params")
+        if "lr" in o:
+            out[net + "_lr"] = float(o["lr"])
+        lr[net] = (o.get("eps"), s.get("step_size"), s.get("gamma"))
+    for i, k in enumerate(("optimizer_eps", "scheduler_step_size", "scheduler_gamma")):
+        a, b = lr["generator"][i], lr["discriminator"][i]
+        if a is not None and b is not None and a != b:
+            raise ValueError("fcl-taco2_amd: train_vocoder: config key %s differs between the two networks (%r, %r): one value serves both" % (k, a, b))
+        if a is not None or b is not None:
+            out[k] = a if a is not None else b
+    return out
+
+
+def resolve(args):
+    """flags over --config over the defaults -> the run's config in parallel_wavegan's layout (what config.yml holds)"""
+    from . import pwg_discriminator, pwg_generator, stft_loss
+
+    base = dict(DEFAULTS, seed=0)
+    file = read_config(args.config) if args.config else {}
+    base.update({k: v for k, v in file.items() if k in base})
+    for k in base:
+        if getattr(args, k, None) is not None:
+            base[k] = getattr(args, k)
+    gp = dict(GENERATOR_DEFAULTS, **file.get("generator_params", {}))
+    gp.update(_params(args.generator_params, "--generator-params"))
+    dp = dict(DISCRIMINATOR_DEFAULTS, **file.get("discriminator_params", {}))
+    dp.update(_params(args.discriminator_params, "--discriminator-params"))
+    _only(gp, GENERATOR_DEFAULTS, "generator_params")
+    _only(dp, DISCRIMINATOR_DEFAULTS, "discriminator_params")
+    gp["upsample_params"] = {"upsample_scales": [int(s) for s in _only(dict(gp["upsample_params"]), ("upsample_scales",), "upsample_params")["upsample_scales"]]}
+    pwg_generator.check_configuration(**gp)
+    pwg_generator.check_ends(gp["upsample_params"]["upsample_scales"], gp["aux_context_window"])
+    slope = dict(dp["nonlinear_activation_params"] or {})
+    _only(slope, ("negative_slope",), "nonlinear_activation_params")
+    pwg_discriminator.check_configuration(**dict({k: v for k, v in dp.items() if k != "nonlinear_activation_params"}, **slope))
+    stft_loss.check_resolutions(base["fft_sizes"], base["hop_sizes"], base["win_lengths"])
+    hop = int(np.prod(gp["upsample_params"]["upsample_scales"]))
+    if "hop_size" in file and int(file["hop_size"]) != hop:
+        raise ValueError("fcl-taco2_amd: train_vocoder: config key hop_size=%r is not the product of upsample_scales (%d)" % (file["hop_size"], hop))
+    if base["batch_max_steps"] % hop or base["batch_max_steps"] < hop:
+        raise ValueError("fcl-taco2_amd: train_vocoder: batch_max_steps=%d is not a positive multiple of the hop (%d)" % (base["batch_max_steps"], hop))
+    for k in ("batch_size", "train_max_steps", "save_interval_steps", "eval_interval_steps", "log_interval_steps", "scheduler_step_size"):
+        if int(base[k]) < 1:
+            raise ValueError("fcl-taco2_amd: train_vocoder: %s=%r must be positive" % (k, base[k]))
+    opt = lambda net: {"lr": float(base[net + "_lr"]), "eps": float(base["optimizer_eps"])}
+    sch = {"step_size": int(base["scheduler_step_size"]), "gamma": float(base["scheduler_gamma"])}
+    return {"sampling_rate": int(base["sampling_rate"]), "hop_size": hop, "generator_type": "ParallelWaveGANGenerator", "generator_params": gp,
+            "discriminator_type": "ParallelWaveGANDiscriminator", "discriminator_params": dp,
+            "stft_loss_params": {k: [int(v) for v in base[k]] for k in ("fft_sizes", "hop_sizes", "win_lengths")}, "lambda_adv": float(base["lambda_adv"]),
+            "batch_size": int(base["batch_size"]), "batch_max_steps": int(base["batch_max_steps"]), "generator_optimizer_type": "RAdam",
+            "generator_optimizer_params": opt("generator"), "generator_scheduler_type": "StepLR", "generator_scheduler_params": dict(sch),
+            "generator_grad_norm": float(base["generator_grad_norm"]), "discriminator_optimizer_type": "RAdam",
+            "discriminator_optimizer_params": opt("discriminator"), "discriminator_scheduler_type": "StepLR", "discriminator_scheduler_params": dict(sch),
+            "discriminator_grad_norm": float(base["discriminator_grad_norm"]),
+            "discriminator_train_start_steps": int(base["discriminator_train_start_steps"]), "train_max_steps": int(base["train_max_steps"]),
+            "save_interval_steps": int(base["save_interval_steps"]), "eval_interval_steps": int(base["eval_interval_steps"]),
+            "log_interval_steps": int(base["log_interval_steps"]), "seed": int(base["seed"])}
+
+
+def adversarial(cfg, step):
+    """whether step `step` (1-based) has an adversarial term and a discriminator update: the first is discriminator_train_start_steps + 1"""
+    return step > cfg["discriminator_train_start_steps"]
+
+
+def learning_rate(cfg, net, step):
+    """the learning rate step `step` (1-based) is taken with: StepLR after step - 1 scheduler steps"""
+    s = cfg[net + "_scheduler_params"]
+    return cfg[net + "_optimizer_params"]["lr"] * s["gamma"] ** ((step - 1) // s["step_size"])
+
+
+class Windows(object):
+    """the window sampler (parallel_wavegan's collater): an utterance of T mel frames gives windows of `frames` frames starting at f0 in
+    [ctx, T - ctx - frames], the mel rows [f0 - ctx, f0 + frames + ctx) and the samples [f0 hop, (f0 + frames) hop).  batch(step) is a function of
+    (seed, step) alone: utterances from a permutation per epoch, window starts and noise from generators seeded by (seed, stream, step)."""
+
+    def __init__(self, lengths, frames, ctx, hop, batch_size, seed):
+        """lengths: [(utt id, mel frames)]"""
+        self.frames, self.ctx, self.hop, self.batch_size, self.seed = int(frames), int(ctx), int(hop), int(batch_size), int(seed)
+        self.utts = [(u, int(T)) for u, T in lengths if int(T) - 2 * self.ctx - self.frames >= 0]
+        self.dropped = [u for u, T in lengths if int(T) - 2 * self.ctx - self.frames < 0]
+        if not self.utts:
+            raise ValueError("fcl-taco2_amd: train_vocoder: no utterance is long enough for one window of %d frames + 2 x %d of context (%d given: %s)"
+                             % (self.frames, self.ctx, len(lengths), ", ".join(self.dropped[:10])))
+
+    def _rng(self, stream, n):
+        return np.random.default_rng([self.seed, stream, n])
+
+    def epoch(self, step):
+        """the epochs finished before step `step`'s last item"""
+        return (step * self.batch_size - 1) // len(self.utts)
+
+    def batch(self, step):
+        """-> [(utt index, f0)] of step `step` (1-based)"""
+        n, out = len(self.utts), []
+        starts = self._rng(2, step).random(self.batch_size)
+        for i in range(self.batch_size):
+            p = (step - 1) * self.batch_size + i
+            k = int(self._rng(1, p // n).permutation(n)[p % n])
+            lo, hi = self.ctx, self.utts[k][1] - self.ctx - self.frames
+            out.append((k, lo + min(int(starts[i] * (hi - lo + 1)), hi - lo)))
+        return out
+
+    def noise(self, step):
+        return self._rng(3, step).standard_normal((self.batch_size, 1, self.frames * self.hop), dtype=np.float32)
+
+    def valid(self, k):
+        """the one fixed window and noise of validation utterance k"""
+        lo, hi = self.ctx, self.utts[k][1] - self.ctx - self.frames
+        return lo + min(int(self._rng(4, k).random() * (hi - lo + 1)), hi - lo), self._rng(5, k).standard_normal((1, 1, self.frames * self.hop), dtype=np.float32)
+
+    def cut(self, mel, wav, f0):
+        """-> (mel window [frames + 2 ctx, n_mels], wav window [frames hop])"""
+        return mel[f0 - self.ctx : f0 + self.frames + self.ctx], wav[f0 * self.hop : (f0 + self.frames) * self.hop]
+
+
+class Corpus(object):
+    """mels/<utt>.npy and the wavs of a list of ids; lengths from the headers, T = samples // hop + 1 checked by id before the first device call"""
+
+    def __init__(self, ids, wavs, feature_root, fs, hop, n_mels):
+        self.fs, self.paths = fs, []
+        for u in ids:
+            if u not in wavs:
+                raise ValueError("%s: no wav for this utterance id" % u)
+            mp = os.path.join(feature_root, "mels", u + ".npy")
+            if not os.path.exists(mp):
+                raise ValueError("%s: %s does not exist" % (u, mp))
+            m = np.load(mp, mmap_mode="r")
+            L = XF.wav_samples(wavs[u], fs)
+            if m.ndim != 2 or m.shape[1] != n_mels or m.shape[0] != L // hop + 1:
+                raise ValueError("%s: a [%d, %d] mel expected for %d samples at hop %d, got %r" % (u, L // hop + 1, n_mels, L, hop, tuple(m.shape)))
+            self.paths.append((u, mp, wavs[u], int(m.shape[0])))
+        self.by_id = {p[0]: p for p in self.paths}
+
+    def lengths(self):
+        return [(u, T) for u, _, _, T in self.paths]
+
+    def load(self, u):
+        _, mp, wp, _ = self.by_id[u]
+        return np.load(mp).astype(np.float32), XF.read_wav(wp, self.fs)
+
+
+def checkpoint_of(gen, disc, opt, sch, steps, epochs):
+    return {"model": {"generator": gen.state_dict(), "discriminator": disc.state_dict()},
+            "optimizer": {"generator": opt["generator"].state_dict(), "discriminator": opt["discriminator"].state_dict()},
+            "scheduler": {"generator": sch["generator"].state_dict(), "discriminator": sch["discriminator"].state_dict()}, "steps": int(steps),
+            "epochs": int(epochs)}
+
+
+def check_resume(cfg, path):
+    """the config.yml beside a checkpoint against this run's values: a disagreement on a model or optimiser value is refused naming the key"""
+    import yaml
+
+    side = os.path.join(os.path.dirname(os.path.abspath(path)), "config.yml")
+    if not os.path.exists(side):
+        raise ValueError("fcl-taco2_amd: train_vocoder: --resume %s has no config.yml beside it" % path)
+    with open(side) as f:
+        old = yaml.safe_load(f) or {}
+    for k in PINNED:
+        if old.get(k) != json.loads(json.dumps(cfg[k])):
+            raise ValueError("fcl-taco2_amd: train_vocoder: --resume: %s is %r in %s and %r now" % (k, old.get(k), side, cfg[k]))
+
+
+def _read_ids(path):
+    with open(path) as f:
+        return [ln.split()[0] for ln in f if ln.strip()]
+
+
+class Trainer(object):
+    def __init__(self, cfg, device, ends="hip"):
+        from .pwg_discriminator import ParallelWaveGANDiscriminator
+        from .pwg_generator import TrainableParallelWaveGANGenerator
+        from .stft_loss import MultiResolutionSTFTLoss
+
+        self.cfg, self.dev, self.ends = cfg, device, ends
+        torch.manual_seed(cfg["seed"])  # (the initial weights)
+        self.gen = TrainableParallelWaveGANGenerator(**cfg["generator_params"]).to(device)
+        self.disc = ParallelWaveGANDiscriminator(**cfg["discriminator_params"]).to(device)
+        s = cfg["stft_loss_params"]
+        self.criterion = MultiResolutionSTFTLoss(device, tuple(s["fft_sizes"]), tuple(s["hop_sizes"]), tuple(s["win_lengths"]))
+        nets = {"generator": self.gen, "discriminator": self.disc}
+        self.opt = {k: torch.optim.RAdam(n.parameters(), **cfg[k + "_optimizer_params"]) for k, n in nets.items()}
+        self.sch = {k: torch.optim.lr_scheduler.StepLR(self.opt[k], **cfg[k + "_scheduler_params"]) for k in nets}
+        self.steps = 0
+
+    def load(self, path, models_only=False):
+        ck = torch.load(path, map_location=self.dev, weights_only=True)
+        self.gen.load_state_dict(ck["model"]["generator"])
+        self.disc.load_state_dict(ck["model"]["discriminator"])
+        if not models_only:
+            for k in self.opt:
+                self.opt[k].load_state_dict(ck["optimizer"][k])
+                self.sch[k].load_state_dict(ck["scheduler"][k])
+            self.steps = int(ck["steps"])
+
+    def _finite(self, step, **terms):
+        for k, v in terms.items():
+            if not math.isfinite(v):
+                raise FloatingPointError("fcl-taco2_amd: train_vocoder: step %d: %s is %r; no checkpoint of this step is written" % (step, k, v))
+
+    def losses(self, z, c, wav, adv):
+        """the generator's terms on one batch (the graph attached) -> (fake, {term: tensor})"""
+        from .pwg_discriminator import generator_adversarial_loss
+
+        fake = self.gen(z, c, ends=self.ends)
+        sc, mag = self.criterion(fake, wav)
+        terms = {"spectral_convergence_loss": sc, "log_stft_magnitude_loss": mag}
+        if adv:
+            # No discriminator weight gradient is computed in the generator's backward pass.  The parameters may be released again BEFORE backward():
+            # the discriminator's autograd function decides at forward time which gradients it owes (needs_input_grad), and its folded weights were
+            # formed while the parameters were frozen, so nothing on this graph leads to them (tested by the launch record: no pwd_dw* launch).
+            for p in self.disc.parameters():
+                p.requires_grad_(False)
+            terms["adversarial_loss"] = generator_adversarial_loss(self.disc(fake))
+            for p in self.disc.parameters():
+                p.requires_grad_(True)
+        return fake, terms
+
+    def step(self, z, c, wav):
+        """one step of parallel_wavegan's trainer -> {term or norm: float}"""
+        from .pwg_discriminator import discriminator_adversarial_loss
+
+        cfg, n = self.cfg, self.steps + 1
+        adv = adversarial(cfg, n)
+        _, terms = self.losses(z, c, wav, adv)
+        loss = terms["spectral_convergence_loss"] + terms["log_stft_magnitude_loss"]
+        if adv:
+            loss = loss + cfg["lambda_adv"] * terms["adversarial_loss"]
+        self.opt["generator"].zero_grad()
+        loss.backward()
+        out = {k: float(v.detach()) for k, v in terms.items()}
+        out["generator_grad_norm"] = float(torch.nn.utils.clip_grad_norm_(self.gen.parameters(), cfg["generator_grad_norm"]))
+        self._finite(n, **out)
+        self.opt["generator"].step()
+        self.sch["generator"].step()
+        if adv:
+            with torch.no_grad():
+                fake = self.gen(z, c, ends=self.ends)
+            real_loss, fake_loss = discriminator_adversarial_loss(self.disc(wav), self.disc(fake))
+            self.opt["discriminator"].zero_grad()
+            (real_loss + fake_loss).backward()
+            more = dict(real_loss=float(real_loss.detach()), fake_loss=float(fake_loss.detach()))
+            more["discriminator_grad_norm"] = float(torch.nn.utils.clip_grad_norm_(self.disc.parameters(), cfg["discriminator_grad_norm"]))
+            self._finite(n, **more)
+            out.update(more)
+            self.opt["discriminator"].step()
+            self.sch["discriminator"].step()
+        self.steps = n
+        return out
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
+    if (args.wav_dir is None) == (args.wav_scp is None) or not args.feature_root or not args.train_list:
+        ap.error("--wav-dir or --wav-scp (one of them), --feature-root and --train-list are needed")
+    if args.resume and args.pretrain:
+        ap.error("--resume and --pretrain are exclusive")
+    cfg = resolve(args)
+    if args.resume:
+        check_resume(cfg, args.resume)
+    gp = cfg["generator_params"]
+    hop, ctx, A, fs = cfg["hop_size"], gp["aux_context_window"], gp["aux_channels"], cfg["sampling_rate"]
+    frames, B = cfg["batch_max_steps"] // hop, cfg["batch_size"]
+    wavs = dict(XF.read_wav_list(args.wav_scp, args.wav_dir))
+    train = Corpus(_read_ids(args.train_list), wavs, args.feature_root, fs, hop, A)
+    sampler = Windows(train.lengths(), frames, ctx, hop, B, cfg["seed"])
+    for u in sampler.dropped:
+        logging.warning("%s: too short for one window of %d frames + 2 x %d of context; left out", u, frames, ctx)
+    valid = vsampler = None
+    if args.valid_list:
+        valid = Corpus(_read_ids(args.valid_list), wavs, args.feature_root, fs, hop, A)
+        try:
+            vsampler = Windows(valid.lengths(), frames, ctx, hop, 1, cfg["seed"])
+        except ValueError:
+            logging.warning("no validation utterance is long enough for one window: no evaluation lines")
+    import yaml
+
+    os.makedirs(args.outdir, exist_ok=True)
+    with open(os.path.join(args.outdir, "config.yml"), "w") as f:
+        yaml.safe_dump(json.loads(json.dumps(cfg)), f, sort_keys=False)
+    # ---- the first device call is below
+    dev = torch.device("cuda:0")
+    tr = Trainer(cfg, dev, args.ends)
+    if args.resume:
+        tr.load(args.resume)
+    elif args.pretrain:
+        tr.load(args.pretrain, models_only=True)
+    log = open(os.path.join(args.outdir, "train_log.jsonl"), "a")
+    write = lambda rec: (log.write(json.dumps(rec) + "\n"), log.flush())
+    if sampler.dropped:
+        write({"left_out": sampler.dropped})
+
+    def prepare(step):
+        """step's batch as pinned host tensors (z, c, wav), on the one host thread, while the step before it runs"""
+        c, w = np.empty((B, A, frames + 2 * ctx), np.float32), np.empty((B, 1, frames * hop), np.float32)
+        for i, (k, f0) in enumerate(sampler.batch(step)):
+            mel, wav = train.load(sampler.utts[k][0])
+            m, w[i, 0] = sampler.cut(mel, wav, f0)
+            c[i] = m.T
+        return tuple(torch.from_numpy(a).pin_memory() for a in (sampler.noise(step), c, w))
+
+    def evaluate(step):
+        sums, n = {}, 0
+        with torch.no_grad():
+            for k, (u, _) in enumerate(vsampler.utts):
+                mel, wav = valid.load(u)
+                f0, z = vsampler.valid(k)
+                m, w = vsampler.cut(mel, wav, f0)
+                _, terms = tr.losses(torch.from_numpy(z).to(dev), torch.from_numpy(np.ascontiguousarray(m.T[None])).to(dev),
+                                     torch.from_numpy(np.ascontiguousarray(w[None, None])).to(dev), adversarial(cfg, step))
+                for name, v in terms.items():
+                    sums[name] = sums.get(name, 0.0) + float(v)
+                n += 1
+        write(dict({"eval_" + k: v / n for k, v in sums.items()}, step=step, eval_windows=n))
+
+    acc, count, t0 = {}, 0, time.perf_counter()
+    with concurrent.futures.ThreadPoolExecutor(1) as pool:
+        nxt = pool.submit(prepare, tr.steps + 1) if tr.steps < cfg["train_max_steps"] else None
+        while tr.steps < cfg["train_max_steps"]:
+            n = tr.steps + 1
+            z, c, wav = (a.to(dev, non_blocking=True) for a in nxt.result())
+            nxt = pool.submit(prepare, n + 1) if n < cfg["train_max_steps"] else None
+            lrs = {k: tr.opt[k].param_groups[0]["lr"] for k in tr.opt}
+            out = tr.step(z, c, wav)
+            for k, v in out.items():
+                s, m = acc.get(k, (0.0, 0))
+                acc[k] = (s + v, m + 1)
+            count += 1
+            if n % cfg["log_interval_steps"] == 0:
+                torch.cuda.synchronize(dev)
+                dt = time.perf_counter() - t0
+                rec = dict({k: s / m for k, (s, m) in acc.items()}, step=n, generator_lr=lrs["generator"], discriminator_lr=lrs["discriminator"],
+                           ms_per_step=1e3 * dt / count, samples_per_second=count * B * frames * hop / dt)
+                for k in LOSS_TERMS[2:] + ("discriminator_grad_norm",):
+                    rec.setdefault(k, None)  # (before the discriminator starts)
+                write(rec)
+                logging.info("step %d: %s", n, json.dumps(rec))
+                acc, count, t0 = {}, 0, time.perf_counter()
+            if vsampler is not None and n % cfg["eval_interval_steps"] == 0:
+                evaluate(n)
+            if n % cfg["save_interval_steps"] == 0 or n == cfg["train_max_steps"]:
+                torch.save(checkpoint_of(tr.gen, tr.disc, tr.opt, tr.sch, n, sampler.epoch(n)), os.path.join(args.outdir, "checkpoint-%dsteps.pkl" % n))
+    log.close()
+    return tr
+
+
+if __name__ == "__main__":
+    main()

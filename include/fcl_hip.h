@@ -1386,6 +1386,79 @@ int fcl_pwt_block_fwd(const fcl_pwt_t* a, fcl_stream_t stream);
 int fcl_pwt_block_dx(const fcl_pwt_t* a, fcl_stream_t stream);
 int fcl_pwt_block_dw(const fcl_pwt_t* a, fcl_stream_t stream);
 
+/* ---- Parallel WaveGAN generator, the ends: what stands in front of the residual stack and behind it, forward and backward
+ *      (csrc/pwg_ends.hip; fcl_taco2_amd/pwg_generator.py; restated in float64 numpy in tests/pwge_ref.py).
+ * Layout: as above -- float32, channel-last, packed rows, utterances back to back.  Utterance b has F_b frames (frame_off [n_utt + 1], frame_off[0] = 0,
+ *      frames = frame_off[n_utt]) and F_b hop samples, hop = the product of scales[0 .. n_scales); seg_lo / seg_hi [samples] as above.  Its conditioning
+ *      c_b has F_b + 2 ctx rows, so c is [frames + 2 ctx n_utt, A].  R and A as above; ctx 0 .. 8; 1 .. 6 scales of 2 .. 16.
+ * Weights: w_in [(2 ctx + 1) A][A], row j A + ai = Win[:, ai, j] of torch's Conv1d (no bias); h[i] [2 s_i + 1] the stage's filter; w0, b0 [R] first_conv;
+ *      w1 [R][R] = W1^T (row: input channel), w1t [R][R] = W1 (row: output channel), b1 [R]; w3 [R], b3 [1] the last layer.
+ * fcl_pwe_in_fwd (pwe_convin_kernel, pwe_stage_kernel once per scale, pwe_first_kernel):
+ *      u[0][f, :] = sum_j c_b[f + j, :] Win_j  [frames, A];
+ *      u[i + 1][t, a] = sum_{j = 0 .. 2 s} h[i][j] u[i][(t + j - s) div s, a] over 0 <= t + j - s < s n_i of the utterance's own rows (s = scales[i]);
+ *      the last stage writes cu [samples, A], the rows the stack reads; u[0 .. n_scales) are KEPT for the backward pass.  x0[t, :] = z[t] w0 + b0.
+ * fcl_pwe_in_bwd: from dcu [samples, A] and dx0 [samples, R].  With dw_in (then dw0, db0 and every dh[i] too; all or none): dw0 = sum_t z[t] dx0[t, :],
+ *      db0 = sum_t dx0 (pwe_outer_kernel), dh[i][j] = sum_{t, a} u[i][(t + j - s) div s, a] du_{i + 1}[t, a] (pwe_dh_kernel), dw_in = sum_f c_run(f)^T du0[f]
+ *      (pwe_dwin_kernel), each as per-chunk partials that pwe_reduce_kernel adds in ascending chunk order.  With dz: dz[t] = dx0[t, :] . w0
+ *      (pwe_first_dz_kernel).  With dc: dc = the transposed conv_in of du0 (pwe_dc_kernel).  The gradients of the stage inputs (pwe_stage_bwd_kernel, the
+ *      transposed stretch and filter) are computed when weight gradients or dc are asked for and live in the workspace.
+ * fcl_pwe_out_fwd (pwe_out_kernel): y1 = relu(relu(sigma skips) W1 + b1) [samples, R], KEPT; wav[t] = y1[t, :] . w3 + b3.
+ * fcl_pwe_out_bwd (pwe_dy1_kernel, pwe_ds_kernel): dy1 = (dwav x w3) [y1 > 0] [samples, R]; ds = sigma (dy1 W1^T) [sigma skips > 0].  With dw1 (then db1,
+ *      dw3, db3 too; all or none): dw1 [R][R] = sum_t relu(sigma skips)^T dy1 (row: input channel), db1 = sum_t dy1 (pwe_dw_kernel<last>), dw3 = sum_t
+ *      dwav[t] y1[t, :], db3 = sum_t dwav (pwe_outer_kernel), reduced as above.
+ * Exact fp32, no atomics, two runs give the same bits.  Every entry validates before any HIP call (FCL_ERR_INVALID / _SHAPE / _ALIGN / _WORKSPACE as
+ *      above); none allocates, synchronises or copies.  fcl_pwe_workspace_bytes: what the backward entries ask for at the struct's sizes. */
+typedef struct {
+    int64_t samples;
+    int32_t frames, n_utt;
+    int32_t residual, aux, ctx, n_scales;
+    int32_t scales[6];
+    float sigma;           /* sqrt(1 / layers): the output side */
+    int32_t reserved;
+    const int32_t* seg_lo;
+    const int32_t* seg_hi;
+    const int32_t* frame_off;
+    const float* c;
+    const float* z;        /* [samples] */
+    const float* w_in;
+    const float* h[6];
+    const float* w0;
+    const float* b0;
+    float* u[6];           /* u[i] [frames s_0 .. s_{i-1}, A]: written by in_fwd, read by in_bwd */
+    float* cu;             /* [samples, A] */
+    float* x0;             /* [samples, R] */
+    const float* dcu;      /* [samples, A] */
+    const float* dx0;      /* [samples, R] */
+    float* dh[6];          /* or null: no weight gradient of the input side */
+    float* dw_in;
+    float* dw0;
+    float* db0;
+    float* dc;             /* [frames + 2 ctx n_utt, A] or null: not computed */
+    float* dz;             /* [samples] or null: not computed */
+    const float* skips;    /* [samples, R] the stack's un-scaled skip sum */
+    const float* w1;
+    const float* w1t;
+    const float* b1;
+    const float* w3;
+    const float* b3;
+    float* y1;             /* [samples, R] written by out_fwd, read by out_bwd */
+    float* wav;            /* [samples] */
+    const float* dwav;     /* [samples] */
+    float* dy1;            /* [samples, R] written by out_bwd */
+    float* ds;             /* [samples, R] */
+    float* dw1;            /* or null: no weight gradient of the output side */
+    float* db1;
+    float* dw3;
+    float* db3;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_pwe_t;
+size_t fcl_pwe_workspace_bytes(const fcl_pwe_t* a);
+int fcl_pwe_in_fwd(const fcl_pwe_t* a, fcl_stream_t stream);
+int fcl_pwe_in_bwd(const fcl_pwe_t* a, fcl_stream_t stream);
+int fcl_pwe_out_fwd(const fcl_pwe_t* a, fcl_stream_t stream);
+int fcl_pwe_out_bwd(const fcl_pwe_t* a, fcl_stream_t stream);
+
 /* ---- the input feed of a capacity graph (..._kd_student.py:821-843: what inference() receives per call) -------------------------------------
  * fcl_feed_copy: ONE kernel that copies `bytes` (a multiple of 16) from pinned, mapped host memory (`src`: the DEVICE view of the block,
  * fcl_host_device_ptr) to `dst`, then increments *seq_dev, stores the new value to *seq_host (device view of a pinned word) and, when given,

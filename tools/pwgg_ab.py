@@ -8,7 +8,15 @@ the same random weights on both legs, no weight norm on either.
 Three cases per leg: the forward pass alone (no_grad); forward + backward (every parameter's gradient); forward + backward + one Adam step.  One
 process, alternating legs, event timers, a synchronise at each end, medians.  Prints one JSON line.
 
-    python tools/pwgg_ab.py [--batch 6] [--frames 100] [--repeats 20] [--warmup 3] [--prof] [--dump PATH]
+    python tools/pwgg_ab.py [--batch 6] [--frames 100] [--repeats 20] [--warmup 3] [--prof] [--dump PATH] [--ends]
+
+--ends times two other legs by the same protocol, two copies of leg B's module that differ in the generator's ends alone:
+
+  T  forward(z, c, ends="torch"): the upsampling network, first_conv and the last layers as torch operations (the path before the pwe_* kernels)
+  H  forward(z, c, ends="hip"):   the same in the pwe_* kernels of csrc/pwg_ends.hip
+
+and adds `outside_ms`, a by-operation account of the host-side work around the kernels at this geometry (medians of the same number of rounds): the
+weight-norm folds of a weight-norm module, pack_weights, and unpack_dweights.
 
 --dump PATH saves leg B's waveform and every parameter's gradient of this fixed-seed run (before any Adam step) as PATH (.npy, one float32 vector): two
 builds of the library computed the same bits where np.array_equal of their dumps holds -- apart from the gradients of first_conv and the upsampling
@@ -43,6 +51,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prof", action="store_true", help="also one profiled forward + backward of leg B: per-kernel ms and TFLOP/s from the library's launch record")
+    ap.add_argument("--ends", action="store_true", help="time the module with torch ends against the module with HIP ends (legs T and H) instead of A and B")
     ap.add_argument("--dump", metavar="PATH", help="save leg B's waveform and all gradients of the fixed-seed run as one .npy vector")
     args = ap.parse_args()
     import fcl_taco2_amd  # noqa: F401
@@ -63,6 +72,15 @@ def main():
     opt = {"A_eager_f32": torch.optim.Adam(list(eager.values()), 1e-4), "B_hip": torch.optim.Adam(hip.parameters(), 1e-4)}
     run = {"A_eager_f32": lambda: O.generator_forward(eager, z, O.upsample(eager, c)), "B_hip": lambda: hip(z, c)}
     params = {"A_eager_f32": list(eager.values()), "B_hip": list(hip.parameters())}
+    first, second = "A_eager_f32", "B_hip"
+    if args.ends:
+        import copy
+
+        other = copy.deepcopy(hip)
+        first, second = "T_torch_ends", "H_hip_ends"
+        opt = {first: torch.optim.Adam(other.parameters(), 1e-4), second: opt["B_hip"]}
+        run = {first: lambda: other(z, c, ends="torch"), second: lambda: hip(z, c, ends="hip")}
+        params = {first: list(other.parameters()), second: list(hip.parameters())}
 
     def forward(leg):
         with torch.no_grad():
@@ -83,13 +101,13 @@ def main():
     # the two legs compute the same waveform and gradients (before any Adam step moves them apart)
     rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
     out = dict(batch=args.batch, samples=T, repeats=args.repeats)
-    ga, gb = backward("A_eager_f32"), backward("B_hip")
+    ga, gb = backward(first), backward(second)
     dead = [i for i, (k, _) in enumerate(hip.named_parameters()) if k.startswith("conv_layers.%d.conv1x1_out" % (hip.config["layers"] - 1))]
-    out["max_rel_B_minus_A"] = dict(waveform=rel(forward("B_hip"), forward("A_eager_f32")),
+    out["max_rel_H_minus_T" if args.ends else "max_rel_B_minus_A"] = dict(waveform=rel(forward(second), forward(first)),
                                     gradients=max(rel(b, a) for i, (a, b) in enumerate(zip(ga, gb)) if i not in dead),
                                     last_block_out_gradient_zero=all(not gb[i].any() and (ga[i] is None or not ga[i].any()) for i in dead))
     if args.dump:
-        np.save(args.dump, torch.cat([v.detach().reshape(-1) for v in [forward("B_hip")] + gb]).cpu().numpy())
+        np.save(args.dump, torch.cat([v.detach().reshape(-1) for v in [forward(second)] + gb]).cpu().numpy())
     times = {k: [] for k in legs}
     for _ in range(args.warmup):
         for fn in legs.values():
@@ -100,16 +118,31 @@ def main():
             times[k].append(timed(fn, dev)[0])
     med = {k: round(float(np.median(v)), 3) for k, v in times.items()}
     out.update(median_ms=med, min_ms={k: round(float(np.min(v)), 3) for k, v in times.items()},
-               A_over_B={c_: round(med[c_ + "/A_eager_f32"] / med[c_ + "/B_hip"], 3) for c_ in cases})
+               spread_ms={k: round(float(np.percentile(v, 75) - np.percentile(v, 25)), 3) for k, v in times.items()},
+               **{"T_over_H" if args.ends else "A_over_B": {c_: round(med[c_ + "/" + first] / med[c_ + "/" + second], 3) for c_ in cases}})
     if args.prof:
         _lib.prof_enable(True)
-        backward("B_hip")
+        backward(second)
         torch.cuda.synchronize(dev)
         rec = _lib.prof_collect()
         _lib.prof_enable(False)
         out["kernels"] = {k: dict(launches=v["launches"], ms=round(v["ms"], 3), tflops=round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2),
-                                  of_ceiling=round(v["flops"] / max(v["ms"], 1e-9) / 1e9 / CEILING_TFLOPS, 3)) for k, v in rec.items() if k.startswith("pwt_")}
+                                  of_ceiling=round(v["flops"] / max(v["ms"], 1e-9) / 1e9 / CEILING_TFLOPS, 3)) for k, v in rec.items() if k.startswith(("pwt_", "pwe_"))}
         out["kept_bytes"] = hip.plan().kept_bytes(args.batch * T)
+    if args.ends:
+        wn = G.TrainableParallelWaveGANGenerator(use_weight_norm=True).to(dev)
+        plan, plain = hip.plan(), [blk.plain() for blk in hip.conv_layers]
+        dws = [tuple(torch.empty(s_, device=dev) for s_ in plan.dweight_shapes()) for _ in plain]
+        ops_ = dict(weight_norm_folds=lambda: [m.folded() for _, m in wn.convs()], pack_weights=lambda: G.pack_weights(plain),
+                    unpack_dweights=lambda: [G.unpack_dweights(plan, *d) for d in dws])
+        acc = {k: [] for k in ops_}
+        for r in range(args.warmup + args.repeats):
+            for k, fn in ops_.items():
+                ms = timed(fn, dev)[0]
+                if r >= args.warmup:
+                    acc[k].append(ms)
+        out["outside_ms"] = {k: round(float(np.median(v)), 3) for k, v in acc.items()}
+        out["outside_ms"]["folded_convolutions"] = len(wn.convs())
     print(json.dumps(out))
 
 
