@@ -165,6 +165,16 @@ class PwtBlock(C.Structure):  # fcl_pwt_t
                           "w_dc", "dz", "dx", "dc", "dw_gate", "db_gate", "dw_out", "db_out", "workspace")] + [("workspace_bytes", _Z)]
 
 
+class HftConv(C.Structure):  # fcl_hft_conv_t
+    _fields_ = [("rows", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "ksize", "dilation", "lrelu")] + [("slope", _F)] + [
+        (n, _P) for n in ("seg_lo", "seg_hi", "x", "w", "bias", "res", "pre", "y", "g", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
+
+
+class HftTconv(C.Structure):  # fcl_hft_tconv_t
+    _fields_ = [("rows", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "stride")] + [("slope", _F)] + [
+        (n, _P) for n in ("seg_lo", "seg_hi", "c", "w", "bias", "u", "du", "dc", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
+
+
 class PweEnds(C.Structure):  # fcl_pwe_t
     _fields_ = [("samples", C.c_int64)] + [(n, C.c_int32) for n in ("frames", "n_utt", "residual", "aux", "ctx", "n_scales")] + [
         ("scales", C.c_int32 * 6), ("sigma", _F), ("reserved", C.c_int32)] + [(n, _P) for n in ("seg_lo", "seg_hi", "frame_off", "c", "z", "w_in")] + [
@@ -362,6 +372,14 @@ SIGNATURES = {
     "fcl_pwt_block_fwd": (_I, [C.POINTER(PwtBlock), _P]),
     "fcl_pwt_block_dx": (_I, [C.POINTER(PwtBlock), _P]),
     "fcl_pwt_block_dw": (_I, [C.POINTER(PwtBlock), _P]),
+    "fcl_hft_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I, _I]),
+    "fcl_hft_conv_fwd": (_I, [C.POINTER(HftConv), _P]),
+    "fcl_hft_conv_dx": (_I, [C.POINTER(HftConv), _P]),
+    "fcl_hft_conv_dw": (_I, [C.POINTER(HftConv), _P]),
+    "fcl_hft_tconv_fwd": (_I, [C.POINTER(HftTconv), _P]),
+    "fcl_hft_tconv_dx": (_I, [C.POINTER(HftTconv), _P]),
+    "fcl_hft_tconv_dw": (_I, [C.POINTER(HftTconv), _P]),
+    "fcl_hft_sum": (_I, [_P, C.POINTER(_P), _I, _F, C.c_int64, _P]),
     "fcl_pwe_workspace_bytes": (_Z, [C.POINTER(PweEnds)]),
     "fcl_pwe_in_fwd": (_I, [C.POINTER(PweEnds), _P]),
     "fcl_pwe_in_bwd": (_I, [C.POINTER(PweEnds), _P]),

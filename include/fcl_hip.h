@@ -1386,6 +1386,79 @@ int fcl_pwt_block_fwd(const fcl_pwt_t* a, fcl_stream_t stream);
 int fcl_pwt_block_dx(const fcl_pwt_t* a, fcl_stream_t stream);
 int fcl_pwt_block_dw(const fcl_pwt_t* a, fcl_stream_t stream);
 
+/* ---- HiFi-GAN generator, training form: the upsampling stages' launches, forward (pre-activations kept) and backward
+ *      (csrc/hifigan_train.hip; fcl_taco2_amd/hifigan_generator.py; restated in float64 numpy in tests/hfgt_ref.py).
+ * Layout: as the Parallel WaveGAN training entries -- float32, channel-last, packed [rows, C], utterances back to back, row t's utterance is
+ *      [seg_lo[t], seg_hi[t]) and a tap outside it contributes zero.  LeakyReLU: l(v) = v > 0 ? v : slope v, formed on load; its backward mask
+ *      m(v) = v > 0 ? 1 : slope is read from the stored pre-activation (v == 0 takes the slope).
+ *
+ * fcl_hft_conv_t, one convolution of cin -> cout channels, k in (1, 3, 5, 7, 11) taps at `dilation`, tap j at row t + (j - (k - 1) / 2) dilation;
+ *      w [k][cin][cout] tap-major (row j cin + ci = W[:, ci, j] of torch's Conv1d for fwd; for dx the taps reversed and W transposed):
+ *   fcl_hft_conv_fwd (hft_conv_kernel):  y = bias + sum_j op(x)[row_j] w_j (+ res when res is given), op = l when lrelu, else the identity;
+ *   fcl_hft_conv_dx (hft_conv_dx_kernel): y = m(pre) * sum_j x[row_j] w_j + res; x is the OUTPUT gradient [rows, cin], the operand is taken as stored;
+ *      pre null: no mask; res null: no carry.  res may be y itself.
+ *   fcl_hft_conv_dw (hft_dw_kernel, hft_dw_reduce_kernel): dw [k][cin][cout] = sum_t op(x)[row_j]^T g[t] in the forward weights' layout and
+ *      db [cout] = sum_t g[t], as per-chunk partials of 1 024 rows in the workspace added in ascending chunk order by the second launch.
+ * fcl_hft_tconv_t, the transposed convolution of stride s, kernel 2 s, padding s / 2 + s % 2, output padding s % 2; rows and the tables are at the INPUT
+ *      rate, u and du have rows x s rows.  Output row s q + p reads, with ph = (p + padding) % s and q1 = q + (p + padding) / s, l(c)[q1] W[:, :, ph] and
+ *      l(c)[q1 - 1] W[:, :, ph + s]:
+ *   fcl_hft_tconv_fwd (hft_tconv_kernel): w [s][2][cin][cout], phase ph holds (W[:, :, ph + s] ; W[:, :, ph]);
+ *   fcl_hft_tconv_dx (hft_tconv_dx_kernel): dc[q] = m(c[q]) * sum_j du[s q + j - padding] w_j, w [2 s][cout][cin] = W[:, :, j]^T (gather form);
+ *   fcl_hft_tconv_dw (hft_tconv_dw_kernel, hft_dw_reduce_kernel): dw [2 s][cin][cout], db [cout]; partials of 1 024 / s input rows (a multiple of 32).
+ * fcl_hft_sum (hft_sum_kernel): out = scale (terms[0] + terms[1] + ..) in ascending order, 1 to 4 terms of `elems` floats (a multiple of 4); `terms` is
+ *      a host array of device pointers.  The stage's output (1 / nk) sum x_last, the backward seed dc / nk and du = the sum of the blocks' dx.
+ * fcl_hft_workspace_bytes(rows, cin, cout, taps, stride): stride 1 for a convolution of `taps`, s (with taps = 2 s) for the transposed convolution.
+ *
+ * Exact fp32 on v_mfma_f32_16x16x4_f32; no atomics; two passes give the same bits; a batch's activations and input gradients are bit for bit those of
+ *      its utterances alone.  Every entry validates before any HIP call: a null pointer or a slope outside [0, 1) FCL_ERR_INVALID; channels (multiples of
+ *      16 from 16 to 512), kernel size, stride (2 .. 16), dilation or rows (rows x stride below 2^31) out of range FCL_ERR_SHAPE; an activation,
+ *      gradient, weight or workspace pointer not 16-byte aligned FCL_ERR_ALIGN; a workspace that is too small FCL_ERR_WORKSPACE.  No entry allocates,
+ *      synchronises or copies. */
+typedef struct {
+    int64_t rows;
+    int32_t cin, cout, ksize, dilation;
+    int32_t lrelu;         /* fwd, dw: 1 = the operand is l(x) */
+    float slope;
+    const int32_t* seg_lo;
+    const int32_t* seg_hi;
+    const float* x;        /* [rows, cin] */
+    const float* w;        /* [ksize][cin][cout] */
+    const float* bias;     /* [cout] (fwd) */
+    const float* res;      /* [rows, cout] or null */
+    const float* pre;      /* [rows, cout] or null (dx) */
+    float* y;              /* [rows, cout] */
+    const float* g;        /* [rows, cout] (dw) */
+    float* dw;
+    float* db;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_hft_conv_t;
+typedef struct {
+    int64_t rows;          /* input rows */
+    int32_t cin, cout, stride;
+    float slope;
+    const int32_t* seg_lo; /* [rows] */
+    const int32_t* seg_hi;
+    const float* c;        /* [rows, cin] the stage's input, a pre-activation */
+    const float* w;
+    const float* bias;     /* [cout] (fwd) */
+    float* u;              /* [rows stride, cout] (fwd) */
+    const float* du;       /* [rows stride, cout] (dx, dw) */
+    float* dc;             /* [rows, cin] (dx) */
+    float* dw;
+    float* db;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_hft_tconv_t;
+size_t fcl_hft_workspace_bytes(int64_t rows, int cin, int cout, int taps, int stride);
+int fcl_hft_conv_fwd(const fcl_hft_conv_t* a, fcl_stream_t stream);
+int fcl_hft_conv_dx(const fcl_hft_conv_t* a, fcl_stream_t stream);
+int fcl_hft_conv_dw(const fcl_hft_conv_t* a, fcl_stream_t stream);
+int fcl_hft_tconv_fwd(const fcl_hft_tconv_t* a, fcl_stream_t stream);
+int fcl_hft_tconv_dx(const fcl_hft_tconv_t* a, fcl_stream_t stream);
+int fcl_hft_tconv_dw(const fcl_hft_tconv_t* a, fcl_stream_t stream);
+int fcl_hft_sum(float* out, const float* const* terms, int count, float scale, int64_t elems, fcl_stream_t stream);
+
 /* ---- Parallel WaveGAN generator, the ends: what stands in front of the residual stack and behind it, forward and backward
  *      (csrc/pwg_ends.hip; fcl_taco2_amd/pwg_generator.py; restated in float64 numpy in tests/pwge_ref.py).
  * Layout: as above -- float32, channel-last, packed rows, utterances back to back.  Utterance b has F_b frames (frame_off [n_utt + 1], frame_off[0] = 0,
