@@ -175,6 +175,11 @@ class HftTconv(C.Structure):  # fcl_hft_tconv_t
         (n, _P) for n in ("seg_lo", "seg_hi", "c", "w", "bias", "u", "du", "dc", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
 
 
+class HpdLayer(C.Structure):  # fcl_hpd_t
+    _fields_ = [("rows_in", C.c_int64), ("rows_out", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "ksize", "stride", "pad")] + [("slope", _F)] + [
+        (n, _P) for n in ("src", "in_lo", "in_hi", "x", "w", "bias", "h", "g", "extra", "y", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
+
+
 class PweEnds(C.Structure):  # fcl_pwe_t
     _fields_ = [("samples", C.c_int64)] + [(n, C.c_int32) for n in ("frames", "n_utt", "residual", "aux", "ctx", "n_scales")] + [
         ("scales", C.c_int32 * 6), ("sigma", _F), ("reserved", C.c_int32)] + [(n, _P) for n in ("seg_lo", "seg_hi", "frame_off", "c", "z", "w_in")] + [
@@ -380,6 +385,10 @@ SIGNATURES = {
     "fcl_hft_tconv_dx": (_I, [C.POINTER(HftTconv), _P]),
     "fcl_hft_tconv_dw": (_I, [C.POINTER(HftTconv), _P]),
     "fcl_hft_sum": (_I, [_P, C.POINTER(_P), _I, _F, C.c_int64, _P]),
+    "fcl_hpd_dw_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I]),
+    "fcl_hpd_layer_fwd": (_I, [C.POINTER(HpdLayer), _P]),
+    "fcl_hpd_layer_dx": (_I, [C.POINTER(HpdLayer), _P]),
+    "fcl_hpd_layer_dw": (_I, [C.POINTER(HpdLayer), _P]),
     "fcl_pwe_workspace_bytes": (_Z, [C.POINTER(PweEnds)]),
     "fcl_pwe_in_fwd": (_I, [C.POINTER(PweEnds), _P]),
     "fcl_pwe_in_bwd": (_I, [C.POINTER(PweEnds), _P]),

@@ -1459,6 +1459,56 @@ int fcl_hft_tconv_dx(const fcl_hft_tconv_t* a, fcl_stream_t stream);
 int fcl_hft_tconv_dw(const fcl_hft_tconv_t* a, fcl_stream_t stream);
 int fcl_hft_sum(float* out, const float* const* terms, int count, float scale, int64_t elems, fcl_stream_t stream);
 
+/* ---- HiFi-GAN period discriminator: a stack of strided (k, 1) Conv2d + LeakyReLU on the waveform folded by its period, one layer per call, forward and
+ *      backward (csrc/hifigan_disc.hip; fcl_taco2_amd/hifigan_discriminator.py; restated in float64 numpy in tests/hfgd_ref.py).
+ * Layout: float32, channel-last, packed [rows, C].  For period p an utterance becomes p segments (segment q holds the samples h p + q), the segments lie
+ *      back to back, and the (k, 1) convolution is a 1-D convolution along each segment.  Every level has its own row count; the geometry comes from
+ *      three int32 tables at the rate of the layer's OUTPUT rows: src[t] = the input row under the kernel's centre (the segment's first input row +
+ *      stride x the row's index in its segment), [in_lo[t], in_hi[t]) the input segment (clamped to [0, rows_in] by the kernels).  Tap j of output row t
+ *      reads input row src[t] + j - pad; outside the segment it reads zero.  The output segment of row t follows from the tables: it starts
+ *      (src[t] - in_lo[t]) / stride rows before t and holds (in_hi[t] - in_lo[t] + 2 pad - ksize) / stride + 1 rows.
+ * A layer is 1 -> C (the first), C -> C' or C -> 1 (the score layer), C, C' multiples of 16 from 16 to 1024.  The first and the C -> C' layers have
+ *      ksize 3 or 5, pad (ksize - 1) / 2, stride 1 to 4, and LeakyReLU(slope); the score layer has ksize 2 or 3, pad 1, stride 1 and no activation (with
+ *      2 taps a segment of H rows gives H + 1 scores).  Weights are tap-major: wf [ksize][cin][cout], wf[j][ci][co] = W[co][ci][j][0] of torch's Conv2d.
+ * fcl_hpd_layer_fwd: y[t, co] = act(bias[co] + sum_j sum_ci x[src[t] + j - pad, ci] wf[j][ci][co]); w = wf, bias optional, x [rows_in, cin], y [rows_out, cout].
+ * fcl_hpd_layer_dx: y[h, ci] = m(hin[h, ci]) (sum over the taps j and output rows o of h's segment with stride o + j - pad == h of
+ *      g[o, co] W[co][ci][j] + extra[h, ci]): the gradient of the PRE-activation of the layer below.  g [rows_out, cout] is the gradient of this layer's
+ *      pre-activation; h = hin [rows_in, cin] the stored post-activation of this layer's input, m = 1 where hin > 0, else slope (0 takes the slope, as
+ *      torch does); extra [rows_in, cin] (optional) the gradient that reaches that feature map directly.  Every row of y is written.  w: for C -> C' the
+ *      per-phase form wb [stride][ceil(ksize / stride)][cout][cin], wb[ph][i][co][ci] = W[co][ci][(ph + pad) % stride + stride i] (zero where that is
+ *      no tap); for the first and the score layer w = wf.  The first layer (cin 1) has no mask: h and extra must be null, y [rows_in] is the
+ *      waveform gradient.
+ * fcl_hpd_layer_dw: dw [ksize][cin][cout] (the layout of wf) = sum_t x[src[t] + j - pad, ci] g[t, co]; db [cout] = sum_t g[t, co] (optional).  Each chunk of
+ *      1024 output rows leaves a partial in the workspace (fcl_hpd_dw_workspace_bytes); a second launch adds them in ascending order.  No atomics
+ *      anywhere: two runs give the same bits, and a batch's maps and input gradients are bit for bit those of its per-utterance runs.
+ * One arithmetic mode, exact fp32: the C -> C' contractions run on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain), the rest on fmaf.  Every entry
+ *      validates before any HIP call: a null pointer or a slope outside [0, 1) FCL_ERR_INVALID; channels, ksize, stride, pad or rows (1 .. 2^31 - 1)
+ *      out of range FCL_ERR_SHAPE; x, g, w, h, extra, y not 16-byte aligned FCL_ERR_ALIGN; a workspace that is too small FCL_ERR_WORKSPACE.  No entry
+ *      allocates, synchronises or copies. */
+typedef struct {
+    int64_t rows_in, rows_out;
+    int32_t cin, cout, ksize, stride, pad;
+    float slope;
+    const int32_t* src;
+    const int32_t* in_lo;
+    const int32_t* in_hi;
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* h;
+    const float* g;
+    const float* extra;
+    float* y;
+    float* dw;
+    float* db;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_hpd_t;
+size_t fcl_hpd_dw_workspace_bytes(int64_t rows_out, int cin, int cout, int ksize);
+int fcl_hpd_layer_fwd(const fcl_hpd_t* a, fcl_stream_t stream);
+int fcl_hpd_layer_dx(const fcl_hpd_t* a, fcl_stream_t stream);
+int fcl_hpd_layer_dw(const fcl_hpd_t* a, fcl_stream_t stream);
+
 /* ---- Parallel WaveGAN generator, the ends: what stands in front of the residual stack and behind it, forward and backward
  *      (csrc/pwg_ends.hip; fcl_taco2_amd/pwg_generator.py; restated in float64 numpy in tests/pwge_ref.py).
  * Layout: as above -- float32, channel-last, packed rows, utterances back to back.  Utterance b has F_b frames (frame_off [n_utt + 1], frame_off[0] = 0,
