@@ -180,6 +180,12 @@ class HpdLayer(C.Structure):  # fcl_hpd_t
         (n, _P) for n in ("src", "in_lo", "in_hi", "x", "w", "bias", "h", "g", "extra", "y", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
 
 
+class HsdLayer(C.Structure):  # fcl_hsd_t
+    _fields_ = [("rows_in", C.c_int64), ("rows_out", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "groups", "ksize", "stride", "pad")] + [
+        ("slope", _F)] + [(n, _P) for n in ("src", "in_lo", "in_hi", "x", "w", "bias", "h", "g", "extra", "y", "dw", "db", "workspace")] + [
+        ("workspace_bytes", _Z)]
+
+
 class PweEnds(C.Structure):  # fcl_pwe_t
     _fields_ = [("samples", C.c_int64)] + [(n, C.c_int32) for n in ("frames", "n_utt", "residual", "aux", "ctx", "n_scales")] + [
         ("scales", C.c_int32 * 6), ("sigma", _F), ("reserved", C.c_int32)] + [(n, _P) for n in ("seg_lo", "seg_hi", "frame_off", "c", "z", "w_in")] + [
@@ -389,6 +395,12 @@ SIGNATURES = {
     "fcl_hpd_layer_fwd": (_I, [C.POINTER(HpdLayer), _P]),
     "fcl_hpd_layer_dx": (_I, [C.POINTER(HpdLayer), _P]),
     "fcl_hpd_layer_dw": (_I, [C.POINTER(HpdLayer), _P]),
+    "fcl_hsd_dw_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I, _I]),
+    "fcl_hsd_layer_fwd": (_I, [C.POINTER(HsdLayer), _P]),
+    "fcl_hsd_layer_dx": (_I, [C.POINTER(HsdLayer), _P]),
+    "fcl_hsd_layer_dw": (_I, [C.POINTER(HsdLayer), _P]),
+    "fcl_hsd_pool_fwd": (_I, [_P, _P, _P, _P, _I, C.c_int64, C.c_int64, _P]),
+    "fcl_hsd_pool_dx": (_I, [_P, _P, _P, _P, _I, C.c_int64, C.c_int64, _P]),
     "fcl_pwe_workspace_bytes": (_Z, [C.POINTER(PweEnds)]),
     "fcl_pwe_in_fwd": (_I, [C.POINTER(PweEnds), _P]),
     "fcl_pwe_in_bwd": (_I, [C.POINTER(PweEnds), _P]),

@@ -1509,6 +1509,53 @@ int fcl_hpd_layer_fwd(const fcl_hpd_t* a, fcl_stream_t stream);
 int fcl_hpd_layer_dx(const fcl_hpd_t* a, fcl_stream_t stream);
 int fcl_hpd_layer_dw(const fcl_hpd_t* a, fcl_stream_t stream);
 
+/* ---- HiFi-GAN scale discriminator: grouped, strided 1-D convolutions + LeakyReLU on the waveform pooled 0, 1, 2, .. times, one layer per call, forward and
+ *      backward, and the pooling with its adjoint (csrc/hifigan_sdisc.hip; fcl_taco2_amd/hifigan_scale_discriminator.py; restated in float64
+ *      numpy in tests/hfgs_ref.py).
+ * Layout and geometry as the period discriminator's above: float32, channel-last, packed [rows, C], the three int32 tables at the rate of the layer's
+ *      OUTPUT rows; a segment is an utterance here.  Tap j of output row t reads input row src[t] + j - pad; outside the utterance it reads zero.
+ * A layer is either the first (cin 1, groups 1, cout a multiple of 16 up to 1024, ksize odd from 3 to 15) or grouped (cin, cout multiples of 16 up to 1024,
+ *      groups >= 1 dividing both, cout / groups a multiple of 16, cin / groups a multiple of 8, ksize odd from 3 to 41); pad (ksize - 1) / 2, stride 1 to 4,
+ *      LeakyReLU(slope).  Output channel co belongs to group co / (cout / groups) and reads the input channels [g cin / groups, (g + 1) cin / groups).  The
+ *      dense ksize 3 or 5 layer and the score layer (C -> 1) of a scale discriminator are fcl_hpd_* layers.
+ *      Weights are tap-major: wf [ksize][cin / groups][cout], wf[j][c][co] = W[co][c][j] of torch's Conv1d(groups=).
+ * fcl_hsd_layer_fwd: y[t, co] = lrelu(bias[co] + sum_j sum_c x[src[t] + j - pad, g(co) cin / groups + c] wf[j][c][co]); bias optional.
+ * fcl_hsd_layer_dx: as fcl_hpd_layer_dx, y = m(hin) (adjoint + extra); w for a grouped layer is the per-phase form
+ *      wb [stride][ceil(ksize / stride)][cout / groups][cin], wb[ph][i][o][ci] = W[g(ci) cout / groups + o][ci mod (cin / groups)][(ph + pad) % stride + stride i]
+ *      (zero where that is no tap); for the first layer w = wf, h and extra must be null and y [rows_in] is the waveform gradient.  Every row is written once.
+ * fcl_hsd_layer_dw: dw [ksize][cin / groups][cout] (the layout of wf), db [cout] (optional); chunked partials over 1024 output rows in the workspace
+ *      (fcl_hsd_dw_workspace_bytes: chunks x (ksize cin / groups + 1) x cout floats), added in ascending order by a second launch.
+ * fcl_hsd_pool_fwd: AvgPool1d(4, 2, padding 2) per utterance: y[n] = (x[2n - 2] + x[2n - 1] + x[2n] + x[2n + 1]) / 4 for n = 0 .. T / 2 (T / 2 + 1 outputs), zeros
+ *      outside the utterance, the pad counted in the divisor.  in_off / out_off [n_utt + 1] int32: the utterances' first rows in x and y, the last entry
+ *      rows_in / rows_out.  fcl_hsd_pool_dx: the adjoint in gather form, dx[m] = (g[m / 2] + g[m / 2 + 1]) / 4, the second term where m / 2 + 1 <= T / 2.
+ * Exact fp32, no atomics, error classes as above (a null pointer or a bad slope FCL_ERR_INVALID; channels, groups, ksize, stride, pad, rows or n_utt out of
+ *      range FCL_ERR_SHAPE; misaligned x, g, w, h, extra, y FCL_ERR_ALIGN; a small workspace FCL_ERR_WORKSPACE), checked before any HIP call. */
+typedef struct {
+    int64_t rows_in, rows_out;
+    int32_t cin, cout, groups, ksize, stride, pad;
+    float slope;
+    const int32_t* src;
+    const int32_t* in_lo;
+    const int32_t* in_hi;
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* h;
+    const float* g;
+    const float* extra;
+    float* y;
+    float* dw;
+    float* db;
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_hsd_t;
+size_t fcl_hsd_dw_workspace_bytes(int64_t rows_out, int cin, int cout, int groups, int ksize);
+int fcl_hsd_layer_fwd(const fcl_hsd_t* a, fcl_stream_t stream);
+int fcl_hsd_layer_dx(const fcl_hsd_t* a, fcl_stream_t stream);
+int fcl_hsd_layer_dw(const fcl_hsd_t* a, fcl_stream_t stream);
+int fcl_hsd_pool_fwd(const float* x, float* y, const int32_t* in_off, const int32_t* out_off, int n_utt, int64_t rows_in, int64_t rows_out, fcl_stream_t stream);
+int fcl_hsd_pool_dx(const float* g, float* dx, const int32_t* in_off, const int32_t* out_off, int n_utt, int64_t rows_in, int64_t rows_out, fcl_stream_t stream);
+
 /* ---- Parallel WaveGAN generator, the ends: what stands in front of the residual stack and behind it, forward and backward
  *      (csrc/pwg_ends.hip; fcl_taco2_amd/pwg_generator.py; restated in float64 numpy in tests/pwge_ref.py).
  * Layout: as above -- float32, channel-last, packed rows, utterances back to back.  Utterance b has F_b frames (frame_off [n_utt + 1], frame_off[0] = 0,
