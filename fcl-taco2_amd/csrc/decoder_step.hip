@@ -11,6 +11,8 @@
 //     * feat_prenet_x3_kernel                       bf16x3 planes, W fragments streamed (any shape)
 //     * feat_prenet_split_kernel<Ops, DROP, RT>     the student's shape, every W fragment register-resident:
 //                                                   OpsX3 (RT = 1, 2 row tiles) and OpsF32 (exact, RT = 1)
+//     * feat_prenet_walk_kernel<DROP>               the same on bf16x3 for launches with many row tiles: a workgroup walks several tiles and
+//                                                   pulls the weights once (feat_out's fragments in LDS)
 //   small LSTM step: one wave per gate (16 rows x 16 units each), gates exchanged through LDS, the LSTMCell +
 //   zoneout epilogue one (row, unit) per thread
 //     * lstm_small_kernel, lstm_small_pair_kernel   fp32 operands, W streamed; the pair: two steps in one launch
@@ -657,6 +659,40 @@ struct OpsF32 {
     }
 };
 
+// Developer aid, compiled out unless the library is built with EXTRA=-DFCL_FP_TS (then FCL_FP_TS=1 at run time prints, after every register-resident
+// bf16x3 feat/prenet launch, where its waves spent their cycles; synchronous, not usable under graph capture).  Eight s_memtime stamps per wave, kept in
+// scalar registers and written once at exit to a buffer of their own:
+//   0 entry   1 h1 rows arrived and split into LDS   2 the barrier after it   3 phase 1 done (feat_out: its MFMAs wait for feat_out's fragments)
+//   4 the barrier(s) after it   5 phase 2 and its barrier (layer 0's fragments)   6 every request of the wave has landed (a vmcnt(0) that only this
+//   build executes: from here on phase 3 waits for nothing)   7 exit.  The walker stamps 0 - 6 on its first tile.
+#ifdef FCL_FP_TS
+constexpr int kFpTsWorkgroups = 1024;
+__device__ long long g_fp_ts[kFpTsWorkgroups * 8 * 8];
+struct FpStamps {
+    long long t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    template <int I>
+    __device__ __forceinline__ void at(bool drain = false) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t[I])::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void flush() {
+        at<7>();
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < kFpTsWorkgroups) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) g_fp_ts[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + i] = t[i];
+        }
+    }
+};
+#define FP_STAMP(ts, i, ...) ts.at<i>(__VA_ARGS__)
+#define FP_STAMP_FLUSH(ts) ts.flush()
+#else
+struct FpStamps {};
+#define FP_STAMP(ts, i, ...)
+#define FP_STAMP_FLUSH(ts)
+#endif
+
 template <class Ops, int DROP, int RT>
 __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenetArgs a) {
     typedef typename Ops::Tile Tile;
@@ -664,6 +700,8 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
     const int M_feat = a.M_feat, M_pre = a.M_pre;
     int Ms_feat, Ms_pre;
     if (!feat_prenet_rows(a, 16 * RT, Ms_feat, Ms_pre)) return;
+    [[maybe_unused]] FpStamps ts;
+    FP_STAMP(ts, 0);
     constexpr int ldU = U + Ops::PAD, ldO = OP + Ops::PAD, ldP = P + Ops::PAD, ROWS = 16 * RT;
     static_assert(ldU == ldP, "the layer-1 operand tile re-uses the h1 tile's LDS");
     auto* lds = Ops::dynamic_lds();
@@ -752,6 +790,7 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             Ops::store4(A1, r, ldU, c, hreg[j]);
         }
     }
+    FP_STAMP(ts, 1);
     // layer-1 fragments (all 16 column tiles: 128 VGPRs) and epilogue operands: requested after phase 1, once feat_out's fragments are dead
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) pb1[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -773,6 +812,7 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         }
     };
     lds_barrier();
+    FP_STAMP(ts, 2);
     // ---- phase 1: H8 feat_out of the previous step (+ H10 scatter) ---------------------------------------------------------------------------
     if (feat_wave) {
 #pragma unroll
@@ -809,7 +849,11 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             if (m < Ms_feat) store_p32(a.before_p, (O + 31) >> 5, a.frame_off[m] + a.t_prev, O + i % padc, 0.f);
         }
     }
-    if (!has_pre) return;
+    FP_STAMP(ts, 3);
+    if (!has_pre) {
+        FP_STAMP_FLUSH(ts);
+        return;
+    }
     request_l1();
     lds_barrier();
     if constexpr (Ops::kPlanes) {
@@ -819,6 +863,7 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             lds_barrier();
         }
     }
+    FP_STAMP(ts, 4);
     // ---- phase 2: H6 prenet layer 0 -> LDS (over the h1 tile) ----------------------------------------------------------------------------------
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
@@ -836,6 +881,8 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
         }
     }
     lds_barrier();
+    FP_STAMP(ts, 5);
+    FP_STAMP(ts, 6, true);
     // ---- phase 3: H6 prenet layer 1 -> global (+ KD tap, + P32 planes) --------------------------------------------------------------------------
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
@@ -861,8 +908,277 @@ __global__ __launch_bounds__(512) void feat_prenet_split_kernel(const FeatPrenet
             if (a.tap_prenet) *reinterpret_cast<f32x4*>(a.tap_prenet + (size_t)(a.frame_off[m] + a.t_cur) * P + nc) = v;
         }
     }
+    FP_STAMP_FLUSH(ts);
 }
 
+// ---- the row-walking form of feat_prenet_split_kernel<OpsX3, DROP, 1>: a workgroup takes `ntw` consecutive row tiles and pulls the weights ONCE.
+// The one-tile kernel loads all 430 KB of fragments to use them on 16 rows; at 50 - 160 row tiles a launch that is 40 - 70 MB through the per-CU
+// vector-memory path.  Here
+//   * layer 0's and layer 1's fragments stay register-resident (48 + 128 VGPRs) and are requested at entry, together: feat_out's fragments are not in
+//     registers any more, so layer 1's need not wait for them to die;
+//   * feat_out's fragments go to LDS once, by LDS-DMA (a wave's fragment-major loads are contiguous 1 KB blocks, so the image is lane-linear: the
+//     fragment of k-step st is one 16-byte read at lane * 16; wave w reads only what wave w requested); the biases go to LDS too (16 registers);
+//   * the first tile is a copy of the tile body of its own, in front of the loop: its phases 0 - 2 run while layer 1's fragments are still landing
+//     (counted waits), and in the loop the only loads ever in flight are the NEXT tile's operands, so that no wait there takes in anything else;
+//   * the h1 / prenet-input tiles are double-buffered.  The next tile's h1 rows, F0 rows and frame offsets are requested right after phase 1 (into
+//     the registers phase 1 has just read for the last time; the keep bytes likewise after phases 2 and 3) and are taken in at ONE point, between
+//     phase 3's MFMAs and its stores -- a wait placed after those stores would wait for them too, stores and loads retiring in issue order.  So an
+//     extra tile costs its MFMAs, epilogues and three barriers, not a memory round trip.
+// Per tile the phases, products, their order, the hash inputs and every epilogue are those of the one-tile kernel: every output is bit-identical.
+// Dynamic LDS: ceil(O / 16) x 16 KB of fragments + 2 x 24 KB of tiles + 2 KB of biases = 130 KB at O = 80.  The launch keeps the rows below 4 096
+// (32-bit element offsets).
+// One LDS-DMA wave-load (64 x 16 bytes from the lanes' addresses g to LDS at the wave-uniform address l, lane * 16 apart) that the COMPILER DOES NOT
+// SEE: after the builtin form hipcc drains vmcnt(0) before the kernel's next LDS store -- here with every weight fragment in flight -- because
+// that store might alias the pending LDS write.  The caller orders the reads of the image itself (feat_prenet_walk: how).  M0 is saved and
+// restored inside the statement: the compiler keeps values of its own in it.
+__device__ __forceinline__ void glds16_unseen(const void* g, const void* l) {
+    typedef const __attribute__((address_space(3))) void* lds_t;
+    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_t)l);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
+}
+
+// FEAT / PRE: the workgroup has a feat_out part (h1 given) / a prenet part (w0 given and its first row below M_pre).  Template arguments, and the
+// next tile's requests and phase 0 run whether or not there is a next tile (rows clamped as everywhere, into the buffer nobody reads): the
+// compiler's wait counts do not follow a condition from a request to its use, and with either in a branch of its own it would wait for
+// "possibly pending" loads at the next request -- which takes in the stores of phase 3.
+template <int DROP, bool FEAT, bool PRE>
+__device__ __forceinline__ void feat_prenet_walk(const FeatPrenetArgs& a, const int ntw, const int Ms_feat, const int Ms_pre) {
+    typedef OpsX3 Ops;
+    typedef Ops::Tile Tile;
+    constexpr int SU = 8, SO = 3, SP = 8, U = 256, OP = 96, P = 256;
+    constexpr int ldU = U + Ops::PAD, ldO = OP + Ops::PAD, ldP = P + Ops::PAD;
+    constexpr int BUF = 2 * 16 * (ldU + ldO);  // elements of one buffer: both planes of an h1 tile and of a prenet-input tile
+    static_assert(ldU == ldP, "the layer-1 operand tile re-uses the h1 tile's LDS");
+    const int M_feat = a.M_feat, M_pre = a.M_pre;
+    [[maybe_unused]] FpStamps ts;
+    FP_STAMP(ts, 0);
+    const int O = a.O;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r16 = lane & 15, kq = lane >> 4;   // operand fragments: row / column r16, k-group kq
+    const int arow = lane & 15, cq = lane >> 4;  // transposed accumulators: activation row arow, columns cq * 4 .. cq * 4 + 3 of the column tile
+    constexpr bool has_feat = FEAT, pre_any = PRE;
+    const bool feat_wave = has_feat && wave * 16 < O;
+    const int mbeg = blockIdx.x * 16 * ntw;
+    // the tiles of this workgroup that the one-tile launch would not have left at entry (feat_prenet_rows): at least one
+    const int nt = min(ntw, ((has_feat ? Ms_feat : Ms_pre) - mbeg + 15) >> 4);
+    u16* lds = Ops::dynamic_lds();
+    u16* const WF = lds + wave * (2 * SU * 512);  // this wave's feat_out fragments: hi plane, k-steps 0 .. SU - 1, then the lo plane
+    lds += ((O + 15) >> 4) * (2 * SU * 512);
+    const Tile A1 = Tile::carve(lds, 16 * ldU);  // h1 tile; layer 0's output from phase 2 on      } of buffer 0; buffer 1: BUF elements further
+    const Tile A2 = Tile::carve(lds, 16 * ldO);  // feat_out / prenet input                        }
+    float* const BL = reinterpret_cast<float*>(lds + BUF);  // b0 [P], b1 [P]
+    const size_t lane8 = (size_t)lane * 8;
+    auto frag = [&](const Ops::W w, int tile, int ns) { return w.at((size_t)tile * ns * 512, lane8); };
+    const int t0 = wave, t1 = wave + 8;  // this wave's layer-0 column tiles
+    const int c1 = wave * 2;             // first of this wave's two layer-1 column tiles
+    const int fnc = wave * 16 + cq * 4;  // feat_out columns fnc .. fnc + 3 of this lane
+    // zero padding of before_p's last 32-column line (O % 8 == 0: 8, 16 or 24 columns): four columns per lane of the first two waves, beside the
+    // lane's own row of feat_out (the same frame offset)
+    const int padc = O + wave * 16 + cq * 4;
+    const bool pad_lane = wave < 2 && padc < ((O + 31) & ~31);
+
+    // what a tile needs besides the weights
+    f32x4 hrow[2];                    // this thread's share of the h1 rows
+    f32x4 f0v = (f32x4){0.f, 0.f, 0.f, 0.f};  // F0 row (feat waves)
+    int fo = 0;                       // frame offset of the accumulator's row
+    unsigned int k0[2] = {0u, 0u}, k1[2] = {0u, 0u};  // keep bytes (mask mode)
+    auto request_rows = [&](int m0) {
+        if (has_feat) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = threadIdx.x + j * 512, r = i >> 6, c = (i & 63) * 4;
+                hrow[j] = *reinterpret_cast<const f32x4*>(a.h1 + (unsigned)(min(m0 + r, M_feat - 1) * U + c));
+            }
+        }
+    };
+    auto request_feat = [&](int m0) {  // phase 1's epilogue operands
+        if (feat_wave && fnc < O) {
+            const int mc = min(m0 + arow, M_feat - 1);
+            f0v = *reinterpret_cast<const f32x4*>(a.F0 + (unsigned)(mc * O + fnc));
+            fo = a.frame_off[(unsigned)mc];
+        }
+    };
+    auto request_keep = [&](unsigned int (&k)[2], const uint8_t* keep, int m0, int ca, int cb) {  // column tiles ca, cb of a layer's mask
+        if (DROP == 1 && pre_any && m0 < M_pre) {
+            const unsigned mk = (unsigned)(min(m0 + arow, M_pre - 1) * P);
+            k[0] = *reinterpret_cast<const unsigned int*>(keep + mk + ca * 16 + cq * 4);
+            k[1] = *reinterpret_cast<const unsigned int*>(keep + mk + cb * 16 + cq * 4);
+        }
+    };
+    auto store_rows = [&](int buf) {  // phase 0 of a tile: its h1 rows -> LDS planes, its prenet-input tile zeroed
+        Ops::zero(A2.at(buf * BUF), 16 * ldO);
+        if (has_feat) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = threadIdx.x + j * 512, r = i >> 6, c = (i & 63) * 4;
+                Ops::store4(A1.at(buf * BUF), r, ldU, c, hrow[j]);
+            }
+        }
+    };
+
+    // ---- every request of the entry, in the order of use (the CU's address path serves its waves' requests in issue order).  feat_out's LDS-DMA goes
+    // FIRST: vmcnt retires in issue order, so a wave's wait for its h1 rows in phase 0 is also the wait for its own LDS-DMA, and the barrier that
+    // ends phase 0 (a memory clobber) keeps its reads of the image behind that wait.
+    if (feat_wave) {
+        const Ops::W w = frag(Ops::wf(a), wave, SU);
+#pragma unroll
+        for (int st = 0; st < SU; ++st) {
+            glds16_unseen(w.hi + st * 512, WF + st * 512);
+            glds16_unseen(w.lo + st * 512, WF + (SU + st) * 512);
+        }
+    }
+    request_rows(mbeg);
+    asm volatile("s_barrier" ::: "memory");  // no data wait: no wave's fragments in front of another wave's rows
+    request_feat(mbeg);
+    request_keep(k0, a.keep0, mbeg, t0, t1);
+    request_keep(k1, a.keep1, mbeg, c1, c1 + 1);
+    Ops::Frag<2, SO> f0;
+    Ops::Frag<2, SP> f1;
+    unsigned int seed0 = 0, seed1 = 0;
+    const unsigned int thr16 = (unsigned int)(a.drop_p * 65536.0f);
+    if (DROP == 2) {
+        const unsigned int sbump = a.seed_dev ? *a.seed_dev * 0x9E3779B9u : 0u;
+        seed0 = hash_u32(a.seed0 + sbump);
+        seed1 = hash_u32(a.seed1 + sbump);
+    }
+    f32x4 bias = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const bool bias_thread = pre_any && threadIdx.x < 2 * (P / 4);
+    if (pre_any) {
+        if (bias_thread) bias = *reinterpret_cast<const f32x4*>((threadIdx.x < P / 4 ? a.b0 : a.b1 - P) + threadIdx.x * 4);
+        const Ops::W w0[2] = {frag(Ops::w0(a), t0, SO), frag(Ops::w0(a), t1, SO)};
+        f0.load(w0);
+        const Ops::W w1[2] = {frag(Ops::w1(a), c1, SP), frag(Ops::w1(a), c1 + 1, SP)};
+        f1.load(w1);
+    }
+    store_rows(0);
+    if (bias_thread) *reinterpret_cast<f32x4*>(BL + threadIdx.x * 4) = bias;
+    FP_STAMP(ts, 1);
+
+    auto tile = [&](const int q) {
+        const int buf = q & 1, m0 = mbeg + q * 16;
+        const Tile T1 = A1.at(buf * BUF), T2 = A2.at(buf * BUF);
+        const bool has_pre = pre_any && m0 < M_pre;
+        lds_barrier();  // this tile's buffer is written; every wave is done with the other buffer (the tile before)
+        if (q == 0) FP_STAMP(ts, 2);
+        // ---- phase 1: H8 feat_out of the previous step (+ H10 scatter), feat_out's fragments from LDS -----------------------------------------------
+        if (feat_wave) {
+            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+            const u16* ah = T1.h + r16 * ldU + kq * 8;
+            const u16* al = T1.l + r16 * ldU + kq * 8;
+            // WF IS WRITTEN BY THIS WAVE'S OWN LDS-DMA, WHICH THE COMPILER DOES NOT SEE (glds16_unseen).  These reads are ordered behind it by exactly
+            // this: the wave issued the DMA before its h1 loads (the entry, above), it has waited for those loads in store_rows(0) (vmcnt retires
+            // in issue order), and a barrier with a memory clobber lies between that wait and here.  Whoever moves request_rows() in front of the
+            // DMA, drops the h1 loads of a feat wave, or lets a wave read another wave's part of the image must put an s_waitcnt vmcnt here.
+            const u16* wf = WF + lane8;
+#pragma unroll
+            for (int st = 0; st < SU; ++st) {  // (Frag::chain<true>, NT = 1)
+                const s16x8 a_hi = *reinterpret_cast<const s16x8*>(ah + st * 32), a_lo = *reinterpret_cast<const s16x8*>(al + st * 32);
+                const s16x8 w_hi = *reinterpret_cast<const s16x8*>(wf + st * 512), w_lo = *reinterpret_cast<const s16x8*>(wf + (SU + st) * 512);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_hi, a_lo, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_lo, a_hi, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_hi, a_hi, acc, 0, 0, 0);
+            }
+            const int m = m0 + arow;
+            if (fnc < O) {
+                f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (m < Ms_feat) {
+                    v = acc + f0v;
+                    const long long fr = (long long)fo + a.t_prev;
+                    *reinterpret_cast<f32x4*>(a.before + (size_t)fr * O + fnc) = v;
+                    if (a.before_p) {
+                        uint2 h, l;
+                        split4(v, h, l);
+                        p32_store4(a.before_p, (O + 31) >> 5, fr, fnc, h, l);
+                        if (pad_lane) p32_store4(a.before_p, (O + 31) >> 5, fr, padc, make_uint2(0u, 0u), make_uint2(0u, 0u));
+                    }
+                    if (a.out_act) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = act_apply(v[r], a.out_act);
+                    }
+                }
+                Ops::store4(T2, arow, ldO, fnc, v);
+            }
+        }
+        request_rows(m0 + 16);  // the next tile's rows and phase-1 operands: in flight during phases 2 and 3
+        request_feat(m0 + 16);
+        if (q == 0) FP_STAMP(ts, 3);
+        f32x4 out1[2];
+        if (has_pre) {
+            lds_barrier();
+            if (a.teacher_in) {  // teacher forcing: prenet input is y_{t-1}, not the decoder's own output
+                load_rowtile_split(T2.h, T2.l, ldO, a.teacher_in, a.teacher_ld, O, m0, M_pre);
+                lds_barrier();
+            }
+            if (q == 0) FP_STAMP(ts, 4);
+            // ---- phase 2: H6 prenet layer 0 -> LDS (over the h1 tile) ------------------------------------------------------------------------------
+            {
+                f32x4 accv[2];
+                f0.mma_t(T2, ldO, r16, kq, accv);
+                const int m = m0 + arow;
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) {
+                    const int nc = (tt ? t1 : t0) * 16 + cq * 4;
+                    f32x4 v = accv[tt] + *reinterpret_cast<const f32x4*>(BL + nc);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                    v = drop4<DROP>(v, DROP == 1 ? k0[tt] : 0u, (unsigned int)m * (unsigned int)P + (unsigned int)nc, seed0, thr16, a.keep_scale);
+                    Ops::store4(T1, arow, ldP, nc, v);
+                }
+            }
+            request_keep(k0, a.keep0, m0 + 16, t0, t1);
+            lds_barrier();
+            if (q == 0) {
+                FP_STAMP(ts, 5);
+                FP_STAMP(ts, 6, true);
+            }
+            // ---- phase 3: H6 prenet layer 1 -> global (+ KD tap, + P32 planes): the MFMAs here, the stores below --------------------------------
+            f1.mma_t(T1, ldP, r16, kq, out1);
+        }
+        // phase 0 of the next tile, into the buffer every wave left before this tile's first barrier -- and the one point of the tile at which
+        // loads are waited for (the asm makes the compiler take the other operands in here as well, not at their use behind phase 3's stores)
+        store_rows(buf ^ 1);
+        asm volatile("" : "+v"(f0v), "+v"(fo), "+v"(k0[0]), "+v"(k0[1]));
+        if (has_pre) {
+            const int m = m0 + arow;
+            if (m < Ms_pre) {
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) {
+                    const int nc = (c1 + tt) * 16 + cq * 4;
+                    f32x4 v = out1[tt] + *reinterpret_cast<const f32x4*>(BL + P + nc);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                    v = drop4<DROP>(v, DROP == 1 ? k1[tt] : 0u, (unsigned int)m * (unsigned int)P + (unsigned int)nc, seed1, thr16, a.keep_scale);
+                    if (a.pre_out) *reinterpret_cast<f32x4*>(a.pre_out + (size_t)m * P + nc) = v;
+                    if (a.pre_out_p) {
+                        uint2 h, l;
+                        split4(v, h, l);
+                        p32_store4(a.pre_out_p, SP, m, nc, h, l);
+                    }
+                    if (a.tap_prenet) *reinterpret_cast<f32x4*>(a.tap_prenet + (size_t)(a.frame_off[m] + a.t_cur) * P + nc) = v;
+                }
+            }
+            request_keep(k1, a.keep1, m0 + 16, c1, c1 + 1);
+        }
+    };
+    tile(0);
+#pragma unroll 1
+    for (int q = 1; q < nt; ++q) tile(q);
+    FP_STAMP_FLUSH(ts);
+}
+
+template <int DROP>
+__global__ __launch_bounds__(512) void feat_prenet_walk_kernel(const FeatPrenetArgs a, const int ntw) {
+    int Ms_feat, Ms_pre;
+    if (!feat_prenet_rows(a, 16 * ntw, Ms_feat, Ms_pre)) return;
+    const bool pre = a.w0 != nullptr && (int)blockIdx.x * 16 * ntw < a.M_pre;  // (the later tiles of the workgroup start at higher rows)
+    if (a.h1 != nullptr) {
+        if (pre) feat_prenet_walk<DROP, true, true>(a, ntw, Ms_feat, Ms_pre);
+        else feat_prenet_walk<DROP, true, false>(a, ntw, Ms_feat, Ms_pre);
+    } else if (pre) {
+        feat_prenet_walk<DROP, false, true>(a, ntw, Ms_feat, Ms_pre);
+    }
+}
 
 // Tail of the small LSTM steps with prefetched cell operands: wave g's accumulators (gate g of the tile's 16 rows x 16 units) go to LDS, then thread
 // (row, unit) of the workgroup collects its four gate pre-activations and runs the cell.  units_in_lane: the accumulator layout -- false: four rows
@@ -1081,24 +1397,72 @@ int launch_lstm_small_pair_any(const LstmStepArgs& a0, const LstmStepArgs& a1, h
 }
 
 // One of a kernel's three dropout forms (FCL_DROP_*: none, mask, rng), opted in for `lds` bytes of dynamic LDS and launched on 512 threads.
-static int launch_fp_drop(const void* const (&fn)[3], int drop_mode, dim3 grid, size_t lds, const FeatPrenetArgs& a, hipStream_t s) {
+// ntw: the walker's second argument (row tiles per workgroup); 0 = the kernel takes the argument block alone.
+static int launch_fp_drop(const void* const (&fn)[3], int drop_mode, dim3 grid, size_t lds, const FeatPrenetArgs& a, hipStream_t s, int ntw = 0) {
     const void* f = fn[drop_mode == 1 || drop_mode == 2 ? drop_mode : 0];
     const int rc = ensure_dyn_lds(f, (int)lds);
     if (rc) return rc;
-    void* args[] = {const_cast<FeatPrenetArgs*>(&a)};
-    return check_hip(hipLaunchKernel(f, grid, dim3(512), args, lds, s), "feat_prenet launch");
+    void* args1[] = {const_cast<FeatPrenetArgs*>(&a)};
+    void* args2[] = {const_cast<FeatPrenetArgs*>(&a), &ntw};
+    return check_hip(hipLaunchKernel(f, grid, dim3(512), ntw ? args2 : args1, lds, s), "feat_prenet launch");
+}
+
+#ifdef FCL_FP_TS
+// developer aid (see FpStamps): the launch just enqueued on s, synchronously -- per stamp, the cycles since the wave's entry, mean and maximum over the
+// waves that ran (feat waves alone for stamp 3: the others pass phase 1 at once)
+static void print_fp_stamps(const char* form, int rows, int wgs) {
+    static const int want = tunable("FP_TS", 0);
+    if (!want) return;
+    if (hipDeviceSynchronize() != hipSuccess) return;
+    static long long h[kFpTsWorkgroups * 64];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fp_ts), sizeof(h)) != hipSuccess) return;
+    double sum[8] = {}, mx[8] = {};
+    int cnt[8] = {};
+    for (int w = 0; w < (wgs < kFpTsWorkgroups ? wgs : kFpTsWorkgroups) * 8; ++w) {
+        const long long* t = &h[(size_t)w * 8];
+        if (!t[0]) continue;  // (a workgroup beyond the live rows left at entry)
+        for (int i = 1; i < 8; ++i) {
+            if (!t[i] || (i == 3 && (w & 7) >= 5)) continue;
+            const double d = (double)(t[i] - t[0]);
+            sum[i] += d; cnt[i]++;
+            if (d > mx[i]) mx[i] = d;
+        }
+    }
+    fprintf(stderr, "fp_ts %s rows %d workgroups %d: cycles since entry, mean (max):", form, rows, wgs);
+    static const char* const name[8] = {"", "rows->LDS", "barrier0", "phase1", "barrier1", "phase2+barrier2", "all landed", "exit"};
+    for (int i = 1; i < 8; ++i) fprintf(stderr, "  %s %.0f (%.0f)", name[i], cnt[i] ? sum[i] / cnt[i] : 0.0, mx[i]);
+    fprintf(stderr, "\n");
+    void* p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_fp_ts)) == hipSuccess) (void)hipMemset(p, 0, sizeof(h));
+}
+#else
+static void print_fp_stamps(const char*, int, int) {}
+#endif
+
+// The walker: ceil(tiles / ntw) workgroups of feat_prenet_walk_kernel, each on ntw consecutive row tiles.
+static int launch_feat_prenet_walk(const FeatPrenetArgs& a, int rows, int ntw, hipStream_t s) {
+    const size_t lds_w = sizeof(u16) * ((size_t)((a.O + 15) / 16) * 2 * 8 * 512 + 2 * 2 * 16 * ((256 + OpsX3::PAD) + (96 + OpsX3::PAD))) + 2 * 256 * sizeof(float);
+    static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_walk_kernel<0>), reinterpret_cast<const void*>(feat_prenet_walk_kernel<1>),
+                                      reinterpret_cast<const void*>(feat_prenet_walk_kernel<2>)};
+    const int tiles = (rows + 15) / 16, wgs = (tiles + ntw - 1) / ntw;
+    const int rc = launch_fp_drop(fn, a.drop_mode, dim3(wgs, 1), lds_w, a, s, ntw);
+    if (!rc) print_fp_stamps("walk", rows, wgs);
+    return rc;
 }
 
 // feat_prenet_split_kernel with RT row tiles per workgroup.  Measured on one box, 2 400 live rows, rocprofv3 durations: the kernel it replaced (RT = 2)
 // 14.1 us; this one at RT = 1 9.5, at RT = 2 11.9.  The 4-stream bench line does not move with either (44.5 - 45.7 M frames/s, same box): with four
-// passes in flight the pass is bound by the sum of workgroup-time, which RT = 1 doubles while it halves the latency.  Launched with one row tile per
-// workgroup (lowest single-pass latency: 339 -> 269 us of a 1.38 ms eager pass) below 4 096 rows, two above.
+// passes in flight the pass is bound by the sum of workgroup-time, which RT = 1 doubles while it halves the latency.  RT = 1 has the lowest single-pass
+// latency (339 -> 269 us of a 1.38 ms eager pass).  Which launch takes which form: launch_feat_prenet, below.
 template <class Ops, int RT>
 static int launch_feat_prenet_split(const FeatPrenetArgs& a, int rows, hipStream_t s) {
     constexpr size_t lds_s = (size_t)Ops::LDS_BYTES * 16 * RT * ((256 + Ops::PAD) + (96 + Ops::PAD));
     static const void* const fn[3] = {reinterpret_cast<const void*>(feat_prenet_split_kernel<Ops, 0, RT>), reinterpret_cast<const void*>(feat_prenet_split_kernel<Ops, 1, RT>),
                                       reinterpret_cast<const void*>(feat_prenet_split_kernel<Ops, 2, RT>)};
-    return launch_fp_drop(fn, a.drop_mode, dim3((rows + 16 * RT - 1) / (16 * RT), 1), lds_s, a, s);
+    const int wgs = (rows + 16 * RT - 1) / (16 * RT);
+    const int rc = launch_fp_drop(fn, a.drop_mode, dim3(wgs, 1), lds_s, a, s);
+    if (!rc && Ops::kPlanes) print_fp_stamps(RT == 2 ? "split RT=2" : "split RT=1", rows, wgs);
+    return rc;
 }
 
 int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
@@ -1115,8 +1479,18 @@ int launch_feat_prenet(const FeatPrenetArgs& a, hipStream_t s) {
     FCL_REQUIRE(!a.w0 || a.pre_out || a.pre_out_p, FCL_ERR_INVALID, "feat_prenet: no prenet output buffer");
     FCL_REQUIRE(!a.pre_out_p || !(a.P & 31), FCL_ERR_SHAPE, "feat_prenet: P32 prenet output needs P %% 32 == 0");
     if (planes) {
-        ProfScope ps("feat_prenet_kernel/bf16x3", fl, rows, s);
-        if (a.U == 256 && a.O > 64 && a.O <= 96 && a.P == 256) {
+        const bool resident = a.U == 256 && a.O > 64 && a.O <= 96 && a.P == 256;
+        // The register-resident forms by row count: below FCL_FP_WALK_MIN_TILES row tiles (default 112 = 1 792 rows) one row tile per workgroup, the
+        // lowest latency; from there up to 4 095 rows the walker with FCL_FP_WALK_TILES tiles per workgroup (default 2; 0 = walker off: one tile
+        // per workgroup); from 4 096 rows on two tiles per workgroup as before (the walker was not measured against that route).  Defaults from
+        // the same-box scans of profiles/r12_fp_walk_ab.log.
+        static const int walk_tiles = tunable("FP_WALK_TILES", 2), walk_min = tunable("FP_WALK_MIN_TILES", 112);
+        const bool walk = resident && walk_tiles > 0 && rows < 4096 && (rows + 15) / 16 >= walk_min;
+        ProfScope ps(walk ? "feat_prenet_walk_kernel/bf16x3" : "feat_prenet_kernel/bf16x3", fl, rows, s);
+        if (walk) {
+            const int rc = launch_feat_prenet_walk(a, rows, walk_tiles, s);
+            if (rc) return rc;
+        } else if (resident) {
             const int rc = rows >= 4096 ? launch_feat_prenet_split<OpsX3, 2>(a, rows, s) : launch_feat_prenet_split<OpsX3, 1>(a, rows, s);
             if (rc) return rc;
         } else {
