@@ -175,6 +175,11 @@ class HftTconv(C.Structure):  # fcl_hft_tconv_t
         (n, _P) for n in ("seg_lo", "seg_hi", "c", "w", "bias", "u", "du", "dc", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
 
 
+class HfeEnd(C.Structure):  # fcl_hfe_t
+    _fields_ = [("rows", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "ksize")] + [("slope", _F)] + [
+        (n, _P) for n in ("seg_lo", "seg_hi", "x", "w", "bias", "wav", "dwav", "dx", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
+
+
 class HpdLayer(C.Structure):  # fcl_hpd_t
     _fields_ = [("rows_in", C.c_int64), ("rows_out", C.c_int64)] + [(n, C.c_int32) for n in ("cin", "cout", "ksize", "stride", "pad")] + [("slope", _F)] + [
         (n, _P) for n in ("src", "in_lo", "in_hi", "x", "w", "bias", "h", "g", "extra", "y", "dw", "db", "workspace")] + [("workspace_bytes", _Z)]
@@ -391,6 +396,10 @@ SIGNATURES = {
     "fcl_hft_tconv_dx": (_I, [C.POINTER(HftTconv), _P]),
     "fcl_hft_tconv_dw": (_I, [C.POINTER(HftTconv), _P]),
     "fcl_hft_sum": (_I, [_P, C.POINTER(_P), _I, _F, C.c_int64, _P]),
+    "fcl_hfe_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I]),
+    "fcl_hfe_fwd": (_I, [C.POINTER(HfeEnd), _P]),
+    "fcl_hfe_dx": (_I, [C.POINTER(HfeEnd), _P]),
+    "fcl_hfe_dw": (_I, [C.POINTER(HfeEnd), _P]),
     "fcl_hpd_dw_workspace_bytes": (_Z, [C.c_int64, _I, _I, _I]),
     "fcl_hpd_layer_fwd": (_I, [C.POINTER(HpdLayer), _P]),
     "fcl_hpd_layer_dx": (_I, [C.POINTER(HpdLayer), _P]),

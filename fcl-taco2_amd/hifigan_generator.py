@@ -11,7 +11,8 @@ nn.Module with the parallel_wavegan package's constructor arguments and paramete
 The launches' contract is stated in include/fcl_hip.h "HiFi-GAN generator, training form" and restated in float64 numpy in tests/hfgt_ref.py.
 Activations are float32, channel-last [rows, C], the batch packed with the utterances back to back; rows are samples at the stage's own rate.  Kept per
 stage: its input c, the transposed convolution's output u and every unit's xt and x' (pre-activations only).  One arithmetic mode (exact fp32).  The output
-end (LeakyReLU, output_conv, tanh) is torch operations on the unpacked batch.  No CPU fallback."""
+end (LeakyReLU at hifigan.OUT_SLOPE, output_conv, tanh) is either torch operations on the unpacked batch (forward(output_end="torch"), the default) or
+the hfe_* kernels of csrc/hifigan_end.hip on the packed rows (output_end="hip"; DESIGN.md §6s, tests/hfge_ref.py).  No CPU fallback."""
 import ctypes as C
 
 import torch
@@ -23,6 +24,8 @@ from .pwg_common import Maps, _Conv, _Module, _norm
 CONV_FWD, CONV_DX, CONV_DW = "hft_conv_kernel", "hft_conv_dx_kernel", ("hft_dw_kernel", "hft_dw_reduce_kernel")
 TCONV_FWD, TCONV_DX, TCONV_DW = "hft_tconv_kernel", "hft_tconv_dx_kernel", ("hft_tconv_dw_kernel", "hft_dw_reduce_kernel")
 SUM_KERNEL = "hft_sum_kernel"
+END_FWD, END_DX, END_DW = "hfe_fwd_kernel", "hfe_dx_kernel", ("hfe_dw_kernel", "hfe_dw_reduce_kernel")
+OUTPUT_ENDS = ("torch", "hip")
 KERNEL_SIZES, MAX_WIDTH, MAX_BLOCKS = (3, 5, 7, 11), 512, 4
 
 
@@ -333,6 +336,64 @@ def input_conv(plan, maps, mel, weight, bias):
     return _InputConv.apply(plan, maps, mel, weight, bias)
 
 
+def pack_end(w):
+    """torch Conv1d weight (cout, C, k) -> [k, cout, C], the one matrix the output end's three launches read"""
+    return _f(w).permute(2, 0, 1).contiguous()
+
+
+def end_args(maps, cin, cout, k, slope, **ptr):
+    a = _lib.HfeEnd()
+    a.rows, a.cin, a.cout, a.ksize, a.slope = maps.samples, cin, cout, k, slope
+    a.seg_lo, a.seg_hi = maps.seg_lo.data_ptr(), maps.seg_hi.data_ptr()
+    for n, v in ptr.items():
+        if n == "workspace" and v is not None:
+            a.workspace, a.workspace_bytes = v.data_ptr(), v.numel() * 4
+        elif v is not None:
+            setattr(a, n, v.data_ptr())
+    return a
+
+
+class _OutputEnd(torch.autograd.Function):
+    """wav [rows, cout] = tanh(output_conv(LeakyReLU(x))) on the last stage's packed rows x [rows, C]; only wav is kept.  Backward launches the weight
+    gradient only if the weight or the bias asks for one, the input gradient only if x does."""
+
+    @staticmethod
+    def forward(ctx, plan, maps, x, weight, bias):
+        dev, m = plan.device, maps.maps[-1]
+        cout, cin, k = (int(v) for v in weight.shape)
+        with torch.cuda.device(dev):
+            x, w = x.detach().to(torch.float32).contiguous(), pack_end(weight)
+            wav = _new(dev)(m.samples, cout)
+            a = end_args(m, cin, cout, k, hifigan.OUT_SLOPE, x=x, w=w, bias=_f(bias).contiguous(), wav=wav)
+            _lib.check(_lib.load().fcl_hfe_fwd(C.byref(a), ops._stream()))
+        ctx.plan, ctx.maps, ctx.x, ctx.w, ctx.wav, ctx.shape = plan, maps, x, w, wav.detach(), (cin, cout, k)
+        return wav
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dwav):
+        m, dev, (cin, cout, k) = ctx.maps.maps[-1], ctx.plan.device, ctx.shape
+        dx = dw = db = None
+        with torch.cuda.device(dev):
+            new, lib, st = _new(dev), _lib.load(), ops._stream()
+            dwav = dwav.detach().to(torch.float32).contiguous()
+            if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+                dwk, db = new(k, cout, cin), new(cout)
+                work = new(lib.fcl_hfe_workspace_bytes(m.samples, cin, cout, k) // 4)
+                a = end_args(m, cin, cout, k, hifigan.OUT_SLOPE, x=ctx.x, wav=ctx.wav, dwav=dwav, dw=dwk, db=db, workspace=work)
+                _lib.check(lib.fcl_hfe_dw(C.byref(a), st))
+                dw = dwk.permute(1, 2, 0).contiguous()
+            if ctx.needs_input_grad[2]:
+                dx = new(m.samples, cin)
+                _lib.check(lib.fcl_hfe_dx(C.byref(end_args(m, cin, cout, k, hifigan.OUT_SLOPE, x=ctx.x, w=ctx.w, wav=ctx.wav, dwav=dwav, dx=dx)), st))
+        return None, None, dx, dw, db
+
+
+def output_end(plan, maps, x, weight, bias):
+    """x [frames x hop, C] (upsampling_stages' result) and output_conv's plain parameters -> the waveform's packed rows [frames x hop, out_channels]"""
+    return _OutputEnd.apply(plan, maps, x, weight, bias)
+
+
 class _TConv(_Conv):
     """a ConvTranspose1d's parameters: weight (cin, cout, k), dim 0 (weight norm's) is the input channel, the bias has cout elements"""
 
@@ -361,8 +422,8 @@ class _Block(torch.nn.Module):
 
 
 class TrainableHiFiGANGenerator(_Module):
-    """forward(c, lens=None) -> waveform [B, out_channels, T' hop].  Parameter names and shapes are hifigan.param_spec's (weight_g / weight_v under
-    use_weight_norm); weights N(0, 0.01), zero biases, as the reference initialises them."""
+    """forward(c, lens=None, output_end="torch") -> waveform [B, out_channels, T' hop].  Parameter names and shapes are hifigan.param_spec's (weight_g /
+    weight_v under use_weight_norm); weights N(0, 0.01), zero biases, as the reference initialises them."""
 
     CHECKPOINT_KEY, PLAN = "generator", TrainingPlan
 
@@ -420,9 +481,12 @@ class TrainableHiFiGANGenerator(_Module):
                     out += [c1.conv.folded(), c1.conv.bias, c2.conv.folded(), c2.conv.bias]
         return out
 
-    def forward(self, c, lens=None):
+    def forward(self, c, lens=None, output_end="torch"):
         """c [B, in_channels, T']; lens (frames per utterance): the rows past lens[b] are padding, come out as zero and get exactly zero gradient, and
-        every utterance is computed as if it were alone"""
+        every utterance is computed as if it were alone.  output_end: "torch" runs LeakyReLU, output_conv and tanh as torch operations on the padded
+        batch, "hip" as the hfe_* launches on the packed rows (only the [rows, out_channels] waveform is unpacked)."""
+        if output_end not in OUTPUT_ENDS:
+            raise ValueError("fcl-taco2_amd: HiFi-GAN generator: output_end=%r is not one of %s" % (output_end, ", ".join(repr(v) for v in OUTPUT_ENDS)))
         plan = self.plan()
         c = torch.as_tensor(c).to(device=plan.device, dtype=torch.float32)
         if c.dim() != 3 or c.shape[1] != self.config["in_channels"]:
@@ -439,10 +503,15 @@ class TrainableHiFiGANGenerator(_Module):
             rows = rows[maps.rows(T, 1)]
         c0 = input_conv(plan, maps, rows.contiguous(), self.input_conv.folded(), self.input_conv.bias)
         x = upsampling_stages(plan, maps, c0, *self.stage_parameters())
+        oc = self.output_conv.conv
+        if output_end == "hip":
+            y = _OutputEnd.apply(plan, maps, x, oc.folded(), oc.bias)
+            if lens is not None:
+                y = torch.zeros(B * T * self.hop, y.shape[1], device=y.device, dtype=y.dtype).index_copy(0, maps.rows(T, self.hop), y)
+            return y.reshape(B, T * self.hop, -1).transpose(1, 2).contiguous()
         if lens is not None:
             x = torch.zeros(B * T * self.hop, x.shape[1], device=x.device, dtype=x.dtype).index_copy(0, maps.rows(T, self.hop), x)
         x = x.reshape(B, T * self.hop, -1).transpose(1, 2)
-        oc = self.output_conv.conv
         y = torch.tanh(F.conv1d(F.leaky_relu(x, hifigan.OUT_SLOPE), oc.folded(), oc.bias, padding=(self.config["kernel_size"] - 1) // 2))
         if lens is not None:
             y = y * (torch.arange(T * self.hop, device=y.device).unsqueeze(0) < torch.tensor(lens, device=y.device).unsqueeze(1) * self.hop).unsqueeze(1)

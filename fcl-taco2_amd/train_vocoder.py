@@ -1,13 +1,20 @@
-"""Parallel WaveGAN training on one MI355X by the published parallel_wavegan.v1 recipe (restated from its paper and config, not diffed against a
-file): the generator step is HIP from (z, c) to the waveform and back (pwg_generator.py), the discriminator and the multi-resolution
-STFT loss are §6l and §6j; torch keeps weight norm, the optimisers and the schedulers.
+"""Vocoder training on one MI355X, two recipes chosen by generator_type (--generator-type, or the key of --config).
+
+ParallelWaveGANGenerator (the default): the published parallel_wavegan.v1 recipe (restated from its paper and config, not diffed against a file): the
+generator step is HIP from (z, c) to the waveform and back (pwg_generator.py), the discriminator and the multi-resolution STFT loss
+are §6l and §6j.  HiFiGANGenerator: the published hifigan.v1 recipe (restated from the paper and the package's published configuration, not diffed
+against a file, like the other): the generator is hifigan_generator.py with its output end in HIP (§6p, §6s), the discriminator the multi-scale +
+multi-period one (§6q, §6r), the losses 45 x the mel-spectrogram L1 (§6k) + the MSE adversarial term + 2 x feature matching, Adam and MultiStepLR.
+Torch keeps weight and spectral norm, the optimisers and the schedulers.
 
     python -m fcl_taco2_amd.train_vocoder --wav-dir wavs --feature-root feats --train-list train.txt --valid-list valid.txt --outdir exp/pwg
+    python -m fcl_taco2_amd.train_vocoder --generator-type HiFiGANGenerator --wav-dir wavs ... --outdir exp/hifigan
 
 reads `feats/mels/<utt>.npy` (the normalised [T, n_mels] mels that preprocess / extract_features write, T = samples // hop + 1) and 16-bit PCM mono wavs,
-and writes config.yml (parallel_wavegan's layout), checkpoint-<steps>steps.pkl (vocoder.PWGPlan, vocoder_decode and tts load them as they are) and
-train_log.jsonl into --outdir.  Which utterances and windows make step n's batch, and the noise of step n, are functions of (--seed, n) alone, so
---resume needs nothing but the checkpoint: 2 + 2 steps give the bytes of 4.  One process, one GPU; data-parallel training is not built."""
+and writes config.yml (parallel_wavegan's layout), checkpoint-<steps>steps.pkl (vocoder.PWGPlan or hifigan.HiFiGANPlan, vocoder_decode and tts load
+them as they are) and train_log.jsonl into --outdir.  Which utterances and windows make step n's batch, and the noise of step n, are functions of
+(--seed, n) alone, so --resume needs nothing but the checkpoint: 2 + 2 steps give the bytes of 4.  One process, one GPU; data-parallel training is not
+built."""
 import argparse
 import concurrent.futures
 import json
@@ -34,8 +41,30 @@ DISCRIMINATOR_DEFAULTS = dict(in_channels=1, out_channels=1, kernel_size=3, laye
 # a checkpoint is resumed only under the values it was trained with: these keys of config.yml must agree with the flags
 PINNED = ("generator_params", "discriminator_params", "batch_size", "batch_max_steps", "generator_optimizer_params", "discriminator_optimizer_params",
           "generator_scheduler_params", "discriminator_scheduler_params", "generator_grad_norm", "discriminator_grad_norm", "lambda_adv",
-          "discriminator_train_start_steps", "stft_loss_params", "sampling_rate", "hop_size", "seed")
+          "discriminator_train_start_steps", "stft_loss_params", "sampling_rate", "hop_size", "seed", "generator_type", "discriminator_type",
+          "mel_loss_params", "lambda_aux", "lambda_feat_match")  # (a key the recipe does not have is absent on both sides)
 LOSS_TERMS = ("spectral_convergence_loss", "log_stft_magnitude_loss", "adversarial_loss", "real_loss", "fake_loss")
+PWG_TYPE, HIFIGAN_TYPE, HIFIGAN_DISCRIMINATOR = "ParallelWaveGANGenerator", "HiFiGANGenerator", "HiFiGANMultiScaleMultiPeriodDiscriminator"
+
+# ---- the published hifigan.v1 recipe
+HIFIGAN_DEFAULTS = dict(sampling_rate=22050, batch_size=16, batch_max_steps=8192, generator_grad_norm=-1.0, discriminator_grad_norm=-1.0, lambda_aux=45.0,
+                        lambda_adv=1.0, lambda_feat_match=2.0, generator_train_start_steps=1, discriminator_train_start_steps=0, train_max_steps=2500000,
+                        save_interval_steps=10000, eval_interval_steps=1000, log_interval_steps=100)
+HIFIGAN_OPTIMIZER = dict(lr=2e-4, betas=[0.5, 0.9], weight_decay=0.0)
+HIFIGAN_SCHEDULER = dict(gamma=0.5, milestones=[200000, 400000, 600000, 800000])
+HIFIGAN_MEL_LOSS = dict(fs=22050, fft_size=1024, hop_size=256, win_length=None, num_mels=80, fmin=0, fmax=None, log_base=None)  # fmax null: fs / 2
+HIFIGAN_GENERATOR_DEFAULTS = dict(in_channels=80, out_channels=1, channels=512, kernel_size=7, upsample_scales=[8, 8, 2, 2],
+                                  upsample_kernel_sizes=[16, 16, 4, 4], resblock_kernel_sizes=[3, 7, 11], resblock_dilations=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+                                  use_additional_convs=True, bias=True, nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.1},
+                                  use_weight_norm=True)
+_ACT = dict(nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.1})
+HIFIGAN_SCALE_DEFAULTS = dict(in_channels=1, out_channels=1, kernel_sizes=[15, 41, 5, 3], channels=128, max_downsample_channels=1024, max_groups=16, bias=True,
+                              downsample_scales=[2, 2, 4, 4, 1], use_weight_norm=True, use_spectral_norm=False, **_ACT)
+HIFIGAN_PERIOD_DEFAULTS = dict(in_channels=1, out_channels=1, kernel_sizes=[5, 3], channels=32, downsample_scales=[3, 3, 3, 3, 1],
+                               max_downsample_channels=1024, bias=True, use_weight_norm=True, use_spectral_norm=False, **_ACT)
+HIFIGAN_DISCRIMINATOR_DEFAULTS = dict(scales=3, scale_downsample_pooling="AvgPool1d", scale_downsample_pooling_params={"kernel_size": 4, "stride": 2, "padding": 2},
+                                      scale_discriminator_params=HIFIGAN_SCALE_DEFAULTS, follow_official_norm=True, periods=[2, 3, 5, 7, 11],
+                                      period_discriminator_params=HIFIGAN_PERIOD_DEFAULTS)
 
 
 def _ints(text):
@@ -60,7 +89,9 @@ def _params(text, what):
 
 def build_parser():
     d = DEFAULTS
-    ap = argparse.ArgumentParser(prog="fcl_taco2_amd.train_vocoder", description="Parallel WaveGAN training on MI355X (parallel_wavegan.v1 recipe)")
+    ap = argparse.ArgumentParser(prog="fcl_taco2_amd.train_vocoder",
+                                 description="Vocoder training on MI355X: the parallel_wavegan.v1 recipe, or hifigan.v1 with --generator-type HiFiGANGenerator")
+    ap.add_argument("--generator-type", default=None, help="%s (default) or %s: the recipe; also read from --config" % (PWG_TYPE, HIFIGAN_TYPE))
     ap.add_argument("--wav-dir", default=None, help="directory of <utt>.wav (16-bit PCM mono at --sampling-rate); this or --wav-scp")
     ap.add_argument("--wav-scp", default=None, help="Kaldi-style `utt path` list")
     ap.add_argument("--feature-root", default=None, help="reads mels/<utt>.npy: normalised [T, n_mels] mels as preprocess / extract_features write them")
@@ -68,12 +99,12 @@ def build_parser():
     ap.add_argument("--valid-list", default=None, help="utterance ids for the evaluation lines (optional)")
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--config", default=None, help="parallel_wavegan-style config.yml for everything below; flags given beside it win")
-    ap.add_argument("--generator-params", default=None, help="TrainableParallelWaveGANGenerator arguments, JSON or a yaml file (v1 without)")
-    ap.add_argument("--discriminator-params", default=None, help="ParallelWaveGANDiscriminator arguments, JSON or a yaml file (v1 without)")
+    ap.add_argument("--generator-params", default=None, help="the trainable generator's constructor arguments, JSON or a yaml file (v1 without)")
+    ap.add_argument("--discriminator-params", default=None, help="the discriminator's constructor arguments, JSON or a yaml file (v1 without)")
     ap.add_argument("--sampling-rate", type=int, default=None, help="default %d" % d["sampling_rate"])
     for k in ("batch_size", "batch_max_steps", "scheduler_step_size", "discriminator_train_start_steps", "train_max_steps", "save_interval_steps",
               "eval_interval_steps", "log_interval_steps"):
-        ap.add_argument("--" + k.replace("_", "-"), type=int, default=None, help="default %d" % d[k])
+        ap.add_argument("--" + k.replace("_", "-"), type=int, default=None, help="default %d%s" % (d[k], " (Parallel WaveGAN only)" * (k == "scheduler_step_size")))
     for k in ("generator_lr", "discriminator_lr", "optimizer_eps", "scheduler_gamma", "generator_grad_norm", "discriminator_grad_norm", "lambda_adv"):
         ap.add_argument("--" + k.replace("_", "-"), type=float, default=None, help="default %g" % d[k])
     for k in ("fft_sizes", "hop_sizes", "win_lengths"):
@@ -81,7 +112,14 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=None, help="default 0; of the batches, the windows and the noise (functions of the seed and the step alone)")
     ap.add_argument("--resume", default=None, help="checkpoint-Nsteps.pkl: continue with models, optimisers, schedulers and the step count")
     ap.add_argument("--pretrain", default=None, help="checkpoint.pkl: load the models only")
-    ap.add_argument("--ends", choices=("hip", "torch"), default="hip", help="the generator's ends (DESIGN §6o)")
+    ap.add_argument("--ends", choices=("hip", "torch"), default=None, help="Parallel WaveGAN: the generator's ends (DESIGN §6o), default hip")
+    ap.add_argument("--output-end", choices=("hip", "torch"), default=None, help="HiFi-GAN: the generator's output end (DESIGN §6s), default hip")
+    ap.add_argument("--lambda-aux", type=float, default=None, help="HiFi-GAN: the mel term's weight, default %g" % HIFIGAN_DEFAULTS["lambda_aux"])
+    ap.add_argument("--lambda-feat-match", type=float, default=None,
+                    help="HiFi-GAN: the feature-matching term's weight, default %g" % HIFIGAN_DEFAULTS["lambda_feat_match"])
+    ap.add_argument("--mel-loss-params", default=None, help="HiFi-GAN: fs, fft_size, hop_size, win_length, num_mels, fmin, fmax, log_base; JSON or a yaml file")
+    ap.add_argument("--scheduler-milestones", type=_ints, default=None,
+                    help="HiFi-GAN: MultiStepLR's milestones, default %s" % ",".join(map(str, HIFIGAN_SCHEDULER["milestones"])))
     ap.add_argument("--verbose", type=int, default=1)
     return ap
 
@@ -150,10 +188,144 @@ def read_config(path):
     return out
 
 
+# flags that belong to one recipe and are refused under the other
+PWG_ONLY_FLAGS = ("ends", "scheduler_step_size", "optimizer_eps", "fft_sizes", "hop_sizes", "win_lengths")
+HIFIGAN_ONLY_FLAGS = ("output_end", "lambda_aux", "lambda_feat_match", "mel_loss_params", "scheduler_milestones")
+
+
+def recipe_of(args):
+    """the generator_type that selects the recipe: the flag, else the key of --config, else Parallel WaveGAN"""
+    gtype = getattr(args, "generator_type", None)
+    if gtype is None and args.config:
+        import yaml
+
+        with open(args.config) as f:
+            gtype = (yaml.safe_load(f) or {}).get("generator_type")
+    gtype = PWG_TYPE if gtype is None else gtype
+    if gtype not in (PWG_TYPE, HIFIGAN_TYPE):
+        raise ValueError("fcl-taco2_amd: train_vocoder: generator_type=%r is not supported (%s, %s)" % (gtype, PWG_TYPE, HIFIGAN_TYPE))
+    return gtype
+
+
+def _refuse_flags(args, names, recipe):
+    given = ["--" + k.replace("_", "-") for k in names if getattr(args, k, None) is not None]
+    if given:
+        raise ValueError("fcl-taco2_amd: train_vocoder: %s %s not a flag of the %s recipe" % (", ".join(given), "is" if len(given) == 1 else "are", recipe))
+
+
+def log_base_factor(log_base):
+    """what the mel loss's scalar (an L1 of log10 mels) is multiplied by under mel_loss_params.log_base: |log_b x - log_b y| = (ln 10 / ln b) |log10 x -
+    log10 y| exactly; null is the natural logarithm"""
+    if log_base is None:
+        return math.log(10.0)
+    if not (isinstance(log_base, (int, float)) and log_base > 0 and log_base != 1):
+        raise ValueError("fcl-taco2_amd: train_vocoder: mel_loss_params.log_base=%r is not a base (null: natural, or a positive number other than 1)" % (log_base,))
+    return 1.0 if float(log_base) == 10.0 else math.log(10.0) / math.log(float(log_base))
+
+
+HIFIGAN_CONFIG_KEYS = {"sampling_rate", "hop_size", "generator_type", "generator_params", "discriminator_type", "discriminator_params", "mel_loss_params",
+                       "lambda_aux", "lambda_adv", "lambda_feat_match", "batch_size", "batch_max_steps", "generator_optimizer_type",
+                       "generator_optimizer_params", "generator_scheduler_type", "generator_scheduler_params", "generator_grad_norm",
+                       "discriminator_optimizer_type", "discriminator_optimizer_params", "discriminator_scheduler_type", "discriminator_scheduler_params",
+                       "discriminator_grad_norm", "generator_train_start_steps", "discriminator_train_start_steps", "train_max_steps", "save_interval_steps",
+                       "eval_interval_steps", "log_interval_steps", "seed"}
+HIFIGAN_SECTIONS = (("generator_params", HIFIGAN_GENERATOR_DEFAULTS), ("discriminator_params", HIFIGAN_DISCRIMINATOR_DEFAULTS), ("mel_loss_params", HIFIGAN_MEL_LOSS),
+                    ("generator_optimizer_params", HIFIGAN_OPTIMIZER), ("discriminator_optimizer_params", HIFIGAN_OPTIMIZER),
+                    ("generator_scheduler_params", HIFIGAN_SCHEDULER), ("discriminator_scheduler_params", HIFIGAN_SCHEDULER))
+
+
+def resolve_hifigan(args):
+    """resolve() under the HiFi-GAN recipe: its own table of defaults and of allowed keys, the same layout"""
+    from . import hifigan, hifigan_generator, mel_loss
+
+    _refuse_flags(args, PWG_ONLY_FLAGS, "HiFi-GAN")
+    file = {}
+    if args.config:
+        import yaml
+
+        with open(args.config) as f:
+            file = yaml.safe_load(f) or {}
+    bad = _extras(file, HIFIGAN_CONFIG_KEYS, "")
+    for sec, allowed in HIFIGAN_SECTIONS:
+        if isinstance(file.get(sec), dict):
+            bad += _extras(file[sec], allowed, sec)
+    dfile = file.get("discriminator_params") if isinstance(file.get("discriminator_params"), dict) else {}
+    for sec, allowed in (("scale_discriminator_params", HIFIGAN_SCALE_DEFAULTS), ("period_discriminator_params", HIFIGAN_PERIOD_DEFAULTS)):
+        if isinstance(dfile.get(sec), dict):
+            bad += _extras(dfile[sec], allowed, "discriminator_params." + sec)
+    _refuse(bad)
+    for k, want in (("discriminator_type", HIFIGAN_DISCRIMINATOR), ("generator_optimizer_type", "Adam"), ("discriminator_optimizer_type", "Adam"),
+                    ("generator_scheduler_type", "MultiStepLR"), ("discriminator_scheduler_type", "MultiStepLR")):
+        if file.get(k, want) != want:
+            raise ValueError("fcl-taco2_amd: train_vocoder: config key %s=%r is not supported (%s)" % (k, file[k], want))
+    base = dict(HIFIGAN_DEFAULTS, seed=0)
+    base.update({k: v for k, v in file.items() if k in base})
+    for k in base:
+        if getattr(args, k, None) is not None:
+            base[k] = getattr(args, k)
+    if int(base["generator_train_start_steps"]) != 1:
+        raise ValueError("fcl-taco2_amd: train_vocoder: generator_train_start_steps=%r is not supported (1: the generator trains from the first step)"
+                         % (base["generator_train_start_steps"],))
+    gp = dict(HIFIGAN_GENERATOR_DEFAULTS, **file.get("generator_params", {}))
+    gp.update(_params(args.generator_params, "--generator-params"))
+    _only(gp, HIFIGAN_GENERATOR_DEFAULTS, "generator_params")
+    hifigan_generator.check_training(hifigan.config({k: v for k, v in gp.items() if k in hifigan.CONFIG}))
+    dp = dict(HIFIGAN_DISCRIMINATOR_DEFAULTS, **dfile)
+    dp.update(_params(args.discriminator_params, "--discriminator-params"))
+    _only(dp, HIFIGAN_DISCRIMINATOR_DEFAULTS, "discriminator_params")
+    for sec, dflt in (("scale_discriminator_params", HIFIGAN_SCALE_DEFAULTS), ("period_discriminator_params", HIFIGAN_PERIOD_DEFAULTS)):
+        dp[sec] = dict(dflt, **_only(dict(dp[sec] or {}), dflt, "discriminator_params." + sec))
+    fs = int(base["sampling_rate"])
+    mp = dict(HIFIGAN_MEL_LOSS, fs=fs)
+    mp.update(file.get("mel_loss_params") or {})
+    mp.update(_params(args.mel_loss_params, "--mel-loss-params"))
+    _only(mp, HIFIGAN_MEL_LOSS, "mel_loss_params")
+    if mp["fmax"] is None:
+        mp["fmax"] = mp["fs"] / 2
+    log_base_factor(mp["log_base"])
+    mel_loss.check_configuration(mp["fs"], [mp["fft_size"]], [mp["hop_size"]], [mp["win_length"]], mp["num_mels"], mp["fmin"], mp["fmax"])
+    hop = int(np.prod(gp["upsample_scales"]))
+    if "hop_size" in file and int(file["hop_size"]) != hop:
+        raise ValueError("fcl-taco2_amd: train_vocoder: config key hop_size=%r is not the product of upsample_scales (%d)" % (file["hop_size"], hop))
+    if base["batch_max_steps"] % hop or base["batch_max_steps"] < hop:
+        raise ValueError("fcl-taco2_amd: train_vocoder: batch_max_steps=%d is not a positive multiple of the hop (%d)" % (base["batch_max_steps"], hop))
+    for k in ("batch_size", "train_max_steps", "save_interval_steps", "eval_interval_steps", "log_interval_steps"):
+        if int(base[k]) < 1:
+            raise ValueError("fcl-taco2_amd: train_vocoder: %s=%r must be positive" % (k, base[k]))
+    if int(base["discriminator_train_start_steps"]) < 0:
+        raise ValueError("fcl-taco2_amd: train_vocoder: discriminator_train_start_steps=%r must not be negative" % (base["discriminator_train_start_steps"],))
+    out = {"sampling_rate": fs, "hop_size": hop, "generator_type": HIFIGAN_TYPE, "generator_params": gp, "discriminator_type": HIFIGAN_DISCRIMINATOR,
+           "discriminator_params": dp, "mel_loss_params": mp, "lambda_aux": float(base["lambda_aux"]), "lambda_adv": float(base["lambda_adv"]),
+           "lambda_feat_match": float(base["lambda_feat_match"]), "batch_size": int(base["batch_size"]), "batch_max_steps": int(base["batch_max_steps"])}
+    for net in ("generator", "discriminator"):
+        o = dict(HIFIGAN_OPTIMIZER, **(file.get(net + "_optimizer_params") or {}))
+        if getattr(args, net + "_lr", None) is not None:
+            o["lr"] = getattr(args, net + "_lr")
+        sc = dict(HIFIGAN_SCHEDULER, **(file.get(net + "_scheduler_params") or {}))
+        if args.scheduler_gamma is not None:
+            sc["gamma"] = args.scheduler_gamma
+        if args.scheduler_milestones is not None:
+            sc["milestones"] = list(args.scheduler_milestones)
+        ms = [int(m) for m in sc["milestones"]]
+        if ms != sorted(ms) or (ms and ms[0] < 1):
+            raise ValueError("fcl-taco2_amd: train_vocoder: %s_scheduler_params.milestones=%r must be ascending positive steps" % (net, sc["milestones"]))
+        out[net + "_optimizer_type"] = "Adam"
+        out[net + "_optimizer_params"] = {"lr": float(o["lr"]), "betas": [float(b) for b in o["betas"]], "weight_decay": float(o["weight_decay"])}
+        out[net + "_scheduler_type"] = "MultiStepLR"
+        out[net + "_scheduler_params"] = {"gamma": float(sc["gamma"]), "milestones": ms}
+        out[net + "_grad_norm"] = float(base[net + "_grad_norm"])
+    out.update({k: int(base[k]) for k in ("generator_train_start_steps", "discriminator_train_start_steps", "train_max_steps", "save_interval_steps",
+                                          "eval_interval_steps", "log_interval_steps", "seed")})
+    return json.loads(json.dumps(out))  # (plain containers: what config.yml holds)
+
+
 def resolve(args):
-    """flags over --config over the defaults -> the run's config in parallel_wavegan's layout (what config.yml holds)"""
+    """flags over --config over the selected recipe's defaults -> the run's config in parallel_wavegan's layout (what config.yml holds)"""
     from . import pwg_discriminator, pwg_generator, stft_loss
 
+    if recipe_of(args) == HIFIGAN_TYPE:
+        return resolve_hifigan(args)
+    _refuse_flags(args, HIFIGAN_ONLY_FLAGS, "Parallel WaveGAN")
     base = dict(DEFAULTS, seed=0)
     file = read_config(args.config) if args.config else {}
     base.update({k: v for k, v in file.items() if k in base})
@@ -197,13 +369,15 @@ def resolve(args):
 
 
 def adversarial(cfg, step):
-    """whether step `step` (1-based) has an adversarial term and a discriminator update: the first is discriminator_train_start_steps + 1"""
+    """whether step `step` (1-based) has an adversarial term and a discriminator update: the first is discriminator_train_start_steps + 1 (0: every step)"""
     return step > cfg["discriminator_train_start_steps"]
 
 
 def learning_rate(cfg, net, step):
-    """the learning rate step `step` (1-based) is taken with: StepLR after step - 1 scheduler steps"""
+    """the learning rate step `step` (1-based) is taken with: StepLR, or MultiStepLR (the milestones passed), after step - 1 scheduler steps"""
     s = cfg[net + "_scheduler_params"]
+    if "milestones" in s:
+        return cfg[net + "_optimizer_params"]["lr"] * s["gamma"] ** sum(1 for m in s["milestones"] if step - 1 >= m)
     return cfg[net + "_optimizer_params"]["lr"] * s["gamma"] ** ((step - 1) // s["step_size"])
 
 
@@ -295,8 +469,8 @@ def check_resume(cfg, path):
     with open(side) as f:
         old = yaml.safe_load(f) or {}
     for k in PINNED:
-        if old.get(k) != json.loads(json.dumps(cfg[k])):
-            raise ValueError("fcl-taco2_amd: train_vocoder: --resume: %s is %r in %s and %r now" % (k, old.get(k), side, cfg[k]))
+        if old.get(k) != json.loads(json.dumps(cfg.get(k))):
+            raise ValueError("fcl-taco2_amd: train_vocoder: --resume: %s is %r in %s and %r now" % (k, old.get(k), side, cfg.get(k)))
 
 
 def _read_ids(path):
@@ -387,6 +561,90 @@ class Trainer(object):
         return out
 
 
+def feature_matching_loss(feats_fake, feats_real):
+    """the recipe's feature matching: the L1 mean of every map but the scores against the detached real map, SUMMED over the layers and over the
+    discriminators (average_by_layers and average_by_discriminators both off; hifigan_discriminator.feature_match_loss averages over both)"""
+    return sum(torch.mean(torch.abs(f - r.detach())) for fake, real in zip(feats_fake, feats_real) for f, r in zip(fake[:-1], real[:-1]))
+
+
+class HiFiGANTrainer(Trainer):
+    """the hifigan.v1 step in the package trainer's order: the generator on mel (+ adversarial + feature matching once the discriminator is on), its Adam
+    and scheduler step, the generator again under no_grad, the discriminator's real / fake loss and its step"""
+
+    LATE = ("adversarial_loss", "feature_matching_loss", "real_loss", "fake_loss", "discriminator_grad_norm")
+
+    def __init__(self, cfg, device, output_end="hip"):
+        from .hifigan_generator import TrainableHiFiGANGenerator
+        from .hifigan_scale_discriminator import HiFiGANMultiScaleMultiPeriodDiscriminator
+        from .mel_loss import MelSpectrogramLoss
+
+        self.cfg, self.dev, self.output_end = cfg, device, output_end
+        torch.manual_seed(cfg["seed"])  # (the initial weights)
+        self.gen = TrainableHiFiGANGenerator(**cfg["generator_params"]).to(device)
+        self.disc = HiFiGANMultiScaleMultiPeriodDiscriminator(**cfg["discriminator_params"]).to(device)
+        m = cfg["mel_loss_params"]
+        self.criterion = MelSpectrogramLoss(device, m["fs"], (m["fft_size"],), (m["hop_size"],), (m["win_length"],), m["num_mels"], m["fmin"], m["fmax"])
+        self.mel_scale = log_base_factor(m["log_base"])
+        nets = {"generator": self.gen, "discriminator": self.disc}
+        adam = lambda p: dict(lr=p["lr"], betas=tuple(p["betas"]), weight_decay=p["weight_decay"])
+        self.opt = {k: torch.optim.Adam(n.parameters(), **adam(cfg[k + "_optimizer_params"])) for k, n in nets.items()}
+        self.sch = {k: torch.optim.lr_scheduler.MultiStepLR(self.opt[k], **cfg[k + "_scheduler_params"]) for k in nets}
+        self.steps = 0
+
+    def losses(self, c, wav, adv):
+        """the generator's terms on one batch (the graph attached) -> (fake, {term: tensor})"""
+        from .hifigan_discriminator import generator_adversarial_loss, split_batch
+
+        fake = self.gen(c, output_end=self.output_end)
+        terms = {"mel_loss": self.mel_scale * self.criterion(fake, wav)}
+        if adv:
+            # as Trainer.losses: the discriminator is frozen around its forward, so the generator's backward launches none of its weight gradients; real and
+            # fake go through it packed into one forward (the two halves have the same lengths) and are split again
+            for p in self.disc.parameters():
+                p.requires_grad_(False)
+            outs_real, outs_fake = split_batch(self.disc(torch.cat([wav[:, 0], fake[:, 0]])))
+            for p in self.disc.parameters():
+                p.requires_grad_(True)
+            terms["adversarial_loss"] = generator_adversarial_loss(outs_fake)
+            terms["feature_matching_loss"] = feature_matching_loss(outs_fake, outs_real)
+        return fake, terms
+
+    def _norm(self, params, limit):
+        """the gradient norm, clipped to `limit` when that is positive"""
+        return float(torch.nn.utils.clip_grad_norm_(params, limit if limit > 0 else float("inf")))
+
+    def step(self, c, wav):
+        from .hifigan_discriminator import discriminator_adversarial_loss
+
+        cfg, n = self.cfg, self.steps + 1
+        adv = adversarial(cfg, n)
+        _, terms = self.losses(c, wav, adv)
+        loss = cfg["lambda_aux"] * terms["mel_loss"]
+        if adv:
+            loss = loss + cfg["lambda_adv"] * terms["adversarial_loss"] + cfg["lambda_feat_match"] * terms["feature_matching_loss"]
+        self.opt["generator"].zero_grad()
+        loss.backward()
+        out = {k: float(v.detach()) for k, v in terms.items()}
+        out["generator_grad_norm"] = self._norm(self.gen.parameters(), cfg["generator_grad_norm"])
+        self._finite(n, **out)
+        self.opt["generator"].step()
+        self.sch["generator"].step()
+        if adv:
+            with torch.no_grad():
+                fake = self.gen(c, output_end=self.output_end)
+            real_loss, fake_loss = discriminator_adversarial_loss(self.disc(wav), self.disc(fake))
+            self.opt["discriminator"].zero_grad()
+            (real_loss + fake_loss).backward()
+            more = dict(real_loss=float(real_loss.detach()), fake_loss=float(fake_loss.detach()))
+            more["discriminator_grad_norm"] = self._norm(self.disc.parameters(), cfg["discriminator_grad_norm"])
+            self._finite(n, **more)
+            out.update(more)
+            self.opt["discriminator"].step()
+            self.sch["discriminator"].step()
+        self.steps = n
+        return out
+
+
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -398,8 +656,9 @@ def main(argv=None):
     cfg = resolve(args)
     if args.resume:
         check_resume(cfg, args.resume)
-    gp = cfg["generator_params"]
-    hop, ctx, A, fs = cfg["hop_size"], gp["aux_context_window"], gp["aux_channels"], cfg["sampling_rate"]
+    gp, hifi = cfg["generator_params"], cfg["generator_type"] == HIFIGAN_TYPE
+    # (the HiFi-GAN generator takes the window's own frames, no context, and no noise)
+    hop, ctx, A, fs = cfg["hop_size"], 0 if hifi else gp["aux_context_window"], gp["in_channels"] if hifi else gp["aux_channels"], cfg["sampling_rate"]
     frames, B = cfg["batch_max_steps"] // hop, cfg["batch_size"]
     wavs = dict(XF.read_wav_list(args.wav_scp, args.wav_dir))
     train = Corpus(_read_ids(args.train_list), wavs, args.feature_root, fs, hop, A)
@@ -420,7 +679,7 @@ def main(argv=None):
         yaml.safe_dump(json.loads(json.dumps(cfg)), f, sort_keys=False)
     # ---- the first device call is below
     dev = torch.device("cuda:0")
-    tr = Trainer(cfg, dev, args.ends)
+    tr = HiFiGANTrainer(cfg, dev, args.output_end or "hip") if hifi else Trainer(cfg, dev, args.ends or "hip")
     if args.resume:
         tr.load(args.resume)
     elif args.pretrain:
@@ -431,26 +690,30 @@ def main(argv=None):
         write({"left_out": sampler.dropped})
 
     def prepare(step):
-        """step's batch as pinned host tensors (z, c, wav), on the one host thread, while the step before it runs"""
+        """step's batch as pinned host tensors (z, c, wav) -- (c, wav) under the HiFi-GAN recipe -- on the one host thread, while the step before it runs"""
         c, w = np.empty((B, A, frames + 2 * ctx), np.float32), np.empty((B, 1, frames * hop), np.float32)
         for i, (k, f0) in enumerate(sampler.batch(step)):
             mel, wav = train.load(sampler.utts[k][0])
             m, w[i, 0] = sampler.cut(mel, wav, f0)
             c[i] = m.T
-        return tuple(torch.from_numpy(a).pin_memory() for a in (sampler.noise(step), c, w))
+        return tuple(torch.from_numpy(a).pin_memory() for a in ((c, w) if hifi else (sampler.noise(step), c, w)))
 
     def evaluate(step):
         sums, n = {}, 0
+        if hifi:
+            tr.disc.eval()  # (no power iteration of the spectral norm on a validation window)
         with torch.no_grad():
             for k, (u, _) in enumerate(vsampler.utts):
                 mel, wav = valid.load(u)
                 f0, z = vsampler.valid(k)
                 m, w = vsampler.cut(mel, wav, f0)
-                _, terms = tr.losses(torch.from_numpy(z).to(dev), torch.from_numpy(np.ascontiguousarray(m.T[None])).to(dev),
-                                     torch.from_numpy(np.ascontiguousarray(w[None, None])).to(dev), adversarial(cfg, step))
+                inputs = (torch.from_numpy(np.ascontiguousarray(m.T[None])).to(dev), torch.from_numpy(np.ascontiguousarray(w[None, None])).to(dev))
+                _, terms = tr.losses(*(inputs if hifi else (torch.from_numpy(z).to(dev),) + inputs), adversarial(cfg, step))
                 for name, v in terms.items():
                     sums[name] = sums.get(name, 0.0) + float(v)
                 n += 1
+        if hifi:
+            tr.disc.train()
         write(dict({"eval_" + k: v / n for k, v in sums.items()}, step=step, eval_windows=n))
 
     acc, count, t0 = {}, 0, time.perf_counter()
@@ -458,10 +721,10 @@ def main(argv=None):
         nxt = pool.submit(prepare, tr.steps + 1) if tr.steps < cfg["train_max_steps"] else None
         while tr.steps < cfg["train_max_steps"]:
             n = tr.steps + 1
-            z, c, wav = (a.to(dev, non_blocking=True) for a in nxt.result())
+            batch = [a.to(dev, non_blocking=True) for a in nxt.result()]
             nxt = pool.submit(prepare, n + 1) if n < cfg["train_max_steps"] else None
             lrs = {k: tr.opt[k].param_groups[0]["lr"] for k in tr.opt}
-            out = tr.step(z, c, wav)
+            out = tr.step(*batch)
             for k, v in out.items():
                 s, m = acc.get(k, (0.0, 0))
                 acc[k] = (s + v, m + 1)
@@ -471,7 +734,7 @@ def main(argv=None):
                 dt = time.perf_counter() - t0
                 rec = dict({k: s / m for k, (s, m) in acc.items()}, step=n, generator_lr=lrs["generator"], discriminator_lr=lrs["discriminator"],
                            ms_per_step=1e3 * dt / count, samples_per_second=count * B * frames * hop / dt)
-                for k in LOSS_TERMS[2:] + ("discriminator_grad_norm",):
+                for k in HiFiGANTrainer.LATE if hifi else LOSS_TERMS[2:] + ("discriminator_grad_norm",):
                     rec.setdefault(k, None)  # (before the discriminator starts)
                 write(rec)
                 logging.info("step %d: %s", n, json.dumps(rec))

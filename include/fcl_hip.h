@@ -1459,6 +1459,45 @@ int fcl_hft_tconv_dx(const fcl_hft_tconv_t* a, fcl_stream_t stream);
 int fcl_hft_tconv_dw(const fcl_hft_tconv_t* a, fcl_stream_t stream);
 int fcl_hft_sum(float* out, const float* const* terms, int count, float scale, int64_t elems, fcl_stream_t stream);
 
+/* ---- HiFi-GAN generator, output end: LeakyReLU at the end's own slope, output_conv and tanh on the last stage's packed rows, forward and backward
+ *      (csrc/hifigan_end.hip; fcl_taco2_amd/hifigan_generator.py; restated in float64 numpy in tests/hfge_ref.py).
+ * Layout: as the training form above -- float32, channel-last, packed [rows, C], row t's utterance is [seg_lo[t], seg_hi[t]) and a tap outside it
+ *      contributes zero; l and m as there, at `slope`.  w [k][cout][cin]: row j cout + o = W[o, :, j] of torch's Conv1d, the same matrix for all three
+ *      entries; h = (k - 1) / 2.
+ *   fcl_hfe_fwd (hfe_fwd_kernel): wav[t, o] = tanh(bias[o] + sum_j sum_ch l(x)[t + j - h, ch] w[j][o][ch]); only wav [rows, cout] is written.
+ *   fcl_hfe_dx (hfe_dx_kernel): with dpre[t, o] = dwav[t, o] (1 - wav[t, o]^2), formed on load and never stored,
+ *      dx[t, ch] = m(x[t, ch]) sum_j sum_o dpre[t - (j - h), o] w[j][o][ch].
+ *   fcl_hfe_dw (hfe_dw_kernel, hfe_dw_reduce_kernel): dw [k][cout][cin] = sum_t dpre[t, o] l(x)[t + j - h, ch] in the weights' layout and
+ *      db [cout] = sum_t dpre[t, o], as per-chunk partials of 1 024 rows in the workspace added in ascending chunk order by the second launch.
+ * fcl_hfe_workspace_bytes(rows, cin, cout, ksize): what fcl_hfe_dw asks of the workspace.
+ *
+ * Plain fp32 FMAs (at most four output columns: no MFMA), the device library's tanhf; no atomics; two passes give the same bits; a batch's wav and dx
+ *      are bit for bit those of its utterances alone.  Every entry validates before any HIP call: a null pointer or a slope outside [0, 1)
+ *      FCL_ERR_INVALID; cin (a multiple of 16 from 16 to 256), cout (1 .. 4), ksize (3, 5, 7, 11) or rows (1 .. 2^31 - 2) out of range FCL_ERR_SHAPE;
+ *      x, w, dx or the workspace not 16-byte aligned FCL_ERR_ALIGN; a workspace that is too small FCL_ERR_WORKSPACE.  No entry allocates, synchronises
+ *      or copies. */
+typedef struct {
+    int64_t rows;
+    int32_t cin, cout, ksize;
+    float slope;
+    const int32_t* seg_lo;
+    const int32_t* seg_hi;
+    const float* x;        /* [rows, cin] the last stage's output, a pre-activation */
+    const float* w;        /* [ksize][cout][cin] */
+    const float* bias;     /* [cout] (fwd) */
+    float* wav;            /* [rows, cout]: written by fwd, read by dx and dw */
+    const float* dwav;     /* [rows, cout] (dx, dw) */
+    float* dx;             /* [rows, cin] (dx) */
+    float* dw;             /* [ksize][cout][cin] (dw) */
+    float* db;             /* [cout] (dw) */
+    float* workspace;
+    size_t workspace_bytes;
+} fcl_hfe_t;
+size_t fcl_hfe_workspace_bytes(int64_t rows, int cin, int cout, int ksize);
+int fcl_hfe_fwd(const fcl_hfe_t* a, fcl_stream_t stream);
+int fcl_hfe_dx(const fcl_hfe_t* a, fcl_stream_t stream);
+int fcl_hfe_dw(const fcl_hfe_t* a, fcl_stream_t stream);
+
 /* ---- HiFi-GAN period discriminator: a stack of strided (k, 1) Conv2d + LeakyReLU on the waveform folded by its period, one layer per call, forward and
  *      backward (csrc/hifigan_disc.hip; fcl_taco2_amd/hifigan_discriminator.py; restated in float64 numpy in tests/hfgd_ref.py).
  * Layout: float32, channel-last, packed [rows, C].  For period p an utterance becomes p segments (segment q holds the samples h p + q), the segments lie
