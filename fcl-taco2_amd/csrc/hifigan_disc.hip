@@ -2,46 +2,19 @@
 // and backward (include/fcl_hip.h "HiFi-GAN period discriminator"; fcl_taco2_amd/hifigan_discriminator.py; restated in float64 numpy in
 // tests/hfgd_ref.py).
 //
-// Layout as pwg_rows.h: float32, channel-last, packed [rows, C].  A period p turns an utterance into p segments (one per phase of the period), the
-// segments lie back to back, and the (k, 1) convolution is a plain 1-D convolution along each segment; no value crosses a segment boundary.  Every
-// level has its own row count, so the geometry is table-driven, per OUTPUT row t: src[t] is the input row under the centre of the kernel
-// (in_lo + stride x the row's index in its segment) and [in_lo[t], in_hi[t]) the input segment.  Tap j reads input row src[t] + j - pad; a tap outside
-// the segment contributes zero.  The output segment follows from the three tables: it holds (in_hi - in_lo + 2 pad - k) / stride + 1 rows and starts
-// (src - in_lo) / stride rows before t.
+// Layout and table-driven row geometry as hfd_rows.h: float32, channel-last, packed [rows, C].  A period p turns an utterance into p segments (one per
+// phase of the period), the segments lie back to back, and the (k, 1) convolution is a plain 1-D convolution along each segment; no value crosses a
+// segment boundary.
 // Exact fp32, the C -> C contractions on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain), unconditional loads from clamped rows masked with pwr_keep,
-// tile counts as template arguments, 64-bit row arithmetic, no atomics.  The loops are local forms of hft_conv_kernel / hft_dw_kernel (the
-// neighbours' kernels are not routed through a more general loop) with the table-driven row geometry.
-#include "pwg_rows.h"
+// tile counts as template arguments, 64-bit row arithmetic, no atomics.  The row descriptor, the first layer's forward and waveform gradient and the
+// small weight-gradient kernel are those of hfd_rows.h, shared with hifigan_sdisc.hip; the C -> C loops here are local forms of hft_conv_kernel /
+// hft_dw_kernel with the table-driven row geometry: through hfd_mma_loop, and through the grouped weight-gradient kernel with one group, they measured
+// slower (as 6n found for the neighbours' kernels).
+#include "hfd_rows.h"
 
 namespace fcl {
 
-constexpr int HPD_SMALL_GROUPS = 8;  // row groups of hpd_dw_small_kernel (1024 threads)
-constexpr int HPD_SMALL_UNROLL = 4;  // rows per register set of hpd_dw_small_kernel
-
 enum { HPD_BIAS = 0, HPD_NOBIAS = 1 };
-
-// d LeakyReLU / d pre-activation from the stored post-activation; h == 0 takes the slope, as torch does
-__device__ __forceinline__ float hpd_mask(float h, float slope) { return h > 0.f ? 1.f : slope; }
-
-// what a row kernel needs to know about output row t (all zero past the end, so that every tap is masked away and nothing is stored)
-struct HpdRow {
-    long long src, lo, hi;    // the input row under tap `pad`, the input segment (clamped to [0, rows_in])
-    long long olo, ohi;       // the output segment
-};
-
-__device__ __forceinline__ HpdRow hpd_row(const int32_t* __restrict__ src, const int32_t* __restrict__ in_lo, const int32_t* __restrict__ in_hi, long long t,
-                                          long long n, long long rows_in, int ksize, int stride, int pad) {
-    HpdRow R = {0, 0, 0, 0, 0};
-    if (t < n) {
-        const long long lo = in_lo[t], hi = in_hi[t];
-        R.src = src[t];
-        R.lo = max(0LL, lo);
-        R.hi = min(rows_in, hi);
-        R.olo = max(0LL, t - (R.src - lo) / stride);
-        R.ohi = min(n, R.olo + (hi - lo + 2 * pad - ksize) / stride + 1);
-    }
-    return R;
-}
 
 // ---- C -> C forward: y[t, co] = lrelu(bias[co] + sum_j sum_ci x[src[t] + j - pad, ci] w[j][ci][co]).  The shape of hft_conv_kernel: a workgroup owns 128
 // output rows x 16 NT columns (blockIdx.y: the column block), a wave 32 rows: 2 x NT accumulator tiles.  A lane loads 4 consecutive input channels of
@@ -58,7 +31,7 @@ __global__ __launch_bounds__(256) void hpd_conv_kernel(const float* __restrict__
     long long centre[2], lo[2], hi[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
-        const HpdRow R = hpd_row(src, in_lo, in_hi, t0 + mt * 16 + r, n, rows_in, ksize, stride, pad);
+        const HfdRow R = hfd_row(src, in_lo, in_hi, t0 + mt * 16 + r, n, rows_in, ksize, stride, pad);
         centre[mt] = R.src - pad, lo[mt] = R.lo, hi[mt] = R.hi;
     }
     f32x4 acc[2][NT];
@@ -155,7 +128,7 @@ __global__ __launch_bounds__(256) void hpd_conv_dx_kernel(const float* __restric
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const long long t = t0 + mt * 16 + r;
-        const HpdRow R = hpd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
+        const HfdRow R = hfd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
         top[mt] = t + c, lo[mt] = R.olo, hi[mt] = R.ohi;
     }
     f32x4 acc[2][NT];
@@ -215,7 +188,7 @@ __global__ __launch_bounds__(256) void hpd_conv_dx_kernel(const float* __restric
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const long long t = t0 + mt * 16 + 4 * q + reg;
-            const HpdRow R = hpd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
+            const HfdRow R = hfd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
             const long long row = R.src + ph;
             if (row < R.lo || row >= R.hi) continue;
 #pragma unroll
@@ -223,7 +196,7 @@ __global__ __launch_bounds__(256) void hpd_conv_dx_kernel(const float* __restric
                 const size_t at = (size_t)row * cw + col0 + nt * 16 + r;
                 float v = acc[mt][nt][reg];
                 if (extra) v += extra[at];
-                y[at] = v * hpd_mask(hin[at], slope);
+                y[at] = v * hfd_mask(hin[at], slope);
             }
         }
 }
@@ -310,34 +283,6 @@ __global__ __launch_bounds__(256) void hpd_dw_kernel(const float* __restrict__ x
     }
 }
 
-// ---- 1 -> C forward (the first layer): y[t, c] = lrelu(bias[c] + sum_j s[src[t] + j - pad] w[j][c]); an item is (output row, 4 channels)
-__global__ __launch_bounds__(256) void hpd_expand_fwd_kernel(const float* __restrict__ s, const float* __restrict__ w, const float* __restrict__ bias,
-                                                             const int32_t* __restrict__ src, const int32_t* __restrict__ in_lo,
-                                                             const int32_t* __restrict__ in_hi, float* __restrict__ y, long long n, long long rows_in, int c,
-                                                             int ksize, int stride, int pad, float slope) {
-    const int cq = c >> 2;
-    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (i >= n * cq) return;
-    const long long t = i / cq;
-    const int ch = (int)(i - t * cq) * 4;
-    const HpdRow R = hpd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < ksize; ++j) {
-        const long long rr = R.src + j - pad;
-        const float sv = (rr >= R.lo && rr < R.hi) ? s[rr] : 0.f;
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)j * c + ch);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(sv, wv[e], v[e]);
-    }
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float u = v[e] + (bias ? bias[ch + e] : 0.f);
-        o[e] = u > 0.f ? u : u * slope;
-    }
-    *reinterpret_cast<f32x4*>(y + t * c + ch) = o;
-}
-
 // ---- 1 -> C adjoint (the score layer's input gradient, stride 1): y[h, c] = m(hin[h, c]) (sum_j g[t + pad - j] w[j][c] + extra[h, c]) for h = src[t] where
 // that lies inside the input segment (the score map may have more rows than its input); an item is (output row, 4 channels)
 __global__ __launch_bounds__(256) void hpd_expand_dx_kernel(const float* __restrict__ g, const float* __restrict__ w, const float* __restrict__ hin,
@@ -349,7 +294,7 @@ __global__ __launch_bounds__(256) void hpd_expand_dx_kernel(const float* __restr
     if (i >= n * cq) return;
     const long long t = i / cq;
     const int ch = (int)(i - t * cq) * 4;
-    const HpdRow R = hpd_row(src, in_lo, in_hi, t, n, rows_in, ksize, 1, pad);
+    const HfdRow R = hfd_row(src, in_lo, in_hi, t, n, rows_in, ksize, 1, pad);
     if (R.src < R.lo || R.src >= R.hi) return;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < ksize; ++j) {
@@ -370,7 +315,7 @@ __global__ __launch_bounds__(256) void hpd_expand_dx_kernel(const float* __restr
         for (int e = 0; e < 4; ++e) o[e] += ev[e];
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] *= hpd_mask(hv[e], slope);
+    for (int e = 0; e < 4; ++e) o[e] *= hfd_mask(hv[e], slope);
     *reinterpret_cast<f32x4*>(y + at) = o;
 }
 
@@ -381,7 +326,7 @@ __global__ __launch_bounds__(256) void hpd_reduce_fwd_kernel(const float* __rest
                                                              int ksize, int stride, int pad) {
     const int sub = threadIdx.x & 15;
     const long long t = blockIdx.x * 16LL + (threadIdx.x >> 4);
-    const HpdRow R = hpd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
+    const HfdRow R = hfd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
     float acc = 0.f;
     for (int j = 0; j < ksize; ++j) {
         const long long rr = R.src + j - pad;
@@ -397,113 +342,9 @@ __global__ __launch_bounds__(256) void hpd_reduce_fwd_kernel(const float* __rest
     if (sub == 0 && t < n) y[t] = acc + (bias ? bias[0] : 0.f);
 }
 
-// ---- C -> 1 adjoint (the first layer's input gradient: the waveform gradient) with the strided adjoint's tap rule: 16 lanes per (output row t, phase ph);
-// y[src[t] + ph] = sum_i sum_c g[t + c0 - i, c] w[j0 + stride i][c], j0 = (ph + pad) % stride, c0 = (ph + pad) / stride
-__global__ __launch_bounds__(256) void hpd_reduce_dx_kernel(const float* __restrict__ g, const float* __restrict__ w, const int32_t* __restrict__ src,
-                                                            const int32_t* __restrict__ in_lo, const int32_t* __restrict__ in_hi, float* __restrict__ y,
-                                                            long long n, long long rows_in, int c, int ksize, int stride, int pad) {
-    const int sub = threadIdx.x & 15;
-    const long long item = blockIdx.x * 16LL + (threadIdx.x >> 4);
-    const long long t = item / stride;
-    const int ph = (int)(item - t * stride);
-    const HpdRow R = hpd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
-    const int c0 = (ph + pad) / stride, j0 = (ph + pad) - c0 * stride;
-    float acc = 0.f;
-    for (int j = j0, i = 0; j < ksize; j += stride, ++i) {
-        const long long rr = t + c0 - i;
-        if (rr < R.olo || rr >= R.ohi) continue;
-        for (int ch = 4 * sub; ch < c; ch += 64) {
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(g + rr * c + ch), wv = *reinterpret_cast<const f32x4*>(w + (size_t)j * c + ch);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = fmaf(gv[e], wv[e], acc);
-        }
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    const long long row = R.src + ph;
-    if (sub == 0 && row >= R.lo && row < R.hi) y[row] = acc;
-}
-
-// ---- weight gradient of the 1 -> C and C -> 1 layers, one chunk's partial per (workgroup, block of 128 channels) in the forward layout.
-// VEC_SHIFTED = 0 (first layer, cin 1): vec = g [n, c], sc = x [rows_in]: partial[j][ch] = sum_t sc[src[t] + j - pad] vec[t, ch], row k = sum_t vec[t, ch].
-// VEC_SHIFTED = 1 (score layer, cout 1): vec = x [rows_in, c], sc = g [n]: partial[j c + ch] = sum_t vec[src[t] + j - pad, ch] sc[t], element k c = sum_t sc[t].
-// Thread = (channel, one of 8 row groups taking every 8th row); the groups' sums meet in LDS and are added in ascending group order.
-template <int VEC_SHIFTED, int KSIZE>
-__global__ __launch_bounds__(1024) void hpd_dw_small_kernel(const float* __restrict__ vec, const float* __restrict__ sc, const int32_t* __restrict__ src,
-                                                            const int32_t* __restrict__ in_lo, const int32_t* __restrict__ in_hi,
-                                                            float* __restrict__ partial, long long n, long long rows_in, int c, int pad) {
-    __shared__ float red[HPD_SMALL_GROUPS - 1][(KSIZE + 1) * 128];
-    const int lch = threadIdx.x & 127, grp = threadIdx.x >> 7;
-    const int ch = blockIdx.y * 128 + lch;
-    const int chc = min(ch, c - 1);  // (the threads past the width load a valid channel and store nothing)
-    const long long t_begin = (long long)blockIdx.x * PWR_DW_CHUNK, t_end = min(n, t_begin + PWR_DW_CHUNK);
-    const long long last = t_end - 1, alast = rows_in - 1;
-    float acc[KSIZE + 1];
-#pragma unroll
-    for (int j = 0; j <= KSIZE; ++j) acc[j] = 0.f;
-    for (int it0 = 0; it0 < PWR_DW_CHUNK / HPD_SMALL_GROUPS; it0 += HPD_SMALL_UNROLL) {
-        int at[HPD_SMALL_UNROLL], lo[HPD_SMALL_UNROLL], hi[HPD_SMALL_UNROLL];
-        float ov[HPD_SMALL_UNROLL], xv[HPD_SMALL_UNROLL][KSIZE];
-#pragma unroll
-        for (int u = 0; u < HPD_SMALL_UNROLL; ++u) {
-            const long long t = t_begin + (long long)(it0 + u) * HPD_SMALL_GROUPS + grp, tc = min(t, last);
-            at[u] = src[tc];
-            lo[u] = in_lo[tc];
-            hi[u] = in_hi[tc];
-            ov[u] = VEC_SHIFTED ? sc[tc] : vec[tc * c + chc];
-#pragma unroll
-            for (int j = 0; j < KSIZE; ++j) {
-                const long long rc = min(max((long long)at[u] + j - pad, 0LL), alast);
-                xv[u][j] = VEC_SHIFTED ? vec[rc * c + chc] : sc[rc];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < HPD_SMALL_UNROLL; ++u) {
-            const long long t = t_begin + (long long)(it0 + u) * HPD_SMALL_GROUPS + grp;
-            const bool live = t <= last;
-            const long long l = max(0, lo[u]), h = min(rows_in, (long long)hi[u]);
-            const float own = pwr_keep(ov[u], live);
-#pragma unroll
-            for (int j = 0; j < KSIZE; ++j) {
-                const long long rr = (long long)at[u] + j - pad;
-                acc[j] = fmaf(pwr_keep(xv[u][j], live && rr >= l && rr < h), own, acc[j]);
-            }
-            acc[KSIZE] += own;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (grp > 0) {
-#pragma unroll
-        for (int j = 0; j <= KSIZE; ++j) red[grp - 1][j * 128 + lch] = acc[j];
-    }
-    __syncthreads();
-    if (grp == 0 && ch < c) {
-#pragma unroll
-        for (int j = 0; j <= KSIZE; ++j)
-#pragma unroll
-            for (int k = 0; k < HPD_SMALL_GROUPS - 1; ++k) acc[j] += red[k][j * 128 + lch];
-        float* out = partial + (size_t)blockIdx.x * (VEC_SHIFTED ? (size_t)KSIZE * c + 1 : ((size_t)KSIZE + 1) * c);
-#pragma unroll
-        for (int j = 0; j < KSIZE; ++j) out[(size_t)j * c + ch] = acc[j];
-        if (!VEC_SHIFTED || ch == 0) out[(size_t)KSIZE * c + (VEC_SHIFTED ? 0 : ch)] = acc[KSIZE];
-    }
-}
-
-static bool hpd_width_ok(int c) { return c >= 16 && c <= 1024 && c % 16 == 0; }
-static int hpd_nt(int cols) { return cols % 64 == 0 ? 4 : cols % 32 == 0 ? 2 : 1; }
-
-#define HPD_TILES(NTV, CALL)     \
-    switch (NTV) {               \
-        case 1: CALL(1); break;  \
-        case 2: CALL(2); break;  \
-        default: CALL(4); break; \
-    }
-
-// what every entry checks: the struct, the layer class (1 -> C, C -> C, C -> 1), the kernel size, the stride, the padding, the slope, the tables
-static int hpd_check(const fcl_hpd_t* a, const char* who) {
-    FCL_REQUIRE(a, FCL_ERR_INVALID, "%s: null argument", who);
-    const bool first = a->cin == 1 && hpd_width_ok(a->cout), mid = hpd_width_ok(a->cin) && hpd_width_ok(a->cout), last = a->cout == 1 && hpd_width_ok(a->cin);
+// the period discriminator's own rules inside hfd_check: the layer class (1 -> C, C -> C, C -> 1), the kernel size, the stride, the padding
+static int hpd_rules(const fcl_hpd_t* a, const char* who) {
+    const bool first = a->cin == 1 && hfd_width_ok(a->cout), mid = hfd_width_ok(a->cin) && hfd_width_ok(a->cout), last = a->cout == 1 && hfd_width_ok(a->cin);
     FCL_REQUIRE(first || mid || last, FCL_ERR_SHAPE, "%s: a layer is 1 -> C, C -> C' or C -> 1 with the widths multiples of 16 from 16 to 1024 (got cin %d, cout %d)",
                 who, a->cin, a->cout);
     if (last)
@@ -512,10 +353,6 @@ static int hpd_check(const fcl_hpd_t* a, const char* who) {
     else
         FCL_REQUIRE((a->ksize == 3 || a->ksize == 5) && a->stride >= 1 && a->stride <= 4 && a->pad == (a->ksize - 1) / 2, FCL_ERR_SHAPE,
                     "%s: kernel size 3 or 5, stride 1 to 4 and padding (k - 1) / 2 expected (got %d, %d, %d)", who, a->ksize, a->stride, a->pad);
-    FCL_REQUIRE(a->rows_in >= 1 && a->rows_in < 0x7fffffffLL && a->rows_out >= 1 && a->rows_out < 0x7fffffffLL, FCL_ERR_SHAPE,
-                "%s: 1 <= rows < 2^31 expected (got %lld in, %lld out)", who, (long long)a->rows_in, (long long)a->rows_out);
-    FCL_REQUIRE(a->slope >= 0.f && a->slope < 1.f, FCL_ERR_INVALID, "%s: 0 <= slope < 1 expected (got %g)", who, (double)a->slope);
-    FCL_REQUIRE(a->src && a->in_lo && a->in_hi, FCL_ERR_INVALID, "%s: null src / in_lo / in_hi", who);
     return FCL_OK;
 }
 
@@ -531,7 +368,7 @@ size_t fcl_hpd_dw_workspace_bytes(int64_t rows_out, int cin, int cout, int ksize
 }
 
 int fcl_hpd_layer_fwd(const fcl_hpd_t* a, fcl_stream_t stream) {
-    const int rc = hpd_check(a, "hpd_layer_fwd");
+    const int rc = hfd_check(a, "hpd_layer_fwd", hpd_rules);
     if (rc) return rc;
     FCL_REQUIRE(a->x && a->w && a->y, FCL_ERR_INVALID, "hpd_layer_fwd: null x / w / y");
     FCL_REQUIRE(aligned16(a->x) && aligned16(a->w) && aligned16(a->y), FCL_ERR_ALIGN, "hpd_layer_fwd: x, w and y must be 16-byte aligned");
@@ -539,14 +376,14 @@ int fcl_hpd_layer_fwd(const fcl_hpd_t* a, fcl_stream_t stream) {
     const long long n = a->rows_out, ni = a->rows_in;
     if (a->cin == 1) {
         ProfScope ps("hpd_expand_kernel<fwd>", 2.0 * a->ksize * a->cout * (double)n, (double)n, s);
-        hipLaunchKernelGGL(hpd_expand_fwd_kernel, dim3((unsigned)((n * (a->cout / 4) + 255) / 256)), dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo,
+        hipLaunchKernelGGL(hfd_expand_fwd_kernel, dim3((unsigned)((n * (a->cout / 4) + 255) / 256)), dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo,
                            a->in_hi, a->y, n, ni, a->cout, a->ksize, a->stride, a->pad, a->slope);
     } else if (a->cout == 1) {
         ProfScope ps("hpd_reduce_kernel<fwd>", 2.0 * a->ksize * a->cin * (double)n, (double)n, s);
         hipLaunchKernelGGL(hpd_reduce_fwd_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo, a->in_hi, a->y, n, ni,
                            a->cin, a->ksize, a->stride, a->pad);
     } else {
-        const int nt = hpd_nt(a->cout);
+        const int nt = hfd_nt(a->cout);
         const dim3 grid((unsigned)((n + PWR_ROWS - 1) / PWR_ROWS), (unsigned)(a->cout / (16 * nt)));
         ProfScope ps("hpd_conv_kernel", 2.0 * a->ksize * a->cin * a->cout * (double)n, (double)n, s);
 #define HPD_FWD_B(NN) \
@@ -554,9 +391,9 @@ int fcl_hpd_layer_fwd(const fcl_hpd_t* a, fcl_stream_t stream) {
 #define HPD_FWD_N(NN) \
     hipLaunchKernelGGL((hpd_conv_kernel<NN, HPD_NOBIAS>), grid, dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cin, a->cout, a->ksize, a->stride, a->pad, a->slope)
         if (a->bias) {
-            HPD_TILES(nt, HPD_FWD_B)
+            HFD_TILES(nt, HPD_FWD_B)
         } else {
-            HPD_TILES(nt, HPD_FWD_N)
+            HFD_TILES(nt, HPD_FWD_N)
         }
 #undef HPD_FWD_B
 #undef HPD_FWD_N
@@ -565,7 +402,7 @@ int fcl_hpd_layer_fwd(const fcl_hpd_t* a, fcl_stream_t stream) {
 }
 
 int fcl_hpd_layer_dx(const fcl_hpd_t* a, fcl_stream_t stream) {
-    const int rc = hpd_check(a, "hpd_layer_dx");
+    const int rc = hfd_check(a, "hpd_layer_dx", hpd_rules);
     if (rc) return rc;
     FCL_REQUIRE(a->g && a->w && a->y, FCL_ERR_INVALID, "hpd_layer_dx: null g / w / y");
     FCL_REQUIRE(a->cin == 1 ? (a->h == nullptr && a->extra == nullptr) : a->h != nullptr, FCL_ERR_INVALID,
@@ -577,26 +414,26 @@ int fcl_hpd_layer_dx(const fcl_hpd_t* a, fcl_stream_t stream) {
     if (a->cin == 1) {
         const long long items = n * a->stride;
         ProfScope ps("hpd_reduce_kernel<dx>", 2.0 * a->ksize * a->cout * (double)n, (double)ni, s);
-        hipLaunchKernelGGL(hpd_reduce_dx_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, s, a->g, a->w, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cout,
+        hipLaunchKernelGGL(hfd_reduce_dx_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, s, a->g, a->w, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cout,
                            a->ksize, a->stride, a->pad);
     } else if (a->cout == 1) {
         ProfScope ps("hpd_expand_kernel<dx>", 2.0 * a->ksize * a->cin * (double)n, (double)ni, s);
         hipLaunchKernelGGL(hpd_expand_dx_kernel, dim3((unsigned)((n * (a->cin / 4) + 255) / 256)), dim3(256), 0, s, a->g, a->w, a->h, a->extra, a->src, a->in_lo,
                            a->in_hi, a->y, n, ni, a->cin, a->ksize, a->pad, a->slope);
     } else {
-        const int nt = hpd_nt(a->cin), slots = (a->ksize + a->stride - 1) / a->stride;
+        const int nt = hfd_nt(a->cin), slots = (a->ksize + a->stride - 1) / a->stride;
         const dim3 grid((unsigned)((n + PWR_ROWS - 1) / PWR_ROWS), (unsigned)(a->cin / (16 * nt)), (unsigned)a->stride);
         ProfScope ps("hpd_conv_dx_kernel", 2.0 * a->ksize * a->cin * a->cout * (double)n, (double)ni, s);
 #define HPD_DX(NN) \
     hipLaunchKernelGGL((hpd_conv_dx_kernel<NN>), grid, dim3(256), 0, s, a->g, a->w, a->h, a->extra, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cout, a->cin, a->ksize, a->stride, a->pad, slots, a->slope)
-        HPD_TILES(nt, HPD_DX)
+        HFD_TILES(nt, HPD_DX)
 #undef HPD_DX
     }
     return check_hip(hipGetLastError(), "hpd_layer_dx");
 }
 
 int fcl_hpd_layer_dw(const fcl_hpd_t* a, fcl_stream_t stream) {
-    const int rc = hpd_check(a, "hpd_layer_dw");
+    const int rc = hfd_check(a, "hpd_layer_dw", hpd_rules);
     if (rc) return rc;
     FCL_REQUIRE(a->x && a->g && a->dw && a->workspace, FCL_ERR_INVALID, "hpd_layer_dw: null x / g / dw / workspace");
     FCL_REQUIRE(aligned16(a->x) && aligned16(a->g) && aligned16(a->workspace), FCL_ERR_ALIGN, "hpd_layer_dw: x, g and workspace must be 16-byte aligned");
@@ -612,7 +449,7 @@ int fcl_hpd_layer_dw(const fcl_hpd_t* a, fcl_stream_t stream) {
         const float *vec = first ? a->g : a->x, *sc = first ? a->x : a->g;
         const dim3 grid(chunks, (unsigned)((c + 127) / 128));
         ProfScope ps(first ? "hpd_dw_small_kernel<first>" : "hpd_dw_small_kernel<score>", 2.0 * (a->ksize + 1) * c * (double)n, (double)n, s);
-#define HPD_SMALL(V, K) hipLaunchKernelGGL((hpd_dw_small_kernel<V, K>), grid, dim3(1024), 0, s, vec, sc, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, c, a->pad)
+#define HPD_SMALL(V, K) hipLaunchKernelGGL((hfd_dw_small_kernel<V, K>), grid, dim3(1024), 0, s, vec, sc, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, c, a->pad)
         if (first) {
             if (a->ksize == 3)
                 HPD_SMALL(0, 3);
@@ -626,19 +463,15 @@ int fcl_hpd_layer_dw(const fcl_hpd_t* a, fcl_stream_t stream) {
         }
 #undef HPD_SMALL
     } else {
-        const int nt = hpd_nt(a->cout), combos = a->ksize * (a->cin / 16) + 1;
+        const int nt = hfd_nt(a->cout), combos = a->ksize * (a->cin / 16) + 1;
         const dim3 grid(chunks, (unsigned)((combos + 3) / 4), (unsigned)(a->cout / (16 * nt)));
         ProfScope ps("hpd_dw_kernel", 2.0 * a->ksize * a->cin * a->cout * (double)n, (double)n, s);
 #define HPD_DW(NN) \
     hipLaunchKernelGGL((hpd_dw_kernel<NN>), grid, dim3(256), 0, s, a->x, a->g, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, a->cin, a->cout, a->ksize, a->pad)
-        HPD_TILES(nt, HPD_DW)
+        HFD_TILES(nt, HPD_DW)
 #undef HPD_DW
     }
-    {
-        const int nw = a->ksize * a->cin * a->cout, nb = a->cout;
-        ProfScope ps("hpd_dw_reduce_kernel", 0.0, (double)chunks, s);
-        hipLaunchKernelGGL(pwr_dw_reduce_kernel, dim3((unsigned)((nw + nb + 255) / 256)), dim3(256), 0, s, a->workspace, (int)chunks, nw, nb, a->dw, a->db);
-    }
+    hfd_launch_dw_reduce(a, a->cin, "hpd_dw_reduce_kernel", s);
     return check_hip(hipGetLastError(), "hpd_layer_dw");
 }
 

@@ -8,36 +8,13 @@
 // workgroup's column block lies inside one group, and cig a multiple of 8.  The contraction runs over the flattened (tap, in-group channel) index in units of
 // 4, so cig = 8 feeds no MFMA with zeros but in the last step of a kernel whose 8 ksize cig is no multiple of 16.
 // Exact fp32 on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain), unconditional loads from clamped rows masked with pwr_keep, tile counts as template
-// arguments, 64-bit row arithmetic, no atomics.  The loops are local forms of the hpd_* kernels.  The dense ksize 5 layer and the score layer
-// of a scale discriminator are period-1 layers of hifigan_disc.hip and are launched through its entries.
-#include "pwg_rows.h"
+// arguments, 64-bit row arithmetic, no atomics.  The row descriptor and the first layer's three kernels are those of hfd_rows.h, shared with
+// hifigan_disc.hip; the grouped forward and input gradient run their fetch through its hfd_mma_loop; hsd_dw_kernel is the grouped form of
+// hpd_dw_kernel.  The dense ksize 5 layer and the score layer of a scale discriminator are period-1 layers of hifigan_disc.hip and are launched
+// through its entries.
+#include "hfd_rows.h"
 
 namespace fcl {
-
-constexpr int HSD_SMALL_GROUPS = 8;  // row groups of hsd_first_dw_kernel (1024 threads)
-
-// d LeakyReLU / d pre-activation from the stored post-activation; h == 0 takes the slope, as torch does
-__device__ __forceinline__ float hsd_mask(float h, float slope) { return h > 0.f ? 1.f : slope; }
-
-// what a row kernel needs to know about output row t (all zero past the end, so that every tap is masked away and nothing is stored)
-struct HsdRow {
-    long long src, lo, hi;  // the input row under tap `pad`, the input utterance (clamped to [0, rows_in])
-    long long olo, ohi;     // the output utterance
-};
-
-__device__ __forceinline__ HsdRow hsd_row(const int32_t* __restrict__ src, const int32_t* __restrict__ in_lo, const int32_t* __restrict__ in_hi, long long t,
-                                          long long n, long long rows_in, int ksize, int stride, int pad) {
-    HsdRow R = {0, 0, 0, 0, 0};
-    if (t < n) {
-        const long long lo = in_lo[t], hi = in_hi[t];
-        R.src = src[t];
-        R.lo = max(0LL, lo);
-        R.hi = min(rows_in, hi);
-        R.olo = max(0LL, t - (R.src - lo) / stride);
-        R.ohi = min(n, R.olo + (hi - lo + 2 * pad - ksize) / stride + 1);
-    }
-    return R;
-}
 
 // ---- grouped forward: y[t, co] = lrelu(bias[co] + sum_j sum_c x[src[t] + j - pad, g cig + c] w[j][c][co]).  A workgroup owns 128 output rows x 16 NT columns of
 // one group (blockIdx.y: the column block), a wave 32 rows.  A step is 16 rows of the flattened contraction index kk = j cig + c: a lane loads the 4
@@ -56,7 +33,7 @@ __global__ __launch_bounds__(256) void hsd_conv_kernel(const float* __restrict__
     long long centre[2], lo[2], hi[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
-        const HsdRow R = hsd_row(src, in_lo, in_hi, t0 + mt * 16 + r, n, rows_in, ksize, stride, pad);
+        const HfdRow R = hfd_row(src, in_lo, in_hi, t0 + mt * 16 + r, n, rows_in, ksize, stride, pad);
         centre[mt] = R.src - pad, lo[mt] = R.lo, hi[mt] = R.hi;
     }
     f32x4 acc[2][NT];
@@ -81,36 +58,7 @@ __global__ __launch_bounds__(256) void hsd_conv_kernel(const float* __restrict__
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) b[s][nt] = wr[(size_t)s * cout + nt * 16];
     };
-    f32x4 a0[2];
-    bool ok0[2];
-    float b0[4][NT];
-    fetch(0, a0, ok0, b0);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) a0[mt][s] = pwr_keep(a0[mt][s], ok0[mt]);
-    for (int step = 0; step < steps; ++step) {
-        f32x4 a1[2];
-        bool ok1[2];
-        float b1[4][NT];
-        fetch(min(step + 1, steps - 1), a1, ok1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[mt][s], b0[s][nt], acc[mt][nt], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) a0[mt][s] = pwr_keep(a1[mt][s], ok1[mt]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b0[s][nt] = b1[s][nt];
-    }
+    hfd_mma_loop<NT>(steps, fetch, acc);
     // results in the C / D layout: column = lane & 15, row = 4 (lane >> 4) + register
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -156,7 +104,7 @@ __global__ __launch_bounds__(256) void hsd_conv_dx_kernel(const float* __restric
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const long long t = t0 + mt * 16 + r;
-        const HsdRow R = hsd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
+        const HfdRow R = hfd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
         top[mt] = t + c, lo[mt] = R.olo, hi[mt] = R.ohi;
     }
     f32x4 acc[2][NT];
@@ -181,43 +129,14 @@ __global__ __launch_bounds__(256) void hsd_conv_dx_kernel(const float* __restric
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) b[s][nt] = pwr_keep(wr[(size_t)s * cin + nt * 16], colgrp[nt] == grp);
     };
-    f32x4 a0[2];
-    bool ok0[2];
-    float b0[4][NT];
-    fetch(0, a0, ok0, b0);  // (a phase without taps: slot 0 exists, holds zeros, and the loop below does not run)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) a0[mt][s] = pwr_keep(a0[mt][s], ok0[mt]);
-    for (int step = 0; step < steps; ++step) {
-        f32x4 a1[2];
-        bool ok1[2];
-        float b1[4][NT];
-        fetch(min(step + 1, steps - 1), a1, ok1, b1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[mt][s], b0[s][nt], acc[mt][nt], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) a0[mt][s] = pwr_keep(a1[mt][s], ok1[mt]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b0[s][nt] = b1[s][nt];
-    }
+    hfd_mma_loop<NT>(steps, fetch, acc);  // (a phase without taps: slot 0 exists, holds zeros, and the loop does not run)
     // the rows this lane stores are those of its accumulator registers, not the one it loaded for: their geometry is read again
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const long long t = t0 + mt * 16 + 4 * q + reg;
-            const HsdRow R = hsd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
+            const HfdRow R = hfd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
             const long long row = R.src + ph;
             if (row < R.lo || row >= R.hi) continue;
 #pragma unroll
@@ -225,7 +144,7 @@ __global__ __launch_bounds__(256) void hsd_conv_dx_kernel(const float* __restric
                 const size_t at = (size_t)row * cin + col0 + nt * 16 + r;
                 float v = acc[mt][nt][reg];
                 if (extra) v += extra[at];
-                y[at] = v * hsd_mask(hin[at], slope);
+                y[at] = v * hfd_mask(hin[at], slope);
             }
         }
 }
@@ -315,123 +234,6 @@ __global__ __launch_bounds__(256) void hsd_dw_kernel(const float* __restrict__ x
     }
 }
 
-// ---- 1 -> C forward (the first layer, up to 15 taps): y[t, c] = lrelu(bias[c] + sum_j s[src[t] + j - pad] w[j][c]); an item is (output row, 4 channels)
-__global__ __launch_bounds__(256) void hsd_first_fwd_kernel(const float* __restrict__ s, const float* __restrict__ w, const float* __restrict__ bias,
-                                                            const int32_t* __restrict__ src, const int32_t* __restrict__ in_lo,
-                                                            const int32_t* __restrict__ in_hi, float* __restrict__ y, long long n, long long rows_in, int c,
-                                                            int ksize, int stride, int pad, float slope) {
-    const int cq = c >> 2;
-    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (i >= n * cq) return;
-    const long long t = i / cq;
-    const int ch = (int)(i - t * cq) * 4;
-    const HsdRow R = hsd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < ksize; ++j) {
-        const long long rr = R.src + j - pad;
-        const float sv = (rr >= R.lo && rr < R.hi) ? s[rr] : 0.f;
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (size_t)j * c + ch);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(sv, wv[e], v[e]);
-    }
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float u = v[e] + (bias ? bias[ch + e] : 0.f);
-        o[e] = u > 0.f ? u : u * slope;
-    }
-    *reinterpret_cast<f32x4*>(y + t * c + ch) = o;
-}
-
-// ---- C -> 1 adjoint of the first layer (the waveform gradient) with the strided adjoint's tap rule: 16 lanes per (output row t, phase ph);
-// y[src[t] + ph] = sum_i sum_c g[t + c0 - i, c] w[j0 + stride i][c], j0 = (ph + pad) % stride, c0 = (ph + pad) / stride
-__global__ __launch_bounds__(256) void hsd_first_dx_kernel(const float* __restrict__ g, const float* __restrict__ w, const int32_t* __restrict__ src,
-                                                           const int32_t* __restrict__ in_lo, const int32_t* __restrict__ in_hi, float* __restrict__ y,
-                                                           long long n, long long rows_in, int c, int ksize, int stride, int pad) {
-    const int sub = threadIdx.x & 15;
-    const long long item = blockIdx.x * 16LL + (threadIdx.x >> 4);
-    const long long t = item / stride;
-    const int ph = (int)(item - t * stride);
-    const HsdRow R = hsd_row(src, in_lo, in_hi, t, n, rows_in, ksize, stride, pad);
-    const int c0 = (ph + pad) / stride, j0 = (ph + pad) - c0 * stride;
-    float acc = 0.f;
-    for (int j = j0, i = 0; j < ksize; j += stride, ++i) {
-        const long long rr = t + c0 - i;
-        if (rr < R.olo || rr >= R.ohi) continue;
-        for (int ch = 4 * sub; ch < c; ch += 64) {
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(g + rr * c + ch), wv = *reinterpret_cast<const f32x4*>(w + (size_t)j * c + ch);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = fmaf(gv[e], wv[e], acc);
-        }
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    const long long row = R.src + ph;
-    if (sub == 0 && row >= R.lo && row < R.hi) y[row] = acc;
-}
-
-// ---- weight gradient of the first layer, one chunk's partial per (workgroup, block of 128 channels) in the forward layout:
-// partial[j][ch] = sum_t s[src[t] + j - pad] g[t, ch], row KSIZE = sum_t g[t, ch].  Thread = (channel, one of 8 row groups taking every 8th row); the groups'
-// sums meet in LDS and are added in ascending group order.
-template <int KSIZE>
-__global__ __launch_bounds__(1024) void hsd_first_dw_kernel(const float* __restrict__ g, const float* __restrict__ s, const int32_t* __restrict__ src,
-                                                            const int32_t* __restrict__ in_lo, const int32_t* __restrict__ in_hi,
-                                                            float* __restrict__ partial, long long n, long long rows_in, int c, int pad) {
-    constexpr int UNROLL = KSIZE > 5 ? 2 : 4;  // rows per register set: the taps of a row are registers too
-    __shared__ float red[HSD_SMALL_GROUPS - 1][(KSIZE + 1) * 128];
-    const int lch = threadIdx.x & 127, grp = threadIdx.x >> 7;
-    const int ch = blockIdx.y * 128 + lch;
-    const int chc = min(ch, c - 1);  // (the threads past the width load a valid channel and store nothing)
-    const long long t_begin = (long long)blockIdx.x * PWR_DW_CHUNK, t_end = min(n, t_begin + PWR_DW_CHUNK);
-    const long long last = t_end - 1, alast = rows_in - 1;
-    float acc[KSIZE + 1];
-#pragma unroll
-    for (int j = 0; j <= KSIZE; ++j) acc[j] = 0.f;
-    for (int it0 = 0; it0 < PWR_DW_CHUNK / HSD_SMALL_GROUPS; it0 += UNROLL) {
-        int at[UNROLL], lo[UNROLL], hi[UNROLL];
-        float ov[UNROLL], xv[UNROLL][KSIZE];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const long long t = t_begin + (long long)(it0 + u) * HSD_SMALL_GROUPS + grp, tc = min(t, last);
-            at[u] = src[tc];
-            lo[u] = in_lo[tc];
-            hi[u] = in_hi[tc];
-            ov[u] = g[tc * c + chc];
-#pragma unroll
-            for (int j = 0; j < KSIZE; ++j) xv[u][j] = s[min(max((long long)at[u] + j - pad, 0LL), alast)];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const long long t = t_begin + (long long)(it0 + u) * HSD_SMALL_GROUPS + grp;
-            const bool live = t <= last;
-            const long long l = max(0, lo[u]), h = min(rows_in, (long long)hi[u]);
-            const float own = pwr_keep(ov[u], live);
-#pragma unroll
-            for (int j = 0; j < KSIZE; ++j) {
-                const long long rr = (long long)at[u] + j - pad;
-                acc[j] = fmaf(pwr_keep(xv[u][j], live && rr >= l && rr < h), own, acc[j]);
-            }
-            acc[KSIZE] += own;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (grp > 0) {
-#pragma unroll
-        for (int j = 0; j <= KSIZE; ++j) red[grp - 1][j * 128 + lch] = acc[j];
-    }
-    __syncthreads();
-    if (grp == 0 && ch < c) {
-#pragma unroll
-        for (int j = 0; j <= KSIZE; ++j)
-#pragma unroll
-            for (int k = 0; k < HSD_SMALL_GROUPS - 1; ++k) acc[j] += red[k][j * 128 + lch];
-        float* out = partial + (size_t)blockIdx.x * ((size_t)KSIZE + 1) * c;
-#pragma unroll
-        for (int j = 0; j <= KSIZE; ++j) out[(size_t)j * c + ch] = acc[j];
-    }
-}
-
 // the utterance of row t: the largest b with off[b] <= t (off [n_utt + 1] ascending, off[0] = 0, t < off[n_utt])
 __device__ __forceinline__ int hsd_utterance(const int32_t* __restrict__ off, int n_utt, long long t) {
     int lo = 0, hi = n_utt;
@@ -472,20 +274,9 @@ __global__ __launch_bounds__(256) void hsd_pool_kernel(const float* __restrict__
     }
 }
 
-static bool hsd_width_ok(int c) { return c >= 16 && c <= 1024 && c % 16 == 0; }
-static int hsd_nt(int cols) { return cols % 64 == 0 ? 4 : cols % 32 == 0 ? 2 : 1; }
-
-#define HSD_TILES(NTV, CALL)     \
-    switch (NTV) {               \
-        case 1: CALL(1); break;  \
-        case 2: CALL(2); break;  \
-        default: CALL(4); break; \
-    }
-
-// what every layer entry checks: the struct, the layer class (first or grouped), the groups, the kernel size, the stride, the padding, the slope, the tables
-static int hsd_check(const fcl_hsd_t* a, const char* who) {
-    FCL_REQUIRE(a, FCL_ERR_INVALID, "%s: null argument", who);
-    const bool first = a->cin == 1 && hsd_width_ok(a->cout), mid = hsd_width_ok(a->cin) && hsd_width_ok(a->cout);
+// the scale discriminator's own rules inside hfd_check: the layer class (first or grouped), the groups, the kernel size, the stride, the padding
+static int hsd_rules(const fcl_hsd_t* a, const char* who) {
+    const bool first = a->cin == 1 && hfd_width_ok(a->cout), mid = hfd_width_ok(a->cin) && hfd_width_ok(a->cout);
     FCL_REQUIRE(first || mid, FCL_ERR_SHAPE,
                 "%s: a layer is 1 -> C or C -> C' with the widths multiples of 16 from 16 to 1024; the score layer is an fcl_hpd layer (got cin %d, cout %d)", who,
                 a->cin, a->cout);
@@ -498,10 +289,6 @@ static int hsd_check(const fcl_hsd_t* a, const char* who) {
     const int kmax = first ? 15 : 41;
     FCL_REQUIRE(a->ksize >= 3 && a->ksize <= kmax && a->ksize % 2 == 1 && a->stride >= 1 && a->stride <= 4 && a->pad == (a->ksize - 1) / 2, FCL_ERR_SHAPE,
                 "%s: an odd kernel size from 3 to %d, stride 1 to 4 and padding (k - 1) / 2 expected (got %d, %d, %d)", who, kmax, a->ksize, a->stride, a->pad);
-    FCL_REQUIRE(a->rows_in >= 1 && a->rows_in < 0x7fffffffLL && a->rows_out >= 1 && a->rows_out < 0x7fffffffLL, FCL_ERR_SHAPE,
-                "%s: 1 <= rows < 2^31 expected (got %lld in, %lld out)", who, (long long)a->rows_in, (long long)a->rows_out);
-    FCL_REQUIRE(a->slope >= 0.f && a->slope < 1.f, FCL_ERR_INVALID, "%s: 0 <= slope < 1 expected (got %g)", who, (double)a->slope);
-    FCL_REQUIRE(a->src && a->in_lo && a->in_hi, FCL_ERR_INVALID, "%s: null src / in_lo / in_hi", who);
     return FCL_OK;
 }
 
@@ -526,7 +313,7 @@ size_t fcl_hsd_dw_workspace_bytes(int64_t rows_out, int cin, int cout, int group
 }
 
 int fcl_hsd_layer_fwd(const fcl_hsd_t* a, fcl_stream_t stream) {
-    const int rc = hsd_check(a, "hsd_layer_fwd");
+    const int rc = hfd_check(a, "hsd_layer_fwd", hsd_rules);
     if (rc) return rc;
     FCL_REQUIRE(a->x && a->w && a->y, FCL_ERR_INVALID, "hsd_layer_fwd: null x / w / y");
     FCL_REQUIRE(aligned16(a->x) && aligned16(a->w) && aligned16(a->y), FCL_ERR_ALIGN, "hsd_layer_fwd: x, w and y must be 16-byte aligned");
@@ -534,22 +321,22 @@ int fcl_hsd_layer_fwd(const fcl_hsd_t* a, fcl_stream_t stream) {
     const long long n = a->rows_out, ni = a->rows_in;
     if (a->cin == 1) {
         ProfScope ps("hsd_first_kernel<fwd>", 2.0 * a->ksize * a->cout * (double)n, (double)n, s);
-        hipLaunchKernelGGL(hsd_first_fwd_kernel, dim3((unsigned)((n * (a->cout / 4) + 255) / 256)), dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo,
+        hipLaunchKernelGGL(hfd_expand_fwd_kernel, dim3((unsigned)((n * (a->cout / 4) + 255) / 256)), dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo,
                            a->in_hi, a->y, n, ni, a->cout, a->ksize, a->stride, a->pad, a->slope);
     } else {
-        const int cig = a->cin / a->groups, cog = a->cout / a->groups, nt = hsd_nt(cog);
+        const int cig = a->cin / a->groups, cog = a->cout / a->groups, nt = hfd_nt(cog);
         const dim3 grid((unsigned)((n + PWR_ROWS - 1) / PWR_ROWS), (unsigned)(a->cout / (16 * nt)));
         ProfScope ps("hsd_conv_kernel", 2.0 * a->ksize * cig * a->cout * (double)n, (double)n, s);
 #define HSD_FWD(NN) \
     hipLaunchKernelGGL((hsd_conv_kernel<NN>), grid, dim3(256), 0, s, a->x, a->w, a->bias, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cin, a->cout, cig, cog, a->ksize, a->stride, a->pad, a->slope)
-        HSD_TILES(nt, HSD_FWD)
+        HFD_TILES(nt, HSD_FWD)
 #undef HSD_FWD
     }
     return check_hip(hipGetLastError(), "hsd_layer_fwd");
 }
 
 int fcl_hsd_layer_dx(const fcl_hsd_t* a, fcl_stream_t stream) {
-    const int rc = hsd_check(a, "hsd_layer_dx");
+    const int rc = hfd_check(a, "hsd_layer_dx", hsd_rules);
     if (rc) return rc;
     FCL_REQUIRE(a->g && a->w && a->y, FCL_ERR_INVALID, "hsd_layer_dx: null g / w / y");
     FCL_REQUIRE(a->cin == 1 ? (a->h == nullptr && a->extra == nullptr) : a->h != nullptr, FCL_ERR_INVALID,
@@ -561,22 +348,22 @@ int fcl_hsd_layer_dx(const fcl_hsd_t* a, fcl_stream_t stream) {
     if (a->cin == 1) {
         const long long items = n * a->stride;
         ProfScope ps("hsd_first_kernel<dx>", 2.0 * a->ksize * a->cout * (double)n, (double)ni, s);
-        hipLaunchKernelGGL(hsd_first_dx_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, s, a->g, a->w, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cout,
+        hipLaunchKernelGGL(hfd_reduce_dx_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, s, a->g, a->w, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cout,
                            a->ksize, a->stride, a->pad);
     } else {
-        const int cig = a->cin / a->groups, cog = a->cout / a->groups, nt = hsd_nt(cig), slots = (a->ksize + a->stride - 1) / a->stride;
+        const int cig = a->cin / a->groups, cog = a->cout / a->groups, nt = hfd_nt(cig), slots = (a->ksize + a->stride - 1) / a->stride;
         const dim3 grid((unsigned)((n + PWR_ROWS - 1) / PWR_ROWS), (unsigned)(a->cin / (16 * nt)), (unsigned)a->stride);
         ProfScope ps("hsd_conv_dx_kernel", 2.0 * a->ksize * cig * a->cout * (double)n, (double)ni, s);
 #define HSD_DX(NN) \
     hipLaunchKernelGGL((hsd_conv_dx_kernel<NN>), grid, dim3(256), 0, s, a->g, a->w, a->h, a->extra, a->src, a->in_lo, a->in_hi, a->y, n, ni, a->cin, a->cout, cig, cog, a->ksize, a->stride, a->pad, slots, a->slope)
-        HSD_TILES(nt, HSD_DX)
+        HFD_TILES(nt, HSD_DX)
 #undef HSD_DX
     }
     return check_hip(hipGetLastError(), "hsd_layer_dx");
 }
 
 int fcl_hsd_layer_dw(const fcl_hsd_t* a, fcl_stream_t stream) {
-    const int rc = hsd_check(a, "hsd_layer_dw");
+    const int rc = hfd_check(a, "hsd_layer_dw", hsd_rules);
     if (rc) return rc;
     FCL_REQUIRE(a->x && a->g && a->dw && a->workspace, FCL_ERR_INVALID, "hsd_layer_dw: null x / g / dw / workspace");
     FCL_REQUIRE(aligned16(a->x) && aligned16(a->g) && aligned16(a->workspace), FCL_ERR_ALIGN, "hsd_layer_dw: x, g and workspace must be 16-byte aligned");
@@ -585,13 +372,12 @@ int fcl_hsd_layer_dw(const fcl_hsd_t* a, fcl_stream_t stream) {
                 a->workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const long long n = a->rows_out, ni = a->rows_in;
-    const unsigned chunks = (unsigned)pwr_chunks(n);
     const int cig = a->cin / a->groups, cog = a->cout / a->groups;
     if (a->cin == 1) {
-        const dim3 grid(chunks, (unsigned)((a->cout + 127) / 128));
+        const dim3 grid((unsigned)pwr_chunks(n), (unsigned)((a->cout + 127) / 128));
         ProfScope ps("hsd_first_kernel<dw>", 2.0 * (a->ksize + 1) * a->cout * (double)n, (double)n, s);
 #define HSD_FIRST(K) \
-    case K: hipLaunchKernelGGL((hsd_first_dw_kernel<K>), grid, dim3(1024), 0, s, a->g, a->x, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, a->cout, a->pad); break
+    case K: hipLaunchKernelGGL((hfd_dw_small_kernel<0, K>), grid, dim3(1024), 0, s, a->g, a->x, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, a->cout, a->pad); break
         switch (a->ksize) {
             HSD_FIRST(3);
             HSD_FIRST(5);
@@ -599,23 +385,19 @@ int fcl_hsd_layer_dw(const fcl_hsd_t* a, fcl_stream_t stream) {
             HSD_FIRST(9);
             HSD_FIRST(11);
             HSD_FIRST(13);
-            default: hipLaunchKernelGGL((hsd_first_dw_kernel<15>), grid, dim3(1024), 0, s, a->g, a->x, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, a->cout, a->pad);
+            default: hipLaunchKernelGGL((hfd_dw_small_kernel<0, 15>), grid, dim3(1024), 0, s, a->g, a->x, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, a->cout, a->pad);
         }
 #undef HSD_FIRST
     } else {
-        const int nt = hsd_nt(cog), combos = (a->ksize * cig + 15) / 16 + 1;
-        const dim3 grid(chunks, (unsigned)((combos + 3) / 4), (unsigned)(a->cout / (16 * nt)));
+        const int nt = hfd_nt(cog), combos = (a->ksize * cig + 15) / 16 + 1;
+        const dim3 grid((unsigned)pwr_chunks(n), (unsigned)((combos + 3) / 4), (unsigned)(a->cout / (16 * nt)));
         ProfScope ps("hsd_dw_kernel", 2.0 * a->ksize * cig * a->cout * (double)n, (double)n, s);
 #define HSD_DW(NN) \
     hipLaunchKernelGGL((hsd_dw_kernel<NN>), grid, dim3(256), 0, s, a->x, a->g, a->src, a->in_lo, a->in_hi, a->workspace, n, ni, a->cin, a->cout, cig, cog, a->ksize, a->pad)
-        HSD_TILES(nt, HSD_DW)
+        HFD_TILES(nt, HSD_DW)
 #undef HSD_DW
     }
-    {
-        const int nw = a->ksize * cig * a->cout, nb = a->cout;
-        ProfScope ps("hsd_dw_reduce_kernel", 0.0, (double)chunks, s);
-        hipLaunchKernelGGL(pwr_dw_reduce_kernel, dim3((unsigned)((nw + nb + 255) / 256)), dim3(256), 0, s, a->workspace, (int)chunks, nw, nb, a->dw, a->db);
-    }
+    hfd_launch_dw_reduce(a, cig, "hsd_dw_reduce_kernel", s);
     return check_hip(hipGetLastError(), "hsd_layer_dw");
 }
 

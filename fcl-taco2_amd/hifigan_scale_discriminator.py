@@ -17,14 +17,14 @@ The contract is stated in include/fcl_hip.h "HiFi-GAN scale discriminator" and r
 channel-last [rows, C], the utterances back to back (to_reference_layout gives the package's [B, C, T_l] for equal lengths).  Only the post-activations
 are kept for the backward pass.  Weight norm and spectral norm are folded in torch operations, so autograd carries them.  One arithmetic mode (exact
 fp32).  No CPU fallback."""
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .hifigan_discriminator import (PERIODS, HiFiGANMultiPeriodDiscriminator, _Activation, discriminator_adversarial_loss, feature_match_loss,  # noqa: F401
-                                    generator_adversarial_loss, out_rows, pack_input, segment_tables, split_batch)
+from .hfd_common import (LayerMaps, Plan, _Activation, _args, _Discriminator, _entry, _Function, activation_slope, launch_backward,  # noqa: F401
+                         launch_forward, out_rows, pack_input, pack_weights, segment_tables, unpack_dweights)
+from .hifigan_discriminator import (PERIODS, HiFiGANMultiPeriodDiscriminator, discriminator_adversarial_loss, feature_match_loss,  # noqa: F401
+                                    generator_adversarial_loss, split_batch)
 from .pwg_common import MAX_SAMPLES, _Conv, _Module
 
 WHO = "fcl-taco2_amd: HiFi-GAN scale discriminator"
@@ -89,63 +89,20 @@ def pooled_length(n):
     return n // 2 + 1
 
 
-class ScalePlan(object):
-    """Per-layer geometry (cin, cout, taps, stride, pad, groups), the score layer last, and the sizes of what a pass needs"""
+class ScalePlan(Plan):
+    """Per-layer geometry (cin, cout, taps, stride, pad, groups), the score layer last, and the sizes of what a pass needs (hfd_common.Plan: heights, rows,
+    act_shapes, kept_bytes, workspace_floats, dweight_shapes, slot_index); an utterance is one segment, and `kinds` says which entries run each layer"""
+
+    period = 1
 
     def __init__(self, device="cuda:0", **config):
         self.geometry = check_configuration(**config)
         self.kinds = layer_kinds(self.geometry)
         self.slope, self.bias = float(config.get("negative_slope", 0.1)), bool(config.get("bias", True))
-        self.layers = len(self.geometry)  # the score layer included
-        if not str(device).startswith("cuda"):
-            raise _lib.FclError("fcl-taco2_amd: ScalePlan needs a GPU device (no CPU fallback)")
-        self.device = torch.device(device)
-        self._slot_index = {}
+        self._on(device)
 
-    def heights(self, n):
-        """rows of an utterance of n samples: [n, T_0, .., T_last, T_score]"""
-        hs = [int(n)]
-        for _, _, k, s, pad, _ in self.geometry:
-            hs.append(out_rows(hs[-1], k, s, pad))
-        return hs
-
-    def rows(self, lens):
-        """rows per level of a batch: rows[0] the samples, rows[l + 1] the output rows of layer l"""
-        per = [self.heights(int(n)) for n in lens]
-        return [sum(h[l] for h in per) for l in range(self.layers + 1)]
-
-    def act_shapes(self, rows):
-        """the outputs of a pass: map_0 .. map_{L-1} [rows[l + 1], cout_l] and the scores [rows[L + 1]]"""
-        return [(rows[l + 1], g[1]) for l, g in enumerate(self.geometry[:-1])] + [(rows[-1],)]
-
-    def kept_bytes(self, lens):
-        """what a forward pass keeps for the backward pass: the packed waveform and every map"""
-        rows = self.rows(lens)
-        return 4 * (rows[0] + sum(n * c for n, c in self.act_shapes(rows)[:-1]))
-
-    def workspace_floats(self, rows):
-        """the partials of the largest layer's weight gradient"""
-        lib = _lib.load()
-        need = 0
-        for l, ((ci, co, k, _, _, gr), kind) in enumerate(zip(self.geometry, self.kinds)):
-            if kind in (FIRST, GROUPED):
-                need = max(need, lib.fcl_hsd_dw_workspace_bytes(rows[l + 1], ci, co, gr, k))
-            else:
-                need = max(need, lib.fcl_hpd_dw_workspace_bytes(rows[l + 1], ci, co, k))
-        return need // 4
-
-    def dweight_shapes(self):
-        """per layer (dw [taps, cin / groups, cout], db [cout]) in the kernels' tap-major layout"""
-        return [((k, ci // gr, co), (co,)) for ci, co, k, _, _, gr in self.geometry]
-
-    def slot_index(self, layer):
-        """which tap (taps: none) each slot of the per-phase input-gradient weights holds, [stride x ceil(taps / stride)] int64 on the device"""
-        if layer not in self._slot_index:
-            _, _, k, s, pad, _ = self.geometry[layer]
-            slots = -(-k // s)
-            idx = [[(ph + pad) % s + s * i for i in range(slots)] for ph in range(s)]
-            self._slot_index[layer] = torch.tensor([j if j < k else k for row in idx for j in row], dtype=torch.int64, device=self.device)
-        return self._slot_index[layer]
+    def hsd(self, layer):
+        return self.kinds[layer] in (FIRST, GROUPED)
 
 
 class LayerPlan(ScalePlan):
@@ -176,15 +133,6 @@ class ScaleMaps(object):
             self.src.append(src), self.in_lo.append(lo), self.in_hi.append(hi)
 
 
-class LayerMaps(object):
-    """the tables of one layer alone over utterances of the given heights, for launches on given inputs"""
-
-    def __init__(self, h_in, k, s, pad, device):
-        self.rows = [int(np.sum(h_in)), int(np.sum(out_rows(np.asarray(h_in, dtype=np.int64), k, s, pad)))]
-        src, lo, hi = segment_tables(h_in, k, s, pad, device)
-        self.src, self.in_lo, self.in_hi = [src], [lo], [hi]
-
-
 class PoolMaps(object):
     """the utterances' first rows before and after one pooling: in_off / out_off [n_utt + 1] int32 on the device, and the pooled lengths"""
 
@@ -200,127 +148,11 @@ class PoolMaps(object):
         self.in_off, self.out_off = off(self.lens), off(self.out_lens)
 
 
-def pack_weights(plan, weights, biases, backward=True):
-    """torch Conv1d weights [cout, cin / groups, taps] -> per layer (wf [taps, cin / groups, cout], wb, bias or None), contiguous; wb is the input gradient's
-    operand: for a C -> C' layer [stride, ceil(taps / stride), cout / groups, cin] (slot i of phase ph holds tap (ph + pad) % stride + stride i of the
-    column's own group, or zeros), else wf itself"""
-    out = []
-    for l, (w, b) in enumerate(zip(weights, biases)):
-        w = w.detach().to(torch.float32)
-        wf, wb = w.permute(2, 1, 0).contiguous(), None
-        if backward:
-            ci, co, k, s, _, gr = plan.geometry[l]
-            if ci > 1 and co > 1:
-                cog, cig = co // gr, ci // gr
-                taps = w.reshape(gr, cog, cig, k).permute(3, 1, 0, 2).reshape(k, cog, ci)
-                taps = torch.cat([taps, w.new_zeros(1, cog, ci)])
-                wb = taps.index_select(0, plan.slot_index(l)).contiguous()
-            else:
-                wb = wf
-        out.append((wf, wb, None if b is None else b.detach().to(torch.float32).contiguous()))
-    return out
-
-
-def unpack_dweights(dws):
-    """the kernels' [taps, cin / groups, cout] -> torch's [cout, cin / groups, taps]"""
-    return [dw.permute(2, 1, 0).contiguous() for dw in dws]
-
-
-def _args(plan, maps, layer, **ptr):
-    ci, co, k, s, pad, gr = plan.geometry[layer]
-    hsd = plan.kinds[layer] in (FIRST, GROUPED)
-    a = _lib.HsdLayer() if hsd else _lib.HpdLayer()
-    a.rows_in, a.rows_out, a.cin, a.cout, a.ksize, a.stride, a.pad, a.slope = maps.rows[layer], maps.rows[layer + 1], ci, co, k, s, pad, plan.slope
-    if hsd:
-        a.groups = gr
-    a.src, a.in_lo, a.in_hi = maps.src[layer].data_ptr(), maps.in_lo[layer].data_ptr(), maps.in_hi[layer].data_ptr()
-    for key, v in ptr.items():
-        if v is not None:
-            setattr(a, key, v.data_ptr())
-    return a
-
-
-def _entry(plan, layer, what):
-    lib = _lib.load()
-    return getattr(lib, ("fcl_hsd_layer_" if plan.kinds[layer] in (FIRST, GROUPED) else "fcl_hpd_layer_") + what)
-
-
-# on caller-owned buffers (the tests surround them with guard zones)
-def launch_forward(plan, maps, x, weights, acts):
-    """x [rows[0]] float32 (the packed waveform), weights from pack_weights -> acts: the maps and the scores (plan.act_shapes)"""
-    st = ops._stream()
-    src = x
-    for l, (wf, _, b) in enumerate(weights):
-        _lib.check(_entry(plan, l, "fwd")(C.byref(_args(plan, maps, l, x=src, w=wf, bias=b, y=acts[l])), st))
-        src = acts[l]
-
-
-def launch_backward(plan, maps, dscore, extras, weights, acts, gx, dweights, x=None, grads=None, workspace=None):
-    """dscore [rows[L + 1]], extras: per map its direct gradient [rows, C] or None -> gx [rows[0]] (None: the waveform gradient is not computed) and dweights =
-    [(dw [taps, cin / groups, cout], db [cout] or None)] per layer (None: no weight gradient is computed).  acts: the maps; x: the packed waveform (needed
-    with dweights); grads: one buffer per map, of its size; workspace: plan.workspace_floats(rows) floats (needed with dweights)."""
-    st = ops._stream()
-    g = dscore
-    for l in range(plan.layers - 1, -1, -1):
-        _, wb, _ = weights[l]
-        below = x if l == 0 else acts[l - 1]
-        if dweights is not None:
-            dw, db = dweights[l]
-            a = _args(plan, maps, l, x=below, g=g, dw=dw, db=db, workspace=workspace)
-            a.workspace_bytes = workspace.numel() * 4
-            _lib.check(_entry(plan, l, "dw")(C.byref(a), st))
-        if l > 0:
-            _lib.check(_entry(plan, l, "dx")(C.byref(_args(plan, maps, l, g=g, w=wb, h=below, extra=extras[l - 1], y=grads[l - 1])), st))
-            g = grads[l - 1]
-        elif gx is not None:
-            _lib.check(_entry(plan, l, "dx")(C.byref(_args(plan, maps, l, g=g, w=wb, y=gx)), st))
-
-
 def launch_pool(pm, x, y, adjoint=False):
     """pm: PoolMaps.  forward: x [rows_in] -> y [rows_out]; adjoint: x = the gradient [rows_out] -> y [rows_in]"""
     lib = _lib.load()
     f = lib.fcl_hsd_pool_dx if adjoint else lib.fcl_hsd_pool_fwd
     _lib.check(f(x.data_ptr(), y.data_ptr(), pm.in_off.data_ptr(), pm.out_off.data_ptr(), pm.n_utt, pm.rows_in, pm.rows_out, ops._stream()))
-
-
-class _Function(torch.autograd.Function):
-    """every map and the scores of the packed waveform under plain weights and biases; backward takes a gradient for each output (None: none) and gives
-    the gradients of all inputs that are asked for"""
-
-    @staticmethod
-    def forward(ctx, plan, maps, x, *params):
-        L, dev = plan.layers, plan.device
-        ws, bs = params[:L], params[L:] if plan.bias else [None] * L
-        with torch.cuda.device(dev):
-            x = x.detach().contiguous()
-            packed = pack_weights(plan, ws, bs, backward=any(ctx.needs_input_grad))
-            acts = [torch.empty(s, device=dev, dtype=torch.float32) for s in plan.act_shapes(maps.rows)]
-            launch_forward(plan, maps, x, packed, acts)
-        ctx.plan, ctx.maps, ctx.packed = plan, maps, packed
-        ctx.save_for_backward(x, *acts[:-1])
-        ctx.set_materialize_grads(False)
-        return tuple(acts)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *douts):
-        plan, maps, dev = ctx.plan, ctx.maps, ctx.plan.device
-        x, acts = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
-        need_x, need_w = ctx.needs_input_grad[2], any(ctx.needs_input_grad[3:])
-        with torch.cuda.device(dev):
-            new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-            f32 = lambda g: None if g is None else g.detach().to(torch.float32).contiguous()
-            dscore = f32(douts[-1]) if douts[-1] is not None else torch.zeros(maps.rows[-1], device=dev, dtype=torch.float32)
-            gx = new(maps.rows[0]) if need_x else None
-            dweights = [(new(sw), new(sb) if plan.bias else None) for sw, sb in plan.dweight_shapes()] if need_w else None
-            launch_backward(plan, maps, dscore, [f32(g) for g in douts[:-1]], ctx.packed, acts, gx, dweights, x=x,
-                            grads=[new(a.shape) for a in acts], workspace=new(plan.workspace_floats(maps.rows)) if need_w else None)
-        out = [None, None, gx]
-        if need_w:
-            out += unpack_dweights([dw for dw, _ in dweights]) + ([db for _, db in dweights] if plan.bias else [])
-        else:
-            out += [None] * (len(ctx.needs_input_grad) - 3)
-        return tuple(out)
 
 
 class _Pool(torch.autograd.Function):
@@ -376,26 +208,21 @@ class _SpectralConv(torch.nn.Module):
         return self.weight_orig / sigma
 
 
-class HiFiGANScaleDiscriminator(_Module):
+class HiFiGANScaleDiscriminator(_Discriminator):
     """forward(x, lens=None) -> [map_0, .., map_{L-1}, scores], packed.  Parameters: layers.{l}.0.weight / .bias for the activated layers and
     layers.{L}.weight / .bias for the score layer (weight_g / weight_v under use_weight_norm; weight_orig with the buffers weight_u / weight_v under
     use_spectral_norm), Conv1d-shaped [cout, cin / groups, k]; Kaiming-normal weights, zero biases."""
 
-    CHECKPOINT_KEY, PLAN = "discriminator", ScalePlan
+    PLAN, MAPS = ScalePlan, ScaleMaps
 
     def __init__(self, in_channels=1, out_channels=1, kernel_sizes=(15, 41, 5, 3), channels=128, max_downsample_channels=1024, max_groups=16, bias=True,
                  downsample_scales=(2, 2, 4, 4, 1), nonlinear_activation="LeakyReLU", nonlinear_activation_params=None, use_weight_norm=True,
                  use_spectral_norm=False, negative_slope=None):
         super().__init__()
-        params = dict(nonlinear_activation_params or {"negative_slope": 0.1})
-        if negative_slope is not None:
-            params["negative_slope"] = negative_slope
-        extra = sorted(set(params) - {"negative_slope", "inplace"})
-        if extra:
-            raise ValueError("%s: nonlinear_activation_params=%r is not supported on the HIP path (negative_slope only)" % (WHO, extra))
+        slope = activation_slope(WHO, nonlinear_activation_params, negative_slope)
         self.config = dict(in_channels=in_channels, out_channels=out_channels, kernel_sizes=tuple(kernel_sizes), channels=channels,
                            max_downsample_channels=max_downsample_channels, max_groups=max_groups, bias=bias, downsample_scales=tuple(downsample_scales),
-                           nonlinear_activation=nonlinear_activation, negative_slope=params.get("negative_slope", 0.01), use_weight_norm=use_weight_norm,
+                           nonlinear_activation=nonlinear_activation, negative_slope=slope, use_weight_norm=use_weight_norm,
                            use_spectral_norm=use_spectral_norm)
         geo = check_configuration(**self.config)
         holder = (lambda shape: _SpectralConv(shape, bias)) if use_spectral_norm else (lambda shape: _Conv(shape, bias, use_weight_norm))
@@ -407,24 +234,6 @@ class HiFiGANScaleDiscriminator(_Module):
 
     def conv_list(self):
         return [m[0] for m in list(self.layers)[:-1]] + [self.layers[-1]]
-
-    def maps(self, lens):
-        """kept for the next batch of the same lengths"""
-        key = tuple(lens)
-        plan = self.plan()
-        if key != self._maps_key:
-            self._maps_key, self._maps = key, ScaleMaps(plan, lens)
-        return self._maps
-
-    def forward_packed(self, x, lens):
-        plan, maps = self.plan(), self.maps(lens)
-        convs = self.conv_list()
-        params = [m.folded() for m in convs] + ([m.bias for m in convs] if self.config["bias"] else [])
-        return list(_Function.apply(plan, maps, x, *params))
-
-    def forward(self, x, lens=None):
-        x, lens = pack_input(x, lens, self.plan().device)
-        return self.forward_packed(x, lens)
 
 
 class HiFiGANMultiScaleDiscriminator(_Module):

@@ -9,7 +9,10 @@ adversarial + 2 x feature matching against a fixed real batch's maps); forward +
 discriminator's update).  One process, alternating legs, event timers, a synchronise at each end, medians with the interquartile spread.  Prints one
 JSON line and writes it to profiles/hfgs_ab.json.
 
-    python tools/hfgs_ab.py [--batch 16] [--samples 8192] [--scales 3] [--repeats 20] [--warmup 3] [--prof]
+    python tools/hfgs_ab.py [--batch 16] [--samples 8192] [--scales 3] [--repeats 20] [--warmup 3] [--prof] [--dump PATH]
+
+--dump PATH saves leg B's scores, waveform gradient and weight and bias gradients of this fixed-seed run as PATH (.npy, one float32 vector): two builds of
+the library computed the same bits where np.array_equal of their dumps holds.
 """
 import argparse
 import json
@@ -73,6 +76,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prof", action="store_true", help="also one profiled update of each kind of leg B: per-kernel ms and TFLOP/s from the library's launch record")
+    ap.add_argument("--dump", metavar="PATH", help="save leg B's scores and all gradients of the fixed-seed run as one .npy vector")
     args = ap.parse_args()
     import fcl_taco2_amd  # noqa: F401
     from fcl_taco2_amd import _lib, hifigan_scale_discriminator as P
@@ -134,6 +138,8 @@ def main():
                                     weight_gradients=max(rel(a, b) for a, b in zip(update(hip), update(eager))))
     # a LeakyReLU mask or an L1 sign next to zero can fall to different sides on two float32 paths: the gradient's 2-norm, not its maximum, is compared
     out["waveform_gradient_rel_2norm_A_minus_B"] = float((ga - gb).norm() / gb.norm())
+    if args.dump:
+        np.save(args.dump, torch.cat([v.detach().reshape(-1) for v in [o[-1] for o in oh] + [ga] + update(hip)]).cpu().numpy())
     if args.prof:
         _lib.prof_enable(True)
         update(hip)
