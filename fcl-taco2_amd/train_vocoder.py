@@ -1,4 +1,4 @@
-"""Vocoder training on one MI355X, two recipes chosen by generator_type (--generator-type, or the key of --config).
+"""Vocoder training on MI355X, two recipes chosen by generator_type (--generator-type, or the key of --config).
 
 ParallelWaveGANGenerator (the default): the published parallel_wavegan.v1 recipe (restated from its paper and config, not diffed against a file): the
 generator step is HIP from (z, c) to the waveform and back (pwg_generator.py), the discriminator and the multi-resolution STFT loss
@@ -13,8 +13,15 @@ Torch keeps weight and spectral norm, the optimisers and the schedulers.
 reads `feats/mels/<utt>.npy` (the normalised [T, n_mels] mels that preprocess / extract_features write, T = samples // hop + 1) and 16-bit PCM mono wavs,
 and writes config.yml (parallel_wavegan's layout), checkpoint-<steps>steps.pkl (vocoder.PWGPlan or hifigan.HiFiGANPlan, vocoder_decode and tts load
 them as they are) and train_log.jsonl into --outdir.  Which utterances and windows make step n's batch, and the noise of step n, are functions of
-(--seed, n) alone, so --resume needs nothing but the checkpoint: 2 + 2 steps give the bytes of 4.  One process, one GPU; data-parallel training is not
-built."""
+(--seed, n) alone, so --resume needs nothing but the checkpoint: 2 + 2 steps give the bytes of 4.
+
+    python -m fcl_taco2_amd.train_vocoder --gpus 8 ... --outdir exp/hifigan
+
+trains data-parallel on one node (vocoder_dp.py): the command starts its ranks itself, or runs as one rank under torch.distributed.run.
+--batch-size stays the GLOBAL batch -- rank r takes items i % W == r of step n's batch and of its noise, so a W-rank run consumes the batches, epochs and
+step counts of the one-GPU run and a checkpoint does not pin the world size (parallel_wavegan's own batch_size is per process: for that meaning pass
+16 * N).  Every rank takes its loss on its own shard and the ranks average their gradients, as DDP does; rank 0 alone writes the files.  A world of one
+(without GradBuckets' FCL_DP_FORCE_COLLECTIVE) is the one-process step as it was."""
 import argparse
 import concurrent.futures
 import json
@@ -44,6 +51,7 @@ PINNED = ("generator_params", "discriminator_params", "batch_size", "batch_max_s
           "discriminator_train_start_steps", "stft_loss_params", "sampling_rate", "hop_size", "seed", "generator_type", "discriminator_type",
           "mel_loss_params", "lambda_aux", "lambda_feat_match")  # (a key the recipe does not have is absent on both sides)
 LOSS_TERMS = ("spectral_convergence_loss", "log_stft_magnitude_loss", "adversarial_loss", "real_loss", "fake_loss")
+MAX_RANKS = 16  # of one job: no more processes than that hold a GPU at a time
 PWG_TYPE, HIFIGAN_TYPE, HIFIGAN_DISCRIMINATOR = "ParallelWaveGANGenerator", "HiFiGANGenerator", "HiFiGANMultiScaleMultiPeriodDiscriminator"
 
 # ---- the published hifigan.v1 recipe
@@ -97,7 +105,11 @@ def build_parser():
     ap.add_argument("--feature-root", default=None, help="reads mels/<utt>.npy: normalised [T, n_mels] mels as preprocess / extract_features write them")
     ap.add_argument("--train-list", default=None, help="utterance ids, one per line")
     ap.add_argument("--valid-list", default=None, help="utterance ids for the evaluation lines (optional)")
-    ap.add_argument("--outdir", required=True)
+    ap.add_argument("--outdir", default=None)
+    ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node, one process each (at most %d); --batch-size stays the GLOBAL batch" % MAX_RANKS)
+    ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl", help="nccl: RCCL, one GPU per rank; gloo: ranks may share a GPU")
+    ap.add_argument("--dist-timeout", type=float, default=600.0, help="seconds a collective waits for a rank before the job ends (default 600)")
+    ap.add_argument("--dry-run-launch", action="store_true", help="rendezvous over gloo and one all-reduce of ones; rank 0 prints one JSON line; no device work")
     ap.add_argument("--config", default=None, help="parallel_wavegan-style config.yml for everything below; flags given beside it win")
     ap.add_argument("--generator-params", default=None, help="the trainable generator's constructor arguments, JSON or a yaml file (v1 without)")
     ap.add_argument("--discriminator-params", default=None, help="the discriminator's constructor arguments, JSON or a yaml file (v1 without)")
@@ -479,6 +491,24 @@ def _read_ids(path):
 
 
 class Trainer(object):
+    dp = None  # a vocoder_dp.DataParallel under a process group (main attaches it); None: one process, and the step is the one-GPU step as it was
+
+    def _zero(self, net):
+        """before a backward pass of `net`: no gradients, or under data parallelism a zeroed arena with its hooks armed"""
+        if self.dp is None:
+            self.opt[net].zero_grad()
+        else:
+            self.dp.begin(net)
+
+    def _exchange(self, net):
+        """after that backward pass: every rank's gradient of `net` becomes the rank mean"""
+        if self.dp is not None:
+            self.dp.finish(net)
+
+    def _agree(self, out):
+        """the phase's logged scalars as every rank will see them: the rank means, in one collective"""
+        return out if self.dp is None else self.dp.mean_terms(out)
+
     def __init__(self, cfg, device, ends="hip"):
         from .pwg_discriminator import ParallelWaveGANDiscriminator
         from .pwg_generator import TrainableParallelWaveGANGenerator
@@ -538,10 +568,12 @@ class Trainer(object):
         loss = terms["spectral_convergence_loss"] + terms["log_stft_magnitude_loss"]
         if adv:
             loss = loss + cfg["lambda_adv"] * terms["adversarial_loss"]
-        self.opt["generator"].zero_grad()
+        self._zero("generator")
         loss.backward()
+        self._exchange("generator")
         out = {k: float(v.detach()) for k, v in terms.items()}
         out["generator_grad_norm"] = float(torch.nn.utils.clip_grad_norm_(self.gen.parameters(), cfg["generator_grad_norm"]))
+        out = self._agree(out)
         self._finite(n, **out)
         self.opt["generator"].step()
         self.sch["generator"].step()
@@ -549,10 +581,12 @@ class Trainer(object):
             with torch.no_grad():
                 fake = self.gen(z, c, ends=self.ends)
             real_loss, fake_loss = discriminator_adversarial_loss(self.disc(wav), self.disc(fake))
-            self.opt["discriminator"].zero_grad()
+            self._zero("discriminator")
             (real_loss + fake_loss).backward()
+            self._exchange("discriminator")
             more = dict(real_loss=float(real_loss.detach()), fake_loss=float(fake_loss.detach()))
             more["discriminator_grad_norm"] = float(torch.nn.utils.clip_grad_norm_(self.disc.parameters(), cfg["discriminator_grad_norm"]))
+            more = self._agree(more)
             self._finite(n, **more)
             out.update(more)
             self.opt["discriminator"].step()
@@ -622,10 +656,12 @@ class HiFiGANTrainer(Trainer):
         loss = cfg["lambda_aux"] * terms["mel_loss"]
         if adv:
             loss = loss + cfg["lambda_adv"] * terms["adversarial_loss"] + cfg["lambda_feat_match"] * terms["feature_matching_loss"]
-        self.opt["generator"].zero_grad()
+        self._zero("generator")
         loss.backward()
+        self._exchange("generator")
         out = {k: float(v.detach()) for k, v in terms.items()}
         out["generator_grad_norm"] = self._norm(self.gen.parameters(), cfg["generator_grad_norm"])
+        out = self._agree(out)
         self._finite(n, **out)
         self.opt["generator"].step()
         self.sch["generator"].step()
@@ -633,10 +669,12 @@ class HiFiGANTrainer(Trainer):
             with torch.no_grad():
                 fake = self.gen(c, output_end=self.output_end)
             real_loss, fake_loss = discriminator_adversarial_loss(self.disc(wav), self.disc(fake))
-            self.opt["discriminator"].zero_grad()
+            self._zero("discriminator")
             (real_loss + fake_loss).backward()
+            self._exchange("discriminator")
             more = dict(real_loss=float(real_loss.detach()), fake_loss=float(fake_loss.detach()))
             more["discriminator_grad_norm"] = self._norm(self.disc.parameters(), cfg["discriminator_grad_norm"])
+            more = self._agree(more)
             self._finite(n, **more)
             out.update(more)
             self.opt["discriminator"].step()
@@ -645,21 +683,128 @@ class HiFiGANTrainer(Trainer):
         return out
 
 
+def shard(items, rank, world):
+    """rank's share of a global batch (or of its noise rows, or of the validation windows): the items i with i % world == rank, in order"""
+    return items[rank::world]
+
+
+def check_gpus(n):
+    if not 1 <= int(n) <= MAX_RANKS:
+        raise ValueError("fcl-taco2_amd: train_vocoder: --gpus %d is not supported: 1 to %d ranks on one node" % (n, MAX_RANKS))
+
+
+def check_ranks(world, backend, devices):
+    """RCCL takes one GPU per rank; refused before the first device call"""
+    if backend == "nccl" and world > devices:
+        raise ValueError("fcl-taco2_amd: train_vocoder: --dist-backend nccl: %d ranks but %d GPU%s; RCCL takes one GPU per rank (gloo lets ranks share one)"
+                         % (world, devices, "" if devices == 1 else "s"))
+
+
+def check_batch(batch_size, world):
+    """batch_size is the GLOBAL batch: every rank takes batch_size / world items of it"""
+    if batch_size % world:
+        raise ValueError("fcl-taco2_amd: train_vocoder: batch_size=%d is not a multiple of the %d ranks (batch_size is the global batch; parallel_wavegan's "
+                         "is per process)" % (batch_size, world))
+
+
+def _free_port():
+    import socket
+
+    sk = socket.socket()
+    sk.bind(("127.0.0.1", 0))
+    port = sk.getsockname()[1]
+    sk.close()
+    return port
+
+
+def self_launch(gpus, argv):
+    """--gpus N without a torch.distributed environment: start the N ranks as children of torch.distributed.run (one node, rendezvous on 127.0.0.1), as
+    bench.py does, and pass their exit code through.  This process makes no device call."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # (where `import fcl_taco2_amd` resolves)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1", "--master-port",
+           str(_free_port()), "-m", "fcl_taco2_amd.train_vocoder"] + list(argv)
+    path = os.pathsep.join(p for p in (root, os.environ.get("PYTHONPATH")) if p)
+    env = dict(os.environ, PYTHONPATH=path, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    return subprocess.run(cmd, env=env).returncode
+
+
+def init_group(backend, rank, world, timeout, device=None):
+    """join the job's process group with a finite timeout: a rank that has died ends the job instead of hanging it"""
+    import datetime
+
+    import torch.distributed as dist
+
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if "MASTER_PORT" not in os.environ:
+        if world > 1:
+            raise ValueError("fcl-taco2_amd: train_vocoder: WORLD_SIZE=%d without MASTER_PORT" % world)
+        os.environ["MASTER_PORT"] = str(_free_port())
+    more = {"device_id": device} if backend == "nccl" and device is not None else {}
+    dist.init_process_group(backend, rank=rank, world_size=world, timeout=datetime.timedelta(seconds=timeout), **more)
+    return dist
+
+
+def dry_run_launch(rank, world, timeout):
+    """--dry-run-launch: the launch path alone -- every rank joins over gloo and contributes a one to one all-reduce; rank 0 prints the JSON line"""
+    dist = init_group("gloo", rank, world, timeout) if world > 1 else None
+    ones = torch.ones(1, dtype=torch.float64)
+    if dist is not None:
+        dist.all_reduce(ones)
+    if rank == 0:
+        print(json.dumps({"metric": "dry run of the launcher (no GPU work)", "dry_run": True, "n_gpus": world, "sum_of_ones": float(ones)}), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
 def main(argv=None):
+    import sys
+
     ap = build_parser()
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARN, format="%(asctime)s %(levelname)s: %(message)s")
-    if (args.wav_dir is None) == (args.wav_scp is None) or not args.feature_root or not args.train_list:
-        ap.error("--wav-dir or --wav-scp (one of them), --feature-root and --train-list are needed")
+    check_gpus(args.gpus)
+    launched = "WORLD_SIZE" in os.environ  # under torch.distributed.run (or a test's own environment): this process is one rank
+    if args.gpus > 1 and not launched:
+        return self_launch(args.gpus, sys.argv[1:] if argv is None else argv)
+    rank, world, local_rank = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
+    check_gpus(world)
+    if args.gpus > 1 and args.gpus != world:
+        raise ValueError("fcl-taco2_amd: train_vocoder: --gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    if args.dry_run_launch:
+        return dry_run_launch(rank, world, args.dist_timeout)
+    # a process group: for more than one rank, and for one rank under GradBuckets' force flag (the N-rank schedule on one card, its collective the
+    # identity); without either this is the one-process driver as it was
+    grouped = world > 1 or os.environ.get("FCL_DP_FORCE_COLLECTIVE", "0") not in ("", "0")
+    if (args.wav_dir is None) == (args.wav_scp is None) or not args.feature_root or not args.train_list or not args.outdir:
+        ap.error("--wav-dir or --wav-scp (one of them), --feature-root, --train-list and --outdir are needed")
     if args.resume and args.pretrain:
         ap.error("--resume and --pretrain are exclusive")
     cfg = resolve(args)
+    check_batch(cfg["batch_size"], world)
+    if grouped:
+        check_ranks(world, args.dist_backend, torch.cuda.device_count())  # (counts the devices; initialises none)
     if args.resume:
-        check_resume(cfg, args.resume)
+        check_resume(cfg, args.resume)  # (every rank, before the rendezvous: rank 0 rewrites config.yml only after all have read it)
+    try:
+        return _train(args, cfg, rank, world, local_rank, grouped)
+    finally:
+        import torch.distributed as dist
+
+        if grouped and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def _train(args, cfg, rank, world, local_rank, grouped):
     gp, hifi = cfg["generator_params"], cfg["generator_type"] == HIFIGAN_TYPE
     # (the HiFi-GAN generator takes the window's own frames, no context, and no noise)
     hop, ctx, A, fs = cfg["hop_size"], 0 if hifi else gp["aux_context_window"], gp["in_channels"] if hifi else gp["aux_channels"], cfg["sampling_rate"]
     frames, B = cfg["batch_max_steps"] // hop, cfg["batch_size"]
+    mine = B // world  # (this rank's items of the global batch)
     wavs = dict(XF.read_wav_list(args.wav_scp, args.wav_dir))
     train = Corpus(_read_ids(args.train_list), wavs, args.feature_root, fs, hop, A)
     sampler = Windows(train.lengths(), frames, ctx, hop, B, cfg["seed"])
@@ -674,36 +819,48 @@ def main(argv=None):
             logging.warning("no validation utterance is long enough for one window: no evaluation lines")
     import yaml
 
-    os.makedirs(args.outdir, exist_ok=True)
-    with open(os.path.join(args.outdir, "config.yml"), "w") as f:
-        yaml.safe_dump(json.loads(json.dumps(cfg)), f, sort_keys=False)
-    # ---- the first device call is below
-    dev = torch.device("cuda:0")
+    # ---- the first device call is below (under a process group the rendezvous comes first: every rank has passed the refusals above when it returns)
+    dev, dp = torch.device("cuda:0"), None
+    if grouped:
+        if not torch.cuda.is_available():
+            raise RuntimeError("fcl-taco2_amd: train_vocoder: training needs a GPU")
+        dev = torch.device("cuda:%d" % (local_rank % torch.cuda.device_count()))
+        torch.cuda.set_device(dev)
+        init_group(args.dist_backend, rank, world, args.dist_timeout, dev)
+    if rank == 0:  # config.yml, train_log.jsonl and the checkpoints are rank 0's alone
+        os.makedirs(args.outdir, exist_ok=True)
+        with open(os.path.join(args.outdir, "config.yml"), "w") as f:
+            yaml.safe_dump(json.loads(json.dumps(cfg)), f, sort_keys=False)
     tr = HiFiGANTrainer(cfg, dev, args.output_end or "hip") if hifi else Trainer(cfg, dev, args.ends or "hip")
     if args.resume:
         tr.load(args.resume)
     elif args.pretrain:
         tr.load(args.pretrain, models_only=True)
-    log = open(os.path.join(args.outdir, "train_log.jsonl"), "a")
-    write = lambda rec: (log.write(json.dumps(rec) + "\n"), log.flush())
+    if grouped:
+        from .vocoder_dp import DataParallel
+
+        tr.dp = dp = DataParallel(tr)  # (rank 0's parameters and buffers on every rank, the gradient arenas, the hooks)
+    log = open(os.path.join(args.outdir, "train_log.jsonl"), "a") if rank == 0 else None
+    write = (lambda rec: (log.write(json.dumps(rec) + "\n"), log.flush())) if rank == 0 else (lambda rec: None)
     if sampler.dropped:
         write({"left_out": sampler.dropped})
 
     def prepare(step):
-        """step's batch as pinned host tensors (z, c, wav) -- (c, wav) under the HiFi-GAN recipe -- on the one host thread, while the step before it runs"""
-        c, w = np.empty((B, A, frames + 2 * ctx), np.float32), np.empty((B, 1, frames * hop), np.float32)
-        for i, (k, f0) in enumerate(sampler.batch(step)):
+        """this rank's items of step's batch as pinned host tensors (z, c, wav) -- (c, wav) under the HiFi-GAN recipe -- on the one host thread, while
+        the step before it runs; only these windows are loaded"""
+        c, w = np.empty((mine, A, frames + 2 * ctx), np.float32), np.empty((mine, 1, frames * hop), np.float32)
+        for i, (k, f0) in enumerate(shard(sampler.batch(step), rank, world)):
             mel, wav = train.load(sampler.utts[k][0])
             m, w[i, 0] = sampler.cut(mel, wav, f0)
             c[i] = m.T
-        return tuple(torch.from_numpy(a).pin_memory() for a in ((c, w) if hifi else (sampler.noise(step), c, w)))
+        return tuple(torch.from_numpy(a).pin_memory() for a in ((c, w) if hifi else (np.ascontiguousarray(shard(sampler.noise(step), rank, world)), c, w)))
 
     def evaluate(step):
         sums, n = {}, 0
         if hifi:
             tr.disc.eval()  # (no power iteration of the spectral norm on a validation window)
         with torch.no_grad():
-            for k, (u, _) in enumerate(vsampler.utts):
+            for k, (u, _) in shard(list(enumerate(vsampler.utts)), rank, world):
                 mel, wav = valid.load(u)
                 f0, z = vsampler.valid(k)
                 m, w = vsampler.cut(mel, wav, f0)
@@ -714,6 +871,11 @@ def main(argv=None):
                 n += 1
         if hifi:
             tr.disc.train()
+        if dp is not None:  # the ranks' sums and window counts, added in float64 (a rank may have had no window: the names are the step's, not its own)
+            adv = adversarial(cfg, step)
+            names = ("mel_loss", "adversarial_loss", "feature_matching_loss")[: 3 if adv else 1] if hifi else LOSS_TERMS[: 3 if adv else 2]
+            total = dp.sum_float64([sums.get(k, 0.0) for k in names] + [n])
+            sums, n = dict(zip(names, total[:-1])), int(total[-1])
         write(dict({"eval_" + k: v / n for k, v in sums.items()}, step=step, eval_windows=n))
 
     acc, count, t0 = {}, 0, time.perf_counter()
@@ -724,7 +886,7 @@ def main(argv=None):
             batch = [a.to(dev, non_blocking=True) for a in nxt.result()]
             nxt = pool.submit(prepare, n + 1) if n < cfg["train_max_steps"] else None
             lrs = {k: tr.opt[k].param_groups[0]["lr"] for k in tr.opt}
-            out = tr.step(*batch)
+            out = tr.step(*batch)  # (under data parallelism the terms are the rank means, the same floats on every rank)
             for k, v in out.items():
                 s, m = acc.get(k, (0.0, 0))
                 acc[k] = (s + v, m + 1)
@@ -733,7 +895,7 @@ def main(argv=None):
                 torch.cuda.synchronize(dev)
                 dt = time.perf_counter() - t0
                 rec = dict({k: s / m for k, (s, m) in acc.items()}, step=n, generator_lr=lrs["generator"], discriminator_lr=lrs["discriminator"],
-                           ms_per_step=1e3 * dt / count, samples_per_second=count * B * frames * hop / dt)
+                           ms_per_step=1e3 * dt / count, samples_per_second=count * B * frames * hop / dt)  # (B: the global batch)
                 for k in HiFiGANTrainer.LATE if hifi else LOSS_TERMS[2:] + ("discriminator_grad_norm",):
                     rec.setdefault(k, None)  # (before the discriminator starts)
                 write(rec)
@@ -742,10 +904,23 @@ def main(argv=None):
             if vsampler is not None and n % cfg["eval_interval_steps"] == 0:
                 evaluate(n)
             if n % cfg["save_interval_steps"] == 0 or n == cfg["train_max_steps"]:
-                torch.save(checkpoint_of(tr.gen, tr.disc, tr.opt, tr.sch, n, sampler.epoch(n)), os.path.join(args.outdir, "checkpoint-%dsteps.pkl" % n))
-    log.close()
+                if dp is not None:  # (raises on every rank, naming the step, if the ranks' networks differ in a bit)
+                    dp.same_everywhere("generator", n)
+                    dp.same_everywhere("discriminator", n)
+                if rank == 0:
+                    torch.save(checkpoint_of(tr.gen, tr.disc, tr.opt, tr.sch, n, sampler.epoch(n)), os.path.join(args.outdir, "checkpoint-%dsteps.pkl" % n))
+    if rank == 0:
+        log.close()
+    if dp is not None:
+        logging.info("exchange schedule: %s", json.dumps(dp.schedule()))
+        import torch.distributed as dist
+
+        dist.barrier()  # (rank 0's last checkpoint is on disk before any rank leaves)
     return tr
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+
+    done = main()
+    sys.exit(done if isinstance(done, int) else 0)  # (the launcher's form returns its ranks' exit code)
