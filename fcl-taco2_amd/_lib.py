@@ -376,6 +376,9 @@ SIGNATURES = {
     "fcl_al_loglik_fwd": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _P]),
     "fcl_al_viterbi_fwd": (_I, [C.POINTER(Align), _P]),
     "fcl_al_stats_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _I, _I, _P]),
+    "fcl_al_gmm_loglik_fwd": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
+    "fcl_al_gmm_post_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
+    "fcl_al_gmm_stats_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _I, _I, _I, _I, _P]),
     "fcl_stl_sums_fwd": (_I, [C.POINTER(StftLoss), _P]),
     "fcl_stl_grad_bwd": (_I, [C.POINTER(StftLoss), _P]),
     "fcl_msl_sums_fwd": (_I, [C.POINTER(MelLoss), _P]),

@@ -6,14 +6,18 @@
 `--transcripts` holds one utterance per line, `utt ph ph ...`: the phonemes, not words (there is no dictionary and no G2P here).  Every utterance of
 the transcripts needs `<utt>.wav` (16-bit PCM mono) in `--wav-dir`.  Without `--model` the inventory is the set of labels and the models are
 trained on these very utterances from a flat start (`--iterations`, default 15: not tuned, the synthetic corpora of the tests converge within 6);
-with `--model` the driver only aligns.  `--optional` names the labels that may be skipped as a whole (pauses between words); such a label must stand
+with `--model` the driver only aligns.  `--mixtures N` (1 .. 8, default 1: single Gaussians) then grows every state into a mixture: the component target
+per state doubles (2, 4, ..., at last N), the components are split at each target and `--mix-iterations` rounds (default 4) of alignment and
+re-estimation follow; a component is split only while it holds at least twice `--min-occupancy` frames (default 10).  `--model-out` keeps the
+mixtures, `--model` aligns with them (and ignores the training flags, as it ignores `--iterations`).  `--optional` names the labels that may be skipped as a whole (pauses between words); such a label must stand
 between two mandatory ones.  A label outside the inventory, an utterance longer than 4096 frames or 1024 rows (phonemes x states) and a misplaced
 optional label are refused by name before the first device call.
 
 Per utterance `<utt>.TextGrid` (long text format, one tier `phones`) goes to `--textgrid-out`: a boundary at frame k is written as
 (k hop + 0.5) / fs, the last interval ends at the wav's end, so that textgrid.alignment() gives back the aligner's durations with the last one less
 by 1, which preprocess's last-duration rule restores.  `--durations-out` also keeps the durations as `<utt>.npy` (int64, summing to the frame
-count).  `--report` holds the mean score per frame of every iteration and the utterances that could not be aligned (they get no TextGrid)."""
+count).  `--report` holds the mean score per frame of every iteration and the utterances that could not be aligned (they get no TextGrid); with mixtures
+its `settings` also name `mixtures` and every iteration its `components`, the component total of that round."""
 import argparse
 import json
 import logging
@@ -52,6 +56,9 @@ def build_parser():
     ap.add_argument("--optional", nargs="*", default=[], metavar="LABEL", help="labels that may be skipped (pauses)")
     ap.add_argument("--states", type=int, default=alignment.STATES_DEFAULT, help="states per phoneme, 1 .. %d" % alignment.STATES_MAX)
     ap.add_argument("--iterations", type=int, default=alignment.ITERATIONS_DEFAULT, help="alignment / re-estimation rounds after the flat start (not tuned)")
+    ap.add_argument("--mixtures", type=int, default=1, help="Gaussians per state after the mixture stage, 1 .. %d (1: single Gaussians)" % alignment.MIXTURES_MAX)
+    ap.add_argument("--mix-iterations", type=int, default=alignment.MIX_ITERATIONS_DEFAULT, help="alignment / re-estimation rounds at each component target")
+    ap.add_argument("--min-occupancy", type=float, default=alignment.MIN_OCCUPANCY_DEFAULT, help="a component is split only while it holds twice this many frames")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--model-out", default=None, metavar="FILE.npz", help="keep the trained models")
     g.add_argument("--model", default=None, metavar="FILE.npz", help="align with these models, without training")
@@ -81,6 +88,12 @@ def parse_args(argv=None):
         ap.error("--states must lie in 1 .. %d" % alignment.STATES_MAX)
     if args.iterations < 0 or args.batch_cells < 1 or args.batch_frames < 1:
         ap.error("--iterations must not be negative, --batch-cells and --batch-frames must be positive")
+    if not 1 <= args.mixtures <= alignment.MIXTURES_MAX:
+        ap.error("--mixtures must lie in 1 .. %d" % alignment.MIXTURES_MAX)
+    if args.mix_iterations < 0:
+        ap.error("--mix-iterations must not be negative")
+    if not args.min_occupancy >= 1.0:
+        ap.error("--min-occupancy must be at least 1")
     if args.n_mels - 1 < alignment.ORDER:
         ap.error("--n-mels must exceed the %d cepstra the features take" % alignment.ORDER)
     try:
@@ -170,11 +183,15 @@ def align(args):
     al.settings = af.settings
     feats = extract(args, utts, af)
     trs = [transcripts[u] for u in ids]
-    history = dict(score=[], failed=[])
+    history = dict(score=[], failed=[], components=[])
     if model is None:
-        history = al.fit(feats, trs, args.iterations, ids=ids)
+        history = al.fit(feats, trs, args.iterations, ids=ids, mixtures=args.mixtures, mix_iterations=args.mix_iterations, min_occupancy=args.min_occupancy)
         for it, s in enumerate(history["score"]):
-            logging.info("iteration %d: mean score per frame %.4f, %d utterances without an alignment", it + 1, s, len(history["failed"][it]))
+            if args.mixtures > 1:
+                logging.info("iteration %d: %d components, mean score per frame %.4f, %d utterances without an alignment", it + 1, history["components"][it], s,
+                             len(history["failed"][it]))
+            else:
+                logging.info("iteration %d: mean score per frame %.4f, %d utterances without an alignment", it + 1, s, len(history["failed"][it]))
         if args.model_out:
             al.model.save(args.model_out)
     res = al.align(feats, trs, ids=ids)
@@ -191,10 +208,16 @@ def align(args):
         textgrid.write_textgrid(os.path.join(args.textgrid_out, u + ".TextGrid"), {"phones": rows}, rows[-1][1])
         if args.durations_out:
             np.save(os.path.join(args.durations_out, u + ".npy"), np.asarray(r["durations"], dtype=np.int64))
-    return dict(n_utt=len(ids), n_aligned=len(ids) - len(failed), not_aligned=failed, score_per_frame=total / max(frames, 1),
-                iterations=[dict(score_per_frame=s, not_aligned=f) for s, f in zip(history["score"], history["failed"])],
-                settings=dict(states=al.K, optional=sorted(al.optional), phones=al.phones, trained=model is None, model=args.model, features=af.settings,
-                              resample=bool(args.resample)))
+    doc = dict(n_utt=len(ids), n_aligned=len(ids) - len(failed), not_aligned=failed, score_per_frame=total / max(frames, 1),
+               iterations=[dict(score_per_frame=s, not_aligned=f) for s, f in zip(history["score"], history["failed"])],
+               settings=dict(states=al.K, optional=sorted(al.optional), phones=al.phones, trained=model is None, model=args.model, features=af.settings,
+                             resample=bool(args.resample)))
+    mixtures = al.model.max_components if model is not None else args.mixtures
+    if mixtures > 1:  # with single Gaussians the report is the one it has always been, byte for byte
+        doc["settings"]["mixtures"] = mixtures
+        for entry, g in zip(doc["iterations"], history["components"]):
+            entry["components"] = g
+    return doc
 
 
 def main(argv=None):

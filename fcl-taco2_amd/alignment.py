@@ -1,15 +1,15 @@
-"""Forced alignment on the HIP path: flat-start Viterbi training of single-Gaussian monophone models, and the alignment they give (csrc/align.hip;
-DESIGN.md §6i).
+"""Forced alignment on the HIP path: flat-start Viterbi training of monophone models -- single Gaussians, optionally grown into mixtures of up to 8
+diagonal Gaussians per state -- and the alignment they give (csrc/align.hip, csrc/align_gmm.hip).
 
 What Kaldi's monophone pass and HTK's flat start do: start from an equal segmentation of every utterance over its transcript, then alternate a
 Viterbi alignment with a re-estimation of the Gaussians, and keep the last alignment.  Every phoneme of the inventory has K left-to-right states
 without transition probabilities; a phoneme named optional (a pause between words) may be skipped as a whole.  The E-step runs on the device
 (log-likelihoods, Viterbi with its backtrack, statistics in float64), the M-step on the host in float64.  The contract is stated in
-include/fcl_hip.h "Forced alignment" and restated in float64 numpy in tests/align_ref.py.  Agreement with the Montreal Forced Aligner on real
+include/fcl_hip.h "Forced alignment" and restated in float64 numpy in tests/align_ref.py (the mixture entries: tests/align_gmm_ref.py).  Agreement with the Montreal Forced Aligner on real
 recordings stays unpinned: neither that tool nor real speech is available here.
 
     al = Aligner("cuda:0", phones, states=3, optional=("sp",))
-    history = al.fit(features, transcripts, iterations=15)      # features: per utterance [T, D] on the device
+    history = al.fit(features, transcripts, iterations=15)      # features: per utterance [T, D] on the device; mixtures=4 grows mixtures
     results = al.align(features, transcripts)                   # per utterance: phones, durations in frames (summing to T), score
 
 No CPU fallback."""
@@ -27,6 +27,8 @@ BATCH_LL = 1 << 28  # frames x M of one batch's log-likelihood matrix (the entri
 VAR_FLOOR = 0.01
 ORDER, DELTA_WINDOW, ENERGY_FLOOR = 13, 2, 1e-10
 ITERATIONS_DEFAULT = 15  # not tuned: the synthetic corpora of the tests converge within 6
+MIXTURES_MAX, COMPONENTS_MAX, MIX_ITERATIONS_DEFAULT, MIN_OCCUPANCY_DEFAULT = 8, 8192, 4, 10.0
+WEIGHT_FLOOR, SPLIT = 1e-5, 0.2
 
 
 # ---- model ------------------------------------------------------------------------------------------------------------------------------------------
@@ -38,22 +40,53 @@ def gconst(var):
 
 class AlignModel(object):
     """phones (the inventory, in index order), K states per phoneme, mean / var [M = len(phones) K][D] in float64, and the settings of the
-    features they were trained on (a dict of plain values; a model is only good for features made the same way)."""
+    features they were trained on (a dict of plain values; a model is only good for features made the same way).  With the keywords weight [G] and
+    comp_off [M + 1] the states are mixtures: state m owns the components comp_off[m] .. comp_off[m + 1] (1 .. 8 of them, G <= 8192 in all) of
+    mean / var [G][D], and their weights sum to 1 inside a state.  Without them every state has one component of weight 1."""
 
-    def __init__(self, phones, states, mean, var, settings=None):
+    def __init__(self, phones, states, mean, var, settings=None, weight=None, comp_off=None):
         self.phones, self.K = [str(p) for p in phones], int(states)
         check_inventory(self.phones, self.K)
         self.mean, self.var = np.array(mean, dtype=np.float64), np.array(var, dtype=np.float64)
         self.settings = dict(settings or {})
         M = len(self.phones) * self.K
-        if self.mean.ndim != 2 or self.mean.shape != self.var.shape or self.mean.shape[0] != M or not 1 <= self.mean.shape[1] <= DIM_MAX:
-            raise ValueError("fcl-taco2_amd: alignment: mean / var must be [%d states][1 .. %d], got %r and %r" % (M, DIM_MAX, self.mean.shape, self.var.shape))
+        if (weight is None) != (comp_off is None):
+            raise ValueError("fcl-taco2_amd: alignment: a mixture model needs both weight and comp_off")
+        if comp_off is None:
+            if self.mean.ndim != 2 or self.mean.shape != self.var.shape or self.mean.shape[0] != M or not 1 <= self.mean.shape[1] <= DIM_MAX:
+                raise ValueError("fcl-taco2_amd: alignment: mean / var must be [%d states][1 .. %d], got %r and %r" % (M, DIM_MAX, self.mean.shape, self.var.shape))
+            self.weight, self.comp_off = np.ones(M), np.arange(M + 1, dtype=np.int32)
+        else:
+            self.weight, self.comp_off = np.array(weight, dtype=np.float64).reshape(-1), np.array(comp_off, dtype=np.int64).reshape(-1)
+            counts = np.diff(self.comp_off)
+            if len(self.comp_off) != M + 1 or self.comp_off[0] != 0 or counts.min() < 1 or counts.max() > MIXTURES_MAX or self.comp_off[-1] > COMPONENTS_MAX:
+                raise ValueError("fcl-taco2_amd: alignment: comp_off must give each of the %d states 1 .. %d components, at most %d in all" % (M, MIXTURES_MAX, COMPONENTS_MAX))
+            G = int(self.comp_off[-1])
+            self.comp_off = self.comp_off.astype(np.int32)
+            if self.mean.ndim != 2 or self.mean.shape != self.var.shape or self.mean.shape[0] != G or not 1 <= self.mean.shape[1] <= DIM_MAX or len(self.weight) != G:
+                raise ValueError("fcl-taco2_amd: alignment: mean / var must be [%d components][1 .. %d] and weight [%d], got %r, %r and %r"
+                                 % (G, DIM_MAX, G, self.mean.shape, self.var.shape, self.weight.shape))
+            if not (np.isfinite(self.weight).all() and (self.weight > 0).all()):
+                raise ValueError("fcl-taco2_amd: alignment: the model needs positive finite component weights")
         if not (np.isfinite(self.mean).all() and np.isfinite(self.var).all() and (self.var > 0).all()):
             raise ValueError("fcl-taco2_amd: alignment: the model needs finite means and positive finite variances")
 
     @property
     def n_states(self):
+        return len(self.comp_off) - 1
+
+    @property
+    def n_components(self):
         return self.mean.shape[0]
+
+    @property
+    def max_components(self):
+        return int(np.diff(self.comp_off).max())
+
+    @property
+    def is_mixture(self):
+        """any state with more than one component"""
+        return self.n_components > self.n_states
 
     @property
     def dim(self):
@@ -63,15 +96,22 @@ class AlignModel(object):
         """(mean, ivar, gconst) as uploaded: formed in float64, rounded to float32"""
         return self.mean.astype(np.float32), (1.0 / self.var).astype(np.float32), gconst(self.var).astype(np.float32)
 
+    def gmm_params32(self):
+        """(mean [G][D], ivar [G][D], cconst [G] = ln w + gconst(var), comp_off [M + 1] int32) as uploaded to the mixture entries"""
+        return (self.mean.astype(np.float32), (1.0 / self.var).astype(np.float32), (np.log(self.weight) + gconst(self.var)).astype(np.float32),
+                self.comp_off.astype(np.int32))
+
     def upload(self, dev):
-        return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.params32())
+        """the device tensors of params32(), or of gmm_params32() for a mixture model"""
+        return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (self.gmm_params32() if self.is_mixture else self.params32()))
 
     def save(self, path):
         import json
 
+        extra = dict(weight=self.weight, comp_off=self.comp_off.astype(np.int32)) if self.is_mixture else {}  # a one-component model writes today's file
         with open(path, "wb") as f:
             np.savez(f, phones=np.asarray(self.phones), states=np.int64(self.K), mean=self.mean, var=self.var,
-                     settings=np.asarray(json.dumps(self.settings, sort_keys=True)))
+                     settings=np.asarray(json.dumps(self.settings, sort_keys=True)), **extra)
 
     @classmethod
     def load(cls, path):
@@ -81,7 +121,8 @@ class AlignModel(object):
             missing = [k for k in ("phones", "states", "mean", "var", "settings") if k not in z.files]
             if missing:
                 raise ValueError("%s: not an alignment model (no %s)" % (path, ", ".join(missing)))
-            return cls([str(p) for p in z["phones"]], int(z["states"]), z["mean"], z["var"], json.loads(str(z["settings"])))
+            mix = dict(weight=z["weight"], comp_off=z["comp_off"]) if "comp_off" in z.files and "weight" in z.files else {}
+            return cls([str(p) for p in z["phones"]], int(z["states"]), z["mean"], z["var"], json.loads(str(z["settings"])), **mix)
 
 
 def check_inventory(phones, states):
@@ -166,6 +207,63 @@ def global_model(n, s, q, n_states):
     return np.tile(gmean, (n_states, 1)), np.tile(np.sum(q, axis=0) / N - gmean * gmean, (n_states, 1))
 
 
+def mixture_targets(mixtures):
+    """the component targets of the mixture stage: 2, 4, ... and the last one is `mixtures` itself (none for 1)"""
+    out, t = [], 2
+    while t < mixtures:
+        out.append(t)
+        t *= 2
+    return out + ([int(mixtures)] if mixtures > 1 else [])
+
+
+def split_components(mean, var, weight, occ, comp_off, target, min_occupancy=MIN_OCCUPANCY_DEFAULT):
+    """Per state, while it has fewer than `target` components: the component of largest weight (the first on ties) is split unless its occupancy is
+    below 2 min_occupancy, which ends the splitting of this state.  A split halves weight and occupancy; the component moves to mean + 0.2 sigma and
+    a copy at mean - 0.2 sigma with the same variance is appended at the end of the state's list.  float64 on the host.
+    -> (mean, var, weight, occ, comp_off) of the grown model"""
+    mean, var, weight, occ = (np.asarray(v, dtype=np.float64) for v in (mean, var, weight, occ))
+    out_m, out_v, out_w, out_o, off = [], [], [], [], [0]
+    for m in range(len(comp_off) - 1):
+        a, b = int(comp_off[m]), int(comp_off[m + 1])
+        mu, va, w, o = [r.copy() for r in mean[a:b]], [r.copy() for r in var[a:b]], [float(v) for v in weight[a:b]], [float(v) for v in occ[a:b]]
+        while len(w) < target:
+            j = int(np.argmax(w))
+            if o[j] < 2.0 * min_occupancy:
+                break
+            w[j], o[j] = w[j] / 2.0, o[j] / 2.0
+            step = SPLIT * np.sqrt(va[j])
+            mu.append(mu[j] - step)
+            va.append(va[j].copy())
+            w.append(w[j])
+            o.append(o[j])
+            mu[j] = mu[j] + step
+        out_m, out_v, out_w, out_o = out_m + mu, out_v + va, out_w + w, out_o + o
+        off.append(len(out_w))
+    return np.asarray(out_m), np.asarray(out_v), np.asarray(out_w), np.asarray(out_o), np.asarray(off, dtype=np.int32)
+
+
+def mstep_mixtures(w, s, q, mean, var, weight, comp_off, var_floor=VAR_FLOOR):
+    """float64 on the host: a component with w >= 2 gets mean = s / w and var = max(q / w - mean^2, var_floor x global variance of this pass), the
+    others keep their parameters; a state whose occupancy (the sum of its w) is >= 2 gets the weights max(w / occupancy, 1e-5), renormalised"""
+    w, s, q = np.asarray(w, dtype=np.float64), np.asarray(s, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    N = w.sum()
+    if N < 2:
+        raise _lib.FclError("fcl-taco2_amd: alignment: no aligned frames to estimate the model from")
+    gmean = s.sum(axis=0) / N
+    floor = float(var_floor) * (q.sum(axis=0) / N - gmean * gmean)
+    mean, var, weight = np.array(mean, dtype=np.float64), np.array(var, dtype=np.float64), np.array(weight, dtype=np.float64)
+    for g in np.flatnonzero(w >= 2):
+        mean[g] = s[g] / w[g]
+        var[g] = np.maximum(q[g] / w[g] - mean[g] * mean[g], floor)
+    for m in range(len(comp_off) - 1):
+        a, b = int(comp_off[m]), int(comp_off[m + 1])
+        occ = w[a:b].sum()
+        if occ >= 2:
+            v = np.maximum(w[a:b] / occ, WEIGHT_FLOOR)
+            weight[a:b] = v / v.sum()
+    return mean, var, weight
+
+
 # ---- packed batches -----------------------------------------------------------------------------------------------------------------------------------
 class AlignMaps(object):
     """The tables of a packed batch on the device: frame_off / row_off [n + 1] int32, cell_off [n + 1] int64 (cumulative S T), row_state /
@@ -191,6 +289,13 @@ class AlignMaps(object):
         self.frame_off, self.row_off, self.cell_off = t(self.frame_offs, np.int32), t(self.row_offs, np.int32), t(self.cell_offs, np.int64)
         self.row_state, self.row_skip = t(self.row_states, np.int32), t(self.row_skips, np.int32)
         self.state_off, self.state_rows = t(self.state_offs, np.int32), t(self.state_rows_h, np.int32)
+
+    @property
+    def frame_utt(self):
+        """[frames] int64 on the device: the utterance of each frame (built on first use: only the mixture stage needs it)"""
+        if getattr(self, "_frame_utt", None) is None:
+            self._frame_utt = torch.from_numpy(np.repeat(np.arange(self.n_utt, dtype=np.int64), self.frame_lens)).to(self.frame_off.device)
+        return self._frame_utt
 
     def workspace_bytes(self):
         return int(_lib.load().fcl_al_workspace_bytes(self.cells, self.n_utt))
@@ -222,6 +327,36 @@ def launch_stats(mp, x, row_begin, row_frames, acc_n, acc_s, acc_q):
     _lib.check(_lib.load().fcl_al_stats_fwd(x.data_ptr(), row_begin.data_ptr(), row_frames.data_ptr(), mp.state_off.data_ptr(), mp.state_rows.data_ptr(),
                                             acc_n.data_ptr(), acc_s.data_ptr(), acc_q.data_ptr(), mp.frames, mp.rows, int(acc_s.shape[1]), mp.n_states,
                                             ops._stream()))
+
+
+def launch_gmm_loglik(params, x, ll, frames, max_comp=MIXTURES_MAX):
+    """params: (mean [G][D], ivar [G][D], cconst [G] float32, comp_off [M + 1] int32) on the device; x [frames][D] -> ll [frames][M]; max_comp: the
+    largest component count of a state (the kernels read no more of any state)"""
+    mean, ivar, cc, comp_off = params
+    _lib.check(_lib.load().fcl_al_gmm_loglik_fwd(x.data_ptr(), mean.data_ptr(), ivar.data_ptr(), cc.data_ptr(), comp_off.data_ptr(), ll.data_ptr(), int(frames),
+                                                 int(mean.shape[1]), int(comp_off.numel()) - 1, int(mean.shape[0]), int(max_comp), ops._stream()))
+
+
+def launch_gmm_post(params, x, frame_state, gamma, frames, max_comp=MIXTURES_MAX):
+    """frame_state [frames] int32 (the model state the alignment gave each frame, -1: none) -> gamma [frames][8] float32"""
+    mean, ivar, cc, comp_off = params
+    _lib.check(_lib.load().fcl_al_gmm_post_fwd(x.data_ptr(), mean.data_ptr(), ivar.data_ptr(), cc.data_ptr(), comp_off.data_ptr(), frame_state.data_ptr(),
+                                               gamma.data_ptr(), int(frames), int(mean.shape[1]), int(comp_off.numel()) - 1, int(mean.shape[0]), int(max_comp),
+                                               ops._stream()))
+
+
+def launch_gmm_stats(mp, comp_off, x, gamma, row_begin, row_frames, acc_w, acc_s, acc_q, max_comp=MIXTURES_MAX):
+    """x [frames][D] and gamma [frames][8] float32 over the rows' runs: ADDS to acc_w [G], acc_s / acc_q [G][D] float64"""
+    _lib.check(_lib.load().fcl_al_gmm_stats_fwd(x.data_ptr(), gamma.data_ptr(), row_begin.data_ptr(), row_frames.data_ptr(), mp.state_off.data_ptr(),
+                                                mp.state_rows.data_ptr(), comp_off.data_ptr(), acc_w.data_ptr(), acc_s.data_ptr(), acc_q.data_ptr(), mp.frames,
+                                                mp.rows, int(acc_s.shape[1]), mp.n_states, int(acc_s.shape[0]), int(max_comp), ops._stream()))
+
+
+def frame_states(mp, frame_row):
+    """frame_state [frames] int32 on the device, by torch indexing: the model state of the row the alignment gave each frame, -1 for the frames of
+    an utterance without an alignment (frame_row -1)"""
+    row = mp.row_off.long()[mp.frame_utt] + frame_row.long()
+    return torch.where(frame_row >= 0, mp.row_state[row.clamp(min=0, max=max(mp.rows - 1, 0))], torch.full_like(frame_row, -1)).to(torch.int32).contiguous()
 
 
 def utt_batches(frame_lens, row_lens, batch_cells, n_states=1):
@@ -344,24 +479,40 @@ class Aligner(object):
     def _viterbi(self, mp, x, params):
         """one batch: log-likelihoods and Viterbi -> (row_begin, row_frames, score, ok) device tensors"""
         dev = self.device
+        return self._viterbi_rows(mp, x, params)[:4]
+
+    def _viterbi_rows(self, mp, x, params, max_comp=MIXTURES_MAX):
+        """_viterbi and frame_row; params of four (AlignModel.gmm_params32) take the mixture log-likelihood"""
+        dev = self.device
         ll = torch.empty(mp.frames, mp.n_states, device=dev, dtype=torch.float32)
-        launch_loglik(params, x, ll, mp.frames)
+        if len(params) == 4:
+            launch_gmm_loglik(params, x, ll, mp.frames, max_comp)
+        else:
+            launch_loglik(params, x, ll, mp.frames)
         ws = torch.empty(mp.workspace_bytes(), device=dev, dtype=torch.uint8)
         frame_row = torch.empty(mp.frames, device=dev, dtype=torch.int32)
         row_begin, row_frames = torch.empty(mp.rows, device=dev, dtype=torch.int32), torch.empty(mp.rows, device=dev, dtype=torch.int32)
         score, ok = torch.empty(mp.n_utt, device=dev, dtype=torch.float32), torch.empty(mp.n_utt, device=dev, dtype=torch.int32)
         launch_viterbi(mp, ll, ws, frame_row, row_begin, row_frames, score, ok)
-        return row_begin, row_frames, score, ok
+        return row_begin, row_frames, score, ok, frame_row
 
     def _acc(self, D):
         dev = self.device
         return (torch.zeros(self.n_states, device=dev, dtype=torch.int64), torch.zeros(self.n_states, D, device=dev, dtype=torch.float64),
                 torch.zeros(self.n_states, D, device=dev, dtype=torch.float64))
 
-    def fit(self, features, transcripts, iterations=ITERATIONS_DEFAULT, ids=None, callback=None):
+    def fit(self, features, transcripts, iterations=ITERATIONS_DEFAULT, ids=None, callback=None, mixtures=1, mix_iterations=MIX_ITERATIONS_DEFAULT,
+            min_occupancy=MIN_OCCUPANCY_DEFAULT):
         """features: per utterance a [T, D] tensor; transcripts: per utterance its labels.  The flat start, then `iterations` times align and
-        re-estimate.  -> dict(score: the mean score per aligned frame of each iteration, failed: per iteration the utterances without an alignment
-        (ids, or positions)); self.model is the trained AlignModel.  callback(iteration, model) runs after every re-estimation."""
+        re-estimate.  With mixtures > 1 the component target per state then doubles -- 2, 4, ..., the last target is `mixtures` --; at each target
+        the components are split (split_components) and `mix_iterations` rounds of Viterbi alignment and re-estimation follow, soft inside a state:
+        the component posteriors of the frames the path gave to that state (csrc/align_gmm.hip), the M-step on the host (mstep_mixtures).
+        -> dict(score: the mean score per aligned frame of each round, failed: per round the utterances without an alignment (ids, or positions),
+        components: the component total of each round); self.model is the trained AlignModel.  callback(round, model) runs after every
+        re-estimation."""
+        if not 1 <= int(mixtures) <= MIXTURES_MAX or int(mix_iterations) < 0 or not float(min_occupancy) >= 1.0:
+            raise ValueError("fcl-taco2_amd: alignment: mixtures must lie in 1 .. %d, mix_iterations must not be negative and min_occupancy must be at least 1 "
+                             "(got %r, %r, %r)" % (MIXTURES_MAX, mixtures, mix_iterations, min_occupancy))
         features = list(features)
         graphs, frame_lens, D = self._prepare(features, transcripts, ids)
         name = lambda i: ids[i] if ids is not None else i
@@ -378,7 +529,7 @@ class Aligner(object):
             n, s, q = (v.cpu().numpy() for v in acc)
             mean, var = mstep(n, s, q, *global_model(n, s, q, self.n_states), var_floor=self.var_floor)
             self.model = AlignModel(self.phones, self.K, mean, var, self.settings)
-            history = dict(score=[], failed=[])
+            history = dict(score=[], failed=[], components=[])
             for it in range(int(iterations)):
                 params, acc = self.model.upload(self.device), self._acc(D)
                 total, frames, failed = 0.0, 0, []
@@ -396,8 +547,42 @@ class Aligner(object):
                 self.model = AlignModel(self.phones, self.K, mean, var, self.settings)
                 history["score"].append(total / max(frames, 1))
                 history["failed"].append(failed)
+                history["components"].append(self.n_states)
                 if callback is not None:
                     callback(it, self.model)
+            # ---- the mixture stage: from one component of weight 1 per state, the occupancies those of the last round (or of the flat start)
+            mean, var, weight = self.model.mean, self.model.var, np.ones(self.n_states)
+            occ, comp_off, it = np.asarray(n, dtype=np.float64), np.arange(self.n_states + 1, dtype=np.int32), int(iterations)
+            for target in mixture_targets(mixtures):
+                mean, var, weight, occ, comp_off = split_components(mean, var, weight, occ, comp_off, target, min_occupancy)
+                self.model = AlignModel(self.phones, self.K, mean, var, self.settings, weight=weight, comp_off=comp_off)
+                for _ in range(int(mix_iterations)):
+                    G, max_comp = self.model.n_components, self.model.max_components
+                    params = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in self.model.gmm_params32())
+                    acc = (torch.zeros(G, device=self.device, dtype=torch.float64), torch.zeros(G, D, device=self.device, dtype=torch.float64),
+                           torch.zeros(G, D, device=self.device, dtype=torch.float64))
+                    total, frames, failed = 0.0, 0, []
+                    for idx, mp, x in batches:
+                        row_begin, row_frames, score, ok, frame_row = self._viterbi_rows(mp, x, params, max_comp)
+                        gamma = torch.empty(mp.frames, MIXTURES_MAX, device=self.device, dtype=torch.float32)
+                        launch_gmm_post(params, x, frame_states(mp, frame_row), gamma, mp.frames, max_comp)
+                        launch_gmm_stats(mp, params[3], x, gamma, row_begin, row_frames, *acc, max_comp=max_comp)
+                        okh, sh = ok.cpu().numpy(), score.cpu().numpy().astype(np.float64)
+                        for k, i in enumerate(idx):
+                            if okh[k]:
+                                total, frames = total + sh[k], frames + frame_lens[i]
+                            else:
+                                failed.append(name(i))
+                    w, s, q = (v.cpu().numpy() for v in acc)
+                    mean, var, weight = mstep_mixtures(w, s, q, mean, var, weight, comp_off, var_floor=self.var_floor)
+                    occ = w
+                    self.model = AlignModel(self.phones, self.K, mean, var, self.settings, weight=weight, comp_off=comp_off)
+                    history["score"].append(total / max(frames, 1))
+                    history["failed"].append(failed)
+                    history["components"].append(G)
+                    if callback is not None:
+                        callback(it, self.model)
+                    it += 1
         return history
 
     def align(self, features, transcripts, ids=None):
@@ -411,9 +596,9 @@ class Aligner(object):
             raise ValueError("fcl-taco2_amd: alignment: the features have %d coefficients, the model %d" % (D, self.model.dim))
         out = [None] * len(features)
         with torch.cuda.device(self.device):
-            params = self.model.upload(self.device)
+            params, max_comp = self.model.upload(self.device), self.model.max_components  # a model with mixtures takes the mixture entries
             for idx, mp, x in self._batches(features, graphs, frame_lens):
-                _, row_frames, score, ok = self._viterbi(mp, x, params)
+                _, row_frames, score, ok, _ = self._viterbi_rows(mp, x, params, max_comp)
                 rf, okh, sh = row_frames.cpu().numpy().astype(np.int64), ok.cpu().numpy(), score.cpu().numpy()
                 for k, i in enumerate(idx):
                     c = rf[mp.row_offs[k] : mp.row_offs[k + 1]]

@@ -1200,6 +1200,36 @@ int fcl_al_loglik_fwd(const float* x, const float* mean, const float* ivar, cons
 int fcl_al_viterbi_fwd(const fcl_al_t* a, fcl_stream_t stream);
 int fcl_al_stats_fwd(const float* x, const int32_t* row_begin, const int32_t* row_frames, const int32_t* state_off, const int32_t* state_rows,
                      int64_t* acc_n, double* acc_s, double* acc_q, int64_t frames, int64_t rows, int d, int n_states, fcl_stream_t stream);
+/* Forced alignment, Gaussian-mixture states (csrc/align_gmm.hip; restated in float64 numpy in tests/align_gmm_ref.py).  The graph, the Viterbi
+ *      entry and everything above are unchanged; these three entries replace the log-likelihood and the statistics when a state has several components.
+ * Model: model state m owns the components comp_off[m] .. comp_off[m + 1] (comp_off [M + 1] int32 on the device), between 1 and max_comp <= 8 of
+ *      them, G <= 8192 in all (M <= G <= M max_comp).  Per component mean [G][D], ivar [G][D] and cconst [G] = ln w + gconst(var), w the component's
+ *      weight inside its state; formed in float64 on the host and uploaded as float32.
+ * fcl_al_gmm_loglik_fwd: ll [frames][M].  Per component l_c = fma(-0.5, q_c, cconst_c) with q_c by the chain of fcl_al_loglik_fwd (ONE float32 fma
+ *      chain in ascending d from 0, D padded to a multiple of 4 by zeros).  mx = max_c l_c (a NaN wins);  ll = mx + logf(sum_c expf(l_c - mx)), the sum
+ *      in float32 over the components in ascending order from 0.  A state with one component gets ll = l_0, no exp or log.  When mx is not finite,
+ *      ll = mx: -inf stays -inf, NaN stays NaN, and the Viterbi entry's failure path handles the utterance.  Consequences that are part of the
+ *      contract: with one component everywhere and cconst = gconst the output is bit for bit fcl_al_loglik_fwd's; a component whose l_c - mx
+ *      underflows expf leaves ll bit for bit the dominant component's value.
+ * fcl_al_gmm_post_fwd: gamma [frames][8] float32 from frame_state [frames] int32, the model state the alignment gave each frame (-1: a frame of an
+ *      utterance without an alignment).  gamma[f][c] = expf(l_c - mx) / sum (a correctly rounded division) over the components of that state, the
+ *      l_c recomputed by the same chain, the sum as above; exactly 1 for a one-component state; 0 for c beyond the state's count and for a negative
+ *      frame_state.
+ * fcl_al_gmm_stats_fwd ADDS to acc_w [G], acc_s [G][D], acc_q [G][D] (float64) over row_begin / row_frames and the state-grouped row lists of
+ *      fcl_al_stats_fwd.  Per (component, coefficient) one float64 chain from 0, rows in list order, frames ascending; a step is
+ *      g = (double)gamma, v = (double)x, p = g v (exact), w += g, s += p, q += p v, each product and each sum rounded on its own (never fused); the
+ *      chain's total is then added to the accumulator.  No atomics: a batch is bit for bit its per-utterance runs, batches chain in stream order.
+ * Each entry validates before any HIP call: a null pointer FCL_ERR_INVALID; D, M, G, max_comp or a count out of range FCL_ERR_SHAPE; an empty
+ *      batch returns 0 and launches nothing; none allocates, synchronises or copies.  Device tables are clamped: a state's components are
+ *      g0 = clamp(comp_off[m], 0, G - 1) and count = clamp(comp_off[m + 1] - g0, 1, min(max_comp, G - g0)); frame_state above M - 1 counts as M - 1;
+ *      the row lists as in fcl_al_stats_fwd.  The kernels stay inside their buffers whatever the tables hold. */
+int fcl_al_gmm_loglik_fwd(const float* x, const float* mean, const float* ivar, const float* cconst, const int32_t* comp_off, float* ll, int64_t frames,
+                          int d, int n_states, int n_comp, int max_comp, fcl_stream_t stream);
+int fcl_al_gmm_post_fwd(const float* x, const float* mean, const float* ivar, const float* cconst, const int32_t* comp_off, const int32_t* frame_state,
+                        float* gamma, int64_t frames, int d, int n_states, int n_comp, int max_comp, fcl_stream_t stream);
+int fcl_al_gmm_stats_fwd(const float* x, const float* gamma, const int32_t* row_begin, const int32_t* row_frames, const int32_t* state_off,
+                         const int32_t* state_rows, const int32_t* comp_off, double* acc_w, double* acc_s, double* acc_q, int64_t frames, int64_t rows, int d,
+                         int n_states, int n_comp, int max_comp, fcl_stream_t stream);
 
 /* ---- Multi-resolution STFT loss: spectral convergence and log-magnitude distance of a generated waveform x against a target y, and the gradient
  *      with respect to x (fcl_taco2_amd/stft_loss.py; restated in float64 numpy in tests/stft_loss_ref.py).  One resolution (n_fft, hop,

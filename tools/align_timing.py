@@ -5,10 +5,12 @@
      `--ref-utts` utterances and scaled)
   B  the three launches of csrc/align.hip on maps and buffers prepared ahead of time: al_loglik_kernel, al_viterbi_kernel, al_stats_kernel
   largest  the largest utterance the kernel takes, S = 1024 rows x T = 4096 frames, M = 1024: the Viterbi launch alone
+  C  with `--mixtures C [C ...]`: the same E-step with C components in every state, the three launches of csrc/align_gmm.hip --
+     al_gmm_loglik_kernel, al_gmm_post_kernel, al_gmm_stats_kernel -- around the same Viterbi launch, on the alignment B gave
 
 One process, event timers, a warm-up launch of every shape, the median of `--repeats`.  Prints one JSON line.  The tool fixes no number.
 
-    python tools/align_timing.py [--utts 64] [--frames 800] [--phonemes 40] [--repeats 5] [--ref-utts 2]
+    python tools/align_timing.py [--utts 64] [--frames 800] [--phonemes 40] [--repeats 5] [--ref-utts 2] [--mixtures 4 8]
 """
 import argparse
 import json
@@ -45,7 +47,9 @@ def main():
     ap.add_argument("--phonemes", type=int, default=40)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--ref-utts", type=int, default=2, help="utterances the float64 statement is timed on")
+    ap.add_argument("--mixtures", type=int, nargs="*", default=[], metavar="C", help="also time the mixture E-step with C components per state, 1 .. 8")
     args = ap.parse_args()
+    assert all(1 <= c <= 8 for c in args.mixtures), "--mixtures takes component counts in 1 .. 8"
     import align_ref as R
     import fcl_taco2_amd  # noqa: F401
     from fcl_taco2_amd import alignment as A
@@ -82,6 +86,21 @@ def main():
         same = same and np.array_equal(r["row_frames"], row_frames.cpu().numpy()[mp.row_offs[k] : mp.row_offs[k + 1]])
     out["float64_ms_scaled"] = (time.perf_counter() - t0) * 1e3 * args.utts / args.ref_utts
     out["same_alignment_as_float64"] = bool(same)
+    # the mixture E-step: C components per state around the state's mean, equal weights, on the alignment the launches above left
+    fs = A.frame_states(mp, frame_row)
+    for c in args.mixtures:
+        comp_off = np.arange(M + 1, dtype=np.int32) * c
+        gm = A.AlignModel(["p%d" % i for i in range(P)], K, np.repeat(mean, c, axis=0) + rng.randn(M * c, D) * 0.5, np.repeat(var, c, axis=0),
+                          weight=np.full(M * c, 1.0 / c), comp_off=comp_off)
+        gp = tuple(torch.from_numpy(a).to(dev) for a in gm.gmm_params32())
+        gamma = torch.empty(mp.frames, 8, device=dev)
+        gacc = (torch.zeros(M * c, device=dev, dtype=torch.float64), torch.zeros(M * c, D, device=dev, dtype=torch.float64),
+                torch.zeros(M * c, D, device=dev, dtype=torch.float64))
+        out["mixtures_%d" % c] = dict(
+            components=M * c,
+            loglik_ms=timed(lambda: A.launch_gmm_loglik(gp, x, ll, mp.frames, c), args.repeats),
+            post_ms=timed(lambda: A.launch_gmm_post(gp, x, fs, gamma, mp.frames, c), args.repeats),
+            stats_ms=timed(lambda: A.launch_gmm_stats(mp, gp[3], x, gamma, row_begin, row_frames, *gacc, max_comp=c), args.repeats))
     # the largest utterance
     S, T = 1024, 4096
     big = A.AlignMaps([T], [(np.arange(S, dtype=np.int32), np.zeros(S, np.int32))], S, dev)
