@@ -126,6 +126,12 @@ class Pitch(C.Structure):  # fcl_px_t
         ("fs", _F), ("threshold", _F)] + [(n, _P) for n in ("x", "smp_off", "frame_utt", "utt_off", "f0", "cmnd_out", "tau_out")]
 
 
+class Pyin(C.Structure):  # fcl_pyin_t
+    _fields_ = [("frames", C.c_int64)] + [(n, C.c_int32) for n in ("n_utt", "n_lag", "tau_min", "tau_max", "nb", "w")] + [("fs", _F), ("reserved", C.c_int32)] + [
+        (n, _P) for n in ("cmnd", "thr", "cw", "edge", "f_bin", "tri", "la", "utt_off", "lv", "lu", "bf0", "ov_out", "workspace")] + [("workspace_bytes", _Z)] + [
+        (n, _P) for n in ("state", "f0", "score")]
+
+
 class Resample(C.Structure):  # fcl_rs_t
     _fields_ = [("samples_in", C.c_int64), ("samples_out", C.c_int64)] + [(n, C.c_int32) for n in ("l", "m", "k", "n_utt", "max_out", "reserved")] + [
         (n, _P) for n in ("x", "smp_off_in", "smp_off_out", "table", "y")]
@@ -367,6 +373,8 @@ SIGNATURES = {
     "fcl_fx_segment_mean_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     "fcl_px_yin_fwd": (_I, [C.POINTER(Pitch), _P]),
     "fcl_px_short_run_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),
+    "fcl_px_pyin_obs_fwd": (_I, [C.POINTER(Pyin), _P]),
+    "fcl_px_pyin_viterbi_fwd": (_I, [C.POINTER(Pyin), _P]),
     "fcl_rs_resample_fwd": (_I, [C.POINTER(Resample), _P]),
     "fcl_ev_dtw_workspace_bytes": (_Z, [C.c_int64, _I]),
     "fcl_ev_cepstra_fwd": (_I, [_P, _P, _P, _P, C.c_int64, _I, _I, _P]),

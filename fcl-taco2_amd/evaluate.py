@@ -348,6 +348,8 @@ def evaluate(args):
             settings["aligned"]["mel"] = dict(n_mels=args.n_mels, mel_basis=args.mel_basis)
     if both_wav:
         settings["f0"] = dict(floor=args.f0_floor, ceil=args.f0_ceil, threshold=args.f0_threshold, min_voiced=args.f0_min_voiced, frame_length=args.f0_frame_length)
+        if args.f0_method != "yin":  # the default's document stays as it was
+            settings["f0"].update(method=args.f0_method, bins_per_semitone=args.f0_bins_per_semitone, max_rate=args.f0_max_rate)
     return summarise(records, settings)
 
 

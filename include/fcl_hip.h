@@ -1063,6 +1063,58 @@ int fcl_px_yin_fwd(const fcl_px_t* a, fcl_stream_t stream);
 int fcl_px_short_run_fwd(const float* f0_in, const int32_t* frame_utt, const int32_t* utt_off, float* f0_out, int64_t frames, int n_utt, int min_voiced,
                          fcl_stream_t stream);
 
+/* Probabilistic YIN (csrc/pyin.hip; Mauch & Dixon 2014; restated in numpy, float64 and float32, in tests/pyin_ref.py): the d' rows above
+ *      (cmnd_out of fcl_px_yin_fwd) -> a track chosen over the whole utterance.  Two launches between fcl_px_yin_fwd and fcl_px_short_run_fwd.
+ * Tables (device, float; the package builds them in float64): thr[i - 1] = i / 100, i = 1 .. 100; cw[0 .. 100], cw[i] = sum_{j <= i} w_j with
+ *      w_i = F(i / 100) - F((i - 1) / 100), F(x) = 1 - (1 - x)^18 (1 + 18 x) the Beta(2, 18) cdf; nb pitch bins, B per semitone, with centres
+ *      f_bin[b] = f0_floor 2^(b / (12 B)) and descending period edges edge[j] = fs / (f0_floor 2^((j + 1/2) / (12 B))), j < nb - 1; the band's half
+ *      width W bins with tri[k] = ln((W + 1 - |k - W|) / (W + 1)^2), k <= 2 W; la[v1][v2] = ln 0.99 (v1 == v2) or ln 0.01.  PA = 0.01f, FLOOR = 1e-30f.
+ *      Every comparison and operation below is ONE float32 operation (no contraction), in the order written.
+ * fcl_px_pyin_obs_fwd, per frame.  Candidates: rec = +inf, rec_i = 100, t = tau_min; while t <= tau_max: if d'(t) < rec { m = t; while m < tau_max and
+ *      d'(m + 1) < d'(m): m += 1; lo_i = #{i : thr[i - 1] <= d'(m)}; candidate m with mass = cw[rec_i] - cw[lo_i]; rec = d'(m), rec_i = lo_i,
+ *      t = m + 1 } else t += 1.  The last candidate (the global record) gets mass += PA * cw[lo_i] (product and sum rounded).  This is the pick of
+ *      fcl_px_yin_fwd run once per threshold.  A row whose comparisons are all false has no candidate.
+ *      Period: a, b, c = d'(m - 1), d'(m), d'(m + 1); D = (a - (b + b)) + c; delta = clamp((0.5f (a - c)) / D, -1/2, 1/2) if D > 0, else 0;
+ *      p = (float)m + delta; f = fs / p.  Bin: b = #{j : edge[j] >= p}.
+ *      In candidate order: ov[b] += mass; a mass strictly greater than the bin's largest so far (0 at first) sets bf0[b] = f.  pv = sum_b ov[b] over
+ *      ascending b.  lv[f][b] = logf(max(ov[b], FLOOR)), lu[f] = logf(max((1 - pv) / nb, FLOOR)), bf0[f][b] (0 where no candidate with mass fell);
+ *      ov_out [frames, nb] optional.  cmnd has row pitch n_lag >= tau_max + 2 (n_lag <= 520, tau_max <= 511).
+ * fcl_px_pyin_viterbi_fwd, per utterance u (frames utt_off[u] .. utt_off[u + 1], T of them).  State (v, b), v = 0 voiced, index v nb + b.
+ *      V0[0][b] = lv[0][b], V0[1][b] = lu[0].  Step: M[v1][b] = max_k (V[v1][b + k - W] + tri[k]) over ascending k, predecessors outside [0, nb) left
+ *      out, a later k winning only when strictly greater; c0 = M[0][b] + la[0][v2], c1 = M[1][b] + la[1][v2];
+ *      V'[v2][b] = (c1 > c0 ? c1 : c0) + (v2 == 0 ? lv[t][b] : lu[t]).  End: the largest V, the lowest index among equals; score[u] is that V.
+ *      state [frames] int32; f0 [frames]: a voiced state gets bf0[t][b] if > 0, else f_bin[b]; an unvoiced one 0.  The backtrack runs in the same
+ *      launch from one back-pointer byte per (frame, state) in the caller's workspace (frames x 2 nb bytes at least), stays inside [0, nb) and ends
+ *      after T steps whatever the workspace holds.  utt_off is clamped to [0, frames]; an empty or descending slice writes score -inf only.
+ * 1 <= nb <= 512, 1 <= W <= 63, n_utt <= 65535, frames x 2 nb and frames x n_lag below 2^31: otherwise FCL_ERR_SHAPE; a null pointer
+ *      FCL_ERR_INVALID; a short workspace FCL_ERR_WORKSPACE; an empty batch: nothing is launched -- all before any HIP call.  No atomics; a batch is
+ *      bit for bit its per-utterance runs.  No entry allocates, synchronises or copies. */
+typedef struct {
+    int64_t frames;
+    int32_t n_utt, n_lag, tau_min, tau_max, nb, w;
+    float fs;
+    int32_t reserved;
+    const float* cmnd;
+    const float* thr;
+    const float* cw;
+    const float* edge;
+    const float* f_bin;
+    const float* tri;
+    const float* la;
+    const int32_t* utt_off;
+    float* lv;
+    float* lu;
+    float* bf0;
+    float* ov_out;
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* state;
+    float* f0;
+    float* score;
+} fcl_pyin_t;
+int fcl_px_pyin_obs_fwd(const fcl_pyin_t* a, fcl_stream_t stream);
+int fcl_px_pyin_viterbi_fwd(const fcl_pyin_t* a, fcl_stream_t stream);
+
 /* ---- Resampling: waveform at fs_in -> waveform at fs_out, band-limited (fcl_taco2_amd/resample.py; restated in float64 numpy in
  *      tests/resample_ref.py).  A Kaiser-windowed sinc evaluated exactly at the L phases of the rational ratio, in front of the two blocks above.
  * fs_out / fs_in = L / M in lowest terms, s = min(1, L / M).  Z = 64 zero crossings, rho = 0.9475937167399596, beta = 14.769656459379492.
