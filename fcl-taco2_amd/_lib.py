@@ -149,6 +149,12 @@ class Align(C.Structure):  # fcl_al_t
         (n, _P) for n in ("frame_row", "row_begin", "row_frames", "score", "ok")]
 
 
+class AlignLattice(C.Structure):  # fcl_al_lattice_t
+    _fields_ = [(n, C.c_int64) for n in ("frames", "rows", "cells")] + [(n, C.c_int32) for n in ("n_utt", "n_states", "max_t", "max_s")] + [
+        (n, _P) for n in ("ll", "frame_off", "row_off", "cell_off", "row_state", "row_pred", "row_flags", "workspace")] + [("workspace_bytes", _Z)] + [
+        (n, _P) for n in ("frame_row", "row_begin", "row_frames", "score", "ok")]
+
+
 class StftLoss(C.Structure):  # fcl_stl_t
     _fields_ = [("frames", C.c_int64), ("samples", C.c_int64)] + [(n, C.c_int32) for n in ("n_fft", "hop", "n_utt", "accumulate")] + [
         (n, _P) for n in ("x", "y", "smp_off", "frame_utt", "utt_off", "window", "twiddle", "frame_sums", "utt_sums", "coef", "fr", "gx")]
@@ -384,6 +390,7 @@ SIGNATURES = {
     "fcl_al_loglik_fwd": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _P]),
     "fcl_al_viterbi_fwd": (_I, [C.POINTER(Align), _P]),
     "fcl_al_stats_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _I, _I, _P]),
+    "fcl_al_lattice_viterbi_fwd": (_I, [C.POINTER(AlignLattice), _P]),
     "fcl_al_gmm_loglik_fwd": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
     "fcl_al_gmm_post_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
     "fcl_al_gmm_stats_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _I, _I, _I, _I, _P]),

@@ -2,8 +2,9 @@
 
     python -m fcl_taco2_amd.align --wav-dir wavs --transcripts phones.txt --textgrid-out TextGrid --optional sp --model-out align.npz
     python -m fcl_taco2_amd.align --wav-dir more_wavs --transcripts more.txt --textgrid-out TextGrid2 --optional sp --model align.npz
+    python -m fcl_taco2_amd.align --wav-dir wavs --transcripts words.txt --lexicon lexicon.txt --optional sp --textgrid-out TextGrid
 
-`--transcripts` holds one utterance per line, `utt ph ph ...`: the phonemes, not words (there is no dictionary and no G2P here).  Every utterance of
+`--transcripts` holds one utterance per line, `utt ph ph ...`: the phonemes -- or, with `--lexicon`, `utt word word ...` (below).  Every utterance of
 the transcripts needs `<utt>.wav` (16-bit PCM mono) in `--wav-dir`.  Without `--model` the inventory is the set of labels and the models are
 trained on these very utterances from a flat start (`--iterations`, default 15: not tuned, the synthetic corpora of the tests converge within 6);
 with `--model` the driver only aligns.  `--mixtures N` (1 .. 8, default 1: single Gaussians) then grows every state into a mixture: the component target
@@ -17,8 +18,19 @@ Per utterance `<utt>.TextGrid` (long text format, one tier `phones`) goes to `--
 (k hop + 0.5) / fs, the last interval ends at the wav's end, so that textgrid.alignment() gives back the aligner's durations with the last one less
 by 1, which preprocess's last-duration rule restores.  `--durations-out` also keeps the durations as `<utt>.npy` (int64, summing to the frame
 count).  `--report` holds the mean score per frame of every iteration and the utterances that could not be aligned (they get no TextGrid); with mixtures
-its `settings` also name `mixtures` and every iteration its `components`, the component total of that round."""
+its `settings` also name `mixtures` and every iteration its `components`, the component total of that round.
+
+`--lexicon FILE` (lines `WORD PH PH ...`, one pronunciation per line, `WORD(2)` for further ones; lexicon.py) makes the transcripts word text: every
+word stands in the utterance's graph with all its pronunciations side by side (at most 7), the one label `--optional` names is inserted as a silence
+between the words and at both ends (`--no-boundary-silence`: between the words only), and the alignment picks pronunciations and pauses (DESIGN.md
+§6x).  Words are compared lower-cased and without surrounding punctuation; there is no G2P: with `--oov refuse` (the default) the words the lexicon
+lacks are listed with their counts and nothing runs, with `--oov skip` the utterances that hold one are left out and named in the report.  Without
+`--model` the inventory is the silence label and every label in the pronunciations of the words that occur.  The TextGrids keep the tier `phones`
+as it is and gain a tier `words`: a word spans its phones, a silence is an interval with empty text.  `--pronunciations-out FILE` writes
+`utt ph ph ...` of the chosen paths, the format `--transcripts` takes without a lexicon; the report gains, per word, how often each of its
+pronunciations was chosen."""
 import argparse
+import collections
 import json
 import logging
 import os
@@ -26,7 +38,7 @@ import os
 import numpy as np
 import torch
 
-from . import alignment, extract_features as X, features, griffinlim, resample, textgrid
+from . import alignment, extract_features as X, features, griffinlim, lexicon, resample, textgrid
 
 
 def read_transcripts(path):
@@ -53,7 +65,11 @@ def build_parser():
     ap.add_argument("--transcripts", required=True, metavar="FILE", help="lines `utt ph ph ...`")
     ap.add_argument("--textgrid-out", required=True, metavar="DIR", help="<utt>.TextGrid with the tier `phones`")
     ap.add_argument("--durations-out", default=None, metavar="DIR", help="<utt>.npy: durations in frames")
-    ap.add_argument("--optional", nargs="*", default=[], metavar="LABEL", help="labels that may be skipped (pauses)")
+    ap.add_argument("--optional", nargs="*", default=[], metavar="LABEL", help="labels that may be skipped (pauses); with --lexicon the one silence label")
+    ap.add_argument("--lexicon", default=None, metavar="FILE", help="lines `WORD PH PH ...`: --transcripts then holds words, aligned through all their pronunciations")
+    ap.add_argument("--oov", choices=("refuse", "skip"), default="refuse", help="words the lexicon lacks: stop and list them, or leave their utterances out")
+    ap.add_argument("--no-boundary-silence", action="store_true", help="with --lexicon: no optional silence at the two ends of an utterance")
+    ap.add_argument("--pronunciations-out", default=None, metavar="FILE", help="with --lexicon: `utt ph ph ...` of the chosen paths")
     ap.add_argument("--states", type=int, default=alignment.STATES_DEFAULT, help="states per phoneme, 1 .. %d" % alignment.STATES_MAX)
     ap.add_argument("--iterations", type=int, default=alignment.ITERATIONS_DEFAULT, help="alignment / re-estimation rounds after the flat start (not tuned)")
     ap.add_argument("--mixtures", type=int, default=1, help="Gaussians per state after the mixture stage, 1 .. %d (1: single Gaussians)" % alignment.MIXTURES_MAX)
@@ -81,7 +97,7 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if not os.path.isdir(args.wav_dir):
         ap.error("--wav-dir %s is not a directory" % args.wav_dir)
-    for flag, p in (("--transcripts", args.transcripts), ("--model", args.model), ("--mel-basis", args.mel_basis)):
+    for flag, p in (("--transcripts", args.transcripts), ("--model", args.model), ("--mel-basis", args.mel_basis), ("--lexicon", args.lexicon)):
         if p is not None and not os.path.isfile(p):
             ap.error("%s %s is not a file" % (flag, p))
     if not 1 <= args.states <= alignment.STATES_MAX:
@@ -94,6 +110,10 @@ def parse_args(argv=None):
         ap.error("--mix-iterations must not be negative")
     if not args.min_occupancy >= 1.0:
         ap.error("--min-occupancy must be at least 1")
+    if args.lexicon is not None and len(args.optional) != 1:
+        ap.error("--lexicon needs --optional to name exactly one label, the silence")
+    if args.lexicon is None and (args.pronunciations_out or args.no_boundary_silence or args.oov != "refuse"):
+        ap.error("--pronunciations-out, --no-boundary-silence and --oov go with --lexicon")
     if args.n_mels - 1 < alignment.ORDER:
         ap.error("--n-mels must exceed the %d cepstra the features take" % alignment.ORDER)
     try:
@@ -162,19 +182,59 @@ def extract(args, utts, af):
     return feats
 
 
+def check_words(args, transcripts, lex):
+    """the words the lexicon lacks: refused with their counts (--oov refuse), or their utterances taken out of `transcripts` (--oov skip)
+    -> {utt: [its words the lexicon lacks]} of the utterances left out"""
+    missing = {u: sorted(set(w for w in lexicon.normalise_words(tr) if w not in lex)) for u, tr in transcripts.items()}
+    missing = {u: m for u, m in missing.items() if m}
+    if not missing:
+        return {}
+    if args.oov == "refuse":
+        counts = collections.Counter(w for u in missing for w in lexicon.normalise_words(transcripts[u]) if w not in lex)
+        raise ValueError("%d words of %s are not in %s (in %d utterances; --oov skip leaves those out): %s"
+                         % (len(counts), args.transcripts, args.lexicon, len(missing), ", ".join("%s (%d)" % (w, counts[w]) for w in sorted(counts))))
+    for u in missing:
+        del transcripts[u]
+    if not transcripts:
+        raise ValueError("every utterance of %s holds a word that is not in %s" % (args.transcripts, args.lexicon))
+    return missing
+
+
+def word_tier(r, fs, hop, n_samples):
+    """the `words` tier of a result of Aligner.align(lexicon=): a word spans its phones, a silence is an interval with empty text"""
+    texts, durs, last = [], [], None
+    for w, d in zip(r["label_words"], r["durations"]):
+        if w >= 0 and w == last:
+            durs[-1] += d
+        else:
+            texts.append(r["words"][w] if w >= 0 else "")
+            durs.append(d)
+        last = w
+    return textgrid.frame_intervals(texts, durs, fs, hop, n_samples)
+
+
 def align(args):
     """-> the --report document"""
     transcripts = read_transcripts(args.transcripts)
+    lex = lexicon.read_lexicon(args.lexicon) if args.lexicon else None
+    skipped = check_words(args, transcripts, lex) if lex is not None else {}
     ids = list(transcripts)
     model = alignment.AlignModel.load(args.model) if args.model else None
-    phones = model.phones if model else sorted(set(p for tr in transcripts.values() for p in tr))
+    if lex is not None:
+        phones = model.phones if model else sorted(set(args.optional) | set(lex.labels(w for tr in transcripts.values() for w in tr)))
+    else:
+        phones = model.phones if model else sorted(set(p for tr in transcripts.values() for p in tr))
     states = model.K if model else args.states
     for p in args.optional:
         if p not in phones:
             logging.warning("--optional %s: no such label in the %s", p, "model" if model else "transcripts")
     al = alignment.Aligner(args.device, phones, states, optional=[p for p in args.optional if p in phones], model=model, batch_cells=args.batch_cells)
+    word_kw = dict(lexicon=lex, boundary=not args.no_boundary_silence) if lex is not None else {}
     for u in ids:  # every refusal of a transcript, before the first device call
-        alignment.build_graph(transcripts[u], al.index, al.optional, al.K, u)
+        if lex is not None:
+            alignment.build_word_graph(transcripts[u], lex, al.index, al.silence(), al.K, word_kw["boundary"], u)
+        else:
+            alignment.build_graph(transcripts[u], al.index, al.optional, al.K, u)
     utts = plan_utterances(args, transcripts)
     af = alignment.AlignFeatures(features.from_args(args, args.device))
     if model is not None and model.settings != af.settings:
@@ -185,7 +245,8 @@ def align(args):
     trs = [transcripts[u] for u in ids]
     history = dict(score=[], failed=[], components=[])
     if model is None:
-        history = al.fit(feats, trs, args.iterations, ids=ids, mixtures=args.mixtures, mix_iterations=args.mix_iterations, min_occupancy=args.min_occupancy)
+        history = al.fit(feats, trs, args.iterations, ids=ids, mixtures=args.mixtures, mix_iterations=args.mix_iterations, min_occupancy=args.min_occupancy,
+                         **word_kw)
         for it, s in enumerate(history["score"]):
             if args.mixtures > 1:
                 logging.info("iteration %d: %d components, mean score per frame %.4f, %d utterances without an alignment", it + 1, history["components"][it], s,
@@ -194,7 +255,7 @@ def align(args):
                 logging.info("iteration %d: mean score per frame %.4f, %d utterances without an alignment", it + 1, s, len(history["failed"][it]))
         if args.model_out:
             al.model.save(args.model_out)
-    res = al.align(feats, trs, ids=ids)
+    res = al.align(feats, trs, ids=ids, **word_kw)
     os.makedirs(args.textgrid_out, exist_ok=True)
     if args.durations_out:
         os.makedirs(args.durations_out, exist_ok=True)
@@ -205,13 +266,29 @@ def align(args):
             continue
         frames, total = frames + sum(r["durations"]), total + r["score"]
         rows = textgrid.frame_intervals(r["phones"], r["durations"], args.fs, args.hop, n)
-        textgrid.write_textgrid(os.path.join(args.textgrid_out, u + ".TextGrid"), {"phones": rows}, rows[-1][1])
+        tiers = {"phones": rows}
+        if lex is not None:
+            tiers["words"] = word_tier(r, args.fs, args.hop, n)
+        textgrid.write_textgrid(os.path.join(args.textgrid_out, u + ".TextGrid"), tiers, rows[-1][1])
         if args.durations_out:
             np.save(os.path.join(args.durations_out, u + ".npy"), np.asarray(r["durations"], dtype=np.int64))
     doc = dict(n_utt=len(ids), n_aligned=len(ids) - len(failed), not_aligned=failed, score_per_frame=total / max(frames, 1),
                iterations=[dict(score_per_frame=s, not_aligned=f) for s, f in zip(history["score"], history["failed"])],
                settings=dict(states=al.K, optional=sorted(al.optional), phones=al.phones, trained=model is None, model=args.model, features=af.settings,
                              resample=bool(args.resample)))
+    if lex is not None:
+        variants = {}
+        for r in res:
+            if r["ok"]:
+                for w, v in zip(r["words"], r["pronunciations"]):
+                    variants.setdefault(w, [0] * len(lex.lookup(w)))[v] += 1
+        doc["lexicon"] = dict(path=args.lexicon, boundary_silence=not args.no_boundary_silence, oov=args.oov, skipped=skipped,
+                              variants={w: variants[w] for w in sorted(variants)})
+        if args.pronunciations_out:
+            with open(args.pronunciations_out, "w", encoding="utf-8") as f:
+                for u, r in zip(ids, res):
+                    if r["ok"]:
+                        f.write(u + " " + " ".join(r["phones"]) + "\n")
     mixtures = al.model.max_components if model is not None else args.mixtures
     if mixtures > 1:  # with single Gaussians the report is the one it has always been, byte for byte
         doc["settings"]["mixtures"] = mixtures

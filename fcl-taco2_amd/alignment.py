@@ -12,14 +12,19 @@ recordings stays unpinned: neither that tool nor real speech is available here.
     history = al.fit(features, transcripts, iterations=15)      # features: per utterance [T, D] on the device; mixtures=4 grows mixtures
     results = al.align(features, transcripts)                   # per utterance: phones, durations in frames (summing to T), score
 
+With lexicon= (lexicon.Lexicon) the transcripts are words: every word contributes all its pronunciations side by side, the one optional label stands
+as a silence between the words and at both ends, and the Viterbi over that lattice picks pronunciations and pauses (csrc/align_lattice.hip, DESIGN.md
+§6x; restated in tests/align_lattice_ref.py).  Everything around the Viterbi launch is shared with the chain path.
+
 No CPU fallback."""
+import collections
 import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _lib, metrics, ops
+from . import _lib, lexicon as LX, metrics, ops
 
 STATES_DEFAULT, STATES_MAX, MODEL_STATES_MAX, DIM_MAX, FRAMES_MAX, ROWS_MAX, UTT_MAX = 3, 3, 1024, 40, 4096, 1024, 65535
 BATCH_CELLS = 16 << 20
@@ -29,6 +34,7 @@ ORDER, DELTA_WINDOW, ENERGY_FLOOR = 13, 2, 1e-10
 ITERATIONS_DEFAULT = 15  # not tuned: the synthetic corpora of the tests converge within 6
 MIXTURES_MAX, COMPONENTS_MAX, MIX_ITERATIONS_DEFAULT, MIN_OCCUPANCY_DEFAULT = 8, 8192, 4, 10.0
 WEIGHT_FLOOR, SPLIT = 1e-5, 0.2
+PRED_SLOTS, START, FINAL = 8, 1, 2  # fcl_al_lattice_t: predecessor slots per row, the bits of row_flags
 
 
 # ---- model ------------------------------------------------------------------------------------------------------------------------------------------
@@ -185,6 +191,109 @@ def uniform_alignment(T, row_skip):
     return out
 
 
+WordGraph = collections.namedtuple("WordGraph", "row_state row_pred row_flags row_phone row_word row_variant")
+
+
+def build_word_graph(words, lex, index, silence, K, boundary=True, utt="#?"):
+    """A word transcript -> WordGraph(row_state, row_pred [S][8], row_flags, row_phone, row_word, row_variant), int32: the lattice
+    [sil_0] w_0 [sil_1] w_1 ... w_(n-1) [sil_n].  Every word is the concatenation of its pronunciations' chains (K rows per label), every silence K rows
+    of the label `silence`; sil_0 and sil_n exist only with `boundary`.  Predecessor slots: 1 on slot 0 of an inner row; on the first row of sil_i
+    (i >= 1) the last rows of the variants of w_(i-1) in variant order; on the first row of a variant of w_i the last row of sil_i first, where there
+    is one, then the last rows of the variants of w_(i-1) in variant order.  START: the first rows of sil_0 and of the variants of w_0; FINAL: the last
+    rows of sil_n and of the variants of w_(n-1).  row_phone is the inventory index of the row's label, row_word / row_variant the word and the
+    variant of a word row and -1 on a silence row.  The tokens are normalised (lexicon.normalise), those of which nothing is left are dropped.
+    Refused naming the utterance: no words, words the lexicon lacks (all of them named), a label that is not in the inventory, more than 1024 rows."""
+    words = LX.normalise_words(words)
+    if not words:
+        raise ValueError("fcl-taco2_amd: alignment: utterance %s has an empty transcript" % utt)
+    missing = sorted(set(w for w in words if lex.lookup(w) is None))
+    if missing:
+        raise ValueError("fcl-taco2_amd: alignment: utterance %s: not in the lexicon: %s" % (utt, ", ".join(missing)))
+    prons = [lex.lookup(w)[: LX.VARIANTS_MAX] for w in words]
+    for p in [silence] + [p for vs in prons for v in vs for p in v]:
+        if p not in index:
+            raise ValueError("fcl-taco2_amd: alignment: utterance %s: label %r is not in the inventory" % (utt, p))
+    n = len(words)
+    S = K * (sum(len(v) for vs in prons for v in vs) + n - 1 + (2 if boundary else 0))
+    if S > ROWS_MAX:
+        raise ValueError("fcl-taco2_amd: alignment: utterance %s: %d words with their pronunciations and silences make %d rows; the alignment covers at most %d"
+                         % (utt, n, S, ROWS_MAX))
+    row_state, row_phone, row_word, row_variant = (np.zeros(S, dtype=np.int32) for _ in range(4))
+    row_pred, row_flags = np.zeros((S, PRED_SLOTS), dtype=np.int32), np.zeros(S, dtype=np.int32)
+    r = 0
+
+    def chain(labels, word, variant):
+        """lays the rows of `labels` from r on -> (first row, last row)"""
+        nonlocal r
+        first = r
+        for p in labels:
+            for k in range(K):
+                row_state[r], row_phone[r], row_word[r], row_variant[r] = index[p] * K + k, index[p], word, variant
+                if r > first:
+                    row_pred[r, 0] = 1
+                r += 1
+        return first, r - 1
+
+    def enter(row, sources):
+        for slot, src in enumerate(sources):
+            row_pred[row, slot] = row - src
+
+    ends = []  # the last rows of the previous word's variants
+    for i in range(n + 1):
+        sil = None
+        if boundary or 0 < i < n:
+            sil = chain([silence], -1, -1)
+            enter(sil[0], ends)
+            if i == 0:
+                row_flags[sil[0]] |= START
+            if i == n:
+                row_flags[sil[1]] |= FINAL
+        if i == n:
+            break
+        new_ends = []
+        for v, labels in enumerate(prons[i]):
+            first, last = chain(labels, i, v)
+            enter(first, ([sil[1]] if sil else []) + ends)
+            if i == 0:
+                row_flags[first] |= START
+            if i == n - 1:
+                row_flags[last] |= FINAL
+            new_ends.append(last)
+        ends = new_ends
+    assert r == S
+    return WordGraph(row_state, row_pred, row_flags, row_phone, row_word, row_variant)
+
+
+def canonical_rows(graph, boundary=True):
+    """the rows of the canonical chain of a WordGraph: the first-listed variant of every word, with sil_0 and sil_n (the silence rows before the first
+    and behind the last word row) when `boundary`"""
+    word = np.flatnonzero(graph.row_word >= 0)
+    keep = graph.row_variant == 0
+    if boundary:
+        r = np.arange(len(graph.row_word))
+        keep = keep | ((graph.row_word < 0) & ((r < word[0]) | (r > word[-1])))
+    return np.flatnonzero(keep)
+
+
+def uniform_word_alignment(T, graph):
+    """row_frames [S] int64 of the flat start of a WordGraph: the equal split of uniform_alignment over the canonical chain -- sil_0, the first-listed
+    variant of every word, sil_n --, without the two silences when T is below that row count, None when that does not fit either.  Inter-word
+    silences and the other variants get no frames."""
+    for boundary in (True, False):
+        rows = canonical_rows(graph, boundary)
+        n = len(rows)
+        if n and T >= n:
+            out = np.zeros(len(graph.row_state), dtype=np.int64)
+            out[rows] = np.diff((np.arange(n + 1, dtype=np.int64) * int(T)) // n)
+            return out
+    return None
+
+
+def flat_start(T, graph):
+    """the flat-start row_frames of a chain (row_state, row_skip, ...) or of a WordGraph"""
+    return uniform_word_alignment(T, graph) if isinstance(graph, WordGraph) else uniform_alignment(T, graph[1])
+
+
 def mstep(n, s, q, mean, var, var_floor=VAR_FLOOR):
     """float64 on the host: mean = s / n, var = max(q / n - mean^2, var_floor x global variance); a state with n < 2 keeps its parameters"""
     n, s, q = np.asarray(n, dtype=np.float64), np.asarray(s, dtype=np.float64), np.asarray(q, dtype=np.float64)
@@ -268,7 +377,8 @@ def mstep_mixtures(w, s, q, mean, var, weight, comp_off, var_floor=VAR_FLOOR):
 class AlignMaps(object):
     """The tables of a packed batch on the device: frame_off / row_off [n + 1] int32, cell_off [n + 1] int64 (cumulative S T), row_state /
     row_skip [rows] int32, and the batch's rows grouped by model state (state_off [M + 1], state_rows [rows]: ascending row index inside a group),
-    with their totals on the host"""
+    with their totals on the host.  Graphs whose second table has two dimensions are lattices (WordGraph, or (row_state, row_pred [S][8],
+    row_flags)): the maps then carry row_pred [rows][8] / row_flags [rows] for fcl_al_lattice_viterbi_fwd and `lattice` is True."""
 
     def __init__(self, frame_lens, graphs, n_states, dev):
         self.frame_lens = [int(t) for t in frame_lens]
@@ -281,6 +391,12 @@ class AlignMaps(object):
         self.frames, self.rows, self.cells = int(self.frame_offs[-1]), int(self.row_offs[-1]), int(self.cell_offs[-1])
         self.max_t, self.max_s = max(self.frame_lens + [0]), max(self.row_lens + [0])
         self.row_states = np.concatenate([np.asarray(g[0], dtype=np.int32) for g in graphs]) if graphs else np.zeros(0, np.int32)
+        self.lattice = bool(graphs) and np.ndim(graphs[0][1]) == 2
+        if self.lattice:
+            assert all(np.ndim(g[1]) == 2 and np.shape(g[1])[1] == PRED_SLOTS for g in graphs)
+            self.row_preds = np.concatenate([np.asarray(g[1], dtype=np.int32) for g in graphs])
+            self.row_flagss = np.concatenate([np.asarray(g[2], dtype=np.int32) for g in graphs])
+            graphs = [(g[0], np.zeros(len(g[0]), np.int32)) for g in graphs]  # no row_skip: the chain entry is not for these maps
         self.row_skips = np.concatenate([np.asarray(g[1], dtype=np.int32) for g in graphs]) if graphs else np.zeros(0, np.int32)
         self.max_skip = int(self.row_skips.max()) if self.rows else 0
         self.state_rows_h = np.argsort(self.row_states, kind="stable").astype(np.int32)
@@ -289,6 +405,8 @@ class AlignMaps(object):
         self.frame_off, self.row_off, self.cell_off = t(self.frame_offs, np.int32), t(self.row_offs, np.int32), t(self.cell_offs, np.int64)
         self.row_state, self.row_skip = t(self.row_states, np.int32), t(self.row_skips, np.int32)
         self.state_off, self.state_rows = t(self.state_offs, np.int32), t(self.state_rows_h, np.int32)
+        if self.lattice:
+            self.row_pred, self.row_flags = t(self.row_preds, np.int32), t(self.row_flagss, np.int32)
 
     @property
     def frame_utt(self):
@@ -320,6 +438,18 @@ def launch_viterbi(mp, ll, workspace, frame_row, row_begin, row_frames, score, o
     a.ll, a.workspace, a.workspace_bytes = ll.data_ptr(), workspace.data_ptr(), int(workspace.numel() * workspace.element_size())
     a.frame_row, a.row_begin, a.row_frames, a.score, a.ok = (v.data_ptr() for v in (frame_row, row_begin, row_frames, score, ok))
     _lib.check(_lib.load().fcl_al_viterbi_fwd(C.byref(a), ops._stream()))
+
+
+def launch_lattice_viterbi(mp, ll, workspace, frame_row, row_begin, row_frames, score, ok):
+    """launch_viterbi over the lattices of mp (AlignMaps.lattice): fcl_al_lattice_viterbi_fwd on mp.row_pred / mp.row_flags"""
+    a = _lib.AlignLattice()
+    a.frames, a.rows, a.cells = mp.frames, mp.rows, mp.cells
+    a.n_utt, a.n_states, a.max_t, a.max_s = mp.n_utt, mp.n_states, mp.max_t, mp.max_s
+    a.frame_off, a.row_off, a.cell_off = mp.frame_off.data_ptr(), mp.row_off.data_ptr(), mp.cell_off.data_ptr()
+    a.row_state, a.row_pred, a.row_flags = mp.row_state.data_ptr(), mp.row_pred.data_ptr(), mp.row_flags.data_ptr()
+    a.ll, a.workspace, a.workspace_bytes = ll.data_ptr(), workspace.data_ptr(), int(workspace.numel() * workspace.element_size())
+    a.frame_row, a.row_begin, a.row_frames, a.score, a.ok = (v.data_ptr() for v in (frame_row, row_begin, row_frames, score, ok))
+    _lib.check(_lib.load().fcl_al_lattice_viterbi_fwd(C.byref(a), ops._stream()))
 
 
 def launch_stats(mp, x, row_begin, row_frames, acc_n, acc_s, acc_q):
@@ -461,12 +591,23 @@ class Aligner(object):
         self.model, self.var_floor, self.batch_cells, self.settings = model, float(var_floor), int(batch_cells), dict(settings or {})
 
     # -- preparation: everything that can be refused is refused before the first launch
-    def _prepare(self, features, transcripts, ids):
+    def _prepare(self, features, transcripts, ids, lex=None, boundary=True):
         if len(features) != len(transcripts):
             raise _lib.FclError("fcl-taco2_amd: alignment: %d feature matrices for %d transcripts" % (len(features), len(transcripts)))
         features[:] = [torch.as_tensor(x) for x in features]
-        graphs = [build_graph(tr, self.index, self.optional, self.K, ids[i] if ids is not None else "#%d" % i) for i, tr in enumerate(transcripts)]
+        name = lambda i: ids[i] if ids is not None else "#%d" % i
+        if lex is not None:
+            graphs = [build_word_graph(tr, lex, self.index, self.silence(), self.K, boundary, name(i)) for i, tr in enumerate(transcripts)]
+        else:
+            graphs = [build_graph(tr, self.index, self.optional, self.K, name(i)) for i, tr in enumerate(transcripts)]
         return (graphs,) + check_features(features, ids)
+
+    def silence(self):
+        """the silence label of the word lattices: with a lexicon `optional` must name exactly one label"""
+        if len(self.optional) != 1:
+            raise ValueError("fcl-taco2_amd: alignment: with a lexicon `optional` names exactly one label, the silence (got %s)"
+                             % (", ".join(sorted(self.optional)) or "none"))
+        return next(iter(self.optional))
 
     def _batches(self, features, graphs, frame_lens):
         """[(indices, AlignMaps, x [frames][D])] of the consecutive batches"""
@@ -493,7 +634,7 @@ class Aligner(object):
         frame_row = torch.empty(mp.frames, device=dev, dtype=torch.int32)
         row_begin, row_frames = torch.empty(mp.rows, device=dev, dtype=torch.int32), torch.empty(mp.rows, device=dev, dtype=torch.int32)
         score, ok = torch.empty(mp.n_utt, device=dev, dtype=torch.float32), torch.empty(mp.n_utt, device=dev, dtype=torch.int32)
-        launch_viterbi(mp, ll, ws, frame_row, row_begin, row_frames, score, ok)
+        (launch_lattice_viterbi if mp.lattice else launch_viterbi)(mp, ll, ws, frame_row, row_begin, row_frames, score, ok)
         return row_begin, row_frames, score, ok, frame_row
 
     def _acc(self, D):
@@ -502,8 +643,10 @@ class Aligner(object):
                 torch.zeros(self.n_states, D, device=dev, dtype=torch.float64))
 
     def fit(self, features, transcripts, iterations=ITERATIONS_DEFAULT, ids=None, callback=None, mixtures=1, mix_iterations=MIX_ITERATIONS_DEFAULT,
-            min_occupancy=MIN_OCCUPANCY_DEFAULT):
-        """features: per utterance a [T, D] tensor; transcripts: per utterance its labels.  The flat start, then `iterations` times align and
+            min_occupancy=MIN_OCCUPANCY_DEFAULT, lexicon=None, boundary=True):
+        """features: per utterance a [T, D] tensor; transcripts: per utterance its labels -- with lexicon= (lexicon.Lexicon) its words: the graphs are
+        then the lattices of build_word_graph (boundary: a silence at both ends), the flat start that of uniform_word_alignment, and the Viterbi launch
+        is fcl_al_lattice_viterbi_fwd; everything else is shared.  The flat start, then `iterations` times align and
         re-estimate.  With mixtures > 1 the component target per state then doubles -- 2, 4, ..., the last target is `mixtures` --; at each target
         the components are split (split_components) and `mix_iterations` rounds of Viterbi alignment and re-estimation follow, soft inside a state:
         the component posteriors of the frames the path gave to that state (csrc/align_gmm.hip), the M-step on the host (mstep_mixtures).
@@ -514,13 +657,13 @@ class Aligner(object):
             raise ValueError("fcl-taco2_amd: alignment: mixtures must lie in 1 .. %d, mix_iterations must not be negative and min_occupancy must be at least 1 "
                              "(got %r, %r, %r)" % (MIXTURES_MAX, mixtures, mix_iterations, min_occupancy))
         features = list(features)
-        graphs, frame_lens, D = self._prepare(features, transcripts, ids)
+        graphs, frame_lens, D = self._prepare(features, transcripts, ids, lexicon, boundary)
         name = lambda i: ids[i] if ids is not None else i
         with torch.cuda.device(self.device):
             batches = list(self._batches(features, graphs, frame_lens))
             acc = self._acc(D)
             for idx, mp, x in batches:  # the flat start: the statistics of the equal split
-                flat = [uniform_alignment(frame_lens[i], graphs[i][1]) for i in idx]
+                flat = [flat_start(frame_lens[i], graphs[i]) for i in idx]
                 counts = np.concatenate([np.zeros(len(graphs[i][0]), np.int64) if c is None else c for i, c in zip(idx, flat)])
                 begin = np.concatenate([mp.frame_offs[k] + np.concatenate([[0], np.cumsum(c)[:-1]]) if c is not None else np.zeros(len(graphs[i][0]), np.int64)
                                         for k, (i, c) in enumerate(zip(idx, flat))])
@@ -585,13 +728,16 @@ class Aligner(object):
                     it += 1
         return history
 
-    def align(self, features, transcripts, ids=None):
+    def align(self, features, transcripts, ids=None, lexicon=None, boundary=True):
         """-> per utterance dict(ok, score, phones, durations, row_frames): durations in frames on the features' grid, summing to T, the skipped
-        optional phonemes dropped from phones and durations; an utterance without an alignment has ok False and phones / durations None"""
+        optional phonemes dropped from phones and durations; an utterance without an alignment has ok False and phones / durations None.
+        With lexicon= the transcripts are words and the entries also hold words (normalised), pronunciations (the chosen variant's index per word),
+        word_durations (frames per word), label_words (per entry of phones its word, -1 for a silence) and graph (the WordGraph); phones / durations
+        run along the chosen path, the silences that received frames included and the others dropped."""
         if self.model is None:
             raise _lib.FclError("fcl-taco2_amd: alignment: no model (fit first, or pass model=)")
         features = list(features)
-        graphs, frame_lens, D = self._prepare(features, transcripts, ids)
+        graphs, frame_lens, D = self._prepare(features, transcripts, ids, lexicon, boundary)
         if D is not None and D != self.model.dim:
             raise ValueError("fcl-taco2_amd: alignment: the features have %d coefficients, the model %d" % (D, self.model.dim))
         out = [None] * len(features)
@@ -604,8 +750,26 @@ class Aligner(object):
                     c = rf[mp.row_offs[k] : mp.row_offs[k + 1]]
                     if not okh[k]:
                         out[i] = dict(ok=False, score=float("-inf"), phones=None, durations=None, row_frames=c)
+                        if lexicon is not None:
+                            out[i].update(words=LX.normalise_words(transcripts[i]), pronunciations=None, word_durations=None, label_words=None, graph=graphs[i])
+                        continue
+                    if lexicon is not None:
+                        out[i] = dict(ok=True, score=float(sh[k]), row_frames=c, **self._word_result(transcripts[i], graphs[i], c))
                         continue
                     per = c.reshape(-1, self.K).sum(axis=1)
                     keep = [j for j, p in enumerate(transcripts[i]) if per[j] > 0 or p not in self.optional]
                     out[i] = dict(ok=True, score=float(sh[k]), phones=[transcripts[i][j] for j in keep], durations=[int(per[j]) for j in keep], row_frames=c)
         return out
+
+    def _word_result(self, words, graph, row_frames):
+        """words, pronunciations, word_durations, phones, durations and label_words of the path row_frames marks through a WordGraph"""
+        K, words = self.K, LX.normalise_words(words)
+        per = row_frames.reshape(-1, K).sum(axis=1)  # frames per label of the lattice
+        word, variant, phone = graph.row_word[::K], graph.row_variant[::K], graph.row_phone[::K]
+        on = np.flatnonzero(per > 0)
+        pron, wdur = [-1] * len(words), [0] * len(words)
+        for j in on:
+            if word[j] >= 0:
+                pron[word[j]], wdur[word[j]] = int(variant[j]), wdur[word[j]] + int(per[j])
+        return dict(words=words, pronunciations=pron, word_durations=wdur, phones=[self.phones[phone[j]] for j in on], durations=[int(per[j]) for j in on],
+                    label_words=[int(word[j]) for j in on], graph=graph)

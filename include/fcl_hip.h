@@ -1252,6 +1252,53 @@ int fcl_al_loglik_fwd(const float* x, const float* mean, const float* ivar, cons
 int fcl_al_viterbi_fwd(const fcl_al_t* a, fcl_stream_t stream);
 int fcl_al_stats_fwd(const float* x, const int32_t* row_begin, const int32_t* row_frames, const int32_t* state_off, const int32_t* state_rows,
                      int64_t* acc_n, double* acc_s, double* acc_q, int64_t frames, int64_t rows, int d, int n_states, fcl_stream_t stream);
+/* Forced alignment, lattice graphs (csrc/align_lattice.hip; restated in numpy in tests/align_lattice_ref.py).  fcl_al_lattice_viterbi_fwd is
+ *      fcl_al_viterbi_fwd over a graph whose rows name their predecessors: the words of a transcript with all their pronunciations side by side and
+ *      an optional silence between them.  The packing is that of fcl_al_t -- ll [frames][M], frame_off, row_off, cell_off, row_state and the
+ *      one-byte-per-cell workspace of fcl_al_workspace_bytes -- and two tables replace row_skip / max_skip:
+ *      row_pred [rows][8] int32: a slot value j >= 1 means "this row may also be entered from row r - j of the same utterance"; a slot with j <= 0
+ *           or r - j < 0 does not count; the eight slots are judged independently.  Predecessors have lower indices: the rows are in topological
+ *           order by construction.
+ *      row_flags [rows] int32: bit 0 (FCL_AL_START) the row may hold frame 0, bit 1 (FCL_AL_FINAL) the row may hold the last frame; the other bits
+ *           are ignored.
+ * Recurrence, in float32:  V(r, 0) = ll(0, row_state[r]) on a START row, -inf elsewhere;  V(r, t) = ll(t, row_state[r]) + best for t > 0, where best
+ *      starts as stay, V(r, t - 1); the usable slots are then visited in slot order 0 .. 7 and a slot replaces the winner only when strictly greater.
+ *      The back-pointer byte is 0 for stay and 1 + slot otherwise.
+ * End and backtrack: the end row r* is the FINAL row with the largest finite V(r, T - 1), the lowest row index on ties, whatever the order of the
+ *      workgroup's reduction; without a FINAL row that holds a finite value the utterance fails.  The backtrack runs from (r*, T - 1) in the same
+ *      launch; it is valid only if it arrives at a START row in frame 0, and every move is checked against [0, S) and against the row's own slots.
+ * Outputs: frame_row [frames] (non-decreasing); row_begin / row_frames [rows], each row's first GLOBAL frame and its count -- a row off the path has
+ *      0 frames and row_begin = the utterance's first global frame --; score [n_utt] = V(r*, T - 1); ok [n_utt].  A failed utterance has the form of
+ *      fcl_al_viterbi_fwd: ok 0, score -inf, frame_row -1, row_frames 0 (row_begin: its first frame); the rest of the batch is unaffected.
+ * Contract: a chain written as a lattice -- slot 0 = 1 on every row r > 0, slot 1 = row_skip[r] where usable, START on row 0 alone, FINAL on row
+ *      S - 1 alone -- gives frame_row, row_frames, score and ok bit for bit equal to fcl_al_viterbi_fwd on finite ll, and an equal row_begin on every
+ *      row with frames.
+ * Supported: 1 <= T <= 4096, 1 <= S <= 1024, n_utt <= 65535, 1 <= M <= 1024.  The kernel clamps every offset, state, slot and flag it reads from
+ *      device memory and keeps every store inside the utterance's slices whatever the tables hold.  One workgroup per utterance, no atomics: a batch
+ *      is bit for bit its single launches.  Validation before any HIP call as in fcl_al_viterbi_fwd: a null pointer FCL_ERR_INVALID; a count, a
+ *      length or M out of range FCL_ERR_SHAPE; a workspace that is too small FCL_ERR_WORKSPACE; an empty batch: nothing is launched.  The entry
+ *      does not allocate, synchronise or copy. */
+#define FCL_AL_START 1
+#define FCL_AL_FINAL 2
+typedef struct {
+    int64_t frames, rows, cells;
+    int32_t n_utt, n_states, max_t, max_s;
+    const float* ll;
+    const int32_t* frame_off;
+    const int32_t* row_off;
+    const int64_t* cell_off;
+    const int32_t* row_state;
+    const int32_t* row_pred;
+    const int32_t* row_flags;
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* frame_row;
+    int32_t* row_begin;
+    int32_t* row_frames;
+    float* score;
+    int32_t* ok;
+} fcl_al_lattice_t;
+int fcl_al_lattice_viterbi_fwd(const fcl_al_lattice_t* a, fcl_stream_t stream);
 /* Forced alignment, Gaussian-mixture states (csrc/align_gmm.hip; restated in float64 numpy in tests/align_gmm_ref.py).  The graph, the Viterbi
  *      entry and everything above are unchanged; these three entries replace the log-likelihood and the statistics when a state has several components.
  * Model: model state m owns the components comp_off[m] .. comp_off[m + 1] (comp_off [M + 1] int32 on the device), between 1 and max_comp <= 8 of

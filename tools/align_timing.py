@@ -5,6 +5,8 @@
      `--ref-utts` utterances and scaled)
   B  the three launches of csrc/align.hip on maps and buffers prepared ahead of time: al_loglik_kernel, al_viterbi_kernel, al_stats_kernel
   largest  the largest utterance the kernel takes, S = 1024 rows x T = 4096 frames, M = 1024: the Viterbi launch alone
+  lattice  the same chains of B (and the largest utterance) written as lattices through al_lattice_viterbi_kernel of
+     csrc/align_lattice.hip: `lattice_viterbi_ms`, its ratio to `viterbi_ms`, and whether both entries gave the same alignment
   C  with `--mixtures C [C ...]`: the same E-step with C components in every state, the three launches of csrc/align_gmm.hip --
      al_gmm_loglik_kernel, al_gmm_post_kernel, al_gmm_stats_kernel -- around the same Viterbi launch, on the alignment B gave
 
@@ -79,6 +81,13 @@ def main():
     out["viterbi_ms"] = timed(lambda: A.launch_viterbi(mp, ll, ws, frame_row, row_begin, row_frames, score, ok), args.repeats)
     out["stats_ms"] = timed(lambda: A.launch_stats(mp, x, row_begin, row_frames, *acc), args.repeats)
     assert bool(ok.cpu().numpy().all())
+    import align_lattice_ref as LR
+
+    lmp = A.AlignMaps([len(x) for x in feats], [(rs,) + LR.chain_as_lattice(sk) for rs, sk in graphs], M, dev)
+    l_frame_row, l_row_begin, l_row_frames, l_ok, l_score = i32(mp.frames), i32(mp.rows), i32(mp.rows), i32(mp.n_utt), torch.empty(mp.n_utt, device=dev)
+    out["lattice_viterbi_ms"] = timed(lambda: A.launch_lattice_viterbi(lmp, ll, ws, l_frame_row, l_row_begin, l_row_frames, l_score, l_ok), args.repeats)
+    out["lattice_over_chain"] = out["lattice_viterbi_ms"] / out["viterbi_ms"]
+    out["lattice_same_as_chain"] = bool(torch.equal(l_frame_row, frame_row) and torch.equal(l_row_frames, row_frames) and torch.equal(l_score, score))
     t0 = time.perf_counter()
     same = True
     for k in range(args.ref_utts):
@@ -108,6 +117,8 @@ def main():
     wsb = torch.empty(big.workspace_bytes(), device=dev, dtype=torch.uint8)
     fb, rb, rf, okb, sb = i32(T), i32(S), i32(S), i32(1), torch.empty(1, device=dev)
     out["largest_viterbi_ms"] = timed(lambda: A.launch_viterbi(big, llb, wsb, fb, rb, rf, sb, okb), args.repeats)
+    lbig = A.AlignMaps([T], [(np.arange(S, dtype=np.int32),) + LR.chain_as_lattice(np.zeros(S, np.int32))], S, dev)
+    out["largest_lattice_viterbi_ms"] = timed(lambda: A.launch_lattice_viterbi(lbig, llb, wsb, fb, rb, rf, sb, okb), args.repeats)
     print(json.dumps(out))
 
 
