@@ -427,28 +427,28 @@ def launch_loglik(params, x, ll, frames):
                                              int(mean.shape[0]), ops._stream()))
 
 
+def _viterbi_args(a, mp, ll, workspace, frame_row, row_begin, row_frames, score, ok):
+    """the fields Align and AlignLattice share: the batch's sizes and tables, ll, the workspace and the outputs -> a"""
+    a.frames, a.rows, a.cells = mp.frames, mp.rows, mp.cells
+    a.n_utt, a.n_states, a.max_t, a.max_s = mp.n_utt, mp.n_states, mp.max_t, mp.max_s
+    a.frame_off, a.row_off, a.cell_off, a.row_state = mp.frame_off.data_ptr(), mp.row_off.data_ptr(), mp.cell_off.data_ptr(), mp.row_state.data_ptr()
+    a.ll, a.workspace, a.workspace_bytes = ll.data_ptr(), workspace.data_ptr(), int(workspace.numel() * workspace.element_size())
+    a.frame_row, a.row_begin, a.row_frames, a.score, a.ok = (v.data_ptr() for v in (frame_row, row_begin, row_frames, score, ok))
+    return a
+
+
 def launch_viterbi(mp, ll, workspace, frame_row, row_begin, row_frames, score, ok):
     """ll [frames][M] float32 -> frame_row [frames], row_begin / row_frames [rows], ok [n_utt] int32, score [n_utt] float32; workspace: uint8,
     AlignMaps.workspace_bytes() of it"""
-    a = _lib.Align()
-    a.frames, a.rows, a.cells = mp.frames, mp.rows, mp.cells
-    a.n_utt, a.n_states, a.max_t, a.max_s, a.max_skip = mp.n_utt, mp.n_states, mp.max_t, mp.max_s, mp.max_skip
-    a.frame_off, a.row_off, a.cell_off = mp.frame_off.data_ptr(), mp.row_off.data_ptr(), mp.cell_off.data_ptr()
-    a.row_state, a.row_skip = mp.row_state.data_ptr(), mp.row_skip.data_ptr()
-    a.ll, a.workspace, a.workspace_bytes = ll.data_ptr(), workspace.data_ptr(), int(workspace.numel() * workspace.element_size())
-    a.frame_row, a.row_begin, a.row_frames, a.score, a.ok = (v.data_ptr() for v in (frame_row, row_begin, row_frames, score, ok))
+    a = _viterbi_args(_lib.Align(), mp, ll, workspace, frame_row, row_begin, row_frames, score, ok)
+    a.max_skip, a.row_skip = mp.max_skip, mp.row_skip.data_ptr()
     _lib.check(_lib.load().fcl_al_viterbi_fwd(C.byref(a), ops._stream()))
 
 
 def launch_lattice_viterbi(mp, ll, workspace, frame_row, row_begin, row_frames, score, ok):
     """launch_viterbi over the lattices of mp (AlignMaps.lattice): fcl_al_lattice_viterbi_fwd on mp.row_pred / mp.row_flags"""
-    a = _lib.AlignLattice()
-    a.frames, a.rows, a.cells = mp.frames, mp.rows, mp.cells
-    a.n_utt, a.n_states, a.max_t, a.max_s = mp.n_utt, mp.n_states, mp.max_t, mp.max_s
-    a.frame_off, a.row_off, a.cell_off = mp.frame_off.data_ptr(), mp.row_off.data_ptr(), mp.cell_off.data_ptr()
-    a.row_state, a.row_pred, a.row_flags = mp.row_state.data_ptr(), mp.row_pred.data_ptr(), mp.row_flags.data_ptr()
-    a.ll, a.workspace, a.workspace_bytes = ll.data_ptr(), workspace.data_ptr(), int(workspace.numel() * workspace.element_size())
-    a.frame_row, a.row_begin, a.row_frames, a.score, a.ok = (v.data_ptr() for v in (frame_row, row_begin, row_frames, score, ok))
+    a = _viterbi_args(_lib.AlignLattice(), mp, ll, workspace, frame_row, row_begin, row_frames, score, ok)
+    a.row_pred, a.row_flags = mp.row_pred.data_ptr(), mp.row_flags.data_ptr()
     _lib.check(_lib.load().fcl_al_lattice_viterbi_fwd(C.byref(a), ops._stream()))
 
 
@@ -569,6 +569,28 @@ def check_features(features, ids=None):
 
 
 # ---- the aligner --------------------------------------------------------------------------------------------------------------------------------------
+class _RoundTally(object):
+    """one round of Aligner.fit: the score total and the frames of the utterances with an alignment, the names of those without"""
+
+    def __init__(self, frame_lens, name):
+        self.frame_lens, self.name, self.total, self.frames, self.failed = frame_lens, name, 0.0, 0, []
+
+    def batch(self, idx, ok, score):
+        """a batch's ok / score device tensors, idx: its utterances"""
+        okh, sh = ok.cpu().numpy(), score.cpu().numpy().astype(np.float64)
+        for k, i in enumerate(idx):
+            if okh[k]:
+                self.total, self.frames = self.total + sh[k], self.frames + self.frame_lens[i]
+            else:
+                self.failed.append(self.name(i))
+
+    def close(self, history, components):
+        """the round's entries of fit's history"""
+        history["score"].append(self.total / max(self.frames, 1))
+        history["failed"].append(self.failed)
+        history["components"].append(components)
+
+
 class Aligner(object):
     """Flat-start training and alignment.  phones: the inventory; optional: the labels that may be skipped (pauses); model: an AlignModel to align
     with (fit replaces it); settings: what the model is to carry about its features."""
@@ -619,7 +641,6 @@ class Aligner(object):
 
     def _viterbi(self, mp, x, params):
         """one batch: log-likelihoods and Viterbi -> (row_begin, row_frames, score, ok) device tensors"""
-        dev = self.device
         return self._viterbi_rows(mp, x, params)[:4]
 
     def _viterbi_rows(self, mp, x, params, max_comp=MIXTURES_MAX):
@@ -675,22 +696,15 @@ class Aligner(object):
             history = dict(score=[], failed=[], components=[])
             for it in range(int(iterations)):
                 params, acc = self.model.upload(self.device), self._acc(D)
-                total, frames, failed = 0.0, 0, []
+                tally = _RoundTally(frame_lens, name)
                 for idx, mp, x in batches:
                     row_begin, row_frames, score, ok = self._viterbi(mp, x, params)
                     launch_stats(mp, x, row_begin, row_frames, *acc)
-                    okh, sh = ok.cpu().numpy(), score.cpu().numpy().astype(np.float64)
-                    for k, i in enumerate(idx):
-                        if okh[k]:
-                            total, frames = total + sh[k], frames + frame_lens[i]
-                        else:
-                            failed.append(name(i))
+                    tally.batch(idx, ok, score)
                 n, s, q = (v.cpu().numpy() for v in acc)
                 mean, var = mstep(n, s, q, self.model.mean, self.model.var, var_floor=self.var_floor)
                 self.model = AlignModel(self.phones, self.K, mean, var, self.settings)
-                history["score"].append(total / max(frames, 1))
-                history["failed"].append(failed)
-                history["components"].append(self.n_states)
+                tally.close(history, self.n_states)
                 if callback is not None:
                     callback(it, self.model)
             # ---- the mixture stage: from one component of weight 1 per state, the occupancies those of the last round (or of the flat start)
@@ -704,25 +718,18 @@ class Aligner(object):
                     params = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in self.model.gmm_params32())
                     acc = (torch.zeros(G, device=self.device, dtype=torch.float64), torch.zeros(G, D, device=self.device, dtype=torch.float64),
                            torch.zeros(G, D, device=self.device, dtype=torch.float64))
-                    total, frames, failed = 0.0, 0, []
+                    tally = _RoundTally(frame_lens, name)
                     for idx, mp, x in batches:
                         row_begin, row_frames, score, ok, frame_row = self._viterbi_rows(mp, x, params, max_comp)
                         gamma = torch.empty(mp.frames, MIXTURES_MAX, device=self.device, dtype=torch.float32)
                         launch_gmm_post(params, x, frame_states(mp, frame_row), gamma, mp.frames, max_comp)
                         launch_gmm_stats(mp, params[3], x, gamma, row_begin, row_frames, *acc, max_comp=max_comp)
-                        okh, sh = ok.cpu().numpy(), score.cpu().numpy().astype(np.float64)
-                        for k, i in enumerate(idx):
-                            if okh[k]:
-                                total, frames = total + sh[k], frames + frame_lens[i]
-                            else:
-                                failed.append(name(i))
+                        tally.batch(idx, ok, score)
                     w, s, q = (v.cpu().numpy() for v in acc)
                     mean, var, weight = mstep_mixtures(w, s, q, mean, var, weight, comp_off, var_floor=self.var_floor)
                     occ = w
                     self.model = AlignModel(self.phones, self.K, mean, var, self.settings, weight=weight, comp_off=comp_off)
-                    history["score"].append(total / max(frames, 1))
-                    history["failed"].append(failed)
-                    history["components"].append(G)
+                    tally.close(history, G)
                     if callback is not None:
                         callback(it, self.model)
                     it += 1

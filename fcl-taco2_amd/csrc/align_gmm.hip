@@ -14,27 +14,22 @@
 //                         of width 8, every lane forms the sum in ascending c itself.  Branch-free up to the store: every lane of a wave takes
 //                         part in every shuffle.
 //   al_gmm_stats_kernel   al_stats_kernel's layout with a component axis: one workgroup of 64 x 8 threads per model state, thread (d, c) owns
-//                         coefficient d of the state's component c and runs the plain float64 chains over the state's rows in list order, frames
-//                         ascending, every product and sum a statement of its own under `#pragma clang fp contract(off)`: nothing is fused (the
-//                         disassembly has v_mul_f64 and v_add_f64 only, no v_fma_f64 / v_fmac_f64).
+//                         coefficient d of the state's component c and runs the plain float64 chains over the state's frames, every product and sum
+//                         a statement of its own under `#pragma clang fp contract(off)`: nothing is fused (the disassembly has v_mul_f64 and
+//                         v_add_f64 only, no v_fma_f64 / v_fmac_f64).
 // A state's components are read as g0 = clamp(comp_off[m], 0, G - 1), count = clamp(comp_off[m + 1] - g0, 1, min(max_comp, G - g0)); frame_state is
-// clamped to M - 1, the row lists as al_stats_kernel clamps them: the kernels stay inside their buffers whatever the tables hold.  No atomics.
-#include <math.h>
-
-#include "fcl_common.h"
+// clamped to M - 1, the row lists by al_state_frames (align_common.h): the kernels stay inside their buffers whatever the tables hold.  No atomics.
+#include "align_common.h"
 
 namespace fcl {
 
-constexpr int ALG_DMAX = 40, ALG_MMAX = 1024, ALG_CMAX = 8, ALG_GMAX = 8192;
-constexpr int ALG_LF = 16, ALG_LS = 64;  // frames per workgroup and component slots per tile of al_gmm_loglik_kernel
-constexpr int ALG_PF = 32;               // frames per workgroup of al_gmm_post_kernel
-
-__device__ __forceinline__ long long alg_clamp(long long v, long long lo, long long hi) { return min(max(v, lo), hi); }
+constexpr int ALG_CMAX = 8, ALG_GMAX = 8192;
+constexpr int ALG_PF = 32;  // frames per workgroup of al_gmm_post_kernel
 
 // the components of state m, inside [0, G) whatever comp_off holds: 1 <= cnt <= max_comp <= 8
 __device__ __forceinline__ void alg_state(const int* __restrict__ comp_off, int m, int G, int max_comp, int& g0, int& cnt) {
-    g0 = (int)alg_clamp(comp_off[m], 0, G - 1);
-    cnt = (int)alg_clamp((long long)comp_off[m + 1] - g0, 1, min(max_comp, G - g0));
+    g0 = (int)al_clamp(comp_off[m], 0, G - 1);
+    cnt = (int)al_clamp((long long)comp_off[m + 1] - g0, 1, min(max_comp, G - g0));
 }
 
 // NaN wins, then the larger value
@@ -43,31 +38,31 @@ __device__ __forceinline__ float alg_max(float mx, float l) { return (l > mx || 
 __global__ __launch_bounds__(256) void al_gmm_loglik_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ ivar,
                                                             const float* __restrict__ cconst, const int* __restrict__ comp_off, float* __restrict__ ll,
                                                             long long frames, int D, int M, int G, int max_comp) {
-    __shared__ float xs[ALG_LF * ALG_DMAX];
-    __shared__ float ms[ALG_LS * (ALG_DMAX + 1)];
-    __shared__ float vs[ALG_LS * (ALG_DMAX + 1)];
-    __shared__ float lv[ALG_LF * ALG_LS];  // l_c of the tile: [frame][slot]
-    __shared__ int slot_g[ALG_LS];         // the component of each slot
-    __shared__ unsigned char st_start[ALG_LS], st_cnt[ALG_LS];  // the first slot and the count of each state of the tile
+    __shared__ float xs[AL_LF * AL_DMAX];
+    __shared__ float ms[AL_LS * (AL_DMAX + 1)];
+    __shared__ float vs[AL_LS * (AL_DMAX + 1)];
+    __shared__ float lv[AL_LF * AL_LS];  // l_c of the tile: [frame][slot]
+    __shared__ int slot_g[AL_LS];        // the component of each slot
+    __shared__ unsigned char st_start[AL_LS], st_cnt[AL_LS];  // the first slot and the count of each state of the tile
     const int tid = threadIdx.x, D4 = (D + 3) & ~3, pitch = D4 | 1;
-    const long long f0 = (long long)blockIdx.x * ALG_LF;
-    const int nf = (int)min((long long)ALG_LF, frames - f0);
-    for (int e = tid; e < ALG_LF * D4; e += 256) {
+    const long long f0 = (long long)blockIdx.x * AL_LF;
+    const int nf = (int)min((long long)AL_LF, frames - f0);
+    for (int e = tid; e < AL_LF * D4; e += 256) {
         const int f = e / D4, d = e - f * D4;
         xs[e] = (f < nf && d < D) ? x[(f0 + f) * D + d] : 0.f;
     }
-    const int lane = tid & (ALG_LS - 1), fg = (tid >> 6) * 4;
+    const int lane = tid & (AL_LS - 1), fg = (tid >> 6) * 4;
     for (int m0 = 0; m0 < M;) {
         // the tile: the longest run of states from m0 whose components fit 64 slots.  Every wave finds it for itself, lane i looking at state m0 + i.
         int g0 = 0, cnt = 0;
         if (m0 + lane < M) alg_state(comp_off, m0 + lane, G, max_comp, g0, cnt);
         int end = cnt;  // inclusive scan: the slot this state ends at
 #pragma unroll
-        for (int o = 1; o < ALG_LS; o <<= 1) {
+        for (int o = 1; o < AL_LS; o <<= 1) {
             const int v = __shfl_up(end, o);
             if (lane >= o) end += v;
         }
-        const int ns = __popcll(__ballot(m0 + lane < M && end <= ALG_LS));  // >= 1: lane 0 ends at cnt <= 8
+        const int ns = __popcll(__ballot(m0 + lane < M && end <= AL_LS));  // >= 1: lane 0 ends at cnt <= 8
         const int nslots = __shfl(end, ns - 1);
         __syncthreads();  // the x rows are there; the last tile's readers are done
         if (tid < ns) {
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(256) void al_gmm_loglik_kernel(const float* __restr
             for (int c = 0; c < cnt; ++c) slot_g[end - cnt + c] = g0 + c;
         }
         __syncthreads();
-        for (int e = tid; e < ALG_LS * D4; e += 256) {
+        for (int e = tid; e < AL_LS * D4; e += 256) {
             const int s = e / D4, d = e - s * D4;
             const bool in = s < nslots && d < D;
             const long long g = in ? slot_g[s] : 0;
@@ -97,16 +92,16 @@ __global__ __launch_bounds__(256) void al_gmm_loglik_kernel(const float* __restr
                 q3 = fmaf(d3 * d3, iv, q3);
             }
             const float cc = cconst[slot_g[lane]];
-            float* out = lv + fg * ALG_LS + lane;  // the rows past nf hold the values of zero frames: finite, never read
+            float* out = lv + fg * AL_LS + lane;  // the rows past nf hold the values of zero frames: finite, never read
             out[0] = fmaf(-0.5f, q0, cc);
-            out[ALG_LS] = fmaf(-0.5f, q1, cc);
-            out[2 * ALG_LS] = fmaf(-0.5f, q2, cc);
-            out[3 * ALG_LS] = fmaf(-0.5f, q3, cc);
+            out[AL_LS] = fmaf(-0.5f, q1, cc);
+            out[2 * AL_LS] = fmaf(-0.5f, q2, cc);
+            out[3 * AL_LS] = fmaf(-0.5f, q3, cc);
         }
         __syncthreads();
         for (int p = tid; p < ns * nf; p += 256) {
             const int f = p / ns, s = p - f * ns, cn = st_cnt[s];
-            const float* lr = lv + f * ALG_LS + st_start[s];
+            const float* lr = lv + f * AL_LS + st_start[s];
             float v = lr[0];
             if (cn > 1) {
                 float mx = v;
@@ -176,20 +171,15 @@ __global__ __launch_bounds__(512) void al_gmm_stats_kernel(const float* __restri
     int g0, cnt;
     alg_state(comp_off, m, G, max_comp, g0, cnt);
     if (d >= D || c >= cnt) return;
-    const long long e0 = alg_clamp(state_off[m], 0, rows), e1 = alg_clamp(state_off[m + 1], e0, rows);
     double w = 0.0, s = 0.0, q = 0.0;
-    for (long long e = e0; e < e1; ++e) {
-        const long long r = alg_clamp(state_rows[e], 0, rows - 1);
-        const long long b = alg_clamp(row_begin[r], 0, frames), n = alg_clamp(row_frames[r], 0, frames - b);
-        for (long long f = b; f < b + n; ++f) {
-            const double gm = (double)gamma[f * ALG_CMAX + c], v = (double)x[f * D + d];
-            const double p = gm * v;  // exact: the product of two floats fits a double
-            const double pv = p * v;
-            w = w + gm;
-            s = s + p;
-            q = q + pv;
-        }
-    }
+    al_state_frames(m, state_off, state_rows, row_begin, row_frames, frames, rows, [&](long long f) {
+        const double gm = (double)gamma[f * ALG_CMAX + c], v = (double)x[f * D + d];
+        const double p = gm * v;  // exact: the product of two floats fits a double
+        const double pv = p * v;
+        w = w + gm;
+        s = s + p;
+        q = q + pv;
+    });
     const long long o = (long long)(g0 + c) * D + d;
     acc_s[o] = acc_s[o] + s;
     acc_q[o] = acc_q[o] + q;
@@ -198,8 +188,8 @@ __global__ __launch_bounds__(512) void al_gmm_stats_kernel(const float* __restri
 
 // what the three entries share: D, M, G and max_comp
 static int alg_check_model(const char* who, int d, int n_states, int n_comp, int max_comp) {
-    FCL_REQUIRE(d >= 1 && d <= ALG_DMAX && n_states >= 1 && n_states <= ALG_MMAX, FCL_ERR_SHAPE, "%s: 1 <= D <= %d and 1 <= M <= %d expected (got %d, %d)", who,
-                ALG_DMAX, ALG_MMAX, d, n_states);
+    FCL_REQUIRE(d >= 1 && d <= AL_DMAX && n_states >= 1 && n_states <= AL_MMAX, FCL_ERR_SHAPE, "%s: 1 <= D <= %d and 1 <= M <= %d expected (got %d, %d)", who,
+                AL_DMAX, AL_MMAX, d, n_states);
     FCL_REQUIRE(max_comp >= 1 && max_comp <= ALG_CMAX, FCL_ERR_SHAPE, "%s: max_comp (the largest component count of a state) must lie in 1 .. %d (got %d)", who,
                 ALG_CMAX, max_comp);
     FCL_REQUIRE(n_comp >= n_states && n_comp <= ALG_GMAX && (long long)n_comp <= (long long)n_states * max_comp, FCL_ERR_SHAPE,
@@ -221,7 +211,7 @@ int fcl_al_gmm_loglik_fwd(const float* x, const float* mean, const float* ivar, 
     if (frames == 0) return FCL_OK;
     FCL_REQUIRE(x && mean && ivar && cconst && comp_off && ll, FCL_ERR_INVALID, "al_gmm_loglik_fwd: null x / mean / ivar / cconst / comp_off / ll");
     ProfScope ps("al_gmm_loglik_kernel", (4.0 * d + 4.0) * n_comp * (double)frames, (double)frames, (hipStream_t)stream);
-    hipLaunchKernelGGL(al_gmm_loglik_kernel, dim3((unsigned)((frames + ALG_LF - 1) / ALG_LF)), dim3(256), 0, (hipStream_t)stream, x, mean, ivar, cconst,
+    hipLaunchKernelGGL(al_gmm_loglik_kernel, dim3((unsigned)((frames + AL_LF - 1) / AL_LF)), dim3(256), 0, (hipStream_t)stream, x, mean, ivar, cconst,
                        comp_off, ll, (long long)frames, d, n_states, n_comp, max_comp);
     return check_hip(hipGetLastError(), "al_gmm_loglik_fwd");
 }
@@ -229,7 +219,7 @@ int fcl_al_gmm_loglik_fwd(const float* x, const float* mean, const float* ivar, 
 int fcl_al_gmm_post_fwd(const float* x, const float* mean, const float* ivar, const float* cconst, const int32_t* comp_off, const int32_t* frame_state,
                         float* gamma, int64_t frames, int d, int n_states, int n_comp, int max_comp, fcl_stream_t stream) {
     if (int rc = alg_check_model("al_gmm_post_fwd", d, n_states, n_comp, max_comp)) return rc;
-    FCL_REQUIRE(frames >= 0 && frames * ALG_DMAX < 0x7fffffffLL, FCL_ERR_SHAPE, "al_gmm_post_fwd: 0 <= frames and frames x 40 < 2^31 expected (got %lld)",
+    FCL_REQUIRE(frames >= 0 && frames * AL_DMAX < 0x7fffffffLL, FCL_ERR_SHAPE, "al_gmm_post_fwd: 0 <= frames and frames x 40 < 2^31 expected (got %lld)",
                 (long long)frames);
     if (frames == 0) return FCL_OK;
     FCL_REQUIRE(x && mean && ivar && cconst && comp_off && frame_state && gamma, FCL_ERR_INVALID,
@@ -244,7 +234,7 @@ int fcl_al_gmm_stats_fwd(const float* x, const float* gamma, const int32_t* row_
                          const int32_t* state_rows, const int32_t* comp_off, double* acc_w, double* acc_s, double* acc_q, int64_t frames, int64_t rows, int d,
                          int n_states, int n_comp, int max_comp, fcl_stream_t stream) {
     if (int rc = alg_check_model("al_gmm_stats_fwd", d, n_states, n_comp, max_comp)) return rc;
-    FCL_REQUIRE(frames >= 0 && rows >= 0 && frames * ALG_DMAX < 0x7fffffffLL && rows < 0x7fffffffLL, FCL_ERR_SHAPE,
+    FCL_REQUIRE(frames >= 0 && rows >= 0 && frames * AL_DMAX < 0x7fffffffLL && rows < 0x7fffffffLL, FCL_ERR_SHAPE,
                 "al_gmm_stats_fwd: 0 <= frames, rows, frames x 40 < 2^31 and rows < 2^31 expected (got %lld, %lld)", (long long)frames, (long long)rows);
     if (frames == 0 || rows == 0) return FCL_OK;
     FCL_REQUIRE(x && gamma && row_begin && row_frames && state_off && state_rows && comp_off && acc_w && acc_s && acc_q, FCL_ERR_INVALID,

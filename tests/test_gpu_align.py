@@ -107,21 +107,18 @@ def padded(ll):
     return out
 
 
-def run_viterbi(A, cases, workspace_bytes=None, n_states=MCOL, tamper=None):
-    """ONE al_viterbi_kernel launch over cases [(ll float32 [T][n_states], row_state, row_skip)] on guarded buffers -> per case dict(ok, score as
-    float32, frame_row, row_begin, row_frames) with row_begin relative to the batch; tamper(mp) may replace device tables first"""
-    mp = A.AlignMaps([len(c[0]) for c in cases], [(c[1], c[2]) for c in cases], n_states, DEV)
-    if tamper is not None:
-        tamper(mp)
+def guarded_launch(mp, cases, n_states, workspace_bytes, launch, tables=()):
+    """the tail run_viterbi and test_gpu_align_lattice.run_lattice share: ll, the workspace and the outputs of ONE launch over the maps mp on guarded
+    buffers, launch(ll, ws, frame_row, row_begin, row_frames, score, ok) on their views, every guard zone (and those of `tables`) intact -> per case
+    dict(ok, score as float32, frame_row, row_begin, row_frames, frame0) with row_begin relative to the batch"""
     ll = Guarded(mp.frames * n_states).set(np.concatenate([c[0] for c in cases]))
     nws = mp.workspace_bytes() if workspace_bytes is None else workspace_bytes
     assert nws % 4 == 0 and (workspace_bytes is not None or nws >= mp.cells)
     ws = Guarded(nws, torch.uint8)
     frame_row, row_begin, row_frames = Guarded(mp.frames, torch.int32), Guarded(mp.rows, torch.int32), Guarded(mp.rows, torch.int32)
     score, ok = Guarded(mp.n_utt), Guarded(mp.n_utt, torch.int32)
-    with launched(VITERBI):
-        A.launch_viterbi(mp, ll.t, ws.t, frame_row.t, row_begin.t, row_frames.t, score.t, ok.t)
-    assert all(g.intact() for g in (ll, ws, frame_row, row_begin, row_frames, score, ok))
+    launch(ll.t, ws.t, frame_row.t, row_begin.t, row_frames.t, score.t, ok.t)
+    assert all(g.intact() for g in (ll, ws, frame_row, row_begin, row_frames, score, ok) + tuple(tables))
     fr, rb, rf, sc, okh = frame_row.np(), row_begin.np(), row_frames.np(), score.np(), ok.np()
     out = []
     for k in range(mp.n_utt):
@@ -129,6 +126,20 @@ def run_viterbi(A, cases, workspace_bytes=None, n_states=MCOL, tamper=None):
         out.append(dict(ok=int(okh[k]), score=sc[k], frame_row=fr[f].astype(np.int64), row_begin=rb[r].astype(np.int64), row_frames=rf[r].astype(np.int64),
                         frame0=int(mp.frame_offs[k])))
     return out
+
+
+def run_viterbi(A, cases, workspace_bytes=None, n_states=MCOL, tamper=None):
+    """ONE al_viterbi_kernel launch over cases [(ll float32 [T][n_states], row_state, row_skip)] on guarded buffers -> guarded_launch's dicts;
+    tamper(mp) may replace device tables first"""
+    mp = A.AlignMaps([len(c[0]) for c in cases], [(c[1], c[2]) for c in cases], n_states, DEV)
+    if tamper is not None:
+        tamper(mp)
+
+    def launch(*bufs):
+        with launched(VITERBI):
+            A.launch_viterbi(mp, *bufs)
+
+    return guarded_launch(mp, cases, n_states, workspace_bytes, launch)
 
 
 def case(size, kind):

@@ -1,7 +1,6 @@
 """The three kernels of csrc/align_gmm.hip, Aligner.fit with mixtures and the align driver's --mixtures against the float64 numpy statement of
 tests/align_gmm_ref.py.  Every buffer a kernel writes sits between guard zones filled with a NaN bit pattern, which must survive;
 every test reads the library's launch record and fails if its kernel did not run.  The statement itself is checked in test_align_gmm_cpu.py."""
-import contextlib
 import functools
 import json
 import wave
@@ -12,68 +11,13 @@ import torch
 
 import align_gmm_ref as G
 import align_ref as R
+from test_gpu_align import DEV, PAT32, A, Guarded, launched  # noqa: F401  (the harness of the chain tests; A is the fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-PAT32 = 0x7FC12345  # an fp32 NaN (and the halves of an fp64 NaN): whatever is read from an unwritten word poisons the result
 U = 2.0 ** -24
 LOGLIK, VITERBI, STATS = "al_loglik_kernel", "al_viterbi_kernel", "al_stats_kernel"
 GLOGLIK, GPOST, GSTATS = "al_gmm_loglik_kernel", "al_gmm_post_kernel", "al_gmm_stats_kernel"
 FRAMES = (1, 2, 63, 64, 65, 300)
-
-
-@pytest.fixture(scope="module")
-def A():
-    assert torch.cuda.is_available()
-    import fcl_taco2_amd  # noqa: F401
-    from fcl_taco2_amd import _lib, alignment
-
-    _lib.load()
-    return alignment
-
-
-@contextlib.contextmanager
-def launched(*names, absent=()):
-    """the launches inside run the named kernels and none of `absent` (the library's own launch record)"""
-    from fcl_taco2_amd import _lib
-
-    _lib.prof_enable(True)
-    try:
-        yield
-        torch.cuda.synchronize()
-        seen = set(_lib.prof_collect())
-    finally:
-        _lib.prof_enable(False)
-    for n in names:
-        assert n in seen, (n, sorted(seen))
-    for n in absent:
-        assert n not in seen, (n, sorted(seen))
-
-
-class Guarded(object):
-    """a device buffer of n elements between two guard zones; everything starts as the NaN pattern"""
-
-    PAD = 8192
-
-    def __init__(self, n, dtype=torch.float32):
-        self.n, self.dtype = int(n), dtype
-        self.words = self.n * torch.empty(0, dtype=dtype).element_size() // 4
-        self.buf = torch.empty(self.words + 2 * self.PAD, dtype=torch.int32, device=DEV)
-        self.buf.fill_(PAT32)
-
-    @property
-    def t(self):
-        return self.buf[self.PAD : self.PAD + self.words].view(self.dtype)
-
-    def set(self, a):
-        self.t.copy_(torch.from_numpy(np.ascontiguousarray(a)).reshape(-1).to(self.dtype))
-        return self
-
-    def np(self):
-        return self.t.cpu().numpy()
-
-    def intact(self):
-        return bool((self.buf[: self.PAD] == PAT32).all()) and bool((self.buf[self.PAD + self.words :] == PAT32).all())
 
 
 def layout(kind, M):

@@ -32,30 +32,20 @@ def A():
 
 
 def run_lattice(A, cases, workspace_bytes=None, n_states=MCOL, tamper=None):
-    """ONE al_lattice_viterbi_kernel launch over cases [(ll float32 [T][n_states], row_state, row_pred, row_flags)] on guarded buffers -> per case
-    dict(ok, score as float32, frame_row, row_begin, row_frames, frame0); tamper(mp) may replace device tables first"""
+    """ONE al_lattice_viterbi_kernel launch over cases [(ll float32 [T][n_states], row_state, row_pred, row_flags)] on guarded buffers ->
+    test_gpu_align.guarded_launch's dicts; tamper(mp) may replace device tables first"""
     mp = A.AlignMaps([len(c[0]) for c in cases], [(c[1], np.asarray(c[2]).reshape(-1, 8), c[3]) for c in cases], n_states, DEV)
     assert mp.lattice
     pred, flags = G.Guarded(mp.rows * 8, torch.int32).set(mp.row_preds), G.Guarded(mp.rows, torch.int32).set(mp.row_flagss)
     mp.row_pred, mp.row_flags = pred.t, flags.t
     if tamper is not None:
         tamper(mp)
-    ll = G.Guarded(mp.frames * n_states).set(np.concatenate([c[0] for c in cases]))
-    nws = mp.workspace_bytes() if workspace_bytes is None else workspace_bytes
-    assert nws % 4 == 0 and (workspace_bytes is not None or nws >= mp.cells)
-    ws = G.Guarded(nws, torch.uint8)
-    frame_row, row_begin, row_frames = G.Guarded(mp.frames, torch.int32), G.Guarded(mp.rows, torch.int32), G.Guarded(mp.rows, torch.int32)
-    score, ok = G.Guarded(mp.n_utt), G.Guarded(mp.n_utt, torch.int32)
-    with G.launched(LATTICE, absent=(CHAIN,)):
-        A.launch_lattice_viterbi(mp, ll.t, ws.t, frame_row.t, row_begin.t, row_frames.t, score.t, ok.t)
-    assert all(g.intact() for g in (ll, ws, frame_row, row_begin, row_frames, score, ok, pred, flags))
-    fr, rb, rf, sc, okh = frame_row.np(), row_begin.np(), row_frames.np(), score.np(), ok.np()
-    out = []
-    for k in range(mp.n_utt):
-        f, r = slice(mp.frame_offs[k], mp.frame_offs[k + 1]), slice(mp.row_offs[k], mp.row_offs[k + 1])
-        out.append(dict(ok=int(okh[k]), score=sc[k], frame_row=fr[f].astype(np.int64), row_begin=rb[r].astype(np.int64), row_frames=rf[r].astype(np.int64),
-                        frame0=int(mp.frame_offs[k])))
-    return out
+
+    def launch(*bufs):
+        with G.launched(LATTICE, absent=(CHAIN,)):
+            A.launch_lattice_viterbi(mp, *bufs)
+
+    return G.guarded_launch(mp, cases, n_states, workspace_bytes, launch, tables=(pred, flags))
 
 
 def case(size, kind):
